@@ -10,12 +10,16 @@ already resident in HBM: forward, soft-target cross-entropy, backward (+ gradien
 clip_grad_norm_(1.0), AdamW, zero_grad.  Workload at N=1: BASELINE.json configs[1] — CALM-ViT-Small,
 224x224, bs=256/GPU, fp32 (SURVEY.md 8(d) variant table).  Weak scaling: every rank keeps bs/GPU.
 
-Rank 0 prints ONE JSON line.  Besides the driver's contract it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps` steps and prints the line
+("ms_per_step" = wall time of one timed step); "roofline" and "attention" are then null.  `--full` adds
   "roofline":     the dominant kernel (the fp32 MFMA GEMM family, calm_gemm): algorithmic FLOPs of the
                   calls of `prof_steps` steps / their summed durations measured with HIP events on the
                   launch stream, against the dense fp32-matrix peak (157.3 TFLOP/s).
+  "attention":    the fused attention kernels of the same profiled steps.
+  "secondary":    the reference's own configuration (Base-224 under autocast bf16) measured in the same run.
   "cpu_baseline": the CPU oracle (oracle/calm_oracle.py, a port; the reference's Python cannot travel)
                   timed on this host on a bounded sample of the same workload.
+`--dump-outputs DIR` writes what the last timed step returned to its caller (dump_outputs) as float32 .npy files.
 """
 import argparse
 import json
@@ -61,6 +65,11 @@ PRECISION_INFO = {
                "gemm_bf16c_kernel<3> (calm_gemm, 3 x v_mfma_f32_32x32x16_bf16 per product)"),
 }
 WEIGHT_SEED = 1234
+# the latent noise of the training forward comes from torch's generator: seeded with a fixed value in every measurement,
+# so that every run with the same arguments draws the same noise
+NOISE_SEED = 67280421310721
+DUMP_SEED = 20240
+DUMP_STATE_ELEMS = 1 << 22          # model-state elements kept by --dump-outputs (16 MB of float32)
 
 
 def synthetic_batch(batch, S, classes, seed, device):
@@ -81,6 +90,20 @@ def build_model(calm, kw, device):
     shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
     m.load_state_dict({k: torch.from_numpy(v) for k, v in W.make_params(shapes, WEIGHT_SEED).items()})
     return m.to(device)
+
+
+def dump_outputs(path, loss, y_hat, model):
+    """--dump-outputs: what a caller of the timed step holds after the last timed step, as float32 .npy files —
+    loss.npy, logits.npy (the step's return values) and state.npy (the updated model: every tensor of state_dict()
+    flattened and concatenated in its order; a fixed seeded sample of DUMP_STATE_ELEMS elements when larger)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "logits.npy"), y_hat.detach().float().cpu().numpy())
+    state = np.concatenate([v.detach().float().reshape(-1).cpu().numpy() for v in model.state_dict().values()])
+    if state.size > DUMP_STATE_ELEMS:
+        idx = np.random.default_rng(DUMP_SEED).choice(state.size, DUMP_STATE_ELEMS, replace=False, shuffle=False)
+        state = state[np.sort(idx)]
+    np.save(os.path.join(path, "state.npy"), state)
 
 
 class GemmProfiler:
@@ -347,7 +370,9 @@ def main():
                     help="matrix pipe of the GEMMs (tensors stay fp32): exact fp32 MFMA (default, config #2), "
                          "bf16 operands (autocast arithmetic, configs #3-5), the fp32-accurate bf16x3 split, or fp8: "
                          "the bf16 pipeline with fp8 Linear forward / input-gradient GEMMs (config #5)")
-    ap.add_argument("--prof-steps", type=int, default=1)
+    ap.add_argument("--prof-steps", type=int, default=None,
+                    help="extra profiled steps behind 'roofline' / 'attention' (default: 1 with --full or --gemm-report, "
+                         "else 0)")
     ap.add_argument("--graph", action="store_true", help="capture the whole step (with the RCCL all-reduces when N > 1) into a hipGraph")
     ap.add_argument("--torch-optim", action="store_true",
                     help="clip_grad_norm_ + torch.optim.AdamW(fused) instead of the library's 3-launch optimizer-side "
@@ -357,9 +382,16 @@ def main():
                          "loss scaled by a torch GradScaler — the GEMMs then run on the bf16 pipe as with --precision bf16")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the Base-224 autocast measurement that the default (small224 fp32) run attaches as 'secondary'")
+                    help="skip the Base-224 autocast measurement that a --full (small224 fp32) run attaches as 'secondary'")
     ap.add_argument("--gemm-report", default="", help="write a per-shape GEMM table (csv) from the profiled steps")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: profiled steps (roofline / attention), the 'secondary' Base-224 autocast "
+                         "measurement and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (loss, logits, sampled model state) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.prof_steps is None:
+        args.prof_steps = 1 if args.full or args.gemm_report else 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
 
@@ -374,8 +406,10 @@ def main():
     torch.cuda.set_device(dev_index)
     device = torch.device("cuda", dev_index)
 
-    def measure(workload, precision, autocast, steps, warmup, prof_steps, gemm_report=""):
-        """Build the workload's model, time `steps` training steps after `warmup`, then profile `prof_steps` more."""
+    def measure(workload, precision, autocast, steps, warmup, prof_steps, gemm_report="", dump_dir=""):
+        """Build the workload's model, time `steps` training steps after `warmup`, dump the last one's outputs to
+        `dump_dir` (if given), then profile `prof_steps` more."""
+        torch.manual_seed(NOISE_SEED)
         wl = WORKLOADS[workload]
         batch = (args.batch if workload == args.workload else 0) or wl["batch"]
         S, classes = wl["kw"]["seq_length"], wl["kw"]["out_features"]
@@ -427,10 +461,12 @@ def main():
         host = 0.0
         for _ in range(steps):
             h0 = time.perf_counter()
-            loss, _ = step(x, y)
+            loss, y_hat = step(x, y)
             host += time.perf_counter() - h0              # host time to ENQUEUE the step (no synchronisation inside)
         sync()
         dt = time.perf_counter() - t0
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, loss, y_hat, model)
         if world > 1:
             t = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -511,7 +547,8 @@ def main():
         torch.cuda.empty_cache()
         return res
 
-    main_res = measure(args.workload, args.precision, args.autocast, args.steps, args.warmup, args.prof_steps, args.gemm_report)
+    main_res = measure(args.workload, args.precision, args.autocast, args.steps, args.warmup, args.prof_steps, args.gemm_report,
+                       args.dump_outputs)
     args.precision = main_res["precision"]
     wl, batch, S = main_res["wl"], main_res["batch"], main_res["S"]
     value, ms_per_step, loss = main_res["value"], main_res["ms_per_step"], main_res["loss"]
@@ -519,7 +556,8 @@ def main():
     # the reference's own configuration (BASELINE configs[2]: Base-224 under autocast(bfloat16) + GradScaler, cls:84-95) in
     # the same run, so that the driver's record carries it beside the fp32 headline: >= 10 timed steps
     secondary = None
-    if world == 1 and not args.no_secondary and args.workload == "small224" and not args.autocast and not args.graph:
+    if (args.full and world == 1 and not args.no_secondary and args.workload == "small224" and not args.autocast
+            and not args.graph):
         torch.cuda.reset_peak_memory_stats(device)
         r2 = measure("base224", "bf16", True, 10, 3, 1)
         secondary = {"workload": f"CALM-ViT base224 cls (the reference's model), 224x224x3 synthetic, bs={r2['batch']}/GPU, "
@@ -554,7 +592,7 @@ def main():
         }
         if secondary is not None:
             out["secondary"] = secondary
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl)
         print(json.dumps(out), flush=True)
     if world > 1:

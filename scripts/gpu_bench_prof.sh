@@ -1,6 +1,7 @@
 #!/bin/bash
 # full-size bench + rocprofv3 kernel-trace summary of the same workload
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+BENCH_ARGS="--full ${BENCH_ARGS}"      # the bench lines below carry roofline / attention, secondary and CPU baseline
 mkdir -p $R/gpurun_out
 cd $R
 timeout -k 10 900 python3 bench.py --steps ${STEPS:-4} --warmup 2 ${BENCH_ARGS} > gpurun_out/bench_full.log 2>&1 || { tail -n 30 gpurun_out/bench_full.log; exit 1; }

@@ -1,6 +1,7 @@
 #!/bin/bash
 # iteration loop on the GPU box: tests, then bench (+ per-shape GEMM report), optional rocprof
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+BENCH_ARGS="--full ${BENCH_ARGS}"      # the bench lines below carry roofline / attention, secondary and CPU baseline
 cd $R; mkdir -p gpurun_out
 python3 -m pytest tests -m gpu -q --timeout 900 ${PYTEST_ARGS} > gpurun_out/pytest_gpu.log 2>&1; rc=$?
 tail -n ${PYTEST_TAIL:-6} gpurun_out/pytest_gpu.log; echo "pytest rc=$rc"

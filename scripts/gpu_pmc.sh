@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes (separate runs, --pmc only) over a short run of the bench workload
 R=${GRAFT_REPO_ROOT:-$(pwd)}; mkdir -p $R/gpurun_out; cd /tmp; export TMPDIR=/tmp
-CMD="python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --prof-steps 0 ${BENCH_ARGS}"
+CMD="python3 $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --prof-steps 0 ${BENCH_ARGS}"
 rm -rf $R/gpurun_out/pmc; mkdir -p $R/gpurun_out/pmc
 timeout -k 10 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $R/gpurun_out/pmc/p1 -o p1 -- $CMD > $R/gpurun_out/pmc1.log 2>&1 || { tail -n 20 $R/gpurun_out/pmc1.log; exit 1; }
 echo pass1 done

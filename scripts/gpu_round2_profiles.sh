@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r2; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 one() {   # tag, bench args
   tag=$1; shift
-  timeout -k 10 400 python3 $R/bench.py --steps 6 --warmup 2 --gemm-report $O/${tag}_gemm_shapes.csv "$@" > $O/${tag}_bench.json 2> $O/${tag}_bench.err || { tail -n 5 $O/${tag}_bench.err; return 1; }
+  timeout -k 10 400 python3 $R/bench.py --steps 6 --warmup 2 --full --gemm-report $O/${tag}_gemm_shapes.csv "$@" > $O/${tag}_bench.json 2> $O/${tag}_bench.err || { tail -n 5 $O/${tag}_bench.err; return 1; }
   tail -c 600 $O/${tag}_bench.json; echo
   CMD="python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --prof-steps 0 $*"
   rm -rf $O/tmp_$tag; mkdir -p $O/tmp_$tag
