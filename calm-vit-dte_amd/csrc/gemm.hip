@@ -1,6 +1,10 @@
-// calm_gemm: strided / batched / split-K GEMM with fused epilogue for gfx950 — the dispatcher.
-// Two kernel families share tiling, remap, split logic and epilogue (gemm_common.h): the exact fp32 MFMA family
-// (gemm_f32.hip) and the bf16-operand family (gemm_bf16.hip).
+// calm_gemm: strided / batched / grouped / split-K GEMM with fused epilogue for gfx950 — the dispatcher.
+// Six kernel families, numbered as calm_gemm_plan::family in include/calm_vit.h:
+//   0 exact fp32 MFMA, 128-row tiles (gemm_f32.hip)           3 bf16 pipelined persistent (gemm_bf16p.h)
+//   1 bf16-operand, 128-row tiles (gemm_bf16.hip)             4 fp32 pipelined persistent (gemm_bf16p.h; opt-in)
+//   2 bf16-operand, 256x128 tiles (gemm_bf16.hip)             5 fp8 operands (gemm_fp8.hip)
+// Families 0-2 share tiling, remap, split logic and epilogue (gemm_common.h).  plan_gemm() decides a launch once and has
+// no side effects; calm_gemm_workspace_bytes, calm_gemm_describe and calm_gemm report or launch that one decision.
 #include <atomic>
 #include "gemm_common.h"
 #include <stdlib.h>
@@ -78,15 +82,27 @@ static void launch_splitk_reduce(const ReduceP& q, int n_out, hipStream_t s) {
     }
 }
 
-inline bool mult4(int64_t x) { return (x & 3) == 0; }
-
-}  // namespace
-
 #ifndef CALM_GEMM_WS_MIN_SLICES
 #define CALM_GEMM_WS_MIN_SLICES 48     // per-slice partial tiles + one reduction instead of atomics from this many k-slices
 #endif                                 // per output (A/B with plain stores in place of the atomics: outputs of 528 rows and
                                        // more, <= 42 slices, do not change; 384x768 ... 240x240, 53-106 slices, -15..-30%)
 
+// calm_gemm_plan::family (include/calm_vit.h; backend.py and tests/locate.py compare against FAM_PIPE / FAM_PIPE32)
+enum : int { FAM_F32 = 0, FAM_BF16 = 1, FAM_BF16_WIDE = 2, FAM_PIPE = 3, FAM_PIPE32 = 4, FAM_FP8 = 5 };
+
+// What a launch decomposes into beyond its GemmP: decided once by plan_gemm, read by every entry point.
+struct Decomp {
+    int family = FAM_F32;
+    int mt = 0, nt = 0;              // pipelined families: (64 mt) x (32 nt) tiles
+    int bn = 0;                      // 128-row and 256x128 tiles: N tile (96 / 128)
+    int npass = 1;                   // bf16-operand 128-row tiles: MFMA passes (3: CALM_BF16X3)
+    bool vec = false;                // fp32 128-row tiles: 16-byte operand staging
+    long items = 0;                  // tiles x (batch entries or k-slices)
+    dim3 grid;                       // workgroups of the main launch
+    int n_out = 1;                   // outputs the k-slices are combined into
+    int slices_per_out = 1;          // k-slices per output (1: not split)
+    int64_t ws_need = 0;             // workspace for one partial tile per slice (0: atomics, or not split)
+};
 
 // ---- pipelined persistent family (gemm_bf16p.h) -----------------------------------------------------------------------
 // Takes the launches whose operands are both bf16 tensors: activation x weight (forward), gradient x weight^T (data
@@ -95,7 +111,7 @@ inline bool mult4(int64_t x) { return (x & 3) == 0; }
 // problems.  CALM_GEMM_PIPE=0 in the environment switches the family off (A/B runs).
 constexpr int PIPE_DECLINED = -1000;
 
-static std::atomic<int>& pipe_option(int which) {
+std::atomic<int>& pipe_option(int which) {
     static std::atomic<int> opt[3] = {
         [] { const char* e = getenv("CALM_GEMM_PIPE"); return (e && e[0] == '0') ? 0 : 1; }(),
         [] { const char* e = getenv("CALM_GEMM_PIPE32"); return e ? atoi(e) : 0; }(),
@@ -103,16 +119,31 @@ static std::atomic<int>& pipe_option(int which) {
     return opt[which];
 }
 // every k-split / batch-reduced launch through the workspace + fixed-order reduction (no fp32 atomics)
-static bool deterministic() { return pipe_option(CALM_GEMM_OPT_DETERMINISTIC).load(std::memory_order_relaxed) != 0; }
-static bool pipe_enabled() { return pipe_option(CALM_GEMM_OPT_PIPE).load(std::memory_order_relaxed) != 0; }
+bool deterministic() { return pipe_option(CALM_GEMM_OPT_DETERMINISTIC).load(std::memory_order_relaxed) != 0; }
+bool pipe_enabled() { return pipe_option(CALM_GEMM_OPT_PIPE).load(std::memory_order_relaxed) != 0; }
 // fp32 instantiation: 0 off (default), 1 every eligible launch, 2 k-contiguous operand pairs only
-static int pipe32_mode() { return pipe_enabled() ? pipe_option(CALM_GEMM_OPT_PIPE32).load(std::memory_order_relaxed) : 0; }
+int pipe32_mode() { return pipe_enabled() ? pipe_option(CALM_GEMM_OPT_PIPE32).load(std::memory_order_relaxed) : 0; }
+
+// How the k-slices of a split launch are combined: fp32 atomics onto a zeroed (or accumulated-into) C, or — in
+// deterministic mode, or many slices per output and a caller-provided workspace — one dense partial tile per slice and a
+// reduction pass.  `slices`: k-slices over all outputs (grid.y / work items per tile).
+void plan_combine(const calm_gemm_args* a, GemmP& p, Decomp& d, int slices) {
+    d.n_out = p.slices_per_batch ? a->batch0 * a->batch1 : 1;
+    d.slices_per_out = p.atomic ? slices / d.n_out : 1;
+    p.ws_slice = (long)a->M * a->N;
+    if (p.atomic && (deterministic() || (d.slices_per_out >= CALM_GEMM_WS_MIN_SLICES && p.ws_slice >= 100000)))     // tiny outputs: the second launch costs more than their atomics
+        d.ws_need = (int64_t)sizeof(float) * slices * p.ws_slice;
+}
+
+bool uses_workspace(const calm_gemm_args* a, const Decomp& d) {
+    return d.ws_need > 0 && a->workspace && a->workspace_bytes >= d.ws_need && aligned16(a->workspace);
+}
 
 // modelled duration of a launch (cycles of one CU, up to a common factor): `rounds` items per persistent workgroup, each
 // nk k-tiles of a (64 mt) x (32 nt) tile; a k-tile is bound by its MFMAs (64 mt nt cycles per SIMD at two waves) or by
 // staging its (64 mt + 32 nt) x 128 bytes at ~40 B per cycle; the epilogue costs about one extra k-tile per tile row set
 // (fp32: eight 32-cycle v_mfma_f32_16x16x4_f32 per tile, k-tile and wave instead of two 16-cycle bf16 ones)
-static double pipe_cost(long items, int mt, int nt, int nk, bool split, bool f32) {
+double pipe_cost(long items, int mt, int nt, int nk, bool split, bool f32) {
     const long rounds = (items + 255) / 256;
     const double mfma = (f32 ? 512.0 : 64.0) * mt * nt, stage = (64.0 * mt + 32.0 * nt) * 128.0 / 40.0;
     const double ktile = (mfma > stage ? mfma : stage) + 120.0;
@@ -120,8 +151,9 @@ static double pipe_cost(long items, int mt, int nt, int nk, bool split, bool f32
     return rounds * (nk * ktile + epi);
 }
 
-static int pipe_run(const calm_gemm_args* a, GemmP& p, bool akc, bool bkc, bool f32, hipStream_t s, int64_t* query,
-                    calm_gemm_plan* plan) {
+// families 3 (bf16) and 4 (fp32): 0 or PIPE_DECLINED
+int plan_pipe(const calm_gemm_args* a, GemmP& p, Decomp& d, bool f32) {
+    const bool akc = a->a_cs == 1, bkc = a->b_cs == 1;
     if (!akc && bkc) return PIPE_DECLINED;                      // row-contiguous A with k-contiguous B: not instantiated
     if (a->reduce_batch || !p.epi_vec) return PIPE_DECLINED;
     if ((a->act == CALM_ACT_GELU_BWD) + (a->residual != nullptr) + (a->accumulate != 0) > 1) return PIPE_DECLINED;   // one C-shaped epilogue operand
@@ -200,46 +232,13 @@ static int pipe_run(const calm_gemm_args* a, GemmP& p, bool akc, bool bkc, bool 
         p.kb_per_z = kpb;
         p.nz = batch;
     }
-    const int n_out = p.slices_per_batch ? batch : 1;
-    const int slices_per_out = p.atomic ? p.nz / n_out : 1;
-    p.ws = nullptr;
-    p.ws_slice = (long)a->M * a->N;
-    int64_t ws_need = 0;
-    if (p.atomic && (deterministic() || (slices_per_out >= CALM_GEMM_WS_MIN_SLICES && p.ws_slice >= 100000)))
-        ws_need = (int64_t)sizeof(float) * p.nz * p.ws_slice;
-    if (query) {
-        *query = ws_need;
-        return 0;
-    }
-    const bool use_ws = ws_need > 0 && a->workspace && a->workspace_bytes >= ws_need && aligned16(a->workspace);
-    if (plan) {
-        const long items_ = (long)p.tiles_m * p.tiles_n * p.nz;
-        const bool u8_ = !p.atomic && a->c_type == CALM_ST_BF16 && (!a->aux || a->aux_type == CALM_ST_BF16) &&
-                         (!a->residual || (a->r_type == CALM_ST_BF16 && !(a->r_rs & 7) && !(a->r_b0 & 7) && !(a->r_b1 & 7))) &&
-                         !(a->N & 7) && !(a->c_rs & 7) && !(a->c_b0 & 7) && !(a->c_b1 & 7);
-        *plan = calm_gemm_plan{f32 ? 4 : 3, 64 * mt, 32 * nt, f32 ? 32 : 64, p.tiles_m, p.tiles_n, slices_per_out,
-                               (int32_t)items_, (int32_t)(items_ < 256 ? items_ : 256), u8_ ? 8 : 4, use_ws ? 1 : 0,
-                               512};
-        return 0;
-    }
-    if (use_ws) {
-        p.ws = (float*)a->workspace;
-    } else if (p.atomic && !a->accumulate) {
-        for (int g = 0; g < n_out; ++g) {
-            float* out = (float*)(p.slices_per_batch ? p.Cg[g] : p.C);
-            hipError_t e;
-            if (a->c_rs == a->N) e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)a->M * a->N, s);
-            else e = hipMemset2DAsync(out, sizeof(float) * a->c_rs, 0, sizeof(float) * a->N, a->M, s);
-            if (e != hipSuccess) return (int)e;
-        }
-    }
-#ifdef CALM_PIPE_STAMP
-    if (!p.atomic && a->workspace && a->workspace_bytes >= 256 * 2 * 8 * 4 * 8) p.ws = (float*)a->workspace;   // diagnostic build: stamps
-#endif
-    const long items = (long)p.tiles_m * p.tiles_n * p.nz;
-    const int grid = (int)(items < 256 ? items : 256);
+    d.family = f32 ? FAM_PIPE32 : FAM_PIPE;
+    d.mt = mt;
+    d.nt = nt;
+    d.items = (long)p.tiles_m * p.tiles_n * p.nz;
+    d.grid = dim3((int)(d.items < 256 ? d.items : 256));
     static const int stagger = [] { const char* e = getenv("CALM_PIPE_STAGGER"); return e ? atoi(e) : 0; }();
-    p.stagger = items > 256 ? stagger : 0;
+    p.stagger = d.items > 256 ? stagger : 0;
     {   // 8 columns per lane in the epilogue when every tensor it touches is bf16 and addressable in aligned groups of 8
         auto m8 = [](int64_t x) { return (x & 7) == 0; };
         const bool u8 = !p.atomic && a->c_type == CALM_ST_BF16 && (!a->aux || a->aux_type == CALM_ST_BF16) &&
@@ -247,134 +246,15 @@ static int pipe_run(const calm_gemm_args* a, GemmP& p, bool akc, bool bkc, bool 
                         m8(a->N) && m8(a->c_rs) && m8(a->c_b0) && m8(a->c_b1);
         p.epi_unit = u8 ? 8 : 4;
     }
-    int rc;
-    if (f32) {
-        if (akc && bkc) rc = launch_pipe32_kk(p, mt, nt, grid, s);
-        else if (akc) rc = launch_pipe32_km(p, mt, nt, grid, s);
-        else rc = launch_pipe32_mm(p, mt, nt, grid, s);
-    } else if (akc && bkc) rc = launch_pipe_kk(p, mt, nt, grid, s);
-    else if (akc) rc = launch_pipe_km(p, mt, nt, grid, s);
-    else rc = launch_pipe_mm(p, mt, nt, grid, s);
-    if (rc || !use_ws) return rc;
-    ReduceP q;
-    q.ws = p.ws; q.ws_slice = p.ws_slice; q.nslices = slices_per_out;
-    q.C = (float*)p.C; q.c_b0 = a->c_b0; q.c_rs = a->c_rs;
-    for (int g = 0; g < 4; ++g) q.Cg[g] = p.slices_per_batch ? (float*)p.Cg[g] : nullptr;
-    q.M = a->M; q.N = a->N; q.accumulate = a->accumulate;
-    launch_splitk_reduce(q, n_out, s);
-    CALM_LAUNCH_CHECK();
+    plan_combine(a, p, d, p.nz);
     return 0;
 }
 
-// query != nullptr: plan only and report the workspace size of the launch (calm_gemm_workspace_bytes);
-// plan != nullptr: plan only and describe the launch (calm_gemm_describe)
-static int gemm_run(const calm_gemm_args* a, void* stream, int64_t* query, calm_gemm_plan* plan = nullptr) {
-    if (!a || !a->A || !a->B || !a->C) return CALM_E_INVAL;
-    if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->batch0 <= 0 || a->batch1 <= 0) return CALM_E_INVAL;
-    if (a->dtype != CALM_F32 && a->dtype != CALM_BF16 && a->dtype != CALM_BF16X3) return CALM_E_UNSUPP;
-    for (int t : {a->c_type, a->aux_type, a->r_type})
-        if (t != CALM_ST_F32 && t != CALM_ST_BF16) return CALM_E_INVAL;
-    for (int t : {a->a_type, a->b_type})
-        if (t < CALM_ST_F32 || t > CALM_ST_FP8_E5M2) return CALM_E_INVAL;
-    const bool fp8 = a->a_type >= CALM_ST_FP8_E4M3 || a->b_type >= CALM_ST_FP8_E4M3;
-    const bool any_bf16_tensor = a->a_type || a->b_type || a->c_type || a->aux_type || a->r_type;      // (or fp8)
-    if (any_bf16_tensor && a->dtype != CALM_BF16) return CALM_E_UNSUPP;       // bf16 tensors: bf16 matrix pipe only
-    if (a->a_rs != 1 && a->a_cs != 1) return CALM_E_LAYOUT;
-    if (a->b_rs != 1 && a->b_cs != 1) return CALM_E_LAYOUT;
-    // the staging cursors address a tile with 32-bit byte offsets from a per-tile base: 255 rows x stride x 4 B < 2^32
-    if (a->a_rs >= (1 << 21) || a->a_cs >= (1 << 21) || a->b_rs >= (1 << 21) || a->b_cs >= (1 << 21)) return CALM_E_UNSUPP;
-    if (a->act == CALM_ACT_GELU_BWD && !a->aux) return CALM_E_INVAL;
-    if (a->act < 0 || a->act > CALM_ACT_GELU_BWD) return CALM_E_INVAL;
-    if (a->n_group < 0 || a->n_group > CALM_GEMM_MAX_GROUP) return CALM_E_INVAL;
-    if (a->n_group) {
-        if (a->batch0 != a->n_group || a->batch1 != 1) return CALM_E_INVAL;
-        if (a->C_pre || a->aux || a->residual || a->inv_scale) return CALM_E_UNSUPP;
-        for (int g = 0; g < a->n_group; ++g) {
-            if ((a->A_group[0] && !a->A_group[g]) || (a->B_group[0] && !a->B_group[g])) return CALM_E_INVAL;
-            if (!a->reduce_batch && a->C_group[0] && !a->C_group[g]) return CALM_E_INVAL;
-        }
-    }
-    hipStream_t s = as_stream(stream);
-
-    GemmP p;
-    p.A = a->A; p.B = a->B; p.C = a->C;
-    p.a_type = a->a_type; p.b_type = a->b_type; p.c_type = a->c_type; p.aux_type = a->aux_type; p.r_type = a->r_type;
-    p.dq_a = fp8 ? a->a_dq : nullptr; p.dq_b = fp8 ? a->b_dq : nullptr;
-    p.M = a->M; p.N = a->N; p.K = a->K;
-    p.batch1 = a->batch1;
-    p.a_rs = a->a_rs; p.a_cs = a->a_cs; p.a_b0 = a->a_b0; p.a_b1 = a->a_b1;
-    p.b_rs = a->b_rs; p.b_cs = a->b_cs; p.b_b0 = a->b_b0; p.b_b1 = a->b_b1;
-    p.c_rs = a->c_rs; p.c_b0 = a->c_b0; p.c_b1 = a->c_b1;
-    p.alpha = a->alpha; p.inv_scale = a->inv_scale; p.bias = a->bias; p.col_scale = a->col_scale;
-    p.residual = a->residual; p.r_rs = a->r_rs; p.r_b0 = a->r_b0; p.r_b1 = a->r_b1;
-    p.C_pre = a->C_pre; p.aux = a->aux;
-    p.act = a->act; p.accumulate = a->accumulate;
-    p.n_group = a->n_group;
-    p.reduce_group = a->n_group && a->reduce_batch;
-    for (int g = 0; g < 4; ++g) {
-        const bool on = g < a->n_group;
-        p.Ag[g] = on ? a->A_group[g] : nullptr;
-        p.Bg[g] = on ? a->B_group[g] : nullptr;
-        p.Cg[g] = on ? a->C_group[g] : nullptr;
-        p.Sg[g] = on ? a->inv_scale_group[g] : nullptr;
-    }
-    {   // vector epilogue: every tensor the epilogue touches addressable in aligned groups of 4 columns
-        auto m4 = [](int64_t x) { return (x & 3) == 0; };
-        bool ev = m4(a->N) && m4(a->c_rs) && m4(a->c_b0) && m4(a->c_b1) && aligned16(a->C) &&
-                  (!a->C_pre || aligned16(a->C_pre)) && (!a->aux || aligned16(a->aux)) &&
-                  (!a->bias || aligned16(a->bias)) && (!a->col_scale || aligned16(a->col_scale)) &&
-                  (!a->residual || (aligned16(a->residual) && m4(a->r_rs) && m4(a->r_b0) && m4(a->r_b1)));
-        for (int g = 0; g < a->n_group; ++g) ev = ev && (!a->C_group[g] || aligned16(a->C_group[g]));
-        p.epi_vec = ev && CALM_GEMM_VEC_EPILOGUE;
-    }
+// ---- 256-thread families: 128-row tiles (0, 1) and 256x128 tiles (2) ----------------------------------------------------
+// dtype: the matrix pipe the kernels run (CALM_F32 for a launch that cannot be vectorised)
+int plan_tiles(const calm_gemm_args* a, GemmP& p, Decomp& d, int dtype, bool vec) {
     const int batch = a->batch0 * a->batch1;
-    const bool akc = a->a_cs == 1;
-    const bool bkc = a->b_cs == 1;
-    if (fp8) {
-        // fp8 family: both operands fp8 (B e4m3; A e4m3 or e5m2), k-contiguous, K and row strides multiples of 16 bytes,
-        // one launch per call (no k-split, no groups), dequantisation factors on the device
-        if (a->b_type != CALM_ST_FP8_E4M3 || a->a_type < CALM_ST_FP8_E4M3 || !a->a_dq || !a->b_dq) return CALM_E_INVAL;
-        if (a->dtype != CALM_BF16 || !akc || !bkc || a->n_group || a->reduce_batch || a->split_k > 1) return CALM_E_UNSUPP;
-        if ((a->K & 15) || (a->a_rs & 15) || (a->b_rs & 15) || (a->a_b0 & 15) || (a->a_b1 & 15) || (a->b_b0 & 15) ||
-            (a->b_b1 & 15) || !aligned16(a->A) || !aligned16(a->B))
-            return CALM_E_LAYOUT;
-        if (batch > 65535) return CALM_E_UNSUPP;
-        p.tiles_m = (a->M + WBM - 1) / WBM;
-        p.tiles_n = (a->N + WBN - 1) / WBN;
-        p.kpb = 0; p.kb_total = 0; p.kb_per_z = 0; p.atomic = 0; p.slices_per_batch = 0; p.reduce_group = 0;
-        p.ws = nullptr; p.ws_slice = 0;
-        if (query) {
-            *query = 0;
-            return 0;
-        }
-        if (plan) {
-            *plan = calm_gemm_plan{5, WBM, WBN, 64, p.tiles_m, p.tiles_n, 1, p.tiles_m * p.tiles_n * batch,
-                                   p.tiles_m * p.tiles_n * batch, 0, 0, WTHREADS};
-            return 0;
-        }
-        return launch_fp8(p, dim3(p.tiles_m * p.tiles_n, batch), s);
-    }
-    // 16-byte staging vectors hold 4 fp32 or 8 bf16 elements: sizes / strides of an operand must be multiples of that
-    const int64_t ea = a->a_type == CALM_ST_BF16 ? 7 : 3, eb = a->b_type == CALM_ST_BF16 ? 7 : 3;
-    auto mult = [](int64_t x, int64_t mask) { return (x & mask) == 0; };
-    bool vec = aligned16(a->A) && aligned16(a->B) && mult(a->a_b0, ea) && mult(a->a_b1, ea) && mult(a->b_b0, eb) &&
-               mult(a->b_b1, eb);
-    for (int g = 0; g < a->n_group; ++g) vec = vec && aligned16(a->A_group[g]) && aligned16(a->B_group[g]);
-    vec = vec && (akc ? (mult(a->K, ea) && mult(a->a_rs, ea)) : (mult(a->M, ea) && mult(a->a_cs, ea)));
-    vec = vec && (bkc ? (mult(a->K, eb) && mult(a->b_rs, eb)) : (mult(a->N, eb) && mult(a->b_cs, eb)));
-    // bf16-operand kernels need the 16-byte staging path; anything else runs on the exact fp32 kernels — which
-    // only read fp32 tensors: a bf16 tensor in a launch that cannot be vectorised is the caller's layout error
-    if (!vec && any_bf16_tensor) return CALM_E_LAYOUT;
-    const int family = vec ? a->dtype : CALM_F32;
-    if (family == CALM_BF16 && a->a_type == CALM_ST_BF16 && a->b_type == CALM_ST_BF16 && pipe_enabled()) {
-        const int rc = pipe_run(a, p, akc, bkc, false, s, query, plan);
-        if (rc != PIPE_DECLINED) return rc;
-    }
-    if (vec && a->dtype == CALM_F32 && !any_bf16_tensor && (pipe32_mode() == 1 || (pipe32_mode() == 2 && akc && bkc))) {
-        const int rc = pipe_run(a, p, akc, bkc, true, s, query, plan);
-        if (rc != PIPE_DECLINED) return rc;
-    }
-    const int bk = family == CALM_F32 ? BK : CK;
+    const int bk = dtype == CALM_F32 ? BK : CK;
     p.kpb = (a->K + bk - 1) / bk;
     const bool trivial_epi = !a->bias && !a->col_scale && !a->residual && !a->C_pre && a->act == CALM_ACT_NONE;
 
@@ -402,22 +282,17 @@ static int gemm_run(const calm_gemm_args* a, void* stream, int64_t* query, calm_
     }
     // bf16 operands, data-parallel launch with at least a full resident round (2 per CU) of 256x128 tiles: wide kernel
     bool wide = false;
-    if (family == CALM_BF16 && !k_split) {
+    if (dtype == CALM_BF16 && !k_split) {
         const long nb = grouped_reduce_unsplit ? 1 : batch;
         const long rows_w = (long)(a->M + WBM - 1) / WBM * WBM;             // at most 1/8 of the rows padded
         wide = 8 * rows_w <= 9 * (long)a->M &&
                rows_w / WBM * ((a->N + WBN - 1) / WBN) * nb >= CALM_GEMM_WIDE_MIN_TILES;
-        if (wide) {
-            bn = WBN;
-            p.tiles_m = (a->M + WBM - 1) / WBM;
-        }
     }
     // ... and the split-K weight gradients (plain or grouped) whose output pads by at most 1/4 in 256-row tiles (672,
     // 768, 1056, 1344 rows): with bf16 operands they are bound by re-reading the fp32 panels from L2, not by padded MFMAs
-    const bool wide_split = family == CALM_BF16 && k_split && !a->reduce_batch && (group_split || batch == 1) &&
-                            4 * ((long)(a->M + WBM - 1) / WBM * WBM) <= 5 * (long)a->M;
-    if (wide_split) {
-        wide = true;
+    wide = wide || (dtype == CALM_BF16 && k_split && !a->reduce_batch && (group_split || batch == 1) &&
+                    4 * ((long)(a->M + WBM - 1) / WBM * WBM) <= 5 * (long)a->M);
+    if (wide) {
         bn = WBN;
         p.tiles_m = (a->M + WBM - 1) / WBM;
     }
@@ -452,7 +327,7 @@ static int gemm_run(const calm_gemm_args* a, void* stream, int64_t* query, calm_
         // contention costs more than the shorter slices save (scripts/ab_reduce_split.py, 256 images: 80x176x528 51.6 us
         // at 512 slices, 33.4 at 128; 224x176x528 69.7 -> 56.5; 128x80x240 24.4 -> 19.7)
         // (measured on the bf16-operand kernels; the fp32 kernels, 16x slower per k-block, keep their full round of slices)
-        if (a->split_k <= 1 && family == CALM_BF16) {
+        if (a->split_k <= 1 && dtype == CALM_BF16) {
             const int cap = tiles == 1 ? 128 : 256 / tiles;
             if (nsplit > cap) nsplit = cap;
         }
@@ -465,7 +340,7 @@ static int gemm_run(const calm_gemm_args* a, void* stream, int64_t* query, calm_
         // small outputs (the 128-row kernels' share of the weight gradients): every slice adds its tiles onto the same
         // output — about one workgroup per CU is the optimum (264 x 240 x 45056: 41.9 us at 88 slices, 29.7 at 32)
         // (bf16-operand kernels only: as above)
-        if (a->split_k <= 1 && family == CALM_BF16 && !wide && nsplit > 256 / tiles) nsplit = 256 / tiles;
+        if (a->split_k <= 1 && dtype == CALM_BF16 && !wide && nsplit > 256 / tiles) nsplit = 256 / tiles;
         if (nsplit < 1) nsplit = 1;
         p.kb_total = p.kpb;
         p.atomic = nsplit > 1;
@@ -486,33 +361,163 @@ static int gemm_run(const calm_gemm_args* a, void* stream, int64_t* query, calm_
     }
     const int gy = p.slices_per_batch ? batch * p.slices_per_batch : (p.kb_total + p.kb_per_z - 1) / p.kb_per_z;
     if (gy > 65535) return CALM_E_UNSUPP;
-    dim3 grid(tiles, gy);
+    d.family = wide ? FAM_BF16_WIDE : dtype == CALM_F32 ? FAM_F32 : FAM_BF16;
+    d.bn = bn;
+    d.npass = dtype == CALM_BF16X3 ? 3 : 1;
+    d.vec = vec;
+    d.items = tiles * gy;
+    d.grid = dim3(tiles, gy);
+    plan_combine(a, p, d, gy);
+    return 0;
+}
 
-    // how the k-slices are combined: fp32 atomics onto a zeroed (or accumulated-into) C, or — many slices per output
-    // and a caller-provided workspace — one dense partial tile per slice and a reduction pass
-    const int n_out = p.slices_per_batch ? batch : 1;
-    const int slices_per_out = gy / n_out;
-    p.ws = nullptr;
-    p.ws_slice = (long)a->M * a->N;
-    int64_t ws_need = 0;
-    if (p.atomic && (deterministic() || (slices_per_out >= CALM_GEMM_WS_MIN_SLICES && p.ws_slice >= 100000)))     // tiny outputs: the second launch costs more than their atomics
-        ws_need = (int64_t)sizeof(float) * gy * p.ws_slice;
-    if (query) {
-        *query = ws_need;
-        return 0;
+// ---- fp8 family (gemm_fp8.hip) ----------------------------------------------------------------------------------------
+// both operands fp8 (B e4m3; A e4m3 or e5m2), k-contiguous, K and row strides multiples of 16 bytes, one launch per call
+// (no k-split, no groups), dequantisation factors on the device
+int plan_fp8(const calm_gemm_args* a, GemmP& p, Decomp& d) {
+    if (a->b_type != CALM_ST_FP8_E4M3 || a->a_type < CALM_ST_FP8_E4M3 || !a->a_dq || !a->b_dq) return CALM_E_INVAL;
+    if (a->dtype != CALM_BF16 || a->a_cs != 1 || a->b_cs != 1 || a->n_group || a->reduce_batch || a->split_k > 1) return CALM_E_UNSUPP;
+    if ((a->K & 15) || (a->a_rs & 15) || (a->b_rs & 15) || (a->a_b0 & 15) || (a->a_b1 & 15) || (a->b_b0 & 15) ||
+        (a->b_b1 & 15) || !aligned16(a->A) || !aligned16(a->B))
+        return CALM_E_LAYOUT;
+    const int batch = a->batch0 * a->batch1;
+    if (batch > 65535) return CALM_E_UNSUPP;
+    p.dq_a = a->a_dq;
+    p.dq_b = a->b_dq;
+    p.tiles_m = (a->M + WBM - 1) / WBM;
+    p.tiles_n = (a->N + WBN - 1) / WBN;
+    d.family = FAM_FP8;
+    d.items = p.tiles_m * p.tiles_n * batch;
+    d.grid = dim3(p.tiles_m * p.tiles_n, batch);
+    return 0;
+}
+
+// Validates the arguments and decides the whole launch: GemmP (p value-initialised by the caller) and Decomp.  No side
+// effects: calm_gemm_workspace_bytes, calm_gemm_describe and calm_gemm all report or launch this one decision.
+int plan_gemm(const calm_gemm_args* a, GemmP& p, Decomp& d) {
+    if (!a || !a->A || !a->B || !a->C) return CALM_E_INVAL;
+    if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->batch0 <= 0 || a->batch1 <= 0) return CALM_E_INVAL;
+    if (a->dtype != CALM_F32 && a->dtype != CALM_BF16 && a->dtype != CALM_BF16X3) return CALM_E_UNSUPP;
+    for (int t : {a->c_type, a->aux_type, a->r_type})
+        if (t != CALM_ST_F32 && t != CALM_ST_BF16) return CALM_E_INVAL;
+    for (int t : {a->a_type, a->b_type})
+        if (t < CALM_ST_F32 || t > CALM_ST_FP8_E5M2) return CALM_E_INVAL;
+    const bool fp8 = a->a_type >= CALM_ST_FP8_E4M3 || a->b_type >= CALM_ST_FP8_E4M3;
+    const bool any_bf16_tensor = a->a_type || a->b_type || a->c_type || a->aux_type || a->r_type;      // (or fp8)
+    if (any_bf16_tensor && a->dtype != CALM_BF16) return CALM_E_UNSUPP;       // bf16 tensors: bf16 matrix pipe only
+    if (a->a_rs != 1 && a->a_cs != 1) return CALM_E_LAYOUT;
+    if (a->b_rs != 1 && a->b_cs != 1) return CALM_E_LAYOUT;
+    // the staging cursors address a tile with 32-bit byte offsets from a per-tile base: 255 rows x stride x 4 B < 2^32
+    if (a->a_rs >= (1 << 21) || a->a_cs >= (1 << 21) || a->b_rs >= (1 << 21) || a->b_cs >= (1 << 21)) return CALM_E_UNSUPP;
+    if (a->act == CALM_ACT_GELU_BWD && !a->aux) return CALM_E_INVAL;
+    if (a->act < 0 || a->act > CALM_ACT_GELU_BWD) return CALM_E_INVAL;
+    if (a->n_group < 0 || a->n_group > CALM_GEMM_MAX_GROUP) return CALM_E_INVAL;
+    if (a->n_group) {
+        if (a->batch0 != a->n_group || a->batch1 != 1) return CALM_E_INVAL;
+        if (a->C_pre || a->aux || a->residual || a->inv_scale) return CALM_E_UNSUPP;
+        for (int g = 0; g < a->n_group; ++g) {
+            if ((a->A_group[0] && !a->A_group[g]) || (a->B_group[0] && !a->B_group[g])) return CALM_E_INVAL;
+            if (!a->reduce_batch && a->C_group[0] && !a->C_group[g]) return CALM_E_INVAL;
+        }
     }
-    const bool use_ws = ws_need > 0 && a->workspace && a->workspace_bytes >= ws_need && aligned16(a->workspace);
-    if (plan) {
-        const int fam = wide ? 2 : family == CALM_F32 ? 0 : 1;
-        *plan = calm_gemm_plan{fam, wide ? WBM : BM, bn, family == CALM_F32 ? BK : CK, p.tiles_m, p.tiles_n,
-                               p.atomic ? slices_per_out : 1, tiles * gy, tiles * gy, 0, use_ws ? 1 : 0,
-                               wide ? WTHREADS : NTHREADS};
-        return 0;
+
+    p.A = a->A; p.B = a->B; p.C = a->C;
+    p.a_type = a->a_type; p.b_type = a->b_type; p.c_type = a->c_type; p.aux_type = a->aux_type; p.r_type = a->r_type;
+    p.M = a->M; p.N = a->N; p.K = a->K;
+    p.batch1 = a->batch1;
+    p.a_rs = a->a_rs; p.a_cs = a->a_cs; p.a_b0 = a->a_b0; p.a_b1 = a->a_b1;
+    p.b_rs = a->b_rs; p.b_cs = a->b_cs; p.b_b0 = a->b_b0; p.b_b1 = a->b_b1;
+    p.c_rs = a->c_rs; p.c_b0 = a->c_b0; p.c_b1 = a->c_b1;
+    p.alpha = a->alpha; p.inv_scale = a->inv_scale; p.bias = a->bias; p.col_scale = a->col_scale;
+    p.residual = a->residual; p.r_rs = a->r_rs; p.r_b0 = a->r_b0; p.r_b1 = a->r_b1;
+    p.C_pre = a->C_pre; p.aux = a->aux;
+    p.act = a->act; p.accumulate = a->accumulate;
+    p.n_group = a->n_group;
+    p.reduce_group = a->n_group && a->reduce_batch;
+    for (int g = 0; g < a->n_group; ++g) {
+        p.Ag[g] = a->A_group[g];
+        p.Bg[g] = a->B_group[g];
+        p.Cg[g] = a->C_group[g];
+        p.Sg[g] = a->inv_scale_group[g];
     }
+    {   // vector epilogue: every tensor the epilogue touches addressable in aligned groups of 4 columns
+        auto m4 = [](int64_t x) { return (x & 3) == 0; };
+        bool ev = m4(a->N) && m4(a->c_rs) && m4(a->c_b0) && m4(a->c_b1) && aligned16(a->C) &&
+                  (!a->C_pre || aligned16(a->C_pre)) && (!a->aux || aligned16(a->aux)) &&
+                  (!a->bias || aligned16(a->bias)) && (!a->col_scale || aligned16(a->col_scale)) &&
+                  (!a->residual || (aligned16(a->residual) && m4(a->r_rs) && m4(a->r_b0) && m4(a->r_b1)));
+        for (int g = 0; g < a->n_group; ++g) ev = ev && (!a->C_group[g] || aligned16(a->C_group[g]));
+        p.epi_vec = ev && CALM_GEMM_VEC_EPILOGUE;
+    }
+    if (fp8) return plan_fp8(a, p, d);
+
+    const bool akc = a->a_cs == 1, bkc = a->b_cs == 1;
+    // 16-byte staging vectors hold 4 fp32 or 8 bf16 elements: sizes / strides of an operand must be multiples of that
+    const int64_t ea = a->a_type == CALM_ST_BF16 ? 7 : 3, eb = a->b_type == CALM_ST_BF16 ? 7 : 3;
+    auto mult = [](int64_t x, int64_t mask) { return (x & mask) == 0; };
+    bool vec = aligned16(a->A) && aligned16(a->B) && mult(a->a_b0, ea) && mult(a->a_b1, ea) && mult(a->b_b0, eb) &&
+               mult(a->b_b1, eb);
+    for (int g = 0; g < a->n_group; ++g) vec = vec && aligned16(a->A_group[g]) && aligned16(a->B_group[g]);
+    vec = vec && (akc ? (mult(a->K, ea) && mult(a->a_rs, ea)) : (mult(a->M, ea) && mult(a->a_cs, ea)));
+    vec = vec && (bkc ? (mult(a->K, eb) && mult(a->b_rs, eb)) : (mult(a->N, eb) && mult(a->b_cs, eb)));
+    // bf16-operand kernels need the 16-byte staging path; anything else runs on the exact fp32 kernels — which
+    // only read fp32 tensors: a bf16 tensor in a launch that cannot be vectorised is the caller's layout error
+    if (!vec && any_bf16_tensor) return CALM_E_LAYOUT;
+    const int dtype = vec ? a->dtype : CALM_F32;
+    if (dtype == CALM_BF16 && a->a_type == CALM_ST_BF16 && a->b_type == CALM_ST_BF16 && pipe_enabled()) {
+        const int rc = plan_pipe(a, p, d, false);
+        if (rc != PIPE_DECLINED) return rc;
+    }
+    if (vec && a->dtype == CALM_F32 && !any_bf16_tensor && (pipe32_mode() == 1 || (pipe32_mode() == 2 && akc && bkc))) {
+        const int rc = plan_pipe(a, p, d, true);
+        if (rc != PIPE_DECLINED) return rc;
+    }
+    return plan_tiles(a, p, d, dtype, vec);
+}
+
+// The only place a calm_gemm_plan is built.
+calm_gemm_plan to_plan(const GemmP& p, const Decomp& d, bool use_ws) {
+    calm_gemm_plan r{d.family, 0, 0, 0, p.tiles_m, p.tiles_n, d.slices_per_out, (int32_t)d.items,
+                     (int32_t)(d.grid.x * d.grid.y), 0, use_ws ? 1 : 0, 0};
+    switch (d.family) {
+    case FAM_F32:       r.tile_m = BM;  r.tile_n = d.bn; r.tile_k = BK; r.threads = NTHREADS; break;
+    case FAM_BF16:      r.tile_m = BM;  r.tile_n = d.bn; r.tile_k = CK; r.threads = NTHREADS; break;
+    case FAM_BF16_WIDE: r.tile_m = WBM; r.tile_n = WBN;  r.tile_k = CK; r.threads = WTHREADS; break;
+    case FAM_FP8:       r.tile_m = WBM; r.tile_n = WBN;  r.tile_k = 64; r.threads = WTHREADS; break;
+    default:            // FAM_PIPE, FAM_PIPE32
+        r.tile_m = 64 * d.mt; r.tile_n = 32 * d.nt; r.tile_k = d.family == FAM_PIPE32 ? 32 : 64; r.threads = 512;
+        r.epi_unit = p.epi_unit;
+    }
+    return r;
+}
+
+int launch_main(const GemmP& p, const Decomp& d, hipStream_t s) {
+    const bool akc = p.a_cs == 1, bkc = p.b_cs == 1;
+    switch (d.family) {
+    case FAM_F32:       return launch_f32(p, d.grid, d.bn, akc, bkc, d.vec, s);
+    case FAM_BF16:      return launch_bf16(p, d.grid, d.bn, akc, bkc, d.npass, s);
+    case FAM_BF16_WIDE: return launch_bf16_wide(p, d.grid, akc, bkc, s);
+    case FAM_FP8:       return launch_fp8(p, d.grid, s);
+    case FAM_PIPE:
+        return (akc && bkc ? launch_pipe_kk : akc ? launch_pipe_km : launch_pipe_mm)(p, d.mt, d.nt, d.grid.x, s);
+    default:            // FAM_PIPE32
+        return (akc && bkc ? launch_pipe32_kk : akc ? launch_pipe32_km : launch_pipe32_mm)(p, d.mt, d.nt, d.grid.x, s);
+    }
+}
+
+}  // namespace
+
+extern "C" int calm_gemm(const calm_gemm_args* a, void* stream) {
+    GemmP p{};
+    Decomp d;
+    int rc = plan_gemm(a, p, d);
+    if (rc) return rc;
+    hipStream_t s = as_stream(stream);
+    const bool use_ws = uses_workspace(a, d);
     if (use_ws) {
         p.ws = (float*)a->workspace;
     } else if (p.atomic && !a->accumulate) {
-        for (int g = 0; g < n_out; ++g) {
+        for (int g = 0; g < d.n_out; ++g) {
             float* out = (float*)(p.slices_per_batch ? p.Cg[g] : p.C);
             hipError_t e;
             if (a->c_rs == a->N) e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)a->M * a->N, s);
@@ -520,27 +525,22 @@ static int gemm_run(const calm_gemm_args* a, void* stream, int64_t* query, calm_
             if (e != hipSuccess) return (int)e;
         }
     }
-
-    auto launch_main = [&]() -> int {
-        if (wide) return launch_bf16_wide(p, grid, akc, bkc, s);
-        if (family == CALM_BF16) return launch_bf16(p, grid, bn, akc, bkc, 1, s);
-        if (family == CALM_BF16X3) return launch_bf16(p, grid, bn, akc, bkc, 3, s);
-        return launch_f32(p, grid, bn, akc, bkc, vec, s);
-    };
-    const int rc = launch_main();
+#ifdef CALM_PIPE_STAMP
+    if ((d.family == FAM_PIPE || d.family == FAM_PIPE32) && !p.atomic && a->workspace &&
+        a->workspace_bytes >= 256 * 2 * 8 * 4 * 8)
+        p.ws = (float*)a->workspace;                    // diagnostic build: stamps
+#endif
+    rc = launch_main(p, d, s);
     if (rc || !use_ws) return rc;
-
     ReduceP q;
-    q.ws = p.ws; q.ws_slice = p.ws_slice; q.nslices = slices_per_out;
+    q.ws = p.ws; q.ws_slice = p.ws_slice; q.nslices = d.slices_per_out;
     q.C = (float*)p.C; q.c_b0 = a->c_b0; q.c_rs = a->c_rs;
     for (int g = 0; g < 4; ++g) q.Cg[g] = p.slices_per_batch ? (float*)p.Cg[g] : nullptr;
     q.M = a->M; q.N = a->N; q.accumulate = a->accumulate;
-    launch_splitk_reduce(q, n_out, s);
+    launch_splitk_reduce(q, d.n_out, s);
     CALM_LAUNCH_CHECK();
     return 0;
 }
-
-extern "C" int calm_gemm(const calm_gemm_args* a, void* stream) { return gemm_run(a, stream, nullptr); }
 
 extern "C" int calm_gemm_set_option(int32_t option, int32_t value) {
     if (option != CALM_GEMM_OPT_PIPE && option != CALM_GEMM_OPT_PIPE32 && option != CALM_GEMM_OPT_DETERMINISTIC)
@@ -551,10 +551,15 @@ extern "C" int calm_gemm_set_option(int32_t option, int32_t value) {
 
 extern "C" int calm_gemm_describe(const calm_gemm_args* a, calm_gemm_plan* plan) {
     if (!plan) return CALM_E_INVAL;
-    return gemm_run(a, nullptr, nullptr, plan);
+    GemmP p{};
+    Decomp d;
+    const int rc = plan_gemm(a, p, d);
+    if (rc == 0) *plan = to_plan(p, d, uses_workspace(a, d));
+    return rc;
 }
 
 extern "C" int64_t calm_gemm_workspace_bytes(const calm_gemm_args* a) {
-    int64_t bytes = 0;
-    return gemm_run(a, nullptr, &bytes) == 0 ? bytes : 0;
+    GemmP p{};
+    Decomp d;
+    return plan_gemm(a, p, d) == 0 ? d.ws_need : 0;
 }

@@ -99,3 +99,71 @@ def test_host_side_planning_entry_points_answer_without_a_gpu():
     g.dtype, g.a_type, g.b_type, g.c_type = 0, 0, 0, 0          # the same product on fp32 tensors: 128-row tiles
     assert lib.calm_gemm_describe(ctypes.byref(g), ctypes.byref(plan)) == 0
     assert plan.family == 0 and plan.tile_m == 128 and plan.tile_n in (96, 128)
+
+
+def test_gemm_workspace_bytes_and_describe_report_one_plan():
+    """calm_gemm_workspace_bytes and calm_gemm_describe read the same plan as the launch.  Over a seeded sweep of argument
+    sets (every option setting, operand layout and storage type, batches, groups, batch-reduced and k-split launches,
+    epilogue operands): an error asks for no workspace; the workspace is whole fp32 partial tiles and is asked for only
+    in deterministic mode or from CALM_GEMM_WS_MIN_SLICES (48) k-slices per output; describe uses exactly the bytes asked
+    for (not 4 fewer); the persistent families launch min(items, 256) workgroups, the others one per item."""
+    import random
+    sys.path.insert(0, ROOT)
+    from importlib import import_module
+    binding = import_module("calm_vit_dte_amd._lib")
+    lib = binding.load()
+    rng = random.Random(1234)
+    sizes = (57344, 20480, 1344, 672, 528, 480, 384, 240, 224, 176, 80, 1, 3, 100, 1000)
+    types = ((0, 0, 0, 0), (1, 0, 0, 0), (2, 0, 0, 0), (1, 1, 1, 0), (1, 1, 1, 1), (1, 2, 2, 1), (1, 3, 2, 0))
+    addr = iter(range(1 << 32, 1 << 56, 1 << 20))                  # fake device addresses: describe never reads them
+    ptr = lambda: next(addr) + (4 if rng.random() < 0.03 else 0)  # noqa: E731
+    opt_pipe, opt_pipe32, opt_det = 0, 1, 2                         # CALM_GEMM_OPT_*
+    saved = [lib.calm_gemm_set_option(o, 0) for o in (opt_pipe, opt_pipe32, opt_det)]
+    families, with_ws = set(), 0
+    try:
+        for _ in range(4000):
+            det = rng.randint(0, 1)
+            for o, v in ((opt_pipe, rng.randint(0, 1)), (opt_pipe32, rng.randint(0, 2)), (opt_det, det)):
+                lib.calm_gemm_set_option(o, v)
+            g = binding.GemmArgs()
+            M, N, K = g.M, g.N, g.K = [rng.choice(sizes) for _ in range(3)]
+            g.dtype, g.a_type, g.b_type, g.c_type = rng.choice(types)
+            g.A, g.B, g.C, g.a_dq, g.b_dq = ptr(), ptr(), ptr(), ptr(), ptr()
+            g.a_rs, g.a_cs = (K, 1) if rng.random() < 0.6 else (1, M)
+            g.b_rs, g.b_cs = (K, 1) if rng.random() < 0.6 else (1, N)
+            g.c_rs = N
+            g.batch0 = g.batch1 = 1
+            if rng.random() < 0.3:
+                g.n_group = g.batch0 = rng.randint(1, 4)
+                for i in range(g.n_group):
+                    g.A_group[i], g.B_group[i], g.C_group[i] = ptr(), ptr(), ptr()
+            elif rng.random() < 0.3:
+                g.batch0 = rng.choice((2, 8, 64))
+            g.a_b0, g.b_b0, g.c_b0 = M * K, N * K, M * N
+            g.reduce_batch = int(rng.random() < 0.2)
+            g.split_k = rng.choice((0, 0, 1, 2, 64))
+            g.bias = ptr() if rng.random() < 0.2 else None
+            g.accumulate = int(rng.random() < 0.2)
+            g.alpha = 1.0
+            plan = binding.GemmPlan()
+            rc = lib.calm_gemm_describe(ctypes.byref(g), ctypes.byref(plan))
+            need = int(lib.calm_gemm_workspace_bytes(ctypes.byref(g)))
+            if rc != 0:
+                assert need == 0
+                continue
+            families.add(plan.family)
+            assert need >= 0 and need % (4 * M * N) == 0, (need, M, N)
+            assert need == 0 or det or plan.k_slices >= 48, (need, plan.k_slices)
+            assert plan.grid == (min(plan.items, 256) if plan.family in (3, 4) else plan.items)
+            assert plan.uses_workspace == 0                              # none offered
+            if need:
+                with_ws += 1
+                g.workspace, g.workspace_bytes = 1 << 60, need - 4
+                assert lib.calm_gemm_describe(ctypes.byref(g), ctypes.byref(plan)) == 0 and plan.uses_workspace == 0
+            g.workspace, g.workspace_bytes = 1 << 60, need
+            assert lib.calm_gemm_describe(ctypes.byref(g), ctypes.byref(plan)) == 0
+            assert plan.uses_workspace == (need > 0)
+    finally:
+        for o, v in zip((opt_pipe, opt_pipe32, opt_det), saved):
+            lib.calm_gemm_set_option(o, v)
+    assert families == {0, 1, 2, 3, 4, 5} and with_ws > 100, (families, with_ws)        # the sweep reaches every case
