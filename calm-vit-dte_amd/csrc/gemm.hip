@@ -1,6 +1,6 @@
 // calm_gemm: strided / batched / grouped / split-K GEMM with fused epilogue for gfx950 — the dispatcher.
 // Six kernel families, numbered as calm_gemm_plan::family in include/calm_vit.h:
-//   0 exact fp32 MFMA, 128-row tiles (gemm_f32.hip)           3 bf16 pipelined persistent (gemm_bf16p.h)
+//   0 exact fp32 MFMA, 128- or 64-row tiles (gemm_f32.hip)    3 bf16 pipelined persistent (gemm_bf16p.h)
 //   1 bf16-operand, 128-row tiles (gemm_bf16.hip)             4 fp32 pipelined persistent (gemm_bf16p.h; opt-in)
 //   2 bf16-operand, 256x128 tiles (gemm_bf16.hip)             5 fp8 operands (gemm_fp8.hip)
 // Families 0-2 share tiling, remap, split logic and epilogue (gemm_common.h).  plan_gemm() decides a launch once and has
@@ -94,7 +94,8 @@ enum : int { FAM_F32 = 0, FAM_BF16 = 1, FAM_BF16_WIDE = 2, FAM_PIPE = 3, FAM_PIP
 struct Decomp {
     int family = FAM_F32;
     int mt = 0, nt = 0;              // pipelined families: (64 mt) x (32 nt) tiles
-    int bn = 0;                      // 128-row and 256x128 tiles: N tile (96 / 128)
+    int bn = 0;                      // 128-row and 256x128 tiles: N tile (96 / 128); 64-row tiles: 16 nb
+    int nb64 = 0;                    // fp32 64-row tiles: N tile / 16 (0: 128-row tiles)
     int npass = 1;                   // bf16-operand 128-row tiles: MFMA passes (3: CALM_BF16X3)
     bool vec = false;                // fp32 128-row tiles: 16-byte operand staging
     long items = 0;                  // tiles x (batch entries or k-slices)
@@ -250,6 +251,24 @@ int plan_pipe(const calm_gemm_args* a, GemmP& p, Decomp& d, bool f32) {
     return 0;
 }
 
+// modelled duration of a 256-thread fp32 launch (cycles of one CU, up to a common factor; the pattern of pipe_cost):
+// `items` workgroups of nk k-blocks, each k-block `rows` live rows (strips past M skip their MFMAs) x `width` columns
+// of MFMA work (x BK x 2 FLOP at 256 FLOP per CU cycle) plus a fixed share (staging, barrier, fragment reads), served
+// ceil(items / 256) deep on the busiest CU at the matrix-pipe efficiency of its resident workgroups (min(slots, items
+// per CU) of them: 0.89 at 4, 0.84 at 3 measured) — or, with too few of them to cover a k-block's memory latency, one
+// exposed latency per k-block and resident round — plus one epilogue per resident round and the combine of the k-slices
+// (atomics or the workspace: `combine` bytes through a chip-wide resource at ~2 TB/s, as in plan_pipe)
+double f32_tile_cost(long items, int nk, double rows, int width, int slots, double combine) {
+    constexpr double KB_FIXED = 192.0, KB_LATENCY = 1100.0, EPILOGUE = 1500.0;
+    const long per_cu = (items + 255) / 256;
+    const double resident = (double)(per_cu < slots ? per_cu : slots);
+    const double kb = rows * width * BK * 2.0 / 256.0 + KB_FIXED;
+    const double mfma = (double)per_cu * nk * kb * (resident + 0.5) / resident;
+    const double rounds = (double)((items + 256L * slots - 1) / (256L * slots));
+    const double lat = rounds * nk * KB_LATENCY;
+    return (mfma > lat ? mfma : lat) + rounds * EPILOGUE + combine / 1000.0;
+}
+
 // ---- 256-thread families: 128-row tiles (0, 1) and 256x128 tiles (2) ----------------------------------------------------
 // dtype: the matrix pipe the kernels run (CALM_F32 for a launch that cannot be vectorised)
 int plan_tiles(const calm_gemm_args* a, GemmP& p, Decomp& d, int dtype, bool vec) {
@@ -302,71 +321,130 @@ int plan_tiles(const calm_gemm_args* a, GemmP& p, Decomp& d, int dtype, bool vec
     // k-slices of a split launch: one resident round of workgroups (256 CUs x 5 for the 96-wide tile, x 4 for the
     // 128-wide one; A/B over the weight-gradient shapes: -3% time against 768, -12% on 1344x672)
     const int split_slots = wide ? 256 * 2 : bn == 96 ? 256 * CALM_GEMM_WAVES96 : 256 * CALM_GEMM_WAVES;
-    int nsplit = 1;
-    p.atomic = 0;
-    p.slices_per_batch = 0;
-    if (group_split) {
-        nsplit = split_slots / (tiles * batch);
-        const int max_split = (p.kpb + 15) / 16;
-        if (nsplit > max_split) nsplit = max_split;
-        if (nsplit < 1) nsplit = 1;
-        p.kb_total = batch * p.kpb;
-        if (nsplit > 1) {
+    if (k_split && !group_split && !a->reduce_batch && batch != 1) return CALM_E_UNSUPP;
+    // k-slices per output for `ntiles` output tiles and `slots` workgroup slots; min_kb: fewest k-blocks per slice
+    auto split_count = [&](int ntiles, int slots, int min_kb) {
+        int nsplit = 1;
+        if (group_split) {
+            nsplit = slots / (ntiles * batch);
+            const int max_split = (p.kpb + min_kb - 1) / min_kb;
+            if (nsplit > max_split) nsplit = max_split;
+        } else if (a->reduce_batch && !grouped_reduce_unsplit) {
+            nsplit = a->split_k > 1 ? a->split_k : slots / ntiles;
+            const int max_split = (batch * p.kpb + 7) / 8;
+            if (nsplit > max_split) nsplit = max_split;
+            // every slice adds its whole tile onto the SAME output with atomics: beyond about one workgroup per CU the
+            // contention costs more than the shorter slices save (scripts/ab_reduce_split.py, 256 images: 80x176x528 51.6 us
+            // at 512 slices, 33.4 at 128; 224x176x528 69.7 -> 56.5; 128x80x240 24.4 -> 19.7)
+            // (measured on the bf16-operand kernels; the fp32 kernels, 16x slower per k-block, keep their full round of slices)
+            if (a->split_k <= 1 && dtype == CALM_BF16) {
+                const int cap = ntiles == 1 ? 128 : 256 / ntiles;
+                if (nsplit > cap) nsplit = cap;
+            }
+        } else if (k_split) {
+            nsplit = a->split_k > 1 ? a->split_k : slots / ntiles;
+            const int max_split = (p.kpb + min_kb - 1) / min_kb;
+            if (nsplit > max_split) nsplit = max_split;
+            // small outputs (the 128-row kernels' share of the weight gradients): every slice adds its tiles onto the same
+            // output — about one workgroup per CU is the optimum (264 x 240 x 45056: 41.9 us at 88 slices, 29.7 at 32)
+            // (bf16-operand kernels only: as above)
+            if (a->split_k <= 1 && dtype == CALM_BF16 && !wide && nsplit > 256 / ntiles) nsplit = 256 / ntiles;
+        }
+        return nsplit < 1 ? 1 : nsplit;
+    };
+    // p.atomic, p.slices_per_batch, p.kb_total and p.kb_per_z of `nsplit` k-slices per output; returns grid.y
+    auto apply_split = [&](int nsplit) {
+        p.atomic = 0;
+        p.slices_per_batch = 0;
+        if (group_split) {
+            p.kb_total = batch * p.kpb;
+            if (nsplit > 1) {
+                p.atomic = 1;
+                p.slices_per_batch = nsplit;
+            }
+        } else if (grouped_reduce_unsplit) {
+            p.kb_total = batch * p.kpb;                     // one k-range over all groups, plain epilogue
+        } else if (a->reduce_batch) {
             p.atomic = 1;
-            p.slices_per_batch = nsplit;
+            p.kb_total = batch * p.kpb;
+        } else if (k_split) {
+            p.kb_total = p.kpb;
+            p.atomic = nsplit > 1;
+        } else {
+            p.kb_total = batch * p.kpb;
         }
-    } else if (grouped_reduce_unsplit) {
-        p.kb_total = batch * p.kpb;                         // one k-range over all groups, plain epilogue
-    } else if (a->reduce_batch) {
-        p.atomic = 1;
-        p.kb_total = batch * p.kpb;
-        nsplit = a->split_k > 1 ? a->split_k : split_slots / tiles;
-        const int max_split = (p.kb_total + 7) / 8;
-        if (nsplit > max_split) nsplit = max_split;
-        // every slice adds its whole tile onto the SAME output with atomics: beyond about one workgroup per CU the
-        // contention costs more than the shorter slices save (scripts/ab_reduce_split.py, 256 images: 80x176x528 51.6 us
-        // at 512 slices, 33.4 at 128; 224x176x528 69.7 -> 56.5; 128x80x240 24.4 -> 19.7)
-        // (measured on the bf16-operand kernels; the fp32 kernels, 16x slower per k-block, keep their full round of slices)
-        if (a->split_k <= 1 && dtype == CALM_BF16) {
-            const int cap = tiles == 1 ? 128 : 256 / tiles;
-            if (nsplit > cap) nsplit = cap;
+        if (p.slices_per_batch) {
+            p.kb_per_z = (p.kpb + nsplit - 1) / nsplit;
+            p.slices_per_batch = (p.kpb + p.kb_per_z - 1) / p.kb_per_z;      // no empty trailing slices
+        } else if (p.atomic) {
+            p.kb_per_z = (p.kb_total + nsplit - 1) / nsplit;
+        } else if (grouped_reduce_unsplit) {
+            p.kb_per_z = p.kb_total;                        // grid.y == 1
+        } else {
+            p.kb_per_z = p.kpb;   // grid.y == batch
         }
-        if (nsplit < 1) nsplit = 1;
-    } else if (k_split) {
-        if (batch != 1) return CALM_E_UNSUPP;
-        nsplit = a->split_k > 1 ? a->split_k : split_slots / tiles;
-        const int max_split = (p.kpb + 15) / 16;
-        if (nsplit > max_split) nsplit = max_split;
-        // small outputs (the 128-row kernels' share of the weight gradients): every slice adds its tiles onto the same
-        // output — about one workgroup per CU is the optimum (264 x 240 x 45056: 41.9 us at 88 slices, 29.7 at 32)
-        // (bf16-operand kernels only: as above)
-        if (a->split_k <= 1 && dtype == CALM_BF16 && !wide && nsplit > 256 / tiles) nsplit = 256 / tiles;
-        if (nsplit < 1) nsplit = 1;
-        p.kb_total = p.kpb;
-        p.atomic = nsplit > 1;
-    } else {
-        p.kb_total = batch * p.kpb;
+        return p.slices_per_batch ? batch * p.slices_per_batch : (p.kb_total + p.kb_per_z - 1) / p.kb_per_z;
+    };
+    int nsplit = split_count(tiles, split_slots, 16);
+    int gy = apply_split(nsplit);
+    int nb64 = 0;
+#if CALM_GEMM_F32_TILE64
+    // fp32 pipe: the 128-row plan above against 64 x (16 nb) tiles, nb = 3..8, by modelled launch time (f32_tile_cost);
+    // a k-split launch recomputes its slice count for the smaller tile (one or two resident rounds, >= 4 k-blocks each).
+    // Launches whose 128-row plan combines its slices through the workspace (plan_combine) keep that plan.
+    const int per_out = p.slices_per_batch ? p.slices_per_batch : gy;
+    const bool ws_plan = p.atomic && per_out >= CALM_GEMM_WS_MIN_SLICES && (long)a->M * a->N >= 100000;
+    if (dtype == CALM_F32 && (!ws_plan || CALM_GEMM_F32_TILE64 == 2)) {
+        const bool auto_split = (group_split || (a->reduce_batch && !grouped_reduce_unsplit) || k_split) && a->split_k <= 1;
+        auto cost_of = [&](int tiles_m, int tiles_n, int rows_live, int width, int slots, int y) {
+            const long items = (long)tiles_m * tiles_n * y;
+            const double comb = p.atomic ? 4.0 * a->M * a->N * y : 0.0;
+            return f32_tile_cost(items, p.kb_per_z, (double)rows_live / tiles_m, width, slots, comb);
+        };
+        const int gran = bn == 128 ? 64 : 32;               // the 128-row tiles skip the MFMAs of whole wave strips
+        double best = CALM_GEMM_F32_TILE64 == 2 ? 1e300 :
+                      cost_of(p.tiles_m, p.tiles_n, (a->M + gran - 1) / gran * gran, bn,
+                              bn == 96 ? CALM_GEMM_WAVES96 : CALM_GEMM_WAVES, gy);
+        int best_split = nsplit;
+        const int tm64 = (a->M + 63) / 64, rows64 = (a->M + 15) / 16 * 16;
+        for (int nb = 3; nb <= 8; ++nb) {
+            const int tn64 = (a->N + 16 * nb - 1) / (16 * nb);
+            const int slots = waves64(nb);
+            int cand[3] = {split_count(tm64 * tn64, 256 * slots, 16), 0, 0};
+            if (auto_split) {
+                cand[1] = split_count(tm64 * tn64, 256 * slots, 4);
+                cand[2] = split_count(tm64 * tn64, 2 * 256 * slots, 4);
+            }
+            for (int ns : cand) {
+                if (ns < 1) continue;
+                const int y = apply_split(ns);
+                const double c = cost_of(tm64, tn64, rows64, 16 * nb, slots, y);
+                if (y <= 65535 && c < best) {
+                    best = c;
+                    nb64 = nb;
+                    best_split = ns;
+                }
+            }
+        }
+        if (nb64) {
+            bn = 16 * nb64;
+            p.tiles_m = tm64;
+            p.tiles_n = (a->N + bn - 1) / bn;
+        }
+        nsplit = best_split;
+        gy = apply_split(nsplit);
     }
+#endif
     if (p.atomic && a->c_type != CALM_ST_F32) return CALM_E_UNSUPP;            // k-slices combine in fp32
-    if (p.slices_per_batch) {
-        p.kb_per_z = (p.kpb + nsplit - 1) / nsplit;
-        p.slices_per_batch = (p.kpb + p.kb_per_z - 1) / p.kb_per_z;      // no empty trailing slices
-    } else if (p.atomic) {
-        if (!trivial_epi) return CALM_E_UNSUPP;
-        p.kb_per_z = (p.kb_total + nsplit - 1) / nsplit;
-    } else if (grouped_reduce_unsplit) {
-        p.kb_per_z = p.kb_total;                            // grid.y == 1
-    } else {
-        p.kb_per_z = p.kpb;   // grid.y == batch
-    }
-    const int gy = p.slices_per_batch ? batch * p.slices_per_batch : (p.kb_total + p.kb_per_z - 1) / p.kb_per_z;
+    if (p.atomic && !p.slices_per_batch && !trivial_epi) return CALM_E_UNSUPP;
     if (gy > 65535) return CALM_E_UNSUPP;
     d.family = wide ? FAM_BF16_WIDE : dtype == CALM_F32 ? FAM_F32 : FAM_BF16;
     d.bn = bn;
+    d.nb64 = nb64;
     d.npass = dtype == CALM_BF16X3 ? 3 : 1;
     d.vec = vec;
-    d.items = tiles * gy;
-    d.grid = dim3(tiles, gy);
+    d.items = (long)p.tiles_m * p.tiles_n * gy;
+    d.grid = dim3(p.tiles_m * p.tiles_n, gy);
     plan_combine(a, p, d, gy);
     return 0;
 }
@@ -480,7 +558,7 @@ calm_gemm_plan to_plan(const GemmP& p, const Decomp& d, bool use_ws) {
     calm_gemm_plan r{d.family, 0, 0, 0, p.tiles_m, p.tiles_n, d.slices_per_out, (int32_t)d.items,
                      (int32_t)(d.grid.x * d.grid.y), 0, use_ws ? 1 : 0, 0};
     switch (d.family) {
-    case FAM_F32:       r.tile_m = BM;  r.tile_n = d.bn; r.tile_k = BK; r.threads = NTHREADS; break;
+    case FAM_F32:       r.tile_m = d.nb64 ? 64 : BM; r.tile_n = d.bn; r.tile_k = BK; r.threads = NTHREADS; break;
     case FAM_BF16:      r.tile_m = BM;  r.tile_n = d.bn; r.tile_k = CK; r.threads = NTHREADS; break;
     case FAM_BF16_WIDE: r.tile_m = WBM; r.tile_n = WBN;  r.tile_k = CK; r.threads = WTHREADS; break;
     case FAM_FP8:       r.tile_m = WBM; r.tile_n = WBN;  r.tile_k = 64; r.threads = WTHREADS; break;
@@ -494,7 +572,8 @@ calm_gemm_plan to_plan(const GemmP& p, const Decomp& d, bool use_ws) {
 int launch_main(const GemmP& p, const Decomp& d, hipStream_t s) {
     const bool akc = p.a_cs == 1, bkc = p.b_cs == 1;
     switch (d.family) {
-    case FAM_F32:       return launch_f32(p, d.grid, d.bn, akc, bkc, d.vec, s);
+    case FAM_F32:
+        return d.nb64 ? launch_f32_t64(p, d.grid, d.nb64, akc, bkc, d.vec, s) : launch_f32(p, d.grid, d.bn, akc, bkc, d.vec, s);
     case FAM_BF16:      return launch_bf16(p, d.grid, d.bn, akc, bkc, d.npass, s);
     case FAM_BF16_WIDE: return launch_bf16_wide(p, d.grid, akc, bkc, s);
     case FAM_FP8:       return launch_fp8(p, d.grid, s);

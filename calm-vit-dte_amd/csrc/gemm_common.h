@@ -22,6 +22,17 @@ constexpr int WTHREADS = 512, WBM = 256, WBN = 128;     // its wide tile
 #ifndef CALM_GEMM_WAVES96
 #define CALM_GEMM_WAVES96 5      // 128x96 tile: B image at its own row stride (29.7 KB LDS) and <=96 VGPRs -> 5 workgroups per CU (A/B -1.3% time)
 #endif
+// 64-row fp32 tiles (64 x 16 nb, v_mfma_f32_16x16x4_f32) beside the 128-row ones, chosen per launch by plan_tiles:
+// 0 builds the library with the 128-row tiles only (A/B runs), 2 takes the 64-row tile for every fp32 launch
+// (calibration sweeps)
+#ifndef CALM_GEMM_F32_TILE64
+#define CALM_GEMM_F32_TILE64 1
+#endif
+#ifndef CALM_GEMM_WAVES64
+#define CALM_GEMM_WAVES64 6      // 64-row tiles: <=80 VGPRs; LDS (16-25 KB up to 112 columns) allows 6 per CU
+#endif
+// ... except the 128-wide one, which spills at 80 VGPRs: 5 (<=96)
+constexpr int waves64(int nb) { return nb == 8 ? 5 : CALM_GEMM_WAVES64; }
 #ifndef CALM_GEMM_VEC_EPILOGUE
 #define CALM_GEMM_VEC_EPILOGUE 1     // 0: always the one-element-per-access epilogue (A/B runs)
 #endif
@@ -331,6 +342,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x16 (&acc)[MT][
 
 // launchers of the kernel families (defined in gemm_f32.hip / gemm_bf16.hip)
 int launch_f32(const GemmP& p, dim3 grid, int bn, bool akc, bool bkc, bool vec, hipStream_t s);
+int launch_f32_t64(const GemmP& p, dim3 grid, int nb, bool akc, bool bkc, bool vec, hipStream_t s);    // 64 x 16 nb tiles
 int launch_bf16(const GemmP& p, dim3 grid, int bn, bool akc, bool bkc, int npass, hipStream_t s);
 int launch_bf16_wide(const GemmP& p, dim3 grid, bool akc, bool bkc, hipStream_t s);
 int launch_fp8(const GemmP& p, dim3 grid, hipStream_t s);           // gemm_fp8.hip

@@ -150,7 +150,8 @@ int calm_gemm_set_option(int32_t option, int32_t value);
 /* ABI v7 — what calm_gemm would launch for `args` (nothing is enqueued): kernel family, tile, work decomposition.
  * Diagnostic surface: tests use it to map a wrong output element back to (tile, persistent workgroup, XCD, wave,
  * 16-row strip) — see tests/locate.py — and the bench to label its per-shape table.
- *   family  0 fp32 128-row tiles (gemm_f32_kernel)        3 bf16 pipelined persistent (gemm_bf16p_kernel)
+ *   family  0 fp32 tiles, 128-row or 64-row               3 bf16 pipelined persistent (gemm_bf16p_kernel)
+ *             (gemm_f32_kernel / gemm_f32_t64_kernel)
  *           1 bf16-operand 128-row tiles                   4 fp32 pipelined persistent (gemm_f32p_kernel)
  *           2 bf16-operand 256x128 tiles                   5 fp8
  *   items = tiles_m * tiles_n * (batch entries or k-slices); the persistent families launch min(items, 256) workgroups
