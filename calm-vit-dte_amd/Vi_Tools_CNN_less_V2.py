@@ -303,6 +303,8 @@ class VMLA_Block(torch.nn.Module):
             k = ops.RopeFn.apply(None, kz, self.rope_k.inv_freq, H, a16)
         m0, m2 = self.linear_mask[0], self.linear_mask[2]
         attention = ops.LatentMaskAttention16Fn if a16 else ops.LatentMaskAttentionFn
+        if not a16 and ops.use_attention_lse(q.shape[1], k.shape[1], H, self.head_dim):
+            attention = ops.LatentMaskAttentionLseFn                     # row-LSE mode: no saved probabilities
         x = attention.apply(                                             # 288-299
             q, k, v, m0.weight_orig, m0.bias, m2.weight_orig, m2.bias,
             m0.weight_u, m0.weight_v, m0.sigma(), m2.weight_u, m2.weight_v, m2.sigma(), H)

@@ -45,6 +45,33 @@ def get_matmul_precision():
     return _precision
 
 
+# What the fp32 attention keeps for its backward: "probs" = the probabilities P [B,H,Sq,Skv] (default), "lse" = the row
+# log-sum-exp [B,H,Sq]; the backward then rebuilds P in a transient scratch (ops.LatentMaskAttentionLseFn).
+ATTENTION_STORAGES = ("probs", "lse")
+
+
+def _check_attention_storage(name):
+    if name not in ATTENTION_STORAGES:
+        raise ValueError(f"unknown attention storage {name!r}; choose from {sorted(ATTENTION_STORAGES)}")
+    return name
+
+
+_attention_storage = _check_attention_storage(os.environ.get("CALM_ATTN_STORAGE") or "probs")   # read once, at import
+
+
+def set_attention_storage(name):
+    """'probs' the fp32 attention saves its probabilities for the backward (default)
+    'lse'   it saves the row log-sum-exp instead and the backward recomputes the probabilities: less memory held
+            between forward and backward, one more Q K^T per head in the backward.  Shapes without a fused kernel
+            (HipBackend.attn_fwd_supported) and the bf16 attention are unaffected."""
+    global _attention_storage
+    _attention_storage = _check_attention_storage(name)
+
+
+def get_attention_storage():
+    return _attention_storage
+
+
 def effective_precision():
     """The pipe a GEMM issued now runs on.  Inside `torch.autocast("cuda", dtype=torch.bfloat16)` — how the reference
     trainer calls the model (distributed_trainer_cls.py:84-85) — Linear/matmul operands are rounded to bf16 with fp32
@@ -564,6 +591,25 @@ class HipBackend:
         _lib.check(self.lib.calm_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(dout), _ptr(P), _ptr(dS), _ptr(dq),
                                                _ptr(dk), _ptr(dv), _ptr(dM), B, Sq, Skv, H, hd, _stream()),
                    "calm_attention_bwd")
+
+    def attn_fwd_lse(self, q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, lse, B, Sq, Skv, H, hd):
+        _lib.check(self.lib.calm_attention_fwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(w1), _ptr(b1), _ptr(s1), _ptr(w2),
+                                                   _ptr(b2), _ptr(s2), _ptr(out), _ptr(R), _ptr(hp), _ptr(hg),
+                                                   _ptr(Mk), _ptr(lse), B, Sq, Skv, H, hd, _stream()),
+                   "calm_attention_fwd_lse")
+
+    def attn_bwd_lse_scratch_bytes(self, B, Sq, Skv, H, hd):
+        """Bytes of scratch attn_bwd_lse needs; 0 = no fused instantiation for the shape."""
+        return int(self.lib.calm_attention_bwd_lse_scratch_bytes(B, Sq, Skv, H, hd))
+
+    def attn_bwd_lse(self, q, k, v, dout, Mk, lse, scratch, dq, dk, dv, dM, B, Sq, Skv, H, hd):
+        """scratch: contiguous CUDA tensor of at least attn_bwd_lse_scratch_bytes(...) bytes (any dtype)."""
+        if scratch is None or not scratch.is_cuda or not scratch.is_contiguous():
+            raise TypeError("attn_bwd_lse: contiguous CUDA scratch tensor expected")
+        _lib.check(self.lib.calm_attention_bwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(dout), _ptr(Mk), _ptr(lse),
+                                                   scratch.data_ptr(), scratch.numel() * scratch.element_size(),
+                                                   _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dM), B, Sq, Skv, H, hd, _stream()),
+                   "calm_attention_bwd_lse")
 
     # ---- the same attention on the bf16 matrix pipe (bf16 pipeline) ----------------------
     def attn16_supported(self, S, H, hd):

@@ -33,6 +33,7 @@ struct AttnFwdP {
     float* R; float* hp; float* hg; float* Mk; float* P;   // saved for backward (P optional)
     int B, Sq, Skv, H, hd;
     float scale;
+    float* lse;                  // [B,H,Sq] row log-sum-exp of the logits (optional; calm_attention_fwd_lse)
 };
 
 constexpr int NV_Q = 1;   // ... for a [16*NW x 16] query chunk
@@ -361,6 +362,8 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
         sum += __shfl_xor(sum, 16, 64);
         sum += __shfl_xor(sum, 32, 64);
         const float inv = 1.0f / sum;
+        // row-LSE mode: what the backward needs to rebuild this row's probabilities (one lane group per query)
+        if (active && p.lse && g == 0) p.lse[((long)b * p.H + h) * p.Sq + iq] = mx + logf(sum);
 #pragma unroll
         for (int t = 0; t < NJ; ++t) accS[t] = accS[t] * inv;
         if (active && p.P) {
@@ -413,9 +416,15 @@ struct AttnBwdP {
     float* dM;                   // [B,Sq,Skv]
     int B, Sq, Skv, H, hd;
     float scale;
+    const float* Mk;             // [B,Sq,Skv] mask  } row-LSE mode only (attn_bwd_q_kernel<.., true>): P is then
+    const float* lse;            // [B,H,Sq]         } scratch that the Q side fills itself before it reads it
 };
 
-template <int NJ, int NW>
+// LSE = true: the forward saved no probabilities.  Each head starts by rebuilding its P rows from q, k, the mask and
+// the row log-sum-exp — S^T = K_h Q_h^T with the forward's staging and MFMA loop, P = exp(scale S + M - lse): no
+// maximum, no sum, no division — and writes them to p.P, where the unchanged body below and the K/V side read them.
+// Only accS is live in that prologue (accD does not exist yet), so the body's register budget is the stored-P one.
+template <int NJ, int NW, bool LSE>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
     constexpr int NTH = 64 * NW;
     constexpr int NV_K = (NJ + NW - 1) / NW;   // float4 per thread for a [16*NJ x 16] chunk
@@ -442,6 +451,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
     const int v_share = (v_total + nchq - 1) / nchq;
 
     const float* dob = p.dout + ((long)b * p.Sq + q0) * D;
+    const float* qb = p.q + ((long)b * p.Sq + q0) * D;
     const float* kb = p.k + (long)b * p.Skv * D;
     const float* vb = p.v + (long)b * p.Skv * D;
 
@@ -454,6 +464,68 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
         const float* doh = dob + h * hd;
         const float* kh = kb + h * hd;
         const float* vh = vb + h * hd;
+        const long prow = (((long)b * p.H + h) * p.Sq + (active ? iq : q0)) * p.Skv;
+        if constexpr (LSE) {
+            const float* qh = qb + h * hd;
+            f32x4v accS[NJ];
+#pragma unroll
+            for (int t = 0; t < NJ; ++t) accS[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+            {
+                Regs<NV_K> rk; Regs<NV_Q> rq;
+                km_load<NTH>(rk, kh, D, SKV, 0, hd);
+                km_load<NTH>(rq, qh, D, nq, 0, hd);
+                km_store<NTH>(rk, bufK(0), LDJ, SKV);
+                km_store<NTH>(rq, bufQ(0), LDQ, nq);
+                __syncthreads();
+#pragma unroll 1
+                for (int c = 0; c < nchq; ++c) {
+                    const int cur = c & 1;
+                    if (c + 1 < nchq) {
+                        km_load<NTH>(rk, kh, D, SKV, 16 * (c + 1), hd);
+                        km_load<NTH>(rq, qh, D, nq, 16 * (c + 1), hd);
+                    }
+                    if (active) {
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) {
+                            const float bq = bufQ(cur)[(4 * s + g) * LDQ + 16 * wave + r16];
+#pragma unroll
+                            for (int t = 0; t < NJ; ++t)
+                                accS[t] = MFMA16(bufK(cur)[(4 * s + g) * LDJ + 16 * t + r16], bq, accS[t]);
+                        }
+                    }
+                    if (c + 1 < nchq) {
+                        km_store<NTH>(rk, bufK(cur ^ 1), LDJ, SKV);
+                        km_store<NTH>(rq, bufQ(cur ^ 1), LDQ, nq);
+                    }
+                    __syncthreads();
+                }
+            }
+            // the logits exactly as the forward rounds them (scale S + M), then exp(. - lse) <= 1 up to rounding
+            const float* Mrow = p.Mk + ((long)b * p.Sq + (active ? iq : q0)) * p.Skv + 4 * g;
+            const float l = p.lse[((long)b * p.H + h) * p.Sq + (active ? iq : q0)];
+            float* Pw = const_cast<float*>(p.P) + prow + 4 * g;
+            constexpr int MG = 4;                              // mask tiles requested four at a time, as P below
+#pragma unroll
+            for (int t0 = 0; t0 < NJ; t0 += MG) {
+                f32x4v m[MG];
+#pragma unroll
+                for (int u = 0; u < MG; ++u)
+                    if (t0 + u < NJ) m[u] = *reinterpret_cast<const f32x4v*>(Mrow + 16 * (t0 + u));
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < MG; ++u) {
+                    if (t0 + u < NJ) {
+                        const int t = t0 + u;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) accS[t][r] = __expf(accS[t][r] * p.scale + m[u][r] - l);
+                        if (active) *reinterpret_cast<f32x4v*>(Pw + 16 * t) = accS[t];
+                    }
+                }
+            }
+            // the body re-reads these rows: same lanes, same addresses, so program order is all it takes — the drain
+            // (and its "memory" clobber) keeps both the compiler and the __restrict__ loads below behind the stores
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
         f32x4v accD[NJ];
 #pragma unroll
         for (int t = 0; t < NJ; ++t) accD[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
@@ -514,7 +586,6 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
         // store of tile t may alias the P load of tile t + 1 and put `s_waitcnt vmcnt(0)` between them (ISA, round 4:
         // 18-24 of the kernel's 26-35 global loads were followed by a full drain) — one exposed L2 round trip per key tile
         // and head.
-        const long prow = (((long)b * p.H + h) * p.Sq + (active ? iq : q0)) * p.Skv;
         const float* __restrict__ Prow = p.P + prow + 4 * g;
         float* __restrict__ dSrow = p.dS + prow + 4 * g;
         // ... and in GROUPS of PG tiles requested together: left to itself the compiler reuses one register quad for all
@@ -670,7 +741,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kv_kernel(const AttnBwdP p) 
     }
 }
 
-template <int NJ, int NW>
+template <int NJ, int NW, bool LSE>
 int launch_bwd(const AttnBwdP& p, hipStream_t s) {
     const int tiles = p.Sq / 16;
     const int TQ = 16 * NW, SKV = 16 * NJ;
@@ -679,14 +750,14 @@ int launch_bwd(const AttnBwdP& p, hipStream_t s) {
     const int hdp = (p.hd + 15) / 16 * 16, LDV = hdp + 4;
     const size_t lds_q = sizeof(float) * (size_t)(32 * LDJ + 32 * LDQ + SKV * LDV);
     const size_t lds_kv = sizeof(float) * (size_t)(SKV * LDV);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<NJ, NW>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<NJ, NW, LSE>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
     if (e != hipSuccess) return (int)e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<NJ, NW>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
     if (e != hipSuccess) return (int)e;
     dim3 grid((tiles + NW - 1) / NW, p.B);
-    hipLaunchKernelGGL((attn_bwd_q_kernel<NJ, NW>), grid, dim3(64 * NW), lds_q, s, p);
+    hipLaunchKernelGGL((attn_bwd_q_kernel<NJ, NW, LSE>), grid, dim3(64 * NW), lds_q, s, p);
     CALM_LAUNCH_CHECK();
     hipLaunchKernelGGL((attn_bwd_kv_kernel<NJ, NW>), grid, dim3(64 * NW), lds_kv, s, p);
     CALM_LAUNCH_CHECK();
@@ -728,6 +799,21 @@ int launch_fwd(const AttnFwdP& p, hipStream_t s) {
     return 0;
 }
 
+int attention_bwd_dispatch(const AttnBwdP& p, bool lse, hipStream_t s) {
+    switch (p.Skv / 16) {
+        // <key tiles, waves per workgroup = pick_waves(Sq/16)>
+#define CALM_ATT_BWD(NJ, NW) case NJ: return lse ? launch_bwd<NJ, NW, true>(p, s) : launch_bwd<NJ, NW, false>(p, s)
+        CALM_ATT_BWD(2, 2);
+        CALM_ATT_BWD(3, 3);
+        CALM_ATT_BWD(5, 5);
+        CALM_ATT_BWD(8, 8);
+        CALM_ATT_BWD(11, ATT_NW11);
+        CALM_ATT_BWD(14, ATT_NW14);
+#undef CALM_ATT_BWD
+    }
+    return CALM_E_UNSUPP;
+}
+
 }  // namespace
 
 extern "C" {
@@ -745,15 +831,15 @@ int calm_attention_fwd_supported(int32_t Sq, int32_t Skv, int32_t H, int32_t hd)
     return 1;
 }
 
-int calm_attention_fwd(const float* q, const float* k, const float* v, const float* w1, const float* b1,
-                       const float* s1, const float* w2, const float* b2, const float* s2, float* out, float* R,
-                       float* hp, float* hg, float* Mk, float* P, int32_t B, int32_t Sq, int32_t Skv, int32_t H, int32_t hd,
-                       void* stream) {
+namespace {
+int attention_fwd(const float* q, const float* k, const float* v, const float* w1, const float* b1, const float* s1,
+                  const float* w2, const float* b2, const float* s2, float* out, float* R, float* hp, float* hg, float* Mk,
+                  float* P, float* lse, int32_t B, int32_t Sq, int32_t Skv, int32_t H, int32_t hd, void* stream) {
     if (!q || !k || !v || !w1 || !b1 || !s1 || !w2 || !b2 || !s2 || !out || !R || !hp || !hg || !Mk || B <= 0)
         return CALM_E_INVAL;
     if (!calm_attention_fwd_supported(Sq, Skv, H, hd)) return CALM_E_UNSUPP;
     if (B > 65535) return CALM_E_UNSUPP;
-    AttnFwdP p{q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, P, B, Sq, Skv, H, hd, 1.0f / sqrtf((float)hd)};
+    AttnFwdP p{q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, P, B, Sq, Skv, H, hd, 1.0f / sqrtf((float)hd), lse};
     hipStream_t s = as_stream(stream);
     switch (Skv / 16) {
         // <key tiles, waves per workgroup = pick_waves(Sq/16)>
@@ -765,6 +851,23 @@ int calm_attention_fwd(const float* q, const float* k, const float* v, const flo
         case 14: return launch_fwd<14, ATT_NW14>(p, s);
     }
     return CALM_E_UNSUPP;
+}
+}  // namespace
+
+int calm_attention_fwd(const float* q, const float* k, const float* v, const float* w1, const float* b1,
+                       const float* s1, const float* w2, const float* b2, const float* s2, float* out, float* R,
+                       float* hp, float* hg, float* Mk, float* P, int32_t B, int32_t Sq, int32_t Skv, int32_t H, int32_t hd,
+                       void* stream) {
+    return attention_fwd(q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, P, nullptr, B, Sq, Skv, H, hd, stream);
+}
+
+// Row-LSE mode: the same launch with the probabilities left in registers and lse [B,H,Sq] written instead.
+int calm_attention_fwd_lse(const float* q, const float* k, const float* v, const float* w1, const float* b1,
+                           const float* s1, const float* w2, const float* b2, const float* s2, float* out, float* R,
+                           float* hp, float* hg, float* Mk, float* lse, int32_t B, int32_t Sq, int32_t Skv, int32_t H,
+                           int32_t hd, void* stream) {
+    if (!lse) return CALM_E_INVAL;
+    return attention_fwd(q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, nullptr, lse, B, Sq, Skv, H, hd, stream);
 }
 
 // Measured on MI355X (scripts/ab_attn_bwd.py, same process): the two fused launches beat the GEMM composition
@@ -783,17 +886,28 @@ int calm_attention_bwd(const float* q, const float* k, const float* v, const flo
     if (!q || !k || !v || !dout || !P || !dS || !dq || !dk || !dv || !dM || B <= 0) return CALM_E_INVAL;
     if (!calm_attention_fwd_supported(Sq, Skv, H, hd)) return CALM_E_UNSUPP;
     if (B > 65535) return CALM_E_UNSUPP;
-    AttnBwdP p{q, k, v, dout, P, dS, dq, dk, dv, dM, B, Sq, Skv, H, hd, 1.0f / sqrtf((float)hd)};
-    hipStream_t s = as_stream(stream);
-    switch (Skv / 16) {
-        case 2: return launch_bwd<2, 2>(p, s);
-        case 3: return launch_bwd<3, 3>(p, s);
-        case 5: return launch_bwd<5, 5>(p, s);
-        case 8: return launch_bwd<8, 8>(p, s);
-        case 11: return launch_bwd<11, ATT_NW11>(p, s);
-        case 14: return launch_bwd<14, ATT_NW14>(p, s);
-    }
-    return CALM_E_UNSUPP;
+    AttnBwdP p{q, k, v, dout, P, dS, dq, dk, dv, dM, B, Sq, Skv, H, hd, 1.0f / sqrtf((float)hd), nullptr, nullptr};
+    return attention_bwd_dispatch(p, false, as_stream(stream));
+}
+
+// Row-LSE backward: the caller's scratch holds the two [B,H,Sq,Skv] planes the two launches hand to each other — the
+// probabilities rebuilt by the query side, then dS.  Nothing of that size outlives the call.
+int64_t calm_attention_bwd_lse_scratch_bytes(int32_t B, int32_t Sq, int32_t Skv, int32_t H, int32_t hd) {
+    if (B <= 0 || B > 65535 || !calm_attention_fwd_supported(Sq, Skv, H, hd)) return 0;
+    return 2 * (int64_t)sizeof(float) * B * H * Sq * Skv;
+}
+
+int calm_attention_bwd_lse(const float* q, const float* k, const float* v, const float* dout, const float* Mk,
+                           const float* lse, void* scratch, int64_t scratch_bytes, float* dq, float* dk, float* dv,
+                           float* dM, int32_t B, int32_t Sq, int32_t Skv, int32_t H, int32_t hd, void* stream) {
+    if (!q || !k || !v || !dout || !Mk || !lse || !scratch || !dq || !dk || !dv || !dM || B <= 0) return CALM_E_INVAL;
+    const int64_t need = calm_attention_bwd_lse_scratch_bytes(B, Sq, Skv, H, hd);
+    if (need == 0) return CALM_E_UNSUPP;
+    if (scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 15)) return CALM_E_INVAL;
+    float* P = static_cast<float*>(scratch);
+    float* dS = P + need / (2 * (int64_t)sizeof(float));
+    AttnBwdP p{q, k, v, dout, P, dS, dq, dk, dv, dM, B, Sq, Skv, H, hd, 1.0f / sqrtf((float)hd), Mk, lse};
+    return attention_bwd_dispatch(p, true, as_stream(stream));
 }
 
 }  // extern "C"

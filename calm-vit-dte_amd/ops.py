@@ -14,7 +14,8 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from .backend import ACT_GELU, ACT_GELU_BWD, ACT_NONE, act_dtype, bf16_pipeline, fp8_linears, get_backend
+from .backend import (ACT_GELU, ACT_GELU_BWD, ACT_NONE, act_dtype, bf16_pipeline, fp8_linears, get_attention_storage,
+                      get_backend)
 from .spectral_norm import W16_ATTR, W16_GEN_ATTR
 
 # The reference calls the model under autocast(bfloat16) (distributed_trainer_cls.py:84): custom_fwd records the
@@ -567,6 +568,34 @@ class RopeFn(Function):
         return d_content, d_xr, d_if, None, None
 
 
+def _attn_mask_bwd(be, defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2):
+    """What follows the attention core in the fp32 attention's backward, shared by the stored-P and the row-LSE
+    function: the mask-MLP backward from dM [B*Sq,Skv] and the two dR products, accumulated into dq / dk.
+    Returns dW1, db1, dW2, db2."""
+    B, Sq, D = q.shape
+    Skv = k.shape[1]
+    dev, dt = q.device, q.dtype
+    G2 = _zeros_big(w2.shape, w2)
+    _lin_wgrad(be, dM, hg, G2)
+    dW2, _ = _sn_wbwd(be, G2, w2, u2, v2, s2, defer=defer[1])
+    db2 = _colsum(be, dM)
+    dhp = torch.empty_like(hp)
+    _lin_dgrad(be, dM, w2, s2, dhp, act=ACT_GELU_BWD, aux=hp)
+    R2 = R.view(B * Sq, Skv)
+    G1 = _zeros_big(w1.shape, w1)
+    _lin_wgrad(be, dhp, R2, G1)
+    dW1, _ = _sn_wbwd(be, G1, w1, u1, v1, s1, defer=defer[0])
+    db1 = _colsum(be, dhp)
+    dR = torch.empty(B, Sq, Skv, dtype=dt, device=dev)
+    _lin_dgrad(be, dhp, w1, s1, dR.view(B * Sq, Skv))
+    # dQ_all += dR K_all ; dK_all += dR^T Q_all
+    be.gemm(dR, k, dq, Sq, D, Skv, (Skv, 1, Sq * Skv, 0), (1, D, Skv * D, 0), (D, Sq * D, 0), batch=(B, 1),
+            accumulate=True)
+    be.gemm(dR, q, dk, Skv, D, Sq, (1, Skv, Sq * Skv, 0), (1, D, Sq * D, 0), (D, Skv * D, 0), batch=(B, 1),
+            accumulate=True)
+    return dW1, db1, dW2, db2
+
+
 class LatentMaskAttentionFn(Function):
     """softmax(Q_h K_h^T / sqrt(hd) + M) V_h with M = W2 gelu(W1 (sum_h Q_h K_h^T) + b1) + b2 applied
     along the key axis and shared by all heads (Vi_Tools:288-299).  q:[B,Sq,H*hd] k,v:[B,Skv,H*hd]."""
@@ -637,25 +666,57 @@ class LatentMaskAttentionFn(Function):
                     alpha=scale)
             be.gemm(dP, q, dk, Skv, hd, Sq, (1, Skv) + pb, (1, D, Sq * D, hd), (D, Skv * D, hd), batch=(B, H),
                     alpha=scale)
-        # mask MLP backward
-        G2 = _zeros_big(w2.shape, w2)
-        _lin_wgrad(be, dM, hg, G2)
-        dW2, _ = _sn_wbwd(be, G2, w2, u2, v2, s2, defer=ctx.defer[1])
-        db2 = _colsum(be, dM)
-        dhp = torch.empty_like(hp)
-        _lin_dgrad(be, dM, w2, s2, dhp, act=ACT_GELU_BWD, aux=hp)
-        R2 = R.view(B * Sq, Skv)
-        G1 = _zeros_big(w1.shape, w1)
-        _lin_wgrad(be, dhp, R2, G1)
-        dW1, _ = _sn_wbwd(be, G1, w1, u1, v1, s1, defer=ctx.defer[0])
-        db1 = _colsum(be, dhp)
-        dR = torch.empty(B, Sq, Skv, dtype=dt, device=dev)
-        _lin_dgrad(be, dhp, w1, s1, dR.view(B * Sq, Skv))
-        # dQ_all += dR K_all ; dK_all += dR^T Q_all
-        be.gemm(dR, k, dq, Sq, D, Skv, (Skv, 1, Sq * Skv, 0), (1, D, Skv * D, 0), (D, Sq * D, 0), batch=(B, 1),
-                accumulate=True)
-        be.gemm(dR, q, dk, Skv, D, Sq, (1, Skv, Sq * Skv, 0), (1, D, Sq * D, 0), (D, Skv * D, 0), batch=(B, 1),
-                accumulate=True)
+        dW1, db1, dW2, db2 = _attn_mask_bwd(be, ctx.defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2)
+        return dq, dk, dv, dW1, db1, dW2, db2, None, None, None, None, None, None, None
+
+
+class LatentMaskAttentionLseFn(Function):
+    """LatentMaskAttentionFn without the saved probabilities (backend.set_attention_storage('lse')): the forward keeps
+    the mask Mk and the row log-sum-exp [B,H,Sq], the backward rebuilds P in a scratch that lives for that call only.
+    Fused shapes only (backend.attn_fwd_supported); same arguments, same gradients."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, q, k, v, w1, b1, w2, b2, u1, v1, s1, u2, v2, s2, H):
+        be = get_backend()
+        q, k, v = _c(q), _c(k), _c(v)
+        B, Sq, D = q.shape
+        Skv = k.shape[1]
+        hd = D // H
+        dev, dt = q.device, q.dtype
+        if not be.attn_fwd_supported(Sq, Skv, H, hd):
+            raise RuntimeError(f"row-LSE attention: no fused kernel for Sq={Sq} Skv={Skv} H={H} hd={hd}")
+        R = torch.empty(B, Sq, Skv, dtype=dt, device=dev)
+        hp = torch.empty(B * Sq, w1.shape[0], dtype=dt, device=dev)
+        hg = torch.empty_like(hp)
+        Mk = torch.empty(B * Sq, Skv, dtype=dt, device=dev)
+        lse = torch.empty(B, H, Sq, dtype=torch.float32, device=dev)
+        out = torch.empty(B, Sq, D, dtype=dt, device=dev)
+        be.attn_fwd_lse(q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, lse, B, Sq, Skv, H, hd)
+        ctx.H = H
+        ctx.defer = (_deferred(w1), _deferred(w2))
+        ctx.save_for_backward(q, k, v, R, hp, hg, Mk, lse, w1, w2, u1, v1, s1, u2, v2, s2)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @_amp_bwd
+    def backward(ctx, dout):
+        be = get_backend()
+        q, k, v, R, hp, hg, Mk, lse, w1, w2, u1, v1, s1, u2, v2, s2 = ctx.saved_tensors
+        H = ctx.H
+        B, Sq, D = q.shape
+        Skv = k.shape[1]
+        hd = D // H
+        dout = _c(dout)
+        dev, dt = q.device, q.dtype
+        dv, dq, dk = torch.empty_like(v), torch.empty_like(q), torch.empty_like(k)
+        dM = torch.empty(B * Sq, Skv, dtype=dt, device=dev)
+        # recomputed P and dS: released to the caching allocator as soon as the two launches are enqueued
+        scratch = torch.empty(be.attn_bwd_lse_scratch_bytes(B, Sq, Skv, H, hd), dtype=torch.uint8, device=dev)
+        be.attn_bwd_lse(q, k, v, dout, Mk, lse, scratch, dq, dk, dv, dM, B, Sq, Skv, H, hd)
+        del scratch
+        dW1, db1, dW2, db2 = _attn_mask_bwd(be, ctx.defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2)
         return dq, dk, dv, dW1, db1, dW2, db2, None, None, None, None, None, None, None
 
 
@@ -729,6 +790,12 @@ def use_attention16(S, H, hd):
     """The bf16 attention kernels serve this block: bf16 pipeline on, shape supported, token width a multiple of 8
     (q / k / v are also operands of the batched dR products)."""
     return bf16_pipeline() and (H * hd) % 8 == 0 and get_backend().attn16_supported(S, H, hd)
+
+
+def use_attention_lse(Sq, Skv, H, hd):
+    """The row-LSE form of the fp32 attention serves this block: the mode is on (backend.set_attention_storage) and the
+    shape has a fused kernel; every other shape keeps the composed path with its saved probabilities."""
+    return get_attention_storage() == "lse" and get_backend().attn_fwd_supported(Sq, Skv, H, hd)
 
 
 class LatentFn(Function):

@@ -263,6 +263,27 @@ int calm_attention_bwd(const float* q, const float* k, const float* v, const flo
                        float* dq, float* dk, float* dv, float* dM, int32_t B, int32_t Sq, int32_t Skv, int32_t H,
                        int32_t hd, void* stream);
 
+/* Row-LSE mode of the fp32 attention (Vi_Tools:288-299; additions to ABI v7 — no existing signature or struct
+ * changes, so the version number stays): train without the saved probabilities.
+ *   calm_attention_fwd_lse: calm_attention_fwd with P left out and lse [B,H,Sq] written instead,
+ *     lse[b,h,i] = log sum_j exp(q_i.k_j / sqrt(hd) + M[i,j]) (natural log).  out, R, hp, hg, Mk are bit-identical
+ *     to calm_attention_fwd's.
+ *   calm_attention_bwd_lse: calm_attention_bwd without P.  The query-side launch first rebuilds each head's
+ *     probabilities, P = exp(Q_h K_h^T / sqrt(hd) + Mk - lse), into the caller's scratch and continues as the
+ *     stored-P kernel; dq, dk, dv, dM are written (not accumulated).  No atomics: results repeat bit for bit.
+ *   calm_attention_bwd_lse_scratch_bytes: host only, no launch.  Bytes of device scratch (16-byte aligned, contents
+ *     undefined before and after) that calm_attention_bwd_lse needs for the shape; 0 = no fused instantiation
+ *     (exactly the shapes calm_attention_fwd_supported refuses, or B outside 1..65535).  A smaller scratch_bytes is
+ *     CALM_E_INVAL.  Served for every supported shape, whatever calm_attention_bwd_preferred answers. */
+int calm_attention_fwd_lse(const float* q, const float* k, const float* v, const float* w1, const float* b1,
+                           const float* s1, const float* w2, const float* b2, const float* s2, float* out, float* R,
+                           float* hp, float* hg, float* Mk, float* lse, int32_t B, int32_t Sq, int32_t Skv, int32_t H,
+                           int32_t hd, void* stream);
+int64_t calm_attention_bwd_lse_scratch_bytes(int32_t B, int32_t Sq, int32_t Skv, int32_t H, int32_t hd);
+int calm_attention_bwd_lse(const float* q, const float* k, const float* v, const float* dout, const float* Mk,
+                           const float* lse, void* scratch, int64_t scratch_bytes, float* dq, float* dk, float* dv,
+                           float* dM, int32_t B, int32_t Sq, int32_t Skv, int32_t H, int32_t hd, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * The same attention on the bf16 matrix pipe (ABI v4; the bf16 pipeline — what autocast(bfloat16) makes of
  * Vi_Tools:288-299): q, k, v, out and the saved R / hp / hg / Mk are bf16 tensors; w1 [2S,S] / w2 [S,2S] are the
