@@ -24,6 +24,7 @@
 #include "common.h"
 #include "lds_dma.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -57,7 +58,7 @@ struct Attn16P {
     __bf16* R; __bf16* hp; __bf16* hg; __bf16* Mk; __bf16* MkT; float* lse;      // saved for backward
     int B, S, H, hd;
     float scale;
-    int kv_shared;      // K_h and V_h do not both fit in LDS: one image, V_h staged after the Q K^T products
+    int stagger;        // attn16_fwd3_core_kernel only: start offset of every SIMD's second wave, x 64 cycles
     int groups;         // query groups (workgroups) per image — attn16_fwd2_kernel's 1-D grid
 };
 
@@ -76,12 +77,15 @@ __device__ __forceinline__ void image_and_group(int id, int groups, int B, int& 
     }
 }
 
-constexpr size_t LDS_BUDGET = 80 * 1024;       // two workgroups per CU when a kernel stays below this
+constexpr int LDS_MAX = 160 * 1024;            // LDS of a CU = the most a workgroup can ask for
+constexpr int LDS_BUDGET = LDS_MAX / 2;        // two workgroups per CU when a kernel stays below this
 
 // stride (in bf16 elements) of a [row][cols] image that is read by 16-byte fragments and by transposed reads
 __host__ __device__ constexpr int ld_rt(int cols) { return cols + 16; }        // cols % 32 == 0 -> bytes = 32 (mod 64)
 // ... of an image read in paired-tile order (two 8-byte reads per lane)
 __host__ __device__ constexpr int ld_pt(int cols) { return ((cols + 15) / 16 * 16) + 8; }   // bytes = 16 (mod 32)
+static_assert(ld_rt(32) * 2 % 64 == 32 && ld_rt(64) * 2 % 64 == 32 && ld_rt(96) * 2 % 64 == 32 && ld_rt(128) * 2 % 64 == 32,
+              "ld_rt: 16-byte fragment and transposed reads conflict-free");
 
 // copy a [rows x cols] block (global row stride gstride, all in elements; cols % 4 == 0, 8-byte aligned rows) into an
 // LDS image with row stride ld; rows >= rows_valid and columns >= cols_valid are zero-filled up to (rows_img, cols_img)
@@ -159,9 +163,30 @@ __host__ __device__ constexpr int fwd_waves_per_simd(int np) {
     return (ATT16_FWD_OCC3 && 2 * waves_for(np) <= 12 && np <= 6) ? 3 : 2;
 }
 
+// LDS geometry of attn16_fwd_kernel, read by the kernel and by its launcher (strides and offsets in bf16 elements).
+// The three phases reuse the allocation from its start.
+template <int NP, int HDP>
+struct Fwd1Geo {
+    static constexpr int SP = 32 * NP, NW = waves_for(NP);
+    static constexpr int CW = 64, LDK = ld_rt(CW);               // phase 1: K_all column chunk [SP][CW]
+    static constexpr int LD1 = ld_pt(SP), LD2 = ld_pt(32);       // phase 2: W1 chunk [32 hidden][SP keys], then
+    static constexpr int W2_OFF = 32 * LD1;                      //          W2 chunk [SP keys][32 hidden]
+    static constexpr int LDH = ld_rt(HDP);                       // phase 3: K_h, V_h [SP][HDP]
+    // K_h and V_h images side by side when that leaves room for two workgroups per CU, else one shared image
+    // (V_h staged after the Q K^T products)
+    static constexpr bool KV_SHARED = (size_t)2 * SP * LDH * sizeof(__bf16) > (size_t)LDS_BUDGET;
+    static constexpr int V_OFF = KV_SHARED ? 0 : SP * LDH;
+    static constexpr int PH1 = SP * LDK, PH2 = W2_OFF + SP * LD2, PH3 = V_OFF + SP * LDH;
+    static constexpr int LDS = (PH1 > PH2 ? (PH1 > PH3 ? PH1 : PH3) : (PH2 > PH3 ? PH2 : PH3)) * (int)sizeof(__bf16);
+    static_assert(LDS <= LDS_MAX, "attn16_fwd_kernel LDS");
+    static_assert(LDK * 2 % 64 == 32 && LDH * 2 % 64 == 32, "16-byte fragment / transposed reads: stride = 32 (mod 64) bytes");
+    static_assert(LD1 * 2 % 32 == 16 && LD2 * 2 % 32 == 16, "paired-tile order reads: stride = 16 (mod 32) bytes");
+};
+
 template <int NP, int HDP>
 __global__ __launch_bounds__(64 * waves_for(NP), fwd_waves_per_simd(NP)) void attn16_fwd_kernel(const Attn16P p) {
-    constexpr int NJ = 2 * NP, SP = 32 * NP, NW = waves_for(NP), NTH = 64 * NW;
+    typedef Fwd1Geo<NP, HDP> G;
+    constexpr int NJ = 2 * NP, SP = G::SP, NW = G::NW, NTH = 64 * NW;
     constexpr bool KEEP_MASK = NP <= 8;
     extern __shared__ __attribute__((aligned(16))) __bf16 smem16[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -189,8 +214,7 @@ __global__ __launch_bounds__(64 * waves_for(NP), fwd_waves_per_simd(NP)) void at
     {
 #pragma unroll
         for (int t = 0; t < NJ; ++t) acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
-        constexpr int CW = 64;
-        constexpr int LDK = ld_rt(CW);
+        constexpr int CW = G::CW, LDK = G::LDK;
         constexpr int NV = (SP * (CW / 4) + NTH - 1) / NTH;
         __bf16* img = smem16;
         const int nch = (D + CW - 1) / CW;
@@ -237,10 +261,10 @@ __global__ __launch_bounds__(64 * waves_for(NP), fwd_waves_per_simd(NP)) void at
     {
         const float inv1 = 1.0f / p.s1[0], inv2 = 1.0f / p.s2[0];
         const int NH = 2 * S;
-        constexpr int LD1 = ld_pt(SP), LD2 = ld_pt(32);
+        constexpr int LD1 = G::LD1, LD2 = G::LD2;
         constexpr int NV = (SP * 8 + NTH - 1) / NTH;                 // both chunk images are SP x 32 elements
         __bf16* img1 = smem16;                                       // W1 chunk  [32 hidden][SP keys]
-        __bf16* img2 = smem16 + 32 * LD1;                            // W2 chunk  [SP keys][32 hidden]
+        __bf16* img2 = smem16 + G::W2_OFF;                           // W2 chunk  [SP keys][32 hidden]
 #pragma unroll
         for (int t = 0; t < NJ; ++t) acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
         const int nch = (NH + 31) / 32;
@@ -330,14 +354,14 @@ __global__ __launch_bounds__(64 * waves_for(NP), fwd_waves_per_simd(NP)) void at
     const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
 #endif
     // ================= phase 3: per head  softmax(scale K_h Q_h^T + M^T),  O^T = V_h^T P^T =================
-    constexpr int hdp = HDP, LDH = ld_rt(HDP), nks = HDP / 32, ndt = HDP / 16;
+    constexpr int hdp = HDP, LDH = G::LDH, nks = HDP / 32, ndt = HDP / 16;
     // K_h / V_h of the NEXT head are fetched into registers while this head computes — where both images are resident
     // and the staging registers fit beside the accumulators without spilling (NP x HDP <= 640)
-    constexpr bool KV_SHARED = (size_t)2 * SP * LDH * sizeof(__bf16) > LDS_BUDGET;
+    constexpr bool KV_SHARED = G::KV_SHARED;
     constexpr bool PRE3 = !KV_SHARED && NP * HDP <= 640;
     constexpr int NVH = PRE3 ? (SP * HDP / 4 + NTH - 1) / NTH : 1;   // 8-byte vectors per thread per head image
     __bf16* imgK = smem16;
-    __bf16* imgV = KV_SHARED ? smem16 : smem16 + SP * LDH;
+    __bf16* imgV = smem16 + G::V_OFF;
     const int q4 = c16 >> 2, p4 = c16 & 3;
     BlockStage<NVH, NTH> sk, sv;
     if (PRE3) {
@@ -480,116 +504,107 @@ __global__ __launch_bounds__(256) void mask_transpose_kernel(const __bf16* __res
 #include "attention_bf16_fwd2.h"
 #include "attention_bf16_fwd3.h"
 
-// CALM_ATTN16_V2=0 in the environment: the register-staged forward for every shape (A/B runs)
-inline bool fwd2_enabled() {
-    static const int on = [] { const char* e = getenv("CALM_ATTN16_V2"); return (e && e[0] == '0') ? 0 : 1; }();
-    return on != 0;
+// The environment switches of this file, read once:
+//   CALM_ATTN16_V2=0    the register-staged forward for every shape (A/B runs)
+//   CALM_ATTN16_V3=1    EXPERIMENTAL (round 4, off by default) — phases 1-2 as attn16_fwd2_kernel<.., MASK_ONLY> and the
+//                       head loop as the persistent per-(image, head) kernel of attention_bf16_fwd3.h.  Parity-tested
+//                       (tests/test_attention16_gpu.py runs it in a child process); at bs = 256 it is 3 % faster than the
+//                       fused kernel at S = 224 and 3-20 % slower at the smaller stages — DESIGN.md section 7 has the
+//                       measurements that led there and what they say bounds the head loop.
+//   CALM_ATTN16_STAGGER start offset of the second wave of every SIMD in that kernel, x 64 cycles (default: about half
+//                       an item at S = 224)
+//   CALM_ATTN16_BWD2=0  the register-staged backward kernels for every shape (A/B runs)
+struct Attn16Env { bool fwd2, fwd3, bwd2; int stagger; };
+inline const Attn16Env& attn16_env() {
+    static const Attn16Env env = [] {
+        auto first = [](const char* name) { const char* e = getenv(name); return e ? e[0] : '\0'; };
+        const char* st = getenv("CALM_ATTN16_STAGGER");
+        return Attn16Env{first("CALM_ATTN16_V2") != '0', first("CALM_ATTN16_V3") == '1', first("CALM_ATTN16_BWD2") != '0',
+                         st ? atoi(st) : 60};
+    }();
+    return env;
 }
-// CALM_ATTN16_V3=1: EXPERIMENTAL (round 4, off by default) — phases 1-2 as attn16_fwd2_kernel<.., MASK_ONLY> and the head
-// loop as the persistent per-(image, head) kernel of attention_bf16_fwd3.h.  Parity-tested (tests/test_attention16_gpu.py
-// runs it in a child process); at bs = 256 it is 3 % faster than the fused kernel at S = 224 and 3-20 % slower at the smaller
-// stages — DESIGN.md section 7 has the measurements that led there and what they say bounds the head loop.
-inline bool fwd3_enabled() {
-    static const int on = [] { const char* e = getenv("CALM_ATTN16_V3"); return (e && e[0] == '1') ? 1 : 0; }();
-    return on != 0;
+
+// set the dynamic-LDS limit of a kernel, launch it, check the launch
+template <class P>
+int launch(void (*kernel)(const P), dim3 grid, int threads, int lds, hipStream_t s, const P& p) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, p);
+    CALM_LAUNCH_CHECK();
+    return 0;
+}
+
+// run-time (S, hd) -> f(integral_constant NP, integral_constant HDP): THE list of compiled shapes
+template <class F>
+int with_shape16(int S, int hd, F&& f) {
+    auto by_hd = [&](auto np) -> int {
+        switch ((hd + 31) / 32) {
+            case 1: return f(np, std::integral_constant<int, 32>{});
+            case 2: return f(np, std::integral_constant<int, 64>{});
+            case 3: return f(np, std::integral_constant<int, 96>{});
+            case 4: return f(np, std::integral_constant<int, 128>{});
+        }
+        return CALM_E_UNSUPP;
+    };
+    switch ((S + 31) / 32) {
+        case 1: return by_hd(std::integral_constant<int, 1>{});
+        case 2: return by_hd(std::integral_constant<int, 2>{});
+        case 3: return by_hd(std::integral_constant<int, 3>{});
+        case 4: return by_hd(std::integral_constant<int, 4>{});
+        case 5: return by_hd(std::integral_constant<int, 5>{});
+        case 6: return by_hd(std::integral_constant<int, 6>{});
+        case 7: return by_hd(std::integral_constant<int, 7>{});
+        case 8: return by_hd(std::integral_constant<int, 8>{});
+        case 9: return by_hd(std::integral_constant<int, 9>{});
+        case 10: return by_hd(std::integral_constant<int, 10>{});
+        case 11: return by_hd(std::integral_constant<int, 11>{});
+        case 12: return by_hd(std::integral_constant<int, 12>{});
+    }
+    return CALM_E_UNSUPP;
 }
 
 template <int NP, int HDP>
-int launch_fwd16_t(const Attn16P& p, size_t lds, hipStream_t s) {
-    if constexpr (Fwd2Geo<NP, HDP>::OK) {
-        if (fwd2_enabled()) {
-            constexpr int lds2 = Fwd2Geo<NP, HDP>::LDS;
-            hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn16_fwd2_kernel<NP, HDP>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-            if (e2 != hipSuccess) return (int)e2;
-            constexpr int nw2 = waves_for(NP);
-            const int tiles2 = (p.S + 15) / 16;
-            Attn16P p2 = p;
-            p2.groups = (tiles2 + nw2 - 1) / nw2;
-            if constexpr (Fwd3Geo<NP, HDP>::OK) {
-                if (fwd3_enabled()) {
-                    // phases 1-2 (R, mask MLP -> Mk), then one workgroup per (image, head) for the head loop
-                    e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn16_fwd2_kernel<NP, HDP, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-                    if (e2 != hipSuccess) return (int)e2;
-                    constexpr int lds3 = Fwd3Geo<NP, HDP>::LDS;
-                    e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn16_fwd3_core_kernel<NP, HDP, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds3);
-                    if (e2 != hipSuccess) return (int)e2;
-                    e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn16_fwd3_core_kernel<NP, HDP, false>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds3);
-                    if (e2 != hipSuccess) return (int)e2;
-                    hipLaunchKernelGGL((attn16_fwd2_kernel<NP, HDP, true>), dim3(p2.groups * p.B), dim3(64 * nw2), lds2, s, p2);
-                    CALM_LAUNCH_CHECK();
-                    // persistent: as many workgroups as the chip holds at once (a multiple of 8: one share per XCD)
-                    constexpr int nw3 = Fwd3Geo<NP, HDP>::NW;
-                    const int slots3 = 256 * Fwd3Geo<NP, HDP>::WG_PER_CU;
-                    const int grid3 = p.B < slots3 ? p.B : slots3;        // one image (all its heads) at a time per workgroup
-                    // start offset of the second wave of every SIMD, x 64 cycles (default: about half an item at S = 224)
-                    static const int stagger = [] { const char* e = getenv("CALM_ATTN16_STAGGER"); return e ? atoi(e) : 60; }();
-                    p2.kv_shared = stagger;
-                    if (p.S == 32 * NP)
-                        hipLaunchKernelGGL((attn16_fwd3_core_kernel<NP, HDP, true>), dim3(grid3), dim3(64 * nw3), lds3, s, p2);
-                    else
-                        hipLaunchKernelGGL((attn16_fwd3_core_kernel<NP, HDP, false>), dim3(grid3), dim3(64 * nw3), lds3, s, p2);
-                    CALM_LAUNCH_CHECK();
-                    const int t32c = (p.S + 31) / 32;
-                    hipLaunchKernelGGL(mask_transpose_kernel, dim3(t32c, t32c, p.B), dim3(256), 0, s, (const __bf16*)p.Mk, p.MkT, p.S);
-                    CALM_LAUNCH_CHECK();
-                    return 0;
-                }
+int launch_fwd16_t(const Attn16P& p0, hipStream_t s) {
+    typedef Fwd2Geo<NP, HDP> G2;
+    typedef Fwd3Geo<NP, HDP> G3;
+    const Attn16Env& env = attn16_env();
+    constexpr int nw = waves_for(NP);
+    Attn16P p = p0;
+    p.groups = ((p.S + 15) / 16 + nw - 1) / nw;
+    // the variant: pipelined forward / its phases 1-2 (R, mask MLP -> Mk), then one workgroup per (image, head) for the
+    // head loop / register-staged forward
+    void (*k1)(const Attn16P) = nullptr;
+    void (*k3)(const Attn16P) = nullptr;
+    int lds1 = G2::LDS;
+    if constexpr (G2::OK) {
+        if (env.fwd2) k1 = &attn16_fwd2_kernel<NP, HDP>;
+        if constexpr (G3::OK) {
+            if (env.fwd2 && env.fwd3) {
+                k1 = &attn16_fwd2_kernel<NP, HDP, true>;
+                k3 = p.S == 32 * NP ? &attn16_fwd3_core_kernel<NP, HDP, true> : &attn16_fwd3_core_kernel<NP, HDP, false>;
+                p.stagger = env.stagger;
             }
-            hipLaunchKernelGGL((attn16_fwd2_kernel<NP, HDP>), dim3(p2.groups * p.B), dim3(64 * nw2), lds2, s, p2);
-            CALM_LAUNCH_CHECK();
-            const int t32b = (p.S + 31) / 32;
-            hipLaunchKernelGGL(mask_transpose_kernel, dim3(t32b, t32b, p.B), dim3(256), 0, s, (const __bf16*)p.Mk, p.MkT, p.S);
-            CALM_LAUNCH_CHECK();
-            return 0;
         }
     }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn16_fwd_kernel<NP, HDP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    constexpr int nw = waves_for(NP);
-    const int tiles = (p.S + 15) / 16;
-    Attn16P p1 = p;
-    p1.groups = (tiles + nw - 1) / nw;
-    hipLaunchKernelGGL((attn16_fwd_kernel<NP, HDP>), dim3(p1.groups * p.B), dim3(64 * nw), lds, s, p1);
-    CALM_LAUNCH_CHECK();
+    if (!k1) {
+        k1 = &attn16_fwd_kernel<NP, HDP>;
+        lds1 = Fwd1Geo<NP, HDP>::LDS;
+    }
+    int e = launch(k1, dim3(p.groups * p.B), 64 * nw, lds1, s, p);
+    if (e) return e;
+    if (k3) {
+        // persistent: as many workgroups as the chip holds at once (a multiple of 8: one share per XCD), one image (all
+        // its heads) at a time per workgroup
+        const int slots3 = 256 * G3::WG_PER_CU;
+        e = launch(k3, dim3(p.B < slots3 ? p.B : slots3), 64 * G3::NW, G3::LDS, s, p);
+        if (e) return e;
+    }
     const int t32 = (p.S + 31) / 32;
     hipLaunchKernelGGL(mask_transpose_kernel, dim3(t32, t32, p.B), dim3(256), 0, s, (const __bf16*)p.Mk, p.MkT, p.S);
     CALM_LAUNCH_CHECK();
     return 0;
 }
-template <int NP>
-int launch_fwd16(const Attn16P& p, int, size_t lds, hipStream_t s) {
-    switch ((p.hd + 31) / 32) {
-        case 1: return launch_fwd16_t<NP, 32>(p, lds, s);
-        case 2: return launch_fwd16_t<NP, 64>(p, lds, s);
-        case 3: return launch_fwd16_t<NP, 96>(p, lds, s);
-        case 4: return launch_fwd16_t<NP, 128>(p, lds, s);
-    }
-    return CALM_E_UNSUPP;
-}
-
-// waves per workgroup of the backward kernels
-inline int pick_waves16(int S) { return waves_for((S + 31) / 32); }
-
-// K_h and V_h images side by side when that leaves room for two workgroups per CU, else one shared image
-inline bool fwd_kv_shared(int S, int hd) {
-    const int SP = (S + 31) / 32 * 32, hdp = (hd + 31) / 32 * 32;
-    return (size_t)2 * SP * ld_rt(hdp) * sizeof(__bf16) > LDS_BUDGET;
-}
-inline size_t fwd_lds_bytes(int S, int hd) {
-    const int NP = (S + 31) / 32, SP = 32 * NP, hdp = (hd + 31) / 32 * 32;
-    const size_t ph1 = (size_t)SP * ld_rt(64);
-    const size_t ph2 = (size_t)32 * ld_pt(SP) + (size_t)SP * ld_pt(32);
-    const size_t ph3 = (size_t)(fwd_kv_shared(S, hd) ? 1 : 2) * SP * ld_rt(hdp);
-    size_t m = ph1 > ph2 ? ph1 : ph2;
-    if (ph3 > m) m = ph3;
-    return m * sizeof(__bf16);
-}
-
 
 // =====================================================================================================
 // Backward of the attention core with P recomputed from q, k, the saved mask and the row log-sum-exp.
@@ -614,12 +629,18 @@ struct Attn16BP {
     int groups;         // row groups (workgroups) per image
 };
 
-// tile pairs whose two images fit the LDS budget of a workgroup (two workgroups per CU)
-__host__ __device__ constexpr int bwd_chunk_pairs_c(int np, int hdp) {
-    const int per_pair = 2 * 32 * ld_rt(hdp) * 2;
-    const int ch = (80 * 1024) / per_pair;
-    return ch < 1 ? 1 : ch > np ? np : ch;
-}
+// LDS geometry of attn16_bwd_q_kernel / attn16_bwd_kv_kernel, read by the kernels and by their launcher: two
+// [32 CH][HDP] images, CH = the tile pairs whose two images fit the LDS budget of a workgroup (two workgroups per CU).
+// The kernels take the chunk size from Attn16BP::ch, which the launcher sets to CH.
+template <int NP, int HDP>
+struct Bwd1Geo {
+    static constexpr int LDH = ld_rt(HDP);
+    static constexpr int PER_PAIR = 2 * 32 * LDH * (int)sizeof(__bf16);
+    static constexpr int CH = LDS_BUDGET / PER_PAIR < 1 ? 1 : LDS_BUDGET / PER_PAIR > NP ? NP : LDS_BUDGET / PER_PAIR;
+    static constexpr int LDS = CH * PER_PAIR;
+    static_assert(LDS <= LDS_MAX, "attn16_bwd_*_kernel LDS");
+    static_assert(LDH * 2 % 64 == 32, "16-byte fragment / transposed reads: stride = 32 (mod 64) bytes");
+};
 
 // Both kernels are compiled per (NP, HDP = head dim padded to 32): with run-time trip counts the fully unrolled
 // tile loops (register-array indices must be constants) cost > 256 VGPRs and kilobytes of scratch.
@@ -646,7 +667,7 @@ __global__ __launch_bounds__(64 * waves_for(NP)) void attn16_bwd_q_kernel(const 
     const long qoff = ((long)b * S + q_ld) * D;
     const __bf16* kb = p.k + (long)b * S * D;
     const __bf16* vb = p.v + (long)b * S * D;
-    constexpr int hdp = HDP, LDH = ld_rt(HDP), nks = HDP / 32, ndt = HDP / 16, MAXKS = nks, MAXDT = ndt;
+    constexpr int hdp = HDP, LDH = Bwd1Geo<NP, HDP>::LDH, nks = HDP / 32, ndt = HDP / 16, MAXKS = nks, MAXDT = ndt;
     const int rows_img = 32 * p.ch;
     __bf16* imgK = smem16;
     __bf16* imgV = smem16 + rows_img * LDH;
@@ -661,7 +682,7 @@ __global__ __launch_bounds__(64 * waves_for(NP)) void attn16_bwd_q_kernel(const 
     // (up to NP x HDP = 448 — the stages of Base-224: beyond 256 the prefetch registers spill (156-184 bytes of scratch per
     // lane), which still pays: the spilled vectors sit in L1 / L2 when the next head needs them, S=176 -6.6 %, S=224 -3.8 %)
     constexpr int NTHB = 64 * waves_for(NP);
-    constexpr bool PRE = bwd_chunk_pairs_c(NP, HDP) == NP && NP * HDP <= ATT16_BWDQ_PRE_MAX;
+    constexpr bool PRE = Bwd1Geo<NP, HDP>::CH == NP && NP * HDP <= ATT16_BWDQ_PRE_MAX;
     constexpr int NVB = PRE ? (32 * NP * HDP / 4 + NTHB - 1) / NTHB : 1;
     constexpr bool pre = PRE;
     BlockStage<NVB, NTHB> sa, sb;
@@ -777,7 +798,7 @@ __global__ __launch_bounds__(64 * waves_for(NP)) void attn16_bwd_kv_kernel(const
     const long koff = ((long)b * S + k_ld) * D;
     const __bf16* qb = p.q + (long)b * S * D;
     const __bf16* dob = p.dout + (long)b * S * D;
-    constexpr int hdp = HDP, LDH = ld_rt(HDP), nks = HDP / 32, ndt = HDP / 16, MAXKS = nks, MAXDT = ndt;
+    constexpr int hdp = HDP, LDH = Bwd1Geo<NP, HDP>::LDH, nks = HDP / 32, ndt = HDP / 16, MAXKS = nks, MAXDT = ndt;
     const int rows_img = 32 * p.ch;
     __bf16* imgQ = smem16;
     __bf16* imgO = smem16 + rows_img * LDH;
@@ -786,7 +807,7 @@ __global__ __launch_bounds__(64 * waves_for(NP)) void attn16_bwd_kv_kernel(const
     const __bf16* Mcol = p.MkT + ((long)b * S + k_ld) * S;
     const bf16x4 zero4 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
     constexpr int NTHB = 64 * waves_for(NP);
-    constexpr bool PRE = bwd_chunk_pairs_c(NP, HDP) == NP && NP * HDP <= ATT16_BWDKV_PRE_MAX;      // see the query-side kernel
+    constexpr bool PRE = Bwd1Geo<NP, HDP>::CH == NP && NP * HDP <= ATT16_BWDKV_PRE_MAX;      // see the query-side kernel
     constexpr int NVB = PRE ? (32 * NP * HDP / 4 + NTHB - 1) / NTHB : 1;
     constexpr bool pre = PRE;
     BlockStage<NVB, NTHB> sa, sb;
@@ -889,64 +910,35 @@ __global__ __launch_bounds__(64 * waves_for(NP)) void attn16_bwd_kv_kernel(const
     }
 }
 
-inline int bwd_chunk_pairs(int S, int hd) { return bwd_chunk_pairs_c((S + 31) / 32, (hd + 31) / 32 * 32); }
-
 #include "attention_bf16_bwd2.h"
 
-// CALM_ATTN16_BWD2=0 in the environment: the register-staged backward kernels for every shape (A/B runs)
-inline bool bwd2_enabled() {
-    static const int on = [] { const char* e = getenv("CALM_ATTN16_BWD2"); return (e && e[0] == '0') ? 0 : 1; }();
-    return on != 0;
-}
-
 template <int NP, int HDP>
-int launch_bwd16_t(const Attn16BP& p, int nw, hipStream_t s) {
-    if constexpr (Bwd2Geo<NP, HDP, false>::OK && Bwd2Geo<NP, HDP, true>::OK) {
-        if (bwd2_enabled()) {
-            Attn16BP p2 = p;
-            const int tiles2 = (p.S + 15) / 16;
-            p2.groups = (tiles2 + nw - 1) / nw;
-            const dim3 grid2(p2.groups * p.B);
-            constexpr int ldq = Bwd2Geo<NP, HDP, false>::LDS, ldk = Bwd2Geo<NP, HDP, true>::LDS;
-            hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn16_bwd2_kernel<NP, HDP, false>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, ldq);
-            if (e2 != hipSuccess) return (int)e2;
-            e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn16_bwd2_kernel<NP, HDP, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, ldk);
-            if (e2 != hipSuccess) return (int)e2;
-            hipLaunchKernelGGL((attn16_bwd2_kernel<NP, HDP, false>), grid2, dim3(64 * nw), ldq, s, p2);
-            CALM_LAUNCH_CHECK();
-            hipLaunchKernelGGL((attn16_bwd2_kernel<NP, HDP, true>), grid2, dim3(64 * nw), ldk, s, p2);
-            CALM_LAUNCH_CHECK();
-            return 0;
+int launch_bwd16_t(const Attn16BP& p0, hipStream_t s) {
+    typedef Bwd1Geo<NP, HDP> G1;
+    typedef Bwd2Geo<NP, HDP, false> GQ;
+    typedef Bwd2Geo<NP, HDP, true> GK;
+    constexpr int nw = waves_for(NP);
+    Attn16BP p = p0;
+    p.ch = G1::CH;
+    p.groups = ((p.S + 15) / 16 + nw - 1) / nw;
+    // the variant: pipelined kernels (query side, key side) / register-staged pair
+    void (*kq)(const Attn16BP) = nullptr;
+    void (*kk)(const Attn16BP) = nullptr;
+    int ldq = GQ::LDS, ldk = GK::LDS;
+    if constexpr (GQ::OK && GK::OK) {
+        if (attn16_env().bwd2) {
+            kq = &attn16_bwd2_kernel<NP, HDP, false>;
+            kk = &attn16_bwd2_kernel<NP, HDP, true>;
         }
     }
-    const size_t lds = (size_t)2 * 32 * p.ch * ld_rt(HDP) * sizeof(__bf16);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn16_bwd_q_kernel<NP, HDP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn16_bwd_kv_kernel<NP, HDP>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    const int tiles = (p.S + 15) / 16;
-    Attn16BP p1 = p;
-    p1.groups = (tiles + nw - 1) / nw;
-    const dim3 grid(p1.groups * p.B);
-    hipLaunchKernelGGL((attn16_bwd_q_kernel<NP, HDP>), grid, dim3(64 * nw), lds, s, p1);
-    CALM_LAUNCH_CHECK();
-    hipLaunchKernelGGL((attn16_bwd_kv_kernel<NP, HDP>), grid, dim3(64 * nw), lds, s, p1);
-    CALM_LAUNCH_CHECK();
-    return 0;
-}
-template <int NP>
-int launch_bwd16(const Attn16BP& p, int nw, hipStream_t s) {
-    switch ((p.hd + 31) / 32) {
-        case 1: return launch_bwd16_t<NP, 32>(p, nw, s);
-        case 2: return launch_bwd16_t<NP, 64>(p, nw, s);
-        case 3: return launch_bwd16_t<NP, 96>(p, nw, s);
-        case 4: return launch_bwd16_t<NP, 128>(p, nw, s);
+    if (!kq) {
+        kq = &attn16_bwd_q_kernel<NP, HDP>;
+        kk = &attn16_bwd_kv_kernel<NP, HDP>;
+        ldq = ldk = G1::LDS;
     }
-    return CALM_E_UNSUPP;
+    const dim3 grid(p.groups * p.B);
+    const int e = launch(kq, grid, 64 * nw, ldq, s, p);
+    return e ? e : launch(kk, grid, 64 * nw, ldk, s, p);
 }
 
 }  // namespace
@@ -956,8 +948,7 @@ extern "C" {
 int calm_attention16_supported(int32_t S, int32_t H, int32_t hd) {
     if (S <= 0 || H <= 0 || hd <= 0) return 0;
     if ((S & 7) || (hd & 3) || hd > 128 || S > 384) return 0;      // bf16 W1 rows / head slices as 8-byte vectors
-    if (fwd_lds_bytes(S, hd) > 160 * 1024) return 0;
-    return 1;
+    return with_shape16(S, hd, [](auto np, auto hdp) -> int { return Fwd1Geo<decltype(np)::value, decltype(hdp)::value>::LDS <= LDS_MAX ? 1 : 0; }) == 1;
 }
 
 int calm_attention16_fwd(const void* q, const void* k, const void* v, const void* w1, const float* b1, const float* s1,
@@ -970,26 +961,9 @@ int calm_attention16_fwd(const void* q, const void* k, const void* v, const void
     if (B > 65535) return CALM_E_UNSUPP;                    // mask_transpose_kernel's grid.z
     Attn16P p{(const __bf16*)q, (const __bf16*)k, (const __bf16*)v, (const __bf16*)w1, b1, s1, (const __bf16*)w2, b2, s2,
               (__bf16*)out, (__bf16*)R, (__bf16*)hp, (__bf16*)hg, (__bf16*)Mk, (__bf16*)MkT, lse, B, S, H, hd,
-              1.0f / sqrtf((float)hd),
-              fwd_kv_shared(S, hd) ? 1 : 0, 0};
+              1.0f / sqrtf((float)hd), 0, 0};
     hipStream_t s = as_stream(stream);
-    const int nw = pick_waves16(S);
-    const size_t lds = fwd_lds_bytes(S, hd);
-    switch ((S + 31) / 32) {
-        case 1: return launch_fwd16<1>(p, nw, lds, s);
-        case 2: return launch_fwd16<2>(p, nw, lds, s);
-        case 3: return launch_fwd16<3>(p, nw, lds, s);
-        case 4: return launch_fwd16<4>(p, nw, lds, s);
-        case 5: return launch_fwd16<5>(p, nw, lds, s);
-        case 6: return launch_fwd16<6>(p, nw, lds, s);
-        case 7: return launch_fwd16<7>(p, nw, lds, s);
-        case 8: return launch_fwd16<8>(p, nw, lds, s);
-        case 9: return launch_fwd16<9>(p, nw, lds, s);
-        case 10: return launch_fwd16<10>(p, nw, lds, s);
-        case 11: return launch_fwd16<11>(p, nw, lds, s);
-        case 12: return launch_fwd16<12>(p, nw, lds, s);
-    }
-    return CALM_E_UNSUPP;
+    return with_shape16(S, hd, [&](auto np, auto hdp) -> int { return launch_fwd16_t<decltype(np)::value, decltype(hdp)::value>(p, s); });
 }
 
 int calm_attention16_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* Mk,
@@ -1001,24 +975,9 @@ int calm_attention16_bwd(const void* q, const void* k, const void* v, const void
 
     Attn16BP p{(const __bf16*)q, (const __bf16*)k, (const __bf16*)v, (const __bf16*)out, (const __bf16*)dout,
                (const __bf16*)Mk, (const __bf16*)MkT, lse, delta, (__bf16*)dq, (__bf16*)dk, (__bf16*)dv, (__bf16*)dM,
-               B, S, H, hd, 1.0f / sqrtf((float)hd), bwd_chunk_pairs(S, hd), 0};
+               B, S, H, hd, 1.0f / sqrtf((float)hd), 0, 0};
     hipStream_t s = as_stream(stream);
-    const int nw = pick_waves16(S);
-    switch ((S + 31) / 32) {
-        case 1: return launch_bwd16<1>(p, nw, s);
-        case 2: return launch_bwd16<2>(p, nw, s);
-        case 3: return launch_bwd16<3>(p, nw, s);
-        case 4: return launch_bwd16<4>(p, nw, s);
-        case 5: return launch_bwd16<5>(p, nw, s);
-        case 6: return launch_bwd16<6>(p, nw, s);
-        case 7: return launch_bwd16<7>(p, nw, s);
-        case 8: return launch_bwd16<8>(p, nw, s);
-        case 9: return launch_bwd16<9>(p, nw, s);
-        case 10: return launch_bwd16<10>(p, nw, s);
-        case 11: return launch_bwd16<11>(p, nw, s);
-        case 12: return launch_bwd16<12>(p, nw, s);
-    }
-    return CALM_E_UNSUPP;
+    return with_shape16(S, hd, [&](auto np, auto hdp) -> int { return launch_bwd16_t<decltype(np)::value, decltype(hdp)::value>(p, s); });
 }
 
 }  // extern "C"

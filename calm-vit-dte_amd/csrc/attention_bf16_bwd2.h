@@ -23,7 +23,7 @@ struct Bwd2Geo {
     static constexpr int NIX = KEYSIDE ? 2 : 0;                        // lse_h / delta_h vectors (SP floats each, <= 1 KiB)
     static constexpr int NINSTR = 2 * NI3 + NIX, ST = NINSTR * 1024;
     static constexpr int LDS = 2 * ST;
-    static constexpr bool OK = NP <= 7 && HDP <= 64 && LDS <= 160 * 1024 && SP * 4 <= 1024;
+    static constexpr bool OK = NP <= 7 && HDP <= 64 && LDS <= LDS_MAX && SP * 4 <= 1024;
 };
 
 template <int NP, int HDP, bool KEYSIDE>

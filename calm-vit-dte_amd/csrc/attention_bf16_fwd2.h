@@ -122,7 +122,7 @@ struct Fwd2Geo {
     static constexpr int ST2 = (NI2A + NI2B) * 1024;                                      // phase 2 stage (W1 + W2 chunk)
     static constexpr int CPRH = HDP / 8 + 2, NI3 = (SP * CPRH + 63) / 64, ST3 = 2 * NI3 * 1024;   // phase 3 stage (K_h + V_h)
     static constexpr int TBL = 12 * SP;                                                   // b1 [2 SP] + b2 [SP] floats
-    static constexpr int AVAIL = 160 * 1024 - TBL;
+    static constexpr int AVAIL = LDS_MAX - TBL;
     static constexpr int ns(int st) { return AVAIL / st > 4 ? 4 : AVAIL / st; }
     static constexpr int NS1 = ns(ST1), NS2 = ns(ST2), NS3 = AVAIL / ST3 >= 2 ? 2 : 1;
     static constexpr int max3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }

@@ -44,7 +44,7 @@ struct Fwd3Geo {
     static constexpr int CPRH = HDP / 8 + 2, NI3 = (SP * CPRH + 63) / 64;        // LDS-DMA instructions per image
     static constexpr int STAGE = 2 * NI3 * 1024;                                 // K_h and V_h images of one item
     static constexpr int LDS = 2 * STAGE + 64;                                   // two stages + the FULL / DONE words
-    static constexpr int BY_LDS = (160 * 1024) / LDS, BY_WAVES = (NP <= 4 ? 12 : 8) / NW;     // (<= 256 VGPRs: two waves per SIMD; <= 168 below NP = 5: three)
+    static constexpr int BY_LDS = LDS_MAX / LDS, BY_WAVES = (NP <= 4 ? 12 : 8) / NW;     // (<= 256 VGPRs: two waves per SIMD; <= 168 below NP = 5: three)
     static constexpr int WG_PER_CU = BY_LDS < BY_WAVES ? BY_LDS : BY_WAVES;
     static constexpr bool OK = NP <= 7 && HDP <= 64 && WG_PER_CU >= 1;
 };
@@ -242,9 +242,9 @@ __global__ __launch_bounds__(64 * fwd3_waves(NP), 2) void attn16_fwd3_core_kerne
     qn = request_q(b, h);
     __builtin_amdgcn_s_barrier();                                      // (the FULL / DONE words are zero)
     asm volatile("" ::: "memory");
-    // start offset of the second wave of every SIMD (waves 4 ..): p.kv_shared x 64 cycles, about half an item
+    // start offset of the second wave of every SIMD (waves 4 ..): p.stagger x 64 cycles, about half an item
     if (wave >= 4)
-        for (int i = 0; i < p.kv_shared; i += 10) __builtin_amdgcn_s_sleep(10);
+        for (int i = 0; i < p.stagger; i += 10) __builtin_amdgcn_s_sleep(10);
     F3_STAMP(1);
 
     const int q4 = c16 >> 2, p4 = c16 & 3;

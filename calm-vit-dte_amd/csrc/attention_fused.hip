@@ -110,19 +110,56 @@ __device__ __forceinline__ void tr_store(const Regs<NV>& rg, float* __restrict__
 }
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
+// ---- LDS geometry: defined here once; the kernels and the host code that sizes their launches both read it ----------
+constexpr size_t LDS_MAX = 160 * 1024;         // LDS of a CU = the most a workgroup can ask for
+
+// row stride (floats) of a K-major [c][row] image: = 16 (mod 32), so the 4 lane groups of a b32 read land 16 banks apart
+__host__ __device__ constexpr int ld_km(int rows) { return rows + ((rows % 32 == 16) ? 0 : 16); }
+
+// NJ 16-row tiles on the accumulator rows (forward / query side: the keys; key side: the queries — the model has
+// Sq == Skv), NW waves = NW 16-row tiles of the other axis per workgroup.  Offsets and sizes in floats.
+template <int NJ_, int NW_>
+struct AttGeo {
+    static constexpr int NJ = NJ_, NW = NW_;
+    static constexpr int SKV = 16 * NJ, TQ = 16 * NW;
+    static constexpr int LDJ = ld_km(SKV), LDQ = ld_km(TQ);    // K / Q column-chunk images [c][j], [c][i]
+    static constexpr int LDN1 = 20;                            // W1 chunk image [j][nn]
+    static constexpr int LDJ2 = SKV + 4;                       // W2 chunk image [nn][j]
+    static_assert(LDJ % 32 == 16 && LDQ % 32 == 16, "K-major strides: lane groups 16 banks apart");
+    // phases 1 and 3 (and the query-side backward): K and Q chunk double buffers, then the whole head stripe
+    static constexpr int Q_OFF = 32 * LDJ, V_OFF = Q_OFF + 32 * LDQ;
+    __device__ static float* buf_k(float* smem, int i) { return smem + i * 16 * LDJ; }
+    __device__ static float* buf_q(float* smem, int i) { return smem + Q_OFF + i * 16 * LDQ; }
+    // phase 2: W1 and W2 chunk double buffers
+    static constexpr int W2_OFF = 2 * SKV * LDN1, PH2 = W2_OFF + 32 * LDJ2;
+    __device__ static float* buf_w1(float* smem, int i) { return smem + i * SKV * LDN1; }
+    __device__ static float* buf_w2(float* smem, int i) { return smem + W2_OFF + i * 16 * LDJ2; }
+    // the part that depends on the run-time head dim: the [SKV][LDV] stripe of one head (V_h, K_h, dO_h or Q_h)
+    struct Hd { int DT, hdp, LDV, stripe; };
+    __host__ __device__ static constexpr Hd at(int hd) {
+        const int DT = (hd + 15) / 16;                         // d-tiles (<= 8)
+        const int hdp = 16 * DT, LDV = hdp + 4;                // 4*LDV % 32 == 16
+        return {DT, hdp, LDV, SKV * LDV};
+    }
+    // dynamic LDS bytes of the three kernels
+    static constexpr size_t fwd_bytes(int hd) {
+        const int ph13 = V_OFF + at(hd).stripe;
+        return sizeof(float) * (size_t)(ph13 > PH2 ? ph13 : PH2);
+    }
+    static constexpr size_t bwd_q_bytes(int hd) { return sizeof(float) * (size_t)(V_OFF + at(hd).stripe); }
+    static constexpr size_t bwd_kv_bytes(int hd) { return sizeof(float) * (size_t)at(hd).stripe; }
+};
+
 template <int NJ, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
     constexpr int NTH = 64 * NW;
     constexpr int NV_K = (NJ + NW - 1) / NW;   // float4 per thread for a [16*NJ x 16] chunk
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int SKV = 16 * NJ;
-    constexpr int LDJ = SKV + ((SKV % 32 == 16) ? 0 : 16);    // [c][j] images: 4 lane groups 16 banks apart
-    constexpr int LDN1 = 20;                                   // W1 chunk image [j][nn]
-    constexpr int LDJ2 = SKV + 4;                              // W2 chunk image [nn][j]
+    typedef AttGeo<NJ, NW> G;
+    constexpr int SKV = G::SKV, LDJ = G::LDJ, LDN1 = G::LDN1, LDJ2 = G::LDJ2;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int TQ = 16 * NW;
-    constexpr int LDQ = TQ + ((TQ % 32 == 16) ? 0 : 16);
+    constexpr int TQ = G::TQ, LDQ = G::LDQ;
     const int r16 = lane & 15, g = lane >> 4;
     const int b = blockIdx.y;
     const int q0 = blockIdx.x * TQ;                            // first query of the workgroup
@@ -135,8 +172,8 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
     const float* kb = p.k + (long)b * p.Skv * D;
     const float* vb = p.v + (long)b * p.Skv * D;
 
-    auto bufK = [&](int i) { return smem + i * 16 * LDJ; };
-    auto bufQ = [&](int i) { return smem + 32 * LDJ + i * 16 * LDQ; };
+    auto bufK = [&](int i) { return G::buf_k(smem, i); };
+    auto bufQ = [&](int i) { return G::buf_q(smem, i); };
 
     f32x4v accR[NJ];
 #pragma unroll
@@ -187,8 +224,8 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
     for (int t = 0; t < NJ; ++t) accM[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
     {
         const float inv1 = 1.0f / p.s1[0], inv2 = 1.0f / p.s2[0];
-        auto bufW1 = [&](int i) { return smem + i * SKV * LDN1; };
-        auto bufW2 = [&](int i) { return smem + 2 * SKV * LDN1 + i * 16 * LDJ2; };
+        auto bufW1 = [&](int i) { return G::buf_w1(smem, i); };
+        auto bufW2 = [&](int i) { return G::buf_w2(smem, i); };
         const int nch = 2 * NJ;                                 // 2*Skv hidden units, 16 per chunk
         Regs<NV_K> r1, r2;
         tr_load<NTH>(r1, p.w1, SKV, SKV);                            // rows n0..n0+15 of W1 [2Skv, Skv]
@@ -264,10 +301,9 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
 
     // ================= phase 3: per head  softmax(scale K_h Q_h^T + M^T) , O^T = V_h^T P^T =================
     const int hd = p.hd;
-    const int DT = (hd + 15) / 16;                              // output d-tiles (<= 8)
-    const int hdp = 16 * DT;
-    const int LDV = hdp + 4;                                    // 4*LDV % 32 == 16
-    float* bufV = smem + 32 * LDJ + 32 * LDQ;                   // the WHOLE V_h [Skv][LDV], filled during the QK loop
+    const auto gh = G::at(hd);
+    const int DT = gh.DT, hdp = gh.hdp, LDV = gh.LDV;           // output d-tiles, padded head dim, stripe row stride
+    float* bufV = smem + G::V_OFF;                              // the WHOLE V_h [Skv][LDV], filled during the QK loop
     const int v_per_row = hdp >> 2;                             // float4 per V row
     const int v_total = SKV * v_per_row;
     const int nchq = (hd + 15) / 16;                            // QK^T column chunks
@@ -429,10 +465,8 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
     constexpr int NTH = 64 * NW;
     constexpr int NV_K = (NJ + NW - 1) / NW;   // float4 per thread for a [16*NJ x 16] chunk
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int SKV = 16 * NJ;
-    constexpr int LDJ = SKV + ((SKV % 32 == 16) ? 0 : 16);
-    constexpr int TQ = 16 * NW;
-    constexpr int LDQ = TQ + ((TQ % 32 == 16) ? 0 : 16);
+    typedef AttGeo<NJ, NW> G;
+    constexpr int SKV = G::SKV, LDJ = G::LDJ, TQ = G::TQ, LDQ = G::LDQ;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, g = lane >> 4;
     const int b = blockIdx.y;
@@ -442,10 +476,11 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
     const int iq = q0 + 16 * wave + r16;
     const int D = p.H * p.hd;
     const int hd = p.hd;
-    const int DT = (hd + 15) / 16, hdp = 16 * DT, LDV = hdp + 4;
-    auto bufK = [&](int i) { return smem + i * 16 * LDJ; };
-    auto bufQ = [&](int i) { return smem + 32 * LDJ + i * 16 * LDQ; };
-    float* bufV = smem + 32 * LDJ + 32 * LDQ;                   // whole K_h stripe for the dQ block
+    const auto gh = G::at(hd);
+    const int DT = gh.DT, hdp = gh.hdp, LDV = gh.LDV;
+    auto bufK = [&](int i) { return G::buf_k(smem, i); };
+    auto bufQ = [&](int i) { return G::buf_q(smem, i); };
+    float* bufV = smem + G::V_OFF;                              // whole K_h stripe for the dQ block
     const int v_per_row = hdp >> 2, v_total = SKV * v_per_row;
     const int nchq = (hd + 15) / 16;
     const int v_share = (v_total + nchq - 1) / nchq;
@@ -659,8 +694,8 @@ template <int NI, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_kv_kernel(const AttnBwdP p) {
     constexpr int NTH = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int SQ = 16 * NI;
-    constexpr int TK = 16 * NW;
+    typedef AttGeo<NI, NW> G;                                   // the same geometry with the axes swapped
+    constexpr int SQ = G::SKV, TK = G::TQ;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, g = lane >> 4;
     const int b = blockIdx.y;
@@ -670,7 +705,8 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kv_kernel(const AttnBwdP p) 
     const int jk = k0 + 16 * wave + r16;                        // this lane's key
     const int D = p.H * p.hd;
     const int hd = p.hd;
-    const int DT = (hd + 15) / 16, hdp = 16 * DT, LDV = hdp + 4;
+    const auto gh = G::at(hd);
+    const int DT = gh.DT, hdp = gh.hdp, LDV = gh.LDV;
     float* bufV = smem;                                         // whole dO_h / Q_h stripe [Sq][LDV]
     const int v_per_row = hdp >> 2, v_total = SQ * v_per_row;
     const float* qb = p.q + (long)b * p.Sq * D;
@@ -741,27 +777,37 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kv_kernel(const AttnBwdP p) 
     }
 }
 
-template <int NJ, int NW, bool LSE>
-int launch_bwd(const AttnBwdP& p, hipStream_t s) {
-    const int tiles = p.Sq / 16;
-    const int TQ = 16 * NW, SKV = 16 * NJ;
-    const int LDJ = SKV + ((SKV % 32 == 16) ? 0 : 16);
-    const int LDQ = TQ + ((TQ % 32 == 16) ? 0 : 16);
-    const int hdp = (p.hd + 15) / 16 * 16, LDV = hdp + 4;
-    const size_t lds_q = sizeof(float) * (size_t)(32 * LDJ + 32 * LDQ + SKV * LDV);
-    const size_t lds_kv = sizeof(float) * (size_t)(SKV * LDV);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<NJ, NW, LSE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
+// set the dynamic-LDS limit of a kernel, launch it, check the launch
+template <class P>
+int launch(void (*kernel)(const P), dim3 grid, int threads, size_t lds, hipStream_t s, const P& p) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds);
     if (e != hipSuccess) return (int)e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<NJ, NW>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
-    if (e != hipSuccess) return (int)e;
-    dim3 grid((tiles + NW - 1) / NW, p.B);
-    hipLaunchKernelGGL((attn_bwd_q_kernel<NJ, NW, LSE>), grid, dim3(64 * NW), lds_q, s, p);
-    CALM_LAUNCH_CHECK();
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<NJ, NW>), grid, dim3(64 * NW), lds_kv, s, p);
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, p);
     CALM_LAUNCH_CHECK();
     return 0;
+}
+
+template <class G, bool LSE>
+int launch_bwd(const AttnBwdP& p, hipStream_t s) {
+    static_assert(G::fwd_bytes(4) <= LDS_MAX, "fits at the smallest head dim; larger ones are checked per launch");
+    constexpr int NJ = G::NJ, NW = G::NW;
+    const int tiles = p.Sq / 16;
+    dim3 grid((tiles + NW - 1) / NW, p.B);
+    const int e = launch(&attn_bwd_q_kernel<NJ, NW, LSE>, grid, 64 * NW, G::bwd_q_bytes(p.hd), s, p);
+    if (e) return e;
+    return launch(&attn_bwd_kv_kernel<NJ, NW>, grid, 64 * NW, G::bwd_kv_bytes(p.hd), s, p);
+}
+
+template <class G>
+int launch_fwd(const AttnFwdP& p, hipStream_t s) {
+    static_assert(G::fwd_bytes(4) <= LDS_MAX, "fits at the smallest head dim; larger ones are checked per launch");
+    constexpr int NJ = G::NJ, NW = G::NW;
+    const int tiles = p.Sq / 16;
+    const size_t lds = G::fwd_bytes(p.hd);
+    if (lds > LDS_MAX) return CALM_E_UNSUPP;
+    dim3 grid((tiles + NW - 1) / NW, p.B);
+    return launch(&attn_fwd_kernel<NJ, NW>, grid, 64 * NW, lds, s, p);
 }
 
 #ifndef ATT_NW11
@@ -770,48 +816,27 @@ int launch_bwd(const AttnBwdP& p, hipStream_t s) {
 #ifndef ATT_NW14
 #define ATT_NW14 7     // 14-tile (S=224) instantiation
 #endif
-inline int pick_waves(int tiles) {
-    if (tiles == 11) return ATT_NW11;
-    if (tiles == 14) return ATT_NW14;
-    const int groups = (tiles + 7) / 8;
-    return (tiles + groups - 1) / groups;
-}
 
-template <int NJ, int NW>
-int launch_fwd(const AttnFwdP& p, hipStream_t s) {
-    const int tiles = p.Sq / 16;
-    const int TQ = 16 * NW;
-    const int SKV = 16 * NJ;
-    const int LDJ = SKV + ((SKV % 32 == 16) ? 0 : 16);
-    const int LDQ = TQ + ((TQ % 32 == 16) ? 0 : 16);
-    const int hdp = (p.hd + 15) / 16 * 16;
-    const int LDV = hdp + 4;
-    const int ph13 = 32 * LDJ + 32 * LDQ + SKV * LDV;       // K/Q chunk double buffers + the whole V_h
-    const int ph2 = 2 * SKV * 20 + 32 * (SKV + 4);
-    const size_t lds = sizeof(float) * (size_t)(ph13 > ph2 ? ph13 : ph2);
-    if (lds > 160 * 1024) return CALM_E_UNSUPP;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<NJ, NW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    dim3 grid((tiles + NW - 1) / NW, p.B);
-    hipLaunchKernelGGL((attn_fwd_kernel<NJ, NW>), grid, dim3(64 * NW), lds, s, p);
-    CALM_LAUNCH_CHECK();
-    return 0;
+// THE list of supported shapes: <key tiles, waves per workgroup> (Sq == Skv: the tiles of one image split evenly over
+// workgroups of at most 8 waves, but for the two measured exceptions).  f(AttGeo<NJ, NW>{}) for Skv = 16 nj.
+template <class F>
+int with_geo(int nj, F&& f) {
+    switch (nj) {
+        case 2: return f(AttGeo<2, 2>{});
+        case 3: return f(AttGeo<3, 3>{});
+        case 5: return f(AttGeo<5, 5>{});
+        case 8: return f(AttGeo<8, 8>{});
+        case 11: return f(AttGeo<11, ATT_NW11>{});
+        case 14: return f(AttGeo<14, ATT_NW14>{});
+    }
+    return CALM_E_UNSUPP;
 }
 
 int attention_bwd_dispatch(const AttnBwdP& p, bool lse, hipStream_t s) {
-    switch (p.Skv / 16) {
-        // <key tiles, waves per workgroup = pick_waves(Sq/16)>
-#define CALM_ATT_BWD(NJ, NW) case NJ: return lse ? launch_bwd<NJ, NW, true>(p, s) : launch_bwd<NJ, NW, false>(p, s)
-        CALM_ATT_BWD(2, 2);
-        CALM_ATT_BWD(3, 3);
-        CALM_ATT_BWD(5, 5);
-        CALM_ATT_BWD(8, 8);
-        CALM_ATT_BWD(11, ATT_NW11);
-        CALM_ATT_BWD(14, ATT_NW14);
-#undef CALM_ATT_BWD
-    }
-    return CALM_E_UNSUPP;
+    return with_geo(p.Skv / 16, [&](auto g) -> int {
+        typedef decltype(g) G;
+        return lse ? launch_bwd<G, true>(p, s) : launch_bwd<G, false>(p, s);
+    });
 }
 
 }  // namespace
@@ -821,14 +846,8 @@ extern "C" {
 int calm_attention_fwd_supported(int32_t Sq, int32_t Skv, int32_t H, int32_t hd) {
     if (Sq <= 0 || Skv <= 0 || H <= 0 || hd <= 0) return 0;
     if (Sq != Skv || (Sq & 15) || (hd & 3) || hd > 128) return 0;   // every attention of the model has Sq == Skv
-    const int nj = Skv / 16;
-    if (!(nj == 2 || nj == 3 || nj == 5 || nj == 8 || nj == 11 || nj == 14)) return 0;
-    // staging registers: a [Skv x 16] chunk is 4*Skv float4 (NV_K per thread), a [16 x hd_pad] V chunk 4*hd_pad
-    const int nt = 64 * pick_waves(Sq / 16);
-    const int hdp = (hd + 15) / 16 * 16, ldj = Skv + ((Skv % 32 == 16) ? 0 : 16), tq = nt / 4;
-    const int ldq = tq + ((tq % 32 == 16) ? 0 : 16);
-    if ((32 * ldj + 32 * ldq + Skv * (hdp + 4)) * 4 > 160 * 1024) return 0;   // whole V_h must fit in LDS
-    return 1;
+    // a listed shape whose whole V_h fits in LDS beside the chunk buffers
+    return with_geo(Skv / 16, [&](auto g) -> int { return decltype(g)::fwd_bytes(hd) <= LDS_MAX ? 1 : 0; }) == 1;
 }
 
 namespace {
@@ -841,16 +860,7 @@ int attention_fwd(const float* q, const float* k, const float* v, const float* w
     if (B > 65535) return CALM_E_UNSUPP;
     AttnFwdP p{q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, P, B, Sq, Skv, H, hd, 1.0f / sqrtf((float)hd), lse};
     hipStream_t s = as_stream(stream);
-    switch (Skv / 16) {
-        // <key tiles, waves per workgroup = pick_waves(Sq/16)>
-        case 2: return launch_fwd<2, 2>(p, s);
-        case 3: return launch_fwd<3, 3>(p, s);
-        case 5: return launch_fwd<5, 5>(p, s);
-        case 8: return launch_fwd<8, 8>(p, s);
-        case 11: return launch_fwd<11, ATT_NW11>(p, s);
-        case 14: return launch_fwd<14, ATT_NW14>(p, s);
-    }
-    return CALM_E_UNSUPP;
+    return with_geo(Skv / 16, [&](auto g) -> int { return launch_fwd<decltype(g)>(p, s); });
 }
 }  // namespace
 

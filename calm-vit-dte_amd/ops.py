@@ -568,10 +568,12 @@ class RopeFn(Function):
         return d_content, d_xr, d_if, None, None
 
 
-def _attn_mask_bwd(be, defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2):
-    """What follows the attention core in the fp32 attention's backward, shared by the stored-P and the row-LSE
-    function: the mask-MLP backward from dM [B*Sq,Skv] and the two dR products, accumulated into dq / dk.
+def _attn_mask_bwd(be, defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2, w1o=None, w2o=None):
+    """What follows the attention core in every attention backward (stored-P, row-LSE, bf16): the mask-MLP backward
+    from dM [B*Sq,Skv] and the two dR products, accumulated into dq / dk.  w1o / w2o are the operands of the two
+    input-gradient GEMMs (the bf16 pipeline passes its bf16 weight copies); dR takes the dtype of q.
     Returns dW1, db1, dW2, db2."""
+    w1o, w2o = w1 if w1o is None else w1o, w2 if w2o is None else w2o
     B, Sq, D = q.shape
     Skv = k.shape[1]
     dev, dt = q.device, q.dtype
@@ -580,14 +582,14 @@ def _attn_mask_bwd(be, defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u
     dW2, _ = _sn_wbwd(be, G2, w2, u2, v2, s2, defer=defer[1])
     db2 = _colsum(be, dM)
     dhp = torch.empty_like(hp)
-    _lin_dgrad(be, dM, w2, s2, dhp, act=ACT_GELU_BWD, aux=hp)
+    _lin_dgrad(be, dM, w2o, s2, dhp, act=ACT_GELU_BWD, aux=hp)
     R2 = R.view(B * Sq, Skv)
     G1 = _zeros_big(w1.shape, w1)
     _lin_wgrad(be, dhp, R2, G1)
     dW1, _ = _sn_wbwd(be, G1, w1, u1, v1, s1, defer=defer[0])
     db1 = _colsum(be, dhp)
     dR = torch.empty(B, Sq, Skv, dtype=dt, device=dev)
-    _lin_dgrad(be, dhp, w1, s1, dR.view(B * Sq, Skv))
+    _lin_dgrad(be, dhp, w1o, s1, dR.view(B * Sq, Skv))
     # dQ_all += dR K_all ; dK_all += dR^T Q_all
     be.gemm(dR, k, dq, Sq, D, Skv, (Skv, 1, Sq * Skv, 0), (1, D, Skv * D, 0), (D, Sq * D, 0), batch=(B, 1),
             accumulate=True)
@@ -766,23 +768,9 @@ class LatentMaskAttention16Fn(Function):
         dM = torch.empty(B * S, S, dtype=torch.bfloat16, device=dev)
         delta = torch.empty(B, H, S, dtype=torch.float32, device=dev)
         be.attn16_bwd(q, k, v, out, dout, Mk, MkT, lse, delta, dq, dk, dv, dM, B, S, H, hd)
-        # mask MLP backward: typed GEMMs on the bf16 tensors
-        G2 = _zeros_big(w2.shape, w2)
-        _lin_wgrad(be, dM, hg, G2)
-        dW2, _ = _sn_wbwd(be, G2, w2, u2, v2, s2, defer=ctx.defer[1])
-        db2 = _colsum(be, dM)
-        dhp = torch.empty_like(hp)
-        _lin_dgrad(be, dM, w2o, s2, dhp, act=ACT_GELU_BWD, aux=hp)
-        R2 = R.view(B * S, S)
-        G1 = _zeros_big(w1.shape, w1)
-        _lin_wgrad(be, dhp, R2, G1)
-        dW1, _ = _sn_wbwd(be, G1, w1, u1, v1, s1, defer=ctx.defer[0])
-        db1 = _colsum(be, dhp)
-        dR = torch.empty(B, S, S, dtype=torch.bfloat16, device=dev)
-        _lin_dgrad(be, dhp, w1o, s1, dR.view(B * S, S))
-        # dQ_all += dR K_all ; dK_all += dR^T Q_all  (accumulated into the bf16 gradients)
-        be.gemm(dR, k, dq, S, D, S, (S, 1, S * S, 0), (1, D, S * D, 0), (D, S * D, 0), batch=(B, 1), accumulate=True)
-        be.gemm(dR, q, dk, S, D, S, (1, S, S * S, 0), (1, D, S * D, 0), (D, S * D, 0), batch=(B, 1), accumulate=True)
+        # mask MLP backward: typed GEMMs on the bf16 tensors, the dR products accumulated into the bf16 gradients
+        dW1, db1, dW2, db2 = _attn_mask_bwd(be, ctx.defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2,
+                                            w1o=w1o, w2o=w2o)
         return dq, dk, dv, dW1, db1, dW2, db2, None, None, None, None, None, None, None
 
 
