@@ -51,6 +51,7 @@ class GemmPlan(C.Structure):
 
 
 RED_LAYERNORM_BWD, RED_ROPE_BWD, RED_LATENT_FWD, RED_COLSUM, RED_CNN_BWD = range(5)     # CALM_RED_*
+RED_SOFT_CE, RED_HUBER = 5, 6                      # the loss entry points (csrc/loss.hip)
 
 
 class OptimTensor(C.Structure):
@@ -137,6 +138,11 @@ SIGNATURES = {
     "calm_row_scale": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p]),
     "calm_mean_seq_fwd": (_i32, [_p, _p, _i32, _i32, _i32, _p]),
     "calm_mean_seq_bwd": (_i32, [_p, _p, _i32, _i32, _i32, _p]),
+    "calm_soft_ce_fwd": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i32, _i32, _p, _p]),
+    "calm_soft_ce_bwd": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i32, _i32, _p]),
+    "calm_huber_tokens_fwd": (_i32, [_p, _p, _f32, _p, _i32, _i32, _p, _p]),
+    "calm_huber_tokens_bwd": (_i32, [_p, _p, _f32, _p, _p, _i32, _i32, _p]),
+    "calm_top1_count": (_i32, [_p, _i64, _p, _p, _i32, _i32, _p]),
 }
 
 _lib = None

@@ -72,6 +72,28 @@ def get_attention_storage():
     return _attention_storage
 
 
+# The loss end of the step on the library's own kernels (csrc/loss.hip) instead of stock torch: off by default.
+_loss_kernels = os.environ.get("CALM_LOSS_KERNELS", "0") not in ("", "0")        # read once, at import
+
+
+def set_loss_kernels(on):
+    """True: trainer.soft_target_cross_entropy / RegTrainStep / evaluate run calm_soft_ce_* / calm_huber_tokens_* /
+    calm_top1_count where their conditions hold (fp32 CUDA tensors; see trainer.py).  False (default): stock torch,
+    bit for bit what the step computed before the kernels existed."""
+    global _loss_kernels
+    _loss_kernels = bool(on)
+
+
+def get_loss_kernels():
+    return _loss_kernels
+
+
+def loss_kernels_take(t):
+    """Whether the loss kernels serve tensor `t` now: the switch is on and `t` is an fp32 tensor the installed backend
+    can address (HipBackend: CUDA tensors only)."""
+    return _loss_kernels and t.dtype == torch.float32 and (t.is_cuda or not isinstance(get_backend(), HipBackend))
+
+
 def effective_precision():
     """The pipe a GEMM issued now runs on.  Inside `torch.autocast("cuda", dtype=torch.bfloat16)` — how the reference
     trainer calls the model (distributed_trainer_cls.py:84-85) — Linear/matmul operands are rounded to bf16 with fp32
@@ -699,6 +721,34 @@ class HipBackend:
                                                   B, S, hidden, int(residual),
                                                   self._partials(_lib.RED_CNN_BWD, B, S, dy.device), _stream()),
                    "calm_cnn_residual_bwd")
+
+    # ---- loss end of the step (csrc/loss.hip) -------------------------------------------
+    def soft_ce_fwd(self, logits, targets, row_stats, loss, metrics, B, C):
+        """logits / targets [B,C] with unit column stride (any row stride); row_stats [B,2], loss 0-dim, metrics [4] or None."""
+        _lib.check(self.lib.calm_soft_ce_fwd(_ptr(logits), logits.stride(0), _ptr(targets), targets.stride(0),
+                                             _ptr(row_stats), _ptr(loss), _ptr(metrics, True), B, C,
+                                             self._partials(_lib.RED_SOFT_CE, B, C, logits.device), _stream()),
+                   "calm_soft_ce_fwd")
+
+    def soft_ce_bwd(self, logits, targets, row_stats, dloss, dlogits, B, C):
+        _lib.check(self.lib.calm_soft_ce_bwd(_ptr(logits), logits.stride(0), _ptr(targets), targets.stride(0),
+                                             _ptr(row_stats), _ptr(dloss), _ptr(dlogits), B, C, _stream()),
+                   "calm_soft_ce_bwd")
+
+    def huber_tokens_fwd(self, tokens, x, delta, loss, B, S):
+        _lib.check(self.lib.calm_huber_tokens_fwd(_ptr(tokens), _ptr(x), float(delta), _ptr(loss), B, S,
+                                                  self._partials(_lib.RED_HUBER, B * S, 3 * S, tokens.device), _stream()),
+                   "calm_huber_tokens_fwd")
+
+    def huber_tokens_bwd(self, tokens, x, delta, dloss, dtokens, B, S):
+        _lib.check(self.lib.calm_huber_tokens_bwd(_ptr(tokens), _ptr(x), float(delta), _ptr(dloss), _ptr(dtokens), B, S,
+                                                  _stream()), "calm_huber_tokens_bwd")
+
+    def top1_count(self, logits, labels, metrics, B, C):
+        if not labels.is_cuda or labels.dtype != torch.int64 or not labels.is_contiguous():
+            raise TypeError("top1_count expects contiguous int64 CUDA labels")
+        _lib.check(self.lib.calm_top1_count(_ptr(logits), logits.stride(0), labels.data_ptr(), _ptr(metrics), B, C,
+                                            _stream()), "calm_top1_count")
 
     # ---- helpers ----------------------------------------------------------------------
     def add(self, a, b, out, n):

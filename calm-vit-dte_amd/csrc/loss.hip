@@ -1,0 +1,360 @@
+// The loss end of the step: soft-target cross-entropy (distributed_trainer_cls.py:63,86), the token-layout Huber loss of
+// the generative trainer (distributed_trainer_reg.py:59,78-81) and the device-side step metrics (cls:98-102,
+// CALM_ViT_V2.py:228-239).  Every cross-workgroup sum goes through the caller's `partials` and ONE final workgroup that
+// adds them in a fixed order: no atomics, results repeat bit for bit.
+#include <math.h>
+
+#include "common.h"
+
+#define LOSS_NT 256
+
+// ---- block-wide helpers (256 threads = 4 waves; `red` is >= 8 floats of LDS) -------------------------------------------
+// (value, index) maximum with ties going to the LOWEST index; NaN never wins a comparison, so it is never selected
+__device__ __forceinline__ void argmax_merge(float& v, int& i, float ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) {
+        v = ov;
+        i = oi;
+    }
+}
+__device__ __forceinline__ void wave_argmax(float& v, int& i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o, 64);
+        const int oi = __shfl_xor(i, o, 64);
+        argmax_merge(v, i, ov, oi);
+    }
+}
+__device__ __forceinline__ void block_argmax_256(float& v, int& i, float* red) {
+    wave_argmax(v, i);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        red[w] = v;
+        red[4 + w] = __int_as_float(i);
+    }
+    __syncthreads();
+    v = red[0];
+    i = __float_as_int(red[4]);
+#pragma unroll
+    for (int k = 1; k < 4; ++k) argmax_merge(v, i, red[k], __float_as_int(red[4 + k]));
+}
+
+// ---- soft-target cross-entropy -----------------------------------------------------------------------------------------
+// One workgroup per row.  Pass 1: row maximum (with its index), the targets' maximum index, sum of the targets, NaN flag.
+// Pass 2 (the row is 4 KB at C = 1000: it comes back from the cache): sum exp(z - max) and sum y (max - z).
+//   row loss = sum_c y_c (max - z_c) + log(sum exp(z - max)) * sum_c y_c
+// — both terms are sums of non-negative products for probability targets, nothing cancels (lse * sum y - sum y z would).
+// c4: number of leading float4 groups of a row that may be read as 16-byte vectors (0: scalar path for the whole row).
+static __global__ __launch_bounds__(LOSS_NT) void soft_ce_fwd_kernel(const float* __restrict__ logits, long ld,
+                                                                     const float* __restrict__ targets, long td,
+                                                                     float* __restrict__ row_stats,
+                                                                     float* __restrict__ partials, int B, int C, int c4) {
+    __shared__ float red[8];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* z = logits + (long)b * ld;
+    const float* y = targets + (long)b * td;
+    float zm = -INFINITY, ym = -INFINITY, ysum = 0.f;
+    int zi = 0x7fffffff, yi = 0x7fffffff;
+    bool bad = false;
+    for (int q = tid; q < c4; q += LOSS_NT) {
+        const f32x4 zv = *reinterpret_cast<const f32x4*>(z + 4 * q);
+        const f32x4 yv = *reinterpret_cast<const f32x4*>(y + 4 * q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            bad |= (zv[k] != zv[k]) | (yv[k] != yv[k]);
+            if (zv[k] > zm) { zm = zv[k]; zi = 4 * q + k; }
+            if (yv[k] > ym) { ym = yv[k]; yi = 4 * q + k; }
+            ysum += yv[k];
+        }
+    }
+    for (int c = 4 * c4 + tid; c < C; c += LOSS_NT) {
+        const float zc = z[c], yc = y[c];
+        bad |= (zc != zc) | (yc != yc);
+        if (zc > zm) { zm = zc; zi = c; }
+        if (yc > ym) { ym = yc; yi = c; }
+        ysum += yc;
+    }
+    // a thread that saw only -inf (or nothing) still holds index INT_MAX: the merge prefers any real index at equal value
+    if (zm == -INFINITY && zi == 0x7fffffff && tid < C) zi = tid;
+    if (ym == -INFINITY && yi == 0x7fffffff && tid < C) yi = tid;
+    block_argmax_256(zm, zi, red);
+    block_argmax_256(ym, yi, red);
+    ysum = block_sum_256(ysum, red);
+    const float nbad = block_sum_256(bad ? 1.f : 0.f, red);
+
+    float se = 0.f, yd = 0.f;
+    for (int q = tid; q < c4; q += LOSS_NT) {
+        const f32x4 zv = *reinterpret_cast<const f32x4*>(z + 4 * q);
+        const f32x4 yv = *reinterpret_cast<const f32x4*>(y + 4 * q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            se += __expf(zv[k] - zm);
+            yd = fmaf(yv[k], zm - zv[k], yd);
+        }
+    }
+    for (int c = 4 * c4 + tid; c < C; c += LOSS_NT) {
+        se += __expf(z[c] - zm);
+        yd = fmaf(y[c], zm - z[c], yd);
+    }
+    se = block_sum_256(se, red);
+    yd = block_sum_256(yd, red);
+    if (tid == 0) {
+        const float ls = logf(se);
+        row_stats[2 * b] = zm;
+        row_stats[2 * b + 1] = ls;
+        partials[b] = fmaf(ls, ysum, yd);
+        partials[B + b] = (nbad == 0.f && zi == yi) ? 1.f : 0.f;
+    }
+}
+
+// The final pass of both losses: ONE workgroup adds n partials in a fixed order (thread t takes t, t + 256, ... in
+// increasing index, then a fixed tree over the 256 running sums) and OVERWRITES the loss.  metrics (nullable) is the
+// caller's float[4]; it is updated by one thread with a plain read-modify-write, ordered by the stream.
+static __global__ __launch_bounds__(LOSS_NT) void loss_final_kernel(const float* __restrict__ part, int n, float scale,
+                                                                    float* __restrict__ loss, const float* __restrict__ agree,
+                                                                    float* __restrict__ metrics, int B) {
+    __shared__ float red[8];
+    float s = 0.f, a = 0.f;
+    for (int g = threadIdx.x; g < n; g += LOSS_NT) s += part[g];
+    if (metrics)
+        for (int g = threadIdx.x; g < B; g += LOSS_NT) a += agree[g];
+    s = block_sum_256(s, red);
+    a = block_sum_256(a, red);
+    if (threadIdx.x == 0) {
+        loss[0] = s * scale;
+        if (metrics) {
+            metrics[0] += s;
+            metrics[1] += a;
+            metrics[2] += (float)B;
+            metrics[3] += 1.f;
+        }
+    }
+}
+
+// dlogits = dloss / B * (exp((z - max) - logsum) * sum_c y - y): one workgroup per row, sum_c y rebuilt in a fixed order
+static __global__ __launch_bounds__(LOSS_NT) void soft_ce_bwd_kernel(const float* __restrict__ logits, long ld,
+                                                                     const float* __restrict__ targets, long td,
+                                                                     const float* __restrict__ row_stats,
+                                                                     const float* __restrict__ dloss,
+                                                                     float* __restrict__ dlogits, int B, int C, int c4) {
+    __shared__ float red[8];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* z = logits + (long)b * ld;
+    const float* y = targets + (long)b * td;
+    float* dz = dlogits + (long)b * C;
+    float ysum = 0.f;
+    for (int q = tid; q < c4; q += LOSS_NT) {
+        const f32x4 yv = *reinterpret_cast<const f32x4*>(y + 4 * q);
+        ysum += (yv[0] + yv[1]) + (yv[2] + yv[3]);
+    }
+    for (int c = 4 * c4 + tid; c < C; c += LOSS_NT) ysum += y[c];
+    ysum = block_sum_256(ysum, red);
+    const float zm = row_stats[2 * b], ls = row_stats[2 * b + 1];
+    const float g = dloss[0] / (float)B;
+    for (int q = tid; q < c4; q += LOSS_NT) {
+        const f32x4 zv = *reinterpret_cast<const f32x4*>(z + 4 * q);
+        const f32x4 yv = *reinterpret_cast<const f32x4*>(y + 4 * q);
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = g * fmaf(__expf((zv[k] - zm) - ls), ysum, -yv[k]);
+        *reinterpret_cast<f32x4*>(dz + 4 * q) = o;
+    }
+    for (int c = 4 * c4 + tid; c < C; c += LOSS_NT) dz[c] = g * fmaf(__expf((z[c] - zm) - ls), ysum, -y[c]);
+}
+
+// ---- top-1 count against integer labels --------------------------------------------------------------------------------
+// ONE workgroup of 16 waves, a wave per row in turn (the eval loop's metric: B x C floats through one CU); the count is
+// combined through LDS and added to the caller's metrics by one thread.
+#define TOP1_NT 1024
+static __global__ __launch_bounds__(TOP1_NT) void top1_count_kernel(const float* __restrict__ logits, long ld,
+                                                                    const long long* __restrict__ labels,
+                                                                    float* __restrict__ metrics, int B, int C, int c4) {
+    __shared__ float cnt[TOP1_NT / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float hits = 0.f;
+    for (int b = w; b < B; b += TOP1_NT / 64) {
+        const float* z = logits + (long)b * ld;
+        float zm = -INFINITY;
+        int zi = 0x7fffffff;
+        bool bad = false;
+        for (int q = lane; q < c4; q += 64) {
+            const f32x4 zv = *reinterpret_cast<const f32x4*>(z + 4 * q);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                bad |= zv[k] != zv[k];
+                if (zv[k] > zm) { zm = zv[k]; zi = 4 * q + k; }
+            }
+        }
+        for (int c = 4 * c4 + lane; c < C; c += 64) {
+            const float zc = z[c];
+            bad |= zc != zc;
+            if (zc > zm) { zm = zc; zi = c; }
+        }
+        if (zm == -INFINITY && zi == 0x7fffffff && lane < C) zi = lane;
+        wave_argmax(zm, zi);
+        const bool any_bad = __any(bad);
+        if (!any_bad && (long long)zi == labels[b]) hits += 1.f;      // (every lane holds the same row result)
+    }
+    if (lane == 0) cnt[w] = hits;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < TOP1_NT / 64; ++k) t += cnt[k];
+        metrics[1] += t;
+        metrics[2] += (float)B;
+    }
+}
+
+// ---- token-layout Huber ------------------------------------------------------------------------------------------------
+// A token row (b,i) is 3S contiguous floats, tokens[b,i,3j+c], against the three S-float rows x[b,c,i,:].  A workgroup
+// takes R consecutive token rows per turn: the 3R image rows are staged into LDS with 16-byte loads ([r][c][j], the
+// channel planes side by side), then every thread reads 16 bytes of tokens and picks its four partners from LDS — the
+// interleave happens on chip, both tensors stream through coalesced vector accesses.  Dynamic LDS: R * 3S floats, then 8
+// floats for the block sum (nothing static in front of it: the 16-byte carve stays aligned).
+struct HuberGeom {
+    int S, R, row4, groups;       // row4 = 3S/4 float4 per token row; groups = ceil(B*S / R)
+    long rows;                    // B*S
+};
+
+template <bool BWD>
+static __global__ __launch_bounds__(LOSS_NT) void huber_tokens_kernel(const float* __restrict__ tokens,
+                                                                      const float* __restrict__ x, float delta,
+                                                                      const float* __restrict__ dloss,
+                                                                      float* __restrict__ out, const HuberGeom g) {
+    extern __shared__ f32x4 huber_lds[];
+    float* xs = reinterpret_cast<float*>(huber_lds);
+    const int S = g.S, row4 = g.row4, s4 = S >> 2, tid = threadIdx.x;
+    float* red = xs + (long)g.R * 3 * S;
+    float acc = 0.f;
+    float scale = 0.f;
+    if (BWD) scale = dloss[0] / (3.f * (float)g.rows * (float)S);
+    for (int grp = blockIdx.x; grp < g.groups; grp += gridDim.x) {
+        const long r0 = (long)grp * g.R;
+        const long left = g.rows - r0;
+        const int nr = left < g.R ? (int)left : g.R;
+        const int n4 = nr * row4;
+        for (int q = tid; q < n4; q += LOSS_NT) {
+            const int rr = q / row4, rem = q - rr * row4;
+            const int c = rem / s4, j4 = rem - c * s4;
+            const long r = r0 + rr;
+            const long b = r / S, i = r - b * S;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(x + (((b * 3 + c) * S + i) * S + 4 * j4));
+            *reinterpret_cast<f32x4*>(xs + (rr * 3 + c) * S + 4 * j4) = v;
+        }
+        __syncthreads();
+        for (int q = tid; q < n4; q += LOSS_NT) {
+            const int rr = q / row4, rem = q - rr * row4;
+            const long off = (r0 + rr) * 3 * S + 4 * rem;
+            const f32x4 t = *reinterpret_cast<const f32x4*>(tokens + off);
+            const float* xr = xs + rr * 3 * S;
+            f32x4 o;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int e = 4 * rem + k;
+                const int j = e / 3, c = e - 3 * j;
+                const float d = t[k] - xr[c * S + j];
+                if (BWD) {
+                    o[k] = scale * fminf(fmaxf(d, -delta), delta);
+                    if (d != d) o[k] = d;                       // (fminf / fmaxf drop a NaN: hand it on)
+                } else {
+                    const float ad = fabsf(d);
+                    acc += ad <= delta ? 0.5f * d * d : (ad != ad ? d : delta * (ad - 0.5f * delta));
+                }
+            }
+            if (BWD) *reinterpret_cast<f32x4*>(out + off) = o;
+        }
+        __syncthreads();
+    }
+    if (!BWD) {
+        acc = block_sum_256(acc, red);
+        if (tid == 0) out[blockIdx.x] = acc;
+    }
+}
+
+#define HUBER_MAX_GRID 2048
+static bool huber_geom(int B, int S, HuberGeom* g) {
+    if ((S & 3) != 0 || S > 4096) return false;                 // 3S floats of LDS per token row: 48 KB at S = 4096
+    g->S = S;
+    g->row4 = 3 * S / 4;
+    const int r = 768 / g->row4;                               // ~3 float4 per thread and turn
+    g->R = r < 1 ? 1 : r;
+    g->rows = (long)B * S;
+    const long groups = (g->rows + g->R - 1) / g->R;
+    if (groups > 0x7fffffffl) return false;
+    g->groups = (int)groups;
+    return true;
+}
+static inline int huber_grid(const HuberGeom& g) { return g.groups < HUBER_MAX_GRID ? g.groups : HUBER_MAX_GRID; }
+static inline size_t huber_lds_bytes(const HuberGeom& g) { return ((size_t)g.R * 3 * g.S + 8) * sizeof(float); }
+
+extern "C" {
+
+static inline int vec_groups(const float* a, long lda, const float* b, long ldb, int C) {
+    return (aligned16(a) && aligned16(b) && (lda & 3) == 0 && (ldb & 3) == 0) ? C >> 2 : 0;
+}
+
+int calm_soft_ce_fwd(const float* logits, int64_t ld, const float* targets, int64_t td, float* row_stats, float* loss,
+                     float* metrics, int32_t B, int32_t C, float* partials, void* stream) {
+    if (!logits || !targets || !row_stats || !loss || !partials || B <= 0 || C <= 0) return CALM_E_INVAL;
+    hipStream_t s = as_stream(stream);
+    const int c4 = vec_groups(logits, (long)ld, targets, (long)td, C);
+    hipLaunchKernelGGL(soft_ce_fwd_kernel, dim3(B), dim3(LOSS_NT), 0, s, logits, (long)ld, targets, (long)td, row_stats,
+                       partials, B, C, c4);
+    CALM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(LOSS_NT), 0, s, partials, B, 1.0f / (float)B, loss, partials + B,
+                       metrics, B);
+    CALM_LAUNCH_CHECK();
+    return 0;
+}
+
+int calm_soft_ce_bwd(const float* logits, int64_t ld, const float* targets, int64_t td, const float* row_stats,
+                     const float* dloss, float* dlogits, int32_t B, int32_t C, void* stream) {
+    if (!logits || !targets || !row_stats || !dloss || !dlogits || B <= 0 || C <= 0) return CALM_E_INVAL;
+    const int c4 = (C & 3) == 0 && aligned16(dlogits) ? vec_groups(logits, (long)ld, targets, (long)td, C) : 0;
+    hipLaunchKernelGGL(soft_ce_bwd_kernel, dim3(B), dim3(LOSS_NT), 0, as_stream(stream), logits, (long)ld, targets,
+                       (long)td, row_stats, dloss, dlogits, B, C, c4);
+    CALM_LAUNCH_CHECK();
+    return 0;
+}
+
+int calm_top1_count(const float* logits, int64_t ld, const int64_t* labels, float* metrics, int32_t B, int32_t C,
+                    void* stream) {
+    if (!logits || !labels || !metrics || B <= 0 || C <= 0) return CALM_E_INVAL;
+    const int c4 = aligned16(logits) && (ld & 3) == 0 ? C >> 2 : 0;
+    hipLaunchKernelGGL(top1_count_kernel, dim3(1), dim3(TOP1_NT), 0, as_stream(stream), logits, (long)ld,
+                       reinterpret_cast<const long long*>(labels), metrics, B, C, c4);
+    CALM_LAUNCH_CHECK();
+    return 0;
+}
+
+int calm_huber_tokens_fwd(const float* tokens, const float* x, float delta, float* loss, int32_t B, int32_t S,
+                          float* partials, void* stream) {
+    if (!tokens || !x || !loss || !partials || B <= 0 || S <= 0) return CALM_E_INVAL;
+    HuberGeom g;
+    if (!huber_geom(B, S, &g)) return CALM_E_UNSUPP;
+    if (!aligned16(tokens) || !aligned16(x)) return CALM_E_LAYOUT;
+    hipStream_t s = as_stream(stream);
+    const int grid = huber_grid(g);
+    hipLaunchKernelGGL(huber_tokens_kernel<false>, dim3(grid), dim3(LOSS_NT), huber_lds_bytes(g), s, tokens, x, delta,
+                       (const float*)nullptr, partials, g);
+    CALM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(LOSS_NT), 0, s, partials, grid,
+                       1.0f / (3.0f * (float)g.rows * (float)S), loss, (const float*)nullptr, (float*)nullptr, 0);
+    CALM_LAUNCH_CHECK();
+    return 0;
+}
+
+int calm_huber_tokens_bwd(const float* tokens, const float* x, float delta, const float* dloss, float* dtokens, int32_t B,
+                          int32_t S, void* stream) {
+    if (!tokens || !x || !dloss || !dtokens || B <= 0 || S <= 0) return CALM_E_INVAL;
+    HuberGeom g;
+    if (!huber_geom(B, S, &g)) return CALM_E_UNSUPP;
+    if (!aligned16(tokens) || !aligned16(x) || !aligned16(dtokens)) return CALM_E_LAYOUT;
+    hipLaunchKernelGGL(huber_tokens_kernel<true>, dim3(huber_grid(g)), dim3(LOSS_NT), huber_lds_bytes(g),
+                       as_stream(stream), tokens, x, delta, dloss, dtokens, g);
+    CALM_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

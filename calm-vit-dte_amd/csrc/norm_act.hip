@@ -1110,6 +1110,8 @@ int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols) {
             return a > b ? a : b;
         }
         case CALM_RED_CNN_BWD: return (int64_t)256 * 560;       // cnn_fused.hip: grid <= 256 rows of CNN_PART_STRIDE
+        case CALM_RED_SOFT_CE: return 2 * rows;                 // loss.hip: the B row losses, then the B agreement flags
+        case CALM_RED_HUBER: return 2048;                       // loss.hip: grid <= HUBER_MAX_GRID block sums
         default: return 0;
     }
 }

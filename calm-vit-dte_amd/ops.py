@@ -824,6 +824,77 @@ class LatentFn(Function):
         return dmv, None
 
 
+def _dloss(g):
+    """The gradient arriving for a scalar loss as the fp32 device scalar the loss kernels read (it carries
+    GradScaler's scale): no host read."""
+    return g.to(torch.float32).reshape(1).contiguous()
+
+
+def _rows_unit_stride(t):
+    return t if t.stride(-1) == 1 else t.contiguous()
+
+
+class SoftTargetCrossEntropyFn(Function):
+    """nn.CrossEntropyLoss() with class-probability targets, mean over the batch (cls:63,86): logits, targets [B,C] fp32 ->
+    0-dim fp32 loss.  metrics: a device float[4] (trainer.StepMetrics) that the forward adds this step's loss sum,
+    dominant-class agreement count (cls:98-102), row count and step count to, or None."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, logits, targets, metrics=None):
+        be = get_backend()
+        logits, targets = _rows_unit_stride(logits), _rows_unit_stride(targets)
+        B, C = logits.shape
+        if targets.shape != logits.shape:
+            raise ValueError("soft-target cross-entropy expects targets of the logits' shape")
+        row_stats = torch.empty(B, 2, dtype=torch.float32, device=logits.device)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        be.soft_ce_fwd(logits, targets, row_stats, loss, metrics, B, C)
+        ctx.save_for_backward(logits, targets, row_stats)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    @_amp_bwd
+    def backward(ctx, g):
+        be = get_backend()
+        logits, targets, row_stats = ctx.saved_tensors
+        B, C = logits.shape
+        dlogits = torch.empty(B, C, dtype=torch.float32, device=logits.device)
+        be.soft_ce_bwd(logits, targets, row_stats, _dloss(g), dlogits, B, C)
+        return dlogits, None, None
+
+
+class HuberTokensFn(Function):
+    """nn.HuberLoss(delta) between the generative model's tokens [B,S,3S] and the image x [B,3,S,S] (reg:59,78-81): the
+    tokens are the channels-last image, so the reference's reshape + permute is index arithmetic inside the kernel."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, tokens, x, delta=1.0):
+        be = get_backend()
+        tokens, x = _c(tokens), _c(x)
+        B, S, W = tokens.shape
+        if W != 3 * S or tuple(x.shape) != (B, 3, S, S):
+            raise ValueError("HuberTokensFn expects tokens [B,S,3S] and x [B,3,S,S]")
+        loss = torch.empty((), dtype=torch.float32, device=tokens.device)
+        be.huber_tokens_fwd(tokens, x, delta, loss, B, S)
+        ctx.save_for_backward(tokens, x)
+        ctx.delta = float(delta)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    @_amp_bwd
+    def backward(ctx, g):
+        be = get_backend()
+        tokens, x = ctx.saved_tensors
+        B, S, _ = tokens.shape
+        dtokens = torch.empty_like(tokens)
+        be.huber_tokens_bwd(tokens, x, ctx.delta, _dloss(g), dtokens, B, S)
+        return dtokens, None, None
+
+
 class AddFn(Function):
     """Residual / U-net skip adds (Vi_Tools:309,315,403,513-522) and the latent running sum (43-44)."""
 

@@ -192,16 +192,46 @@ class BucketedGradReducer:
             b["pending"] = len(b["params"])
 
 
-def soft_target_cross_entropy(logits, soft_targets):
-    """torch.nn.CrossEntropyLoss() with class-probability targets (cls:63,86; CutMix/MixUp labels)."""
+def soft_target_cross_entropy(logits, soft_targets, metrics=None):
+    """torch.nn.CrossEntropyLoss() with class-probability targets (cls:63,86; CutMix/MixUp labels).
+
+    With the loss kernels switched on (backend.set_loss_kernels / CALM_LOSS_KERNELS=1) a 2-D fp32 CUDA logits tensor with
+    fp32 targets goes through calm_soft_ce_fwd / _bwd (ops.SoftTargetCrossEntropyFn); `metrics` (a StepMetrics) then
+    receives the step's loss sum and dominant-class agreement on the device.  Everything else — the switch off, 1-D logits
+    (squeeze() at batch 1), CPU tensors, other dtypes — is F.cross_entropy as before."""
+    from . import backend
+    if (backend.get_loss_kernels() and logits.dim() == 2 and soft_targets.dtype == torch.float32
+            and soft_targets.shape == logits.shape and backend.loss_kernels_take(logits)):
+        from .ops import SoftTargetCrossEntropyFn
+        return SoftTargetCrossEntropyFn.apply(logits, soft_targets, None if metrics is None else metrics.buf)
     return torch.nn.functional.cross_entropy(logits, soft_targets)
+
+
+class StepMetrics:
+    """The device float[4] that calm_soft_ce_fwd / calm_top1_count add to (include/calm_vit.h): loss sum, agreement
+    count, rows, steps.  A training loop hands it to its steps and reads it once per epoch — one device-to-host copy
+    instead of a `loss.item()` per step (cls:97)."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(4, dtype=torch.float32, device=device)
+
+    def read(self):
+        """(loss_sum, agree, rows, steps) as Python numbers: ONE device-to-host copy.  The counts are fp32 on the device,
+        exact below 2^24; read and reset() before an accumulation period exceeds that."""
+        loss_sum, agree, rows, steps = self.buf.to("cpu").tolist()
+        return float(loss_sum), int(agree), int(rows), int(steps)
+
+    def reset(self):
+        self.buf.zero_()                    # in place: a captured step keeps adding at this address
 
 
 class TrainStep:
     """One iteration of distributed_trainer_cls.py:79-96 (per rank)."""
 
-    def __init__(self, model, optimizer, reducer=None, max_norm=1.0, scaler=None, autocast_dtype=None):
+    def __init__(self, model, optimizer, reducer=None, max_norm=1.0, scaler=None, autocast_dtype=None, metrics=None):
+        """metrics: a StepMetrics the loss kernel accumulates into (only with the loss kernels switched on)."""
         self.model, self.opt, self.reducer = model, optimizer, reducer
+        self.metrics = metrics
         self.max_norm = max_norm
         self.scaler = scaler
         self.autocast_dtype = autocast_dtype          # torch.bfloat16: the reference's `with autocast(...)` (cls:84)
@@ -211,7 +241,7 @@ class TrainStep:
         with torch.autocast(device_type="cuda", dtype=self.autocast_dtype or torch.bfloat16,
                             enabled=self.autocast_dtype is not None and x.is_cuda):        # cls:84
             y_hat, _ = self.model(x)                                       # cls:85
-            loss = soft_target_cross_entropy(y_hat.squeeze(), y_soft)      # cls:86
+            loss = soft_target_cross_entropy(y_hat.squeeze(), y_soft, self.metrics)      # cls:86
         return self._finish(loss, y_hat)
 
     def _finish(self, loss, y_hat):
@@ -273,9 +303,21 @@ class RegTrainStep(TrainStep):
         with torch.autocast(device_type="cuda", dtype=self.autocast_dtype or torch.bfloat16,
                             enabled=self.autocast_dtype is not None and x.is_cuda):        # reg:76
             y_hat, kl = self.model(x)                                      # reg:77
-            img = y_hat.reshape(-1, S, S, 3).permute(0, 3, 1, 2)           # reg:78-79
-            loss = torch.nn.functional.huber_loss(img, x) + kl * self.kl_weight   # reg:81,87
+            img = y_hat.reshape(-1, S, S, 3).permute(0, 3, 1, 2)           # reg:78-79 (a view)
+            loss = self._huber(y_hat, img, x) + kl * self.kl_weight        # reg:81,87
         return self._finish(loss, img)
+
+    @staticmethod
+    def _huber(tokens, img, x):
+        """nn.HuberLoss() (reg:59, delta = 1): on the token layout through calm_huber_tokens_* when the loss kernels are
+        switched on and serve the shape (S % 4 == 0, fp32), stock torch on the permuted view otherwise."""
+        from . import backend
+        if (backend.get_loss_kernels() and tokens.dim() == 3 and x.dim() == 4 and x.dtype == torch.float32
+                and x.shape[-1] % 4 == 0 and x.shape[-1] <= 4096 and tokens.shape[0] == x.shape[0]
+                and backend.loss_kernels_take(tokens)):
+            from .ops import HuberTokensFn
+            return HuberTokensFn.apply(tokens, x, 1.0)
+        return torch.nn.functional.huber_loss(img, x)
 
 
 class DeviceCollate:
@@ -331,15 +373,30 @@ class DeviceCollate:
 
 
 def evaluate(model, batches):
-    """Top-1 accuracy over (x, labels) batches in eval mode (CALM_ViT_V2.py:228-239)."""
+    """Top-1 accuracy over (x, labels) batches in eval mode (CALM_ViT_V2.py:228-239).  With the loss kernels switched on
+    the hits are counted on the device (calm_top1_count into a StepMetrics) and read once after the last batch instead of
+    once per batch."""
+    from . import backend
     was_training = model.training
     model.eval()
     correct = total = 0
+    metrics = None
     with torch.no_grad():
         for x, labels in batches:
             y_hat, _ = model(x)
-            correct += int((y_hat.reshape(x.shape[0], -1).argmax(dim=1) == labels).sum())
+            logits = y_hat.reshape(x.shape[0], -1)
+            if backend.get_loss_kernels() and labels.dim() == 1 and backend.loss_kernels_take(logits):
+                if metrics is None:
+                    metrics = StepMetrics(logits.device)
+                logits = logits if logits.stride(-1) == 1 else logits.contiguous()
+                backend.get_backend().top1_count(logits, labels.to(logits.device, torch.int64).contiguous(), metrics.buf,
+                                                 logits.shape[0], logits.shape[1])
+                continue
+            correct += int((logits.argmax(dim=1) == labels).sum())
             total += int(labels.numel())
+    if metrics is not None:
+        _, hits, rows, _ = metrics.read()
+        correct, total = correct + hits, total + rows
     model.train(was_training)
     return correct / max(total, 1)
 
@@ -547,7 +604,7 @@ class GraphedTrainStep:
     capture, so that the first replay is step 1 of the run — the replayed trajectory then equals the eager one."""
 
     def __init__(self, model, optimizer, example_x, example_y, max_norm=1.0, warmup=3, scaler=None, autocast_dtype=None,
-                 reducer=None, restore_after_warmup=False):
+                 reducer=None, restore_after_warmup=False, metrics=None):
         """reducer: a BucketedGradReducer whose bucket copies and RCCL all-reduces are captured with the step (round 4:
         the collectives are issued in the capture-compatible form, see BucketedGradReducer._launch; exercised in a world
         of one in a child process by scripts/rccl_capture_check.py — DESIGN.md section 6 records the outcome)."""
@@ -555,7 +612,9 @@ class GraphedTrainStep:
             # the captured step would contain no gradient exchange: replicas would silently train apart
             raise RuntimeError("GraphedTrainStep captures a single-GPU step unless it is given the BucketedGradReducer "
                                "to capture with it; with world_size > 1 pass reducer=... or use TrainStep")
-        self.inner = TrainStep(model, optimizer, reducer, max_norm=max_norm, scaler=scaler, autocast_dtype=autocast_dtype)
+        # metrics: the StepMetrics buffer's address is baked into the graph, so replays keep accumulating into it
+        self.inner = TrainStep(model, optimizer, reducer, max_norm=max_norm, scaler=scaler, autocast_dtype=autocast_dtype,
+                               metrics=metrics)
         self.opt = optimizer
         if isinstance(optimizer, FusedClipAdamW):
             optimizer.lr_on_device = True          # replays read the learning rate from a device scalar
@@ -566,7 +625,7 @@ class GraphedTrainStep:
             if not isinstance(optimizer, FusedClipAdamW):
                 raise ValueError("restore_after_warmup needs FusedClipAdamW (its whole state is a known set of tensors)")
             live = list(model.parameters()) + list(model.buffers()) + optimizer.exp_avg + optimizer.exp_avg_sq + \
-                [optimizer._plan.step_dev]
+                [optimizer._plan.step_dev] + ([metrics.buf] if metrics is not None else [])
             snap = ([(t, t.detach().clone()) for t in live], torch.cuda.get_rng_state(example_x.device),
                     None if scaler is None or not scaler.is_enabled() else scaler.get_scale())
         side = torch.cuda.Stream()
@@ -669,7 +728,8 @@ class SoftMixCollate:
 
 def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, epochs=15, batch_size=128,
           checkpoint_path=None, num_classes=1000, num_workers=0, collate_fn="mix", log_every=100, max_steps=None,
-          destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise"):
+          destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
+          device_metrics=False):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -706,8 +766,17 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     all-reduces of a world > 1, unscale / clip / AdamW — is captured into a hipGraph on the first batch
     (GraphedTrainStep with restore_after_warmup: the capture's warm-up steps are undone) and replayed per batch: one
     graph launch of host work per step instead of ~3000 kernel launches.  The DataLoader then drops the last partial
-    batch of an epoch (a graph has one batch shape); a batch of any other shape would run the eager step."""
+    batch of an epoch (a graph has one batch shape); a batch of any other shape would run the eager step.
+
+    device_metrics=True (GPU, loss kernels switched on — backend.set_loss_kernels / CALM_LOSS_KERNELS=1): the per-step
+    `epoch_loss += loss.item()` of cls:97 — a host sync per step whose sum nothing reads — is dropped; the loss kernel
+    accumulates loss and dominant-class agreement in a StepMetrics buffer on the device and rank 0 prints one line per
+    epoch from a single read of it.  The log_every lines are unchanged (they synchronise as before)."""
     from torch.utils.data import DataLoader, DistributedSampler
+    from . import backend as _backend
+    if device_metrics and not (use_gpu and _backend.get_loss_kernels()):
+        raise ValueError("device_metrics=True needs use_gpu=True and the loss kernels switched on "
+                         "(backend.set_loss_kernels(True) or CALM_LOSS_KERNELS=1)")
     if device_collate and not use_gpu:                     # (argument errors before any process group exists)
         raise ValueError("device_collate=True needs use_gpu=True (the collate is a HIP kernel)")
     if graph and not (use_gpu and (optimizer == "fused" or isinstance(optimizer, FusedClipAdamW))):
@@ -748,8 +817,9 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     loader = DataLoader(dataset, batch_size=batch_size, sampler=sampler, collate_fn=collate_fn, num_workers=num_workers,
                         pin_memory=use_gpu, persistent_workers=num_workers > 0, drop_last=bool(graph))
     scaler = torch.amp.GradScaler("cuda", enabled=use_gpu)                                                 # cls:64
+    metrics = StepMetrics(device) if device_metrics else None
     step = TrainStep(model, optimizer, reducer, max_norm=1.0, scaler=scaler if use_gpu else None,
-                     autocast_dtype=torch.bfloat16 if use_gpu else None)
+                     autocast_dtype=torch.bfloat16 if use_gpu else None, metrics=metrics)
     model.train()
     n_steps = 0
     gstep = None
@@ -764,12 +834,14 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                     x, y = dcoll(x, y.long(), crop=crop, tokens=True)   # uint8 batch -> row tokens + soft labels
                 if graph and gstep is None:
                     gstep = GraphedTrainStep(model, optimizer, x, y, max_norm=1.0, scaler=scaler,
-                                             autocast_dtype=torch.bfloat16, reducer=reducer, restore_after_warmup=True)
+                                             autocast_dtype=torch.bfloat16, reducer=reducer, restore_after_warmup=True,
+                                             metrics=metrics)
                 if gstep is not None and x.shape == gstep.x.shape and y.shape == gstep.y.shape:
                     loss, y_hat = gstep(x, y)
                 else:
                     loss, y_hat = step(x, y)
-                epoch_loss += loss.item()                                                                  # cls:97
+                if metrics is None:
+                    epoch_loss += loss.item()                                                              # cls:97
                 if rank == 0 and local_rank == 0 and i % log_every == 0:
                     correct = (y_hat.reshape(y.shape[0], -1).argmax(1) == y.argmax(1)).sum().item()
                     print(f"Epoch: {epoch + 1}, Batch: {i + 1}, Device: [{rank}, {local_rank}], Loss: {float(loss)}, "
@@ -777,6 +849,12 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                 n_steps += 1
                 if max_steps is not None and n_steps >= max_steps:
                     break
+            if metrics is not None:
+                loss_sum, agree, rows, _ = metrics.read()          # the epoch's one device-to-host copy
+                metrics.reset()
+                if rank == 0 and local_rank == 0:
+                    print(f"Epoch: {epoch + 1}, Device: [{rank}, {local_rank}], Mean loss: {loss_sum / max(rows, 1)}, "
+                          f"Dominant-class accuracy: {100.0 * agree / max(rows, 1):.4f}%")
             if rank == 0 and local_rank == 0 and checkpoint_path:
                 os.makedirs(os.path.dirname(os.path.abspath(checkpoint_path)), exist_ok=True)
                 torch.save(model.state_dict(), checkpoint_path)                                            # cls:105-107

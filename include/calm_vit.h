@@ -182,8 +182,11 @@ int calm_gemm_describe(const calm_gemm_args* args, calm_gemm_plan* plan);
  *   CALM_RED_LATENT_FWD       rows                 mvh
  *   CALM_RED_COLSUM           rows                 cols
  *   CALM_RED_CNN_BWD          B                    S
+ *   CALM_RED_SOFT_CE          B                    C            (the loss entry points, additions to ABI v7)
+ *   CALM_RED_HUBER            B*S                  3S
  * ------------------------------------------------------------------------------------- */
-enum { CALM_RED_LAYERNORM_BWD = 0, CALM_RED_ROPE_BWD = 1, CALM_RED_LATENT_FWD = 2, CALM_RED_COLSUM = 3, CALM_RED_CNN_BWD = 4 };
+enum { CALM_RED_LAYERNORM_BWD = 0, CALM_RED_ROPE_BWD = 1, CALM_RED_LATENT_FWD = 2, CALM_RED_COLSUM = 3, CALM_RED_CNN_BWD = 4,
+       CALM_RED_SOFT_CE = 5, CALM_RED_HUBER = 6 };
 int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols);
 
 /* ---------------------------------------------------------------------------------------
@@ -513,6 +516,49 @@ int calm_row_scale(const float* x, const float* s, void* out, int32_t rows, int3
                    void* stream);
 int calm_mean_seq_fwd(const float* x, float* y, int32_t B, int32_t S, int32_t D, void* stream);
 int calm_mean_seq_bwd(const float* dy, float* dx, int32_t B, int32_t S, int32_t D, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The loss end of the step (additions to ABI v7 — no existing signature or struct changes, so the version number
+ * stays): logits -> loss and loss -> dL/dlogits as entry points, so that a host driving this boundary without torch can
+ * train (forward, one of these, backward, calm_optim_step).  Logits are fp32 (module outputs stay fp32 in every
+ * precision mode).  Cross-workgroup sums go through `partials` (calm_reduce_scratch_floats with CALM_RED_SOFT_CE /
+ * CALM_RED_HUBER) and one final workgroup that adds them in a fixed order: no atomics, results repeat bit for bit.
+ *
+ * calm_soft_ce_fwd / _bwd: nn.CrossEntropyLoss() with class-probability targets (distributed_trainer_cls.py:63,86; the
+ *   CutMix / MixUp labels of cls:58-61), mean over the batch.  ld / td: row strides in elements (rows are read as 16-byte
+ *   vectors where pointers and strides allow, element by element otherwise).  The row maximum is subtracted before the
+ *   exponential in both directions; targets need not sum to one.  row_stats [B,2] (row maximum, log sum exp(z - max)) is
+ *   what the backward needs besides its inputs.  dloss is a DEVICE scalar: it carries GradScaler's scale (cls:87).
+ * metrics (nullable): caller-owned device float[4], updated in place by the last launch of calm_soft_ce_fwd with a plain
+ *   read-modify-write of one thread (ordered by the stream):
+ *     [0] += sum of the B row losses     [1] += #{b : argmax_c z[b,:] == argmax_c y[b,:]}  (the "dominant class"
+ *     [2] += B                                  accuracy of cls:98-102; ties go to the lowest index, a row holding a
+ *     [3] += 1                                  NaN counts as no agreement)
+ *   The counts are exact below 2^24.  A training loop reads them once per epoch instead of `loss.item()` per step (cls:97).
+ * calm_top1_count: the eval loop's top-1 count against integer labels (CALM_ViT_V2.py:228-239): metrics[1] += hits,
+ *   metrics[2] += B; [0] and [3] are left alone.
+ * calm_huber_tokens_fwd / _bwd: nn.HuberLoss(delta) between the generative model's token output and the input image
+ *   (distributed_trainer_reg.py:59,78-81): tokens [B,S,3S] ARE the channels-last image, so the reference's
+ *   reshape(-1,S,S,3).permute(0,3,1,2) costs nothing here — the interleave against x [B,3,S,S] happens in LDS, both
+ *   tensors are read (and dtokens written) as 16-byte vectors.  S % 4 == 0 and S <= 4096, CALM_E_UNSUPP otherwise;
+ *   16-byte aligned bases, CALM_E_LAYOUT otherwise.
+ * ------------------------------------------------------------------------------------- */
+/* loss = mean_b sum_c y[b,c] * (logsumexp(z[b,:]) - z[b,c])          (cls:63,86; CrossEntropyLoss with class-probability targets) */
+int calm_soft_ce_fwd(const float* logits, int64_t ld, const float* targets, int64_t td,
+                     float* row_stats /* [B,2]: row maximum, log(sum exp(z - max)) */,
+                     float* loss /* scalar, overwritten */, float* metrics /* nullable, [4], see above */,
+                     int32_t B, int32_t C, float* partials, void* stream);
+/* dlogits[b,c] = dloss/B * (exp((z - max_b) - logsum_b) * sum_c y[b,c] - y[b,c]);  dloss: device scalar (carries GradScaler's scale) */
+int calm_soft_ce_bwd(const float* logits, int64_t ld, const float* targets, int64_t td, const float* row_stats,
+                     const float* dloss, float* dlogits /* [B,C] contiguous */, int32_t B, int32_t C, void* stream);
+/* loss = mean over B*3*S*S of huber_delta(tokens[b,i,3j+c] - x[b,c,i,j])   (reg:59,78-81; tokens [B,S,3S], x [B,3,S,S]) */
+int calm_huber_tokens_fwd(const float* tokens, const float* x, float delta, float* loss, int32_t B, int32_t S,
+                          float* partials, void* stream);
+/* dtokens[b,i,3j+c] = dloss/(3*B*S*S) * clamp(tokens[b,i,3j+c] - x[b,c,i,j], -delta, delta) */
+int calm_huber_tokens_bwd(const float* tokens, const float* x, float delta, const float* dloss, float* dtokens,
+                          int32_t B, int32_t S, void* stream);
+/* metrics[1] += #{b : argmax_c z[b,:] == labels[b]},  metrics[2] += B        (CALM_ViT_V2.py:228-239) */
+int calm_top1_count(const float* logits, int64_t ld, const int64_t* labels, float* metrics, int32_t B, int32_t C, void* stream);
 
 #ifdef __cplusplus
 }
