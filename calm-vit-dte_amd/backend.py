@@ -255,19 +255,24 @@ class HipBackend:
     def __init__(self):
         self.lib = _lib.load()
         self._scratch_bufs = {}
+        self._scratch_retired = []      # buffers a larger one replaced: a captured graph may hold their addresses
         self._scratch_need = {}
         self.upcast_launches = 0        # calm_gemm launches re-run on fp32 copies (CALM_E_LAYOUT with bf16 tensors)
 
     def _partials(self, op, rows, cols, device):
         """Device scratch for the fixed-order cross-workgroup reduction of one call (calm_reduce_scratch_floats).  One
         buffer per (device, stream), reused by every call on that stream: the launches of one stream run in order, so a
-        call's rows of partials have been consumed by its own reduction pass before the next call writes any."""
+        call's rows of partials have been consumed by its own reduction pass before the next call writes any.  A buffer
+        that a larger one replaces stays referenced: its address may be baked into a captured graph, whose replays would
+        otherwise write partial sums into memory the allocator has handed to another tensor."""
         need = self._scratch_need.get((op, rows, cols))
         if need is None:                                         # (a step has ~170 such calls over ~20 distinct shapes)
             need = self._scratch_need[(op, rows, cols)] = int(self.lib.calm_reduce_scratch_floats(op, rows, cols))
         key = (device.index, _stream())
         buf = self._scratch_bufs.get(key)
         if buf is None or buf.numel() < need:
+            if buf is not None:
+                self._scratch_retired.append(buf)
             buf = torch.empty(max(need, 1 << 20), dtype=torch.float32, device=device)
             self._scratch_bufs[key] = buf
         return buf.data_ptr()

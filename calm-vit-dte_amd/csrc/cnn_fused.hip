@@ -143,7 +143,7 @@ constexpr int BG = BW_NT / 16;   // 32 pixel groups
 constexpr int H2 = T + 4;        // h1 region edge (halo 2) = 20
 constexpr int H1 = T + 2;        // dh2p region edge (halo 1) = 18
 
-constexpr int CNN_PART_N = 17 * CH + 3, CNN_PART_STRIDE = 560;      // one row of weight-gradient partials per workgroup
+constexpr int CNN_PART_N = 17 * CH + 3;      // one row of weight-gradient partials per workgroup, CNN_PART_STRIDE apart (common.h)
 static_assert(CNN_PART_N <= CNN_PART_STRIDE, "partial row");
 __global__ __launch_bounds__(BW_NT) void cnn_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, CnnW W,
                                                         float* __restrict__ dx, float* __restrict__ part, int B, int S,
@@ -352,10 +352,7 @@ int calm_cnn_residual_fwd(const float* x, const float* w0, const float* s0, cons
     const long n_tiles = (long)B * tps * tps;
     const int grid = (int)(n_tiles < 256 * 6 ? n_tiles : 256 * 6);
     CnnW W{w0, s0, b0, w2, s2, b2, w4, s4, b4};
-    hipLaunchKernelGGL(cnn_fwd_kernel, dim3(grid), dim3(FW_NT), 0, as_stream(stream), x, W, out, B, S, tps, n_tiles,
-                       residual ? 1.f : 0.f);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(cnn_fwd_kernel, grid, FW_NT, 0, stream, x, W, out, B, S, tps, n_tiles, residual ? 1.f : 0.f);
 }
 
 int calm_cnn_residual_bwd(const float* dy, const float* x, const float* w0, const float* s0, const float* b0,
@@ -369,19 +366,16 @@ int calm_cnn_residual_bwd(const float* dy, const float* x, const float* w0, cons
     if (hidden != CH) return CALM_E_UNSUPP;
     const int tps = (S + T - 1) / T;
     const long n_tiles = (long)B * tps * tps;
-    const int grid = (int)(n_tiles < 256 ? n_tiles : 256);
+    const int grid = (int)(n_tiles < CNN_BWD_MAX_GRID ? n_tiles : CNN_BWD_MAX_GRID);
     CnnW W{w0, s0, b0, w2, s2, b2, w4, s4, b4};
-    hipLaunchKernelGGL(cnn_bwd_kernel, dim3(grid), dim3(BW_NT), 0, as_stream(stream), dy, x, W, dx, partials, B, S, tps,
-                       n_tiles, residual ? 1.f : 0.f);
-    CALM_LAUNCH_CHECK();
+    if (int e = calm_launch(cnn_bwd_kernel, grid, BW_NT, 0, stream, dy, x, W, dx, partials, B, S, tps, n_tiles,
+                            residual ? 1.f : 0.f))
+        return e;
     CalmReduceDst d{};
     d.out[0] = g0; d.out[1] = gb0; d.out[2] = g2; d.out[3] = gb2; d.out[4] = g4; d.out[5] = gb4;
     d.begin[0] = 0; d.begin[1] = 3 * CH; d.begin[2] = 4 * CH; d.begin[3] = 13 * CH; d.begin[4] = 14 * CH;
     d.begin[5] = 17 * CH; d.begin[6] = CNN_PART_N; d.nseg = 6;
-    hipLaunchKernelGGL(calm_reduce_partials_kernel, dim3((CNN_PART_N + 63) / 64), dim3(CALM_RED_THREADS), 0, as_stream(stream),
-                       partials, grid, CNN_PART_N, CNN_PART_STRIDE, d);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_reduce_partials(partials, grid, CNN_PART_N, CNN_PART_STRIDE, d, stream);
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/calm_vit.h"
 
 #define CALM_WAVE 64
@@ -85,6 +86,29 @@ __device__ __forceinline__ float block_max_256(float v, float* red) {
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// One kernel launch with its error check: 0, or the HIP error as the entry point's return value.  The arguments are
+// converted to the kernel's parameter types here (a nullptr, an int64_t for a long).  `stream` is the ABI's void* (a
+// hipStream_t converts to it).
+template <class... P, class... A>
+static inline int calm_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, void* stream, A&&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, as_stream(stream), static_cast<P>(args)...);
+    CALM_LAUNCH_CHECK();
+    return 0;
+}
+
+// A run-time value as a template argument: f(std::integral_constant<int, V>{}) for the V of the list that equals v — the
+// LAST one when none does, so a list ends with the value its selector returns otherwise — and f(std::true_type /
+// std::false_type{}) for a flag.  Every branch of f returns the same type (an error code, a kernel pointer).
+template <int V, int... Rest, class F>
+static inline auto with_int(int v, F&& f) -> decltype(f(std::integral_constant<int, V>{})) {
+    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, V>{});
+    else return v == V ? f(std::integral_constant<int, V>{}) : with_int<Rest...>(v, f);
+}
+template <class F>
+static inline auto with_bool(bool b, F&& f) -> decltype(f(std::true_type{})) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
 // ---- fixed-order cross-workgroup reductions (ABI v7) -------------------------------------------------------------------
 // Sums that span workgroups (LayerNorm dw, RoPE d_inv_freq, bias column sums, the latent KL sum, the CNN tail's weight
 // gradients) are two-stage: workgroup g writes its partial row to partials[g * stride .. + n) (caller-provided scratch)
@@ -134,8 +158,30 @@ static __global__ __launch_bounds__(CALM_RED_THREADS) void calm_reduce_partials_
         dst.out[k][c - dst.begin[k]] += (t[0] + t[1]) + (t[2] + t[3]);
     }
 }
-static inline void calm_reduce_partials(const float* part, int G, int n, float* out, hipStream_t s) {
+// G rows of n partials, `stride` floats apart, into the outputs of dst / into one output of n floats (rows packed)
+static inline int calm_reduce_partials(const float* part, int G, int n, int stride, const CalmReduceDst& dst, void* stream) {
+    return calm_launch(calm_reduce_partials_kernel, (n + 63) / 64, CALM_RED_THREADS, 0, stream, part, G, n, stride, dst);
+}
+static inline int calm_reduce_partials(const float* part, int G, int n, float* out, void* stream) {
     CalmReduceDst d{};
     d.out[0] = out; d.begin[0] = 0; d.begin[1] = n; d.nseg = 1;
-    hipLaunchKernelGGL(calm_reduce_partials_kernel, dim3((n + 63) / 64), dim3(CALM_RED_THREADS), 0, s, part, G, n, n, d);
+    return calm_reduce_partials(part, G, n, n, d, stream);
 }
+
+// ---- the reduction plan: the most workgroups each of these sums launches, i.e. the most partial rows it writes ----------
+// The grid functions clamp to these constants and calm_reduce_scratch_floats() (norm_act.hip, the ABI's contract for the
+// size of `partials`) multiplies the same constants, or calls the same grid functions, by the row length: a launch cannot
+// write more rows than the caller was told to provide.
+constexpr int LN_BWD_MAX_GRID = 512;
+constexpr int ROPE_BWD_MAX_GRID = 2048;
+constexpr int ROPE_SCRATCH_ROWS = 4096;        // rows the ABI sizes the RoPE backward for (>= every grid it launches)
+constexpr int LATENT_MAX_GRID = 2048;
+constexpr int COLSUM_MAX_GRID = 512;           // one-element form
+#ifndef COLSUM_GRID
+#define COLSUM_GRID 128      // A/B on [57344,448]: 66 us (scalar form) -> 28.6 us; 256 blocks: 39.6 (atomics), 128x256 threads: 34
+#endif
+constexpr int COLSUM_VEC_MAX_GRID = COLSUM_GRID;   // 16-byte form: few blocks, every block ends in a row of partials
+constexpr int CNN_BWD_MAX_GRID = 256;
+constexpr int CNN_PART_STRIDE = 560;           // floats between the CNN tail's partial rows (cnn_fused.hip: CNN_PART_N of them used)
+constexpr int SOFT_CE_PART_ROWS = 2;           // soft-target CE: one workgroup per sample; B row losses, then B agreement flags
+constexpr int HUBER_MAX_GRID = 2048;           // one block sum per workgroup

@@ -272,7 +272,6 @@ static __global__ __launch_bounds__(LOSS_NT) void huber_tokens_kernel(const floa
     }
 }
 
-#define HUBER_MAX_GRID 2048
 static bool huber_geom(int B, int S, HuberGeom* g) {
     if ((S & 3) != 0 || S > 4096) return false;                 // 3S floats of LDS per token row: 48 KB at S = 4096
     g->S = S;
@@ -285,6 +284,7 @@ static bool huber_geom(int B, int S, HuberGeom* g) {
     g->groups = (int)groups;
     return true;
 }
+// (HUBER_MAX_GRID: the reduction plan in common.h, which also sizes `partials`)
 static inline int huber_grid(const HuberGeom& g) { return g.groups < HUBER_MAX_GRID ? g.groups : HUBER_MAX_GRID; }
 static inline size_t huber_lds_bytes(const HuberGeom& g) { return ((size_t)g.R * 3 * g.S + 8) * sizeof(float); }
 
@@ -297,35 +297,26 @@ static inline int vec_groups(const float* a, long lda, const float* b, long ldb,
 int calm_soft_ce_fwd(const float* logits, int64_t ld, const float* targets, int64_t td, float* row_stats, float* loss,
                      float* metrics, int32_t B, int32_t C, float* partials, void* stream) {
     if (!logits || !targets || !row_stats || !loss || !partials || B <= 0 || C <= 0) return CALM_E_INVAL;
-    hipStream_t s = as_stream(stream);
     const int c4 = vec_groups(logits, (long)ld, targets, (long)td, C);
-    hipLaunchKernelGGL(soft_ce_fwd_kernel, dim3(B), dim3(LOSS_NT), 0, s, logits, (long)ld, targets, (long)td, row_stats,
-                       partials, B, C, c4);
-    CALM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(LOSS_NT), 0, s, partials, B, 1.0f / (float)B, loss, partials + B,
-                       metrics, B);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    // one workgroup per sample: B row losses at partials, B agreement flags behind them (SOFT_CE_PART_ROWS * B floats)
+    if (int e = calm_launch(soft_ce_fwd_kernel, B, LOSS_NT, 0, stream, logits, ld, targets, td, row_stats, partials, B, C, c4))
+        return e;
+    return calm_launch(loss_final_kernel, 1, LOSS_NT, 0, stream, partials, B, 1.0f / (float)B, loss, partials + B, metrics, B);
 }
 
 int calm_soft_ce_bwd(const float* logits, int64_t ld, const float* targets, int64_t td, const float* row_stats,
                      const float* dloss, float* dlogits, int32_t B, int32_t C, void* stream) {
     if (!logits || !targets || !row_stats || !dloss || !dlogits || B <= 0 || C <= 0) return CALM_E_INVAL;
     const int c4 = (C & 3) == 0 && aligned16(dlogits) ? vec_groups(logits, (long)ld, targets, (long)td, C) : 0;
-    hipLaunchKernelGGL(soft_ce_bwd_kernel, dim3(B), dim3(LOSS_NT), 0, as_stream(stream), logits, (long)ld, targets,
-                       (long)td, row_stats, dloss, dlogits, B, C, c4);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(soft_ce_bwd_kernel, B, LOSS_NT, 0, stream, logits, ld, targets, td, row_stats, dloss, dlogits, B, C, c4);
 }
 
 int calm_top1_count(const float* logits, int64_t ld, const int64_t* labels, float* metrics, int32_t B, int32_t C,
                     void* stream) {
     if (!logits || !labels || !metrics || B <= 0 || C <= 0) return CALM_E_INVAL;
     const int c4 = aligned16(logits) && (ld & 3) == 0 ? C >> 2 : 0;
-    hipLaunchKernelGGL(top1_count_kernel, dim3(1), dim3(TOP1_NT), 0, as_stream(stream), logits, (long)ld,
-                       reinterpret_cast<const long long*>(labels), metrics, B, C, c4);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(top1_count_kernel, 1, TOP1_NT, 0, stream, logits, ld, reinterpret_cast<const long long*>(labels),
+                       metrics, B, C, c4);
 }
 
 int calm_huber_tokens_fwd(const float* tokens, const float* x, float delta, float* loss, int32_t B, int32_t S,
@@ -334,15 +325,12 @@ int calm_huber_tokens_fwd(const float* tokens, const float* x, float delta, floa
     HuberGeom g;
     if (!huber_geom(B, S, &g)) return CALM_E_UNSUPP;
     if (!aligned16(tokens) || !aligned16(x)) return CALM_E_LAYOUT;
-    hipStream_t s = as_stream(stream);
     const int grid = huber_grid(g);
-    hipLaunchKernelGGL(huber_tokens_kernel<false>, dim3(grid), dim3(LOSS_NT), huber_lds_bytes(g), s, tokens, x, delta,
-                       (const float*)nullptr, partials, g);
-    CALM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(LOSS_NT), 0, s, partials, grid,
-                       1.0f / (3.0f * (float)g.rows * (float)S), loss, (const float*)nullptr, (float*)nullptr, 0);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    if (int e = calm_launch(huber_tokens_kernel<false>, grid, LOSS_NT, huber_lds_bytes(g), stream, tokens, x, delta, nullptr,
+                            partials, g))
+        return e;
+    return calm_launch(loss_final_kernel, 1, LOSS_NT, 0, stream, partials, grid, 1.0f / (3.0f * (float)g.rows * (float)S),
+                       loss, nullptr, nullptr, 0);
 }
 
 int calm_huber_tokens_bwd(const float* tokens, const float* x, float delta, const float* dloss, float* dtokens, int32_t B,
@@ -351,10 +339,8 @@ int calm_huber_tokens_bwd(const float* tokens, const float* x, float delta, cons
     HuberGeom g;
     if (!huber_geom(B, S, &g)) return CALM_E_UNSUPP;
     if (!aligned16(tokens) || !aligned16(x) || !aligned16(dtokens)) return CALM_E_LAYOUT;
-    hipLaunchKernelGGL(huber_tokens_kernel<true>, dim3(huber_grid(g)), dim3(LOSS_NT), huber_lds_bytes(g),
-                       as_stream(stream), tokens, x, delta, dloss, dtokens, g);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(huber_tokens_kernel<true>, huber_grid(g), LOSS_NT, huber_lds_bytes(g), stream, tokens, x, delta, dloss,
+                       dtokens, g);
 }
 
 }  // extern "C"

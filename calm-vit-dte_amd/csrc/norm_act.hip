@@ -4,6 +4,12 @@
 // row reductions; cross-row reductions (dw, d_inv_freq, kl, bias grads) are summed per block in registers / LDS in a
 // fixed order, leave the block as one row of caller-provided scratch and are combined by calm_reduce_partials
 // (common.h) in workgroup order: no atomics, every result repeats bit for bit (ABI v7).
+//
+// Layout: the kernels first, then the host side (from "host side" on) — the launch decisions that more than one entry point
+// takes, each written once, and the extern "C" entry points, which validate and return calm_launch()'s result.  Run-time
+// values become template arguments through with_int / with_bool (common.h); the file defines no function-like macro.
+// calm_reduce_scratch_floats(), the ABI's answer to "how large must `partials` be", is here because most of the grid
+// functions are; the caps it shares with cnn_fused.hip and loss.hip are the reduction plan in common.h.
 #include "common.h"
 
 namespace {
@@ -18,8 +24,15 @@ inline int grid_for(int64_t work_items, int per_block) {
     return (int)g;
 }
 
+// one wave per row, rows grid-strided over waves: a thread's lane, its wave's first row and the row stride.  (The two
+// scalar LayerNorm kernels spell the three values out: through this helper they compile to the same instructions on
+// other registers, and this file's device code is held identical, register for register, across host-side refactors.)
+struct WaveRows { int lane; long wave, nwaves; };
+__device__ __forceinline__ WaveRows wave_rows() {
+    return {(int)(threadIdx.x & 63), (long)blockIdx.x * (NT / 64) + (threadIdx.x >> 6), (long)gridDim.x * (NT / 64)};
+}
+
 // ------------------------------------------------------------------ LayerNorm
-// one wave per row, rows grid-strided over waves
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 // Y16 / G16: the normalised output / the incoming gradient is a bf16 tensor (bf16 pipeline: the LayerNorm output only
 // feeds GEMMs, which round their operands to bf16 anyway — it is rounded once, here, when stored)
@@ -106,9 +119,7 @@ template <int NV, bool Y16>
 __global__ __launch_bounds__(NT) void ln_fwd_vec_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         void* __restrict__ y_, float* __restrict__ mean,
                                                         float* __restrict__ rstd, long rows, int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const long wave = (long)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    const long nwaves = (long)gridDim.x * (NT / 64);
+    const auto [lane, wave, nwaves] = wave_rows();
     const int nv4 = D >> 2;
     f32x4 wv[NV];
 #pragma unroll
@@ -161,9 +172,7 @@ __global__ __launch_bounds__(NT) void ln_bwd_vec_kernel(const void* __restrict__
                                                         const float* __restrict__ rstd, float* __restrict__ dx,
                                                         float* __restrict__ dw_part, const float* __restrict__ dx_add,
                                                         long rows, int D) {
-    const int lane = threadIdx.x & 63;
-    const long wave = (long)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    const long nwaves = (long)gridDim.x * (NT / 64);
+    const auto [lane, wave, nwaves] = wave_rows();
     const int nv4 = D >> 2;
     f32x4 wv[NV], dwacc[NV];
 #pragma unroll
@@ -455,9 +464,7 @@ __global__ __launch_bounds__(NT) void rope_bwd_vec_kernel(const void* __restrict
 constexpr int SM_MAXC = 16;   // cols <= 1024
 
 __global__ __launch_bounds__(NT) void softmax_fwd_kernel(float* __restrict__ x, long rows, int cols) {
-    const int lane = threadIdx.x & 63;
-    const long wave = (long)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    const long nwaves = (long)gridDim.x * (NT / 64);
+    const auto [lane, wave, nwaves] = wave_rows();
     for (long row = wave; row < rows; row += nwaves) {
         float* xr = x + row * cols;
         float v[SM_MAXC];
@@ -487,9 +494,7 @@ __global__ __launch_bounds__(NT) void softmax_fwd_kernel(float* __restrict__ x, 
 
 __global__ __launch_bounds__(NT) void softmax_bwd_kernel(const float* __restrict__ p, float* __restrict__ dp,
                                                          long rows, int cols) {
-    const int lane = threadIdx.x & 63;
-    const long wave = (long)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    const long nwaves = (long)gridDim.x * (NT / 64);
+    const auto [lane, wave, nwaves] = wave_rows();
     for (long row = wave; row < rows; row += nwaves) {
         const float* pr = p + row * cols;
         float* gr = dp + row * cols;
@@ -515,9 +520,7 @@ __global__ __launch_bounds__(NT) void softmax_bwd_kernel(const float* __restrict
 // gradient of the head-broadcast mask (Vi_Tools:291) — kept in registers: saves sum_heads' re-read of dL.
 __global__ __launch_bounds__(NT) void softmax_bwd_heads_kernel(const float* __restrict__ p, float* __restrict__ dp,
                                                                float* __restrict__ dm, long n_bq, int H, int Sq, int cols) {
-    const int lane = threadIdx.x & 63;
-    const long wave = (long)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    const long nwaves = (long)gridDim.x * (NT / 64);
+    const auto [lane, wave, nwaves] = wave_rows();
     for (long bq = wave; bq < n_bq; bq += nwaves) {
         const long b = bq / Sq, i = bq - b * Sq;
         float msum[SM_MAXC];
@@ -670,9 +673,6 @@ __global__ __launch_bounds__(NT) void gelu_bwd_kernel(const float* __restrict__ 
 }
 
 constexpr int COLSUM_MAXC = 4096;
-#ifndef COLSUM_GRID
-#define COLSUM_GRID 128      // A/B on [57344,448]: 66 us (scalar form) -> 28.6 us; 256 blocks: 39.6 (atomics), 128x256 threads: 34
-#endif
 __global__ __launch_bounds__(NT) void colsum_kernel(const void* __restrict__ x, float* __restrict__ part, long rows,
                                                     int cols, int x_type) {
     // block owns the rows r = blockIdx.x (mod gridDim.x); partial row of the block -> part[blockIdx.x * cols ..]
@@ -779,6 +779,86 @@ __global__ __launch_bounds__(NT) void mean_seq_bwd_kernel(const float* __restric
     }
 }
 
+// ------------------------------------------------------------------ host side
+// Every entry point validates, picks a grid (and, where kernels are templates, the instantiation: with_int / with_bool,
+// common.h) and returns calm_launch()'s result.  A decision that more than one entry point takes is one function here:
+// ln_vec_nv (forward and backward), rope_plan (forward, backward), the grid functions (launch and scratch sizing).
+constexpr int LN_VEC_MAX_NV = 5;   // ln_*_vec_kernel<NV, *> is instantiated for NV = 1 .. LN_VEC_MAX_NV
+template <class F>
+auto with_ln_nv(int nv, F&& f) { return with_int<1, 2, 3, 4, LN_VEC_MAX_NV>(nv, f); }
+// NV of the vector LayerNorm kernels (float4 per lane that hold a row), 0 = they do not apply: D % 4 == 0, a row fits the
+// largest instantiation, every tensor that is accessed as float4 is 16-byte aligned (a null dx_add is)
+template <class... T>
+int ln_vec_nv(int D, const T*... vec_tensors) {
+    if ((D & 3) != 0 || D > 256 * LN_VEC_MAX_NV || !(aligned16(vec_tensors) && ...)) return 0;
+    return (D / 4 + 63) / 64;
+}
+int ln_bwd_grid(int64_t rows) {
+    const int g = grid_for(rows, NT / 64);
+    return g > LN_BWD_MAX_GRID ? LN_BWD_MAX_GRID : g;
+}
+
+bool st_ok(int t) { return t == CALM_ST_F32 || t == CALM_ST_BF16; }
+
+// What a RoPE call launches.  fits: the row-walking kernels can serve the shape (a thread per rotation pair, 32-bit
+// element offsets); vw, grid and bwd_grid are set only then.
+constexpr int ROPE_VEC_MAX_GRID = 256 * 16;
+struct RopePlan {
+    long nrows;
+    bool fits;
+    int tt;            // the storage type all tensors of the call share, -1 = they differ (kernel template argument TT)
+    int vw;            // widest column group that does not straddle the content / half boundaries
+    int grid;          // forward
+    int bwd_grid;      // backward: every workgroup ends with a row of dr/2 partials
+};
+static_assert(ROPE_BWD_MAX_GRID <= ROPE_SCRATCH_ROWS && CALM_ROPE_BWD_GRID <= ROPE_SCRATCH_ROWS,
+              "calm_reduce_scratch_floats sizes the RoPE backward for ROPE_SCRATCH_ROWS partial rows");
+// main_type: out / d_out; content_type counts only when there are content columns; the forward has no d_xr (pass xr's)
+RopePlan rope_plan(int B, int S, int H, int dc, int dr, int main_type, int content_type, int xr_type, int dxr_type) {
+    const int half = dr / 2;
+    RopePlan p{(long)B * S * H, false, -1, 1, 0, 0};
+    if (xr_type == main_type && dxr_type == main_type && (dc == 0 || content_type == main_type)) p.tt = main_type;
+    p.fits = half <= ROPE_MAX_HALF && half <= NT && p.nrows * (dc + dr) < (1L << 31);
+    if (!p.fits) return p;
+    p.vw = ((dc & 3) == 0 && (half & 3) == 0 && CALM_ROPE_VW4) ? 4 : ((dc & 1) == 0 && (half & 1) == 0) ? 2 : 1;
+    const int rpb = NT / (half / p.vw);                                    // rows per workgroup pass
+    const long blocks = (p.nrows + rpb - 1) / rpb;
+    p.grid = (int)(blocks < ROPE_VEC_MAX_GRID ? blocks : ROPE_VEC_MAX_GRID);
+    // few workgroups for small launches (A/B at S=80 with the atomics of rounds 1-3: 1024 -> 25 us, 2048 -> 36,
+    // 4096 -> 60), ~16 row passes per workgroup for large ones
+    const int want = p.grid / 16;
+    p.bwd_grid = want < CALM_ROPE_BWD_GRID ? (p.grid < CALM_ROPE_BWD_GRID ? p.grid : CALM_ROPE_BWD_GRID)
+                                           : (want < ROPE_BWD_MAX_GRID ? want : ROPE_BWD_MAX_GRID);
+    return p;
+}
+// f(VW, TT) as integral constants for the plan's instantiation of the row-walking kernels
+template <class F>
+int with_rope(const RopePlan& p, F&& f) {
+    return with_int<4, 2, 1>(p.vw, [&](auto vw) {
+        return with_int<CALM_ST_BF16, CALM_ST_F32, -1>(p.tt, [&](auto tt) { return f(vw, tt); });
+    });
+}
+
+int latent_grid(int64_t rows, int mvh) {
+    const int g = grid_for(rows * mvh, NT * 4);        // (four elements per thread in the vector kernel)
+    return g > LATENT_MAX_GRID ? LATENT_MAX_GRID : g;
+}
+
+// workgroups of a column-sum launch in the 16-byte form (*tx_out: its TX) or the one-element form
+int colsum_grid(int64_t rows, int cols, bool vec, int* tx_out) {
+    if (vec) {
+        const int c4n = cols >> 2;
+        const int tx = c4n <= 32 ? 32 : c4n <= 64 ? 64 : c4n <= 128 ? 128 : 256;
+        const int ty = CS_NT / tx;
+        const long gl = (rows + (long)ty * 8 - 1) / ((long)ty * 8);          // >= 8 rows per row lane
+        if (tx_out) *tx_out = tx;
+        return (int)(gl < 1 ? 1 : gl > COLSUM_VEC_MAX_GRID ? COLSUM_VEC_MAX_GRID : gl);
+    }
+    const long per = cols >= NT ? 1 : NT / cols;                              // rows per block pass
+    long g = (rows + per * 8 - 1) / (per * 8);
+    return (int)(g < 1 ? 1 : g > COLSUM_MAX_GRID ? COLSUM_MAX_GRID : g);
+}
+
 }  // namespace
 
 extern "C" {
@@ -786,91 +866,29 @@ extern "C" {
 int calm_layernorm_fwd(const float* x, const float* w, void* y, float* mean, float* rstd, int64_t rows, int32_t D,
                        float eps, int32_t y_type, void* stream) {
     if (!x || !w || !y || !mean || !rstd || rows <= 0 || D <= 0) return CALM_E_INVAL;
-    if (y_type != CALM_ST_F32 && y_type != CALM_ST_BF16) return CALM_E_INVAL;
-    const bool y16 = y_type == CALM_ST_BF16;
-    hipStream_t s = as_stream(stream);
-    const dim3 g(grid_for(rows, NT / 64)), b(NT);
-    if ((D & 3) == 0 && D <= 256 * 5 && aligned16(x) && aligned16(y) && aligned16(w)) {
-        const int nv = (D / 4 + 63) / 64;
-#define LN_FWD(NVV)                                                                                                  \
-    do {                                                                                                             \
-        if (y16) hipLaunchKernelGGL((ln_fwd_vec_kernel<NVV, true>), g, b, 0, s, x, w, y, mean, rstd, (long)rows, D, eps); \
-        else hipLaunchKernelGGL((ln_fwd_vec_kernel<NVV, false>), g, b, 0, s, x, w, y, mean, rstd, (long)rows, D, eps);    \
-    } while (0)
-        switch (nv) {
-            case 1: LN_FWD(1); break;
-            case 2: LN_FWD(2); break;
-            case 3: LN_FWD(3); break;
-            case 4: LN_FWD(4); break;
-            default: LN_FWD(5); break;
-        }
-#undef LN_FWD
-        CALM_LAUNCH_CHECK();
-        return 0;
-    }
-    if (y16) hipLaunchKernelGGL(ln_fwd_kernel<true>, g, b, 0, s, x, w, y, mean, rstd, (long)rows, D, eps);
-    else hipLaunchKernelGGL(ln_fwd_kernel<false>, g, b, 0, s, x, w, y, mean, rstd, (long)rows, D, eps);
-    CALM_LAUNCH_CHECK();
-    return 0;
-}
-
-static int ln_bwd_grid(int64_t rows) {
-    const int g = grid_for(rows, NT / 64);
-    return g > 512 ? 512 : g;
+    if (!st_ok(y_type)) return CALM_E_INVAL;
+    const int nv = ln_vec_nv(D, x, y, w);
+    const auto kernel = with_bool(y_type == CALM_ST_BF16, [&](auto y16) {
+        constexpr bool Y16 = decltype(y16)::value;
+        return nv ? with_ln_nv(nv, [](auto n) { return &ln_fwd_vec_kernel<decltype(n)::value, Y16>; }) : &ln_fwd_kernel<Y16>;
+    });
+    return calm_launch(kernel, grid_for(rows, NT / 64), NT, 0, stream, x, w, y, mean, rstd, rows, D, eps);
 }
 
 int calm_layernorm_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
                        float* dx, float* dw, const float* dx_add, int64_t rows, int32_t D, int32_t dy_type,
                        float* partials, void* stream) {
     if (!dy || !x || !w || !mean || !rstd || !dx || !dw || !partials || rows <= 0 || D <= 0) return CALM_E_INVAL;
-    if (dy_type != CALM_ST_F32 && dy_type != CALM_ST_BF16) return CALM_E_INVAL;
+    if (!st_ok(dy_type)) return CALM_E_INVAL;
     if (D > 64 * LN_MAXC) return CALM_E_UNSUPP;
-    const bool g16 = dy_type == CALM_ST_BF16;
+    const int nv = ln_vec_nv(D, x, dy, dx, w, dx_add);
+    const auto kernel = with_bool(dy_type == CALM_ST_BF16, [&](auto g16) {
+        constexpr bool G16 = decltype(g16)::value;
+        return nv ? with_ln_nv(nv, [](auto n) { return &ln_bwd_vec_kernel<decltype(n)::value, G16>; }) : &ln_bwd_kernel<G16>;
+    });
     const int g = ln_bwd_grid(rows);
-    hipStream_t s = as_stream(stream);
-    const dim3 gd(g), b(NT);
-    if ((D & 3) == 0 && D <= 256 * 5 && aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(w) &&
-        aligned16(dx_add)) {
-        const int nv = (D / 4 + 63) / 64;
-#define LN_BWD(NVV)                                                                                                        \
-    do {                                                                                                                   \
-        if (g16) hipLaunchKernelGGL((ln_bwd_vec_kernel<NVV, true>), gd, b, 0, s, dy, x, w, mean, rstd, dx, partials, dx_add, (long)rows, D); \
-        else hipLaunchKernelGGL((ln_bwd_vec_kernel<NVV, false>), gd, b, 0, s, dy, x, w, mean, rstd, dx, partials, dx_add, (long)rows, D);    \
-    } while (0)
-        switch (nv) {
-            case 1: LN_BWD(1); break;
-            case 2: LN_BWD(2); break;
-            case 3: LN_BWD(3); break;
-            case 4: LN_BWD(4); break;
-            default: LN_BWD(5); break;
-        }
-#undef LN_BWD
-        CALM_LAUNCH_CHECK();
-        calm_reduce_partials(partials, g, D, dw, s);
-        CALM_LAUNCH_CHECK();
-        return 0;
-    }
-    if (g16) hipLaunchKernelGGL(ln_bwd_kernel<true>, gd, b, 0, s, dy, x, w, mean, rstd, dx, partials, dx_add, (long)rows, D);
-    else hipLaunchKernelGGL(ln_bwd_kernel<false>, gd, b, 0, s, dy, x, w, mean, rstd, dx, partials, dx_add, (long)rows, D);
-    CALM_LAUNCH_CHECK();
-    calm_reduce_partials(partials, g, D, dw, s);
-    CALM_LAUNCH_CHECK();
-    return 0;
-}
-
-static bool st_ok(int t) { return t == CALM_ST_F32 || t == CALM_ST_BF16; }
-// row-walking RoPE kernels: 32-bit row index; VW = 2 when column pairs do not straddle the content / half boundaries
-static bool rope_vec_ok(long nrows, int dc, int dr) {
-    return CALM_ROPE_VEC && nrows * (dc + dr) < (1L << 31) && dr / 2 <= NT && dr / 2 <= ROPE_MAX_HALF;      // 32-bit element offsets
-}
-static int rope_vw(int dc, int dr) {     // widest column group that does not straddle the content / half boundaries
-    const int half = dr / 2;
-    return ((dc & 3) == 0 && (half & 3) == 0 && CALM_ROPE_VW4) ? 4 : ((dc & 1) == 0 && (half & 1) == 0) ? 2 : 1;
-}
-static int rope_vec_grid(long nrows, int dc, int dr) {
-    const int rpb = NT / (dr / 2 / rope_vw(dc, dr));
-    const long blocks = (nrows + rpb - 1) / rpb;
-    return (int)(blocks < 256 * 16 ? blocks : 256 * 16);
+    if (int e = calm_launch(kernel, g, NT, 0, stream, dy, x, w, mean, rstd, dx, partials, dx_add, rows, D)) return e;
+    return calm_reduce_partials(partials, g, D, dw, stream);
 }
 
 int calm_rope_fwd(const void* content, const void* xr, const float* inv_freq, float* table, void* out, int32_t B,
@@ -881,43 +899,15 @@ int calm_rope_fwd(const void* content, const void* xr, const float* inv_freq, fl
     if (dc > 0 && !content) return CALM_E_INVAL;
     if (!st_ok(content_type) || !st_ok(xr_type) || !st_ok(out_type)) return CALM_E_INVAL;
     const int half = dr / 2;
-    hipLaunchKernelGGL(rope_table_kernel, dim3((S * half + 255) / 256), dim3(256), 0, as_stream(stream), inv_freq,
-                       table, S, half);
-    CALM_LAUNCH_CHECK();
-    const long nrows = (long)B * S * H;
-    if (rope_vec_ok(nrows, dc, dr)) {
-        const dim3 gv(rope_vec_grid(nrows, dc, dr));
-        const bool same = xr_type == out_type && (dc == 0 || content_type == out_type);
-        const int tt = !same ? -1 : out_type;
-#define ROPE_FWD(VWV, TTV)                                                                                              \
-    hipLaunchKernelGGL((rope_fwd_vec_kernel<VWV, TTV>), gv, dim3(NT), 0, as_stream(stream), content, xr, table, out,   \
-                       (int)nrows, S, H, dc, dr, content_type, xr_type, out_type)
-#define ROPE_FWD_T(VWV)                                                                                                 \
-    do {                                                                                                                \
-        if (tt == CALM_ST_BF16) ROPE_FWD(VWV, CALM_ST_BF16);                                                            \
-        else if (tt == CALM_ST_F32) ROPE_FWD(VWV, CALM_ST_F32);                                                         \
-        else ROPE_FWD(VWV, -1);                                                                                         \
-    } while (0)
-        if (rope_vw(dc, dr) == 4) ROPE_FWD_T(4);
-        else if (rope_vw(dc, dr) == 2) ROPE_FWD_T(2);
-        else ROPE_FWD_T(1);
-#undef ROPE_FWD_T
-#undef ROPE_FWD
-        CALM_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(rope_fwd_kernel, dim3(grid_for(nrows * (dc + half), NT)), dim3(NT), 0, as_stream(stream),
-                       content, xr, table, out, nrows, S, H, dc, dr, content_type, xr_type, out_type);
-    CALM_LAUNCH_CHECK();
-    return 0;
-}
-
-static int rope_bwd_grid(long nrows, int dc, int dr) {
-    int gv = rope_vec_grid(nrows, dc, dr);
-    // every workgroup ends with a row of dr/2 partials: few workgroups for small launches (A/B at S=80 with the
-    // atomics of rounds 1-3: 1024 -> 25 us, 2048 -> 36, 4096 -> 60), ~16 row passes per workgroup for large ones
-    const int want = gv / 16;
-    return want < CALM_ROPE_BWD_GRID ? (gv < CALM_ROPE_BWD_GRID ? gv : CALM_ROPE_BWD_GRID) : (want < 2048 ? want : 2048);
+    if (int e = calm_launch(rope_table_kernel, (S * half + 255) / 256, 256, 0, stream, inv_freq, table, S, half)) return e;
+    const RopePlan p = rope_plan(B, S, H, dc, dr, out_type, content_type, xr_type, xr_type);
+    if (CALM_ROPE_VEC && p.fits)
+        return with_rope(p, [&](auto vw, auto tt) {
+            return calm_launch(rope_fwd_vec_kernel<decltype(vw)::value, decltype(tt)::value>, p.grid, NT, 0, stream, content,
+                               xr, table, out, (int)p.nrows, S, H, dc, dr, content_type, xr_type, out_type);
+        });
+    return calm_launch(rope_fwd_kernel, grid_for(p.nrows * (dc + half), NT), NT, 0, stream, content, xr, table, out,
+                       p.nrows, S, H, dc, dr, content_type, xr_type, out_type);
 }
 
 int calm_rope_bwd(const void* d_out, const void* xr, const float* table, void* d_content, void* d_xr,
@@ -928,49 +918,29 @@ int calm_rope_bwd(const void* d_out, const void* xr, const float* table, void* d
         return CALM_E_INVAL;
     if (dc > 0 && !d_content) return CALM_E_INVAL;
     if (!st_ok(dout_type) || !st_ok(xr_type) || !st_ok(dcontent_type) || !st_ok(dxr_type)) return CALM_E_INVAL;
-    const long nrows = (long)B * S * H;
     // (the one-element-per-thread backward of round 1 combined its angle gradients with LDS atomics; the row-walking
     // kernel serves every shape of the path: dr/2 <= 256 rotation pairs, tensors below 2^31 elements)
-    if (dr / 2 > ROPE_MAX_HALF || dr / 2 > NT || nrows * (dc + dr) >= (1L << 31)) return CALM_E_UNSUPP;
-    const int gv = rope_bwd_grid(nrows, dc, dr);
-    const bool same = xr_type == dout_type && dxr_type == dout_type && (dc == 0 || dcontent_type == dout_type);
-    const int tt = !same ? -1 : dout_type;
-#define ROPE_BWD(VWV, TTV)                                                                                              \
-    hipLaunchKernelGGL((rope_bwd_vec_kernel<VWV, TTV>), dim3(gv), dim3(NT), 0, as_stream(stream), d_out, xr, table,    \
-                       d_content, d_xr, partials, (int)nrows, S, H, dc, dr, dout_type, xr_type, dcontent_type, dxr_type)
-#define ROPE_BWD_T(VWV)                                                                                                 \
-    do {                                                                                                                \
-        if (tt == CALM_ST_BF16) ROPE_BWD(VWV, CALM_ST_BF16);                                                            \
-        else if (tt == CALM_ST_F32) ROPE_BWD(VWV, CALM_ST_F32);                                                         \
-        else ROPE_BWD(VWV, -1);                                                                                         \
-    } while (0)
-    if (rope_vw(dc, dr) == 4) ROPE_BWD_T(4);
-    else if (rope_vw(dc, dr) == 2) ROPE_BWD_T(2);
-    else ROPE_BWD_T(1);
-#undef ROPE_BWD_T
-#undef ROPE_BWD
-    CALM_LAUNCH_CHECK();
-    calm_reduce_partials(partials, gv, dr / 2, d_inv_freq, as_stream(stream));
-    CALM_LAUNCH_CHECK();
-    return 0;
+    const RopePlan p = rope_plan(B, S, H, dc, dr, dout_type, dcontent_type, xr_type, dxr_type);
+    if (!p.fits) return CALM_E_UNSUPP;
+    if (int e = with_rope(p, [&](auto vw, auto tt) {
+            return calm_launch(rope_bwd_vec_kernel<decltype(vw)::value, decltype(tt)::value>, p.bwd_grid, NT, 0, stream,
+                               d_out, xr, table, d_content, d_xr, partials, (int)p.nrows, S, H, dc, dr, dout_type, xr_type,
+                               dcontent_type, dxr_type);
+        }))
+        return e;
+    return calm_reduce_partials(partials, p.bwd_grid, dr / 2, d_inv_freq, stream);
 }
 
 int calm_softmax_fwd(float* x, int64_t rows, int32_t cols, void* stream) {
     if (!x || rows <= 0 || cols <= 0) return CALM_E_INVAL;
     if (cols > 64 * SM_MAXC) return CALM_E_UNSUPP;
-    hipLaunchKernelGGL(softmax_fwd_kernel, dim3(grid_for(rows, NT / 64)), dim3(NT), 0, as_stream(stream), x,
-                       (long)rows, cols);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(softmax_fwd_kernel, grid_for(rows, NT / 64), NT, 0, stream, x, rows, cols);
 }
 
 int calm_softmax_bwd(const float* p, float* dp, int64_t rows, int32_t cols, void* stream) {
     if (!p || !dp || rows <= 0 || cols <= 0) return CALM_E_INVAL;
     if (cols > 64 * SM_MAXC) return CALM_E_UNSUPP;
-    hipLaunchKernelGGL(softmax_bwd_kernel, dim3(grid_for(rows, NT / 64)), dim3(NT), 0, as_stream(stream), p, dp,
-                       (long)rows, cols);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(softmax_bwd_kernel, grid_for(rows, NT / 64), NT, 0, stream, p, dp, rows, cols);
 }
 
 int calm_softmax_bwd_heads(const float* p, float* dp, float* dm, int32_t B, int32_t H, int32_t Sq, int32_t cols,
@@ -978,140 +948,84 @@ int calm_softmax_bwd_heads(const float* p, float* dp, float* dm, int32_t B, int3
     if (!p || !dp || !dm || B <= 0 || H <= 0 || Sq <= 0 || cols <= 0) return CALM_E_INVAL;
     if (cols > 64 * SM_MAXC) return CALM_E_UNSUPP;
     const long n_bq = (long)B * Sq;
-    hipLaunchKernelGGL(softmax_bwd_heads_kernel, dim3(grid_for(n_bq, NT / 64)), dim3(NT), 0, as_stream(stream), p, dp, dm,
-                       n_bq, H, Sq, cols);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(softmax_bwd_heads_kernel, grid_for(n_bq, NT / 64), NT, 0, stream, p, dp, dm, n_bq, H, Sq, cols);
 }
 
 int calm_sum_heads(const float* dl, float* dm, int32_t B, int32_t H, int64_t per_head, void* stream) {
     if (!dl || !dm || B <= 0 || H <= 0 || per_head <= 0) return CALM_E_INVAL;
-    hipLaunchKernelGGL(sum_heads_kernel, dim3(grid_for((int64_t)B * per_head, NT)), dim3(NT), 0, as_stream(stream),
-                       dl, dm, B, H, (long)per_head);
-    CALM_LAUNCH_CHECK();
-    return 0;
-}
-
-static int latent_grid(int64_t rows, int mvh) {
-    const int g = grid_for(rows * mvh, NT * 4);        // (four elements per thread in the vector kernel)
-    return g > 2048 ? 2048 : g;
+    return calm_launch(sum_heads_kernel, grid_for((int64_t)B * per_head, NT), NT, 0, stream, dl, dm, B, H, per_head);
 }
 
 int calm_latent_fwd(const float* mv, const float* noise, float* z, float* std_out, float* kl_sum, int64_t rows,
                     int32_t mvh, float* partials, void* stream) {
     if (!mv || !z || !std_out || !kl_sum || !partials || rows <= 0 || mvh <= 0) return CALM_E_INVAL;
     const int g = latent_grid(rows, mvh);
-    if ((mvh & 3) == 0 && rows * mvh < (1ll << 31) && aligned16(mv) && aligned16(z) && aligned16(std_out) &&
-        aligned16(noise))
-        hipLaunchKernelGGL(latent_fwd_vec_kernel, dim3(g), dim3(NT), 0, as_stream(stream), mv, noise, z, std_out, partials,
-                           (unsigned)rows, (unsigned)mvh);
-    else
-        hipLaunchKernelGGL(latent_fwd_kernel, dim3(g), dim3(NT), 0, as_stream(stream), mv, noise, z, std_out, partials,
-                           (long)rows, mvh);
-    CALM_LAUNCH_CHECK();
-    calm_reduce_partials(partials, g, 1, kl_sum, as_stream(stream));
-    CALM_LAUNCH_CHECK();
-    return 0;
+    const bool vec = (mvh & 3) == 0 && rows * mvh < (1ll << 31) && aligned16(mv) && aligned16(z) && aligned16(std_out) &&
+                     aligned16(noise);
+    if (int e = vec ? calm_launch(latent_fwd_vec_kernel, g, NT, 0, stream, mv, noise, z, std_out, partials, rows, mvh)
+                    : calm_launch(latent_fwd_kernel, g, NT, 0, stream, mv, noise, z, std_out, partials, rows, mvh))
+        return e;
+    return calm_reduce_partials(partials, g, 1, kl_sum, stream);
 }
 
 int calm_latent_bwd(const float* dz, const float* d_kl_sum, const float* mv, const float* noise, const float* std_in,
                     float* dmv, int64_t rows, int32_t mvh, void* stream) {
     if (!mv || !std_in || !dmv || rows <= 0 || mvh <= 0) return CALM_E_INVAL;
-    hipLaunchKernelGGL(latent_bwd_kernel, dim3(grid_for(rows * mvh, NT)), dim3(NT), 0, as_stream(stream), dz,
-                       d_kl_sum, mv, noise, std_in, dmv, (long)rows, mvh);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(latent_bwd_kernel, grid_for(rows * mvh, NT), NT, 0, stream, dz, d_kl_sum, mv, noise, std_in, dmv,
+                       rows, mvh);
 }
 
 int calm_add(const float* a, const float* b, float* out, int64_t n, void* stream) {
     if (!a || !b || !out || n <= 0) return CALM_E_INVAL;
     const bool vec = aligned16(a) && aligned16(b) && aligned16(out);
     const long n4 = vec ? n / 4 : 0;
-    hipLaunchKernelGGL(add_kernel, dim3(grid_for(vec ? n4 + 1 : n, NT)), dim3(NT), 0, as_stream(stream), a, b, out,
-                       n4, (long)n);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(add_kernel, grid_for(vec ? n4 + 1 : n, NT), NT, 0, stream, a, b, out, n4, n);
 }
 
 int calm_gelu_fwd(const float* x, float* y, int64_t n, void* stream) {
     if (!x || !y || n <= 0) return CALM_E_INVAL;
-    hipLaunchKernelGGL(gelu_fwd_kernel, dim3(grid_for(n, NT)), dim3(NT), 0, as_stream(stream), x, y, (long)n);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(gelu_fwd_kernel, grid_for(n, NT), NT, 0, stream, x, y, n);
 }
 
 int calm_gelu_bwd(const float* dy, const float* z, float* dz, int64_t n, void* stream) {
     if (!dy || !z || !dz || n <= 0) return CALM_E_INVAL;
-    hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_for(n, NT)), dim3(NT), 0, as_stream(stream), dy, z, dz, (long)n);
-    CALM_LAUNCH_CHECK();
-    return 0;
-}
-
-// (vector form?, workgroups) of a column-sum launch
-static int colsum_grid(int64_t rows, int cols, bool vec, int* tx_out) {
-    if (vec) {
-        const int c4n = cols >> 2;
-        const int tx = c4n <= 32 ? 32 : c4n <= 64 ? 64 : c4n <= 128 ? 128 : 256;
-        const int ty = CS_NT / tx;
-        const long gl = (rows + (long)ty * 8 - 1) / ((long)ty * 8);          // >= 8 rows per row lane
-        if (tx_out) *tx_out = tx;
-        return (int)(gl < 1 ? 1 : gl > COLSUM_GRID ? COLSUM_GRID : gl);      // few blocks: every block ends in a row of partials
-    }
-    const long per = cols >= NT ? 1 : NT / cols;                              // rows per block pass
-    long g = (rows + per * 8 - 1) / (per * 8);
-    return (int)(g < 1 ? 1 : g > 512 ? 512 : g);
+    return calm_launch(gelu_bwd_kernel, grid_for(n, NT), NT, 0, stream, dy, z, dz, n);
 }
 
 int calm_colsum(const void* x, float* out, int64_t rows, int32_t cols, int32_t x_type, float* partials, void* stream) {
     if (!x || !out || !partials || rows <= 0 || cols <= 0) return CALM_E_INVAL;
     if (!st_ok(x_type)) return CALM_E_INVAL;
     if (cols > COLSUM_MAXC) return CALM_E_UNSUPP;
-    const bool x16 = x_type == CALM_ST_BF16;
-    hipStream_t s = as_stream(stream);
-    if ((cols & 3) == 0 && aligned16(x) && aligned16(partials) && rows >= 64) {
-        int tx = 0;
-        const int gv = colsum_grid(rows, cols, true, &tx);
-#define CS_LAUNCH(TXV)                                                                                              \
-    do {                                                                                                            \
-        if (x16) hipLaunchKernelGGL((colsum_vec_kernel<TXV, true>), dim3(gv), dim3(CS_NT), 0, s, x, partials, (long)rows, cols); \
-        else hipLaunchKernelGGL((colsum_vec_kernel<TXV, false>), dim3(gv), dim3(CS_NT), 0, s, x, partials, (long)rows, cols);    \
-    } while (0)
-        switch (tx) {
-            case 32: CS_LAUNCH(32); break;
-            case 64: CS_LAUNCH(64); break;
-            case 128: CS_LAUNCH(128); break;
-            default: CS_LAUNCH(256); break;
-        }
-#undef CS_LAUNCH
-        CALM_LAUNCH_CHECK();
-        calm_reduce_partials(partials, gv, cols, out, s);
-        CALM_LAUNCH_CHECK();
-        return 0;
-    }
-    const int g = colsum_grid(rows, cols, false, nullptr);
-    hipLaunchKernelGGL(colsum_kernel, dim3(g), dim3(NT), 0, s, x, partials, (long)rows, cols, x_type);
-    CALM_LAUNCH_CHECK();
-    calm_reduce_partials(partials, g, cols, out, s);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    const bool vec = (cols & 3) == 0 && aligned16(x) && aligned16(partials) && rows >= 64;
+    int tx = 0;
+    const int g = colsum_grid(rows, cols, vec, &tx);
+    const int e = !vec ? calm_launch(colsum_kernel, g, NT, 0, stream, x, partials, rows, cols, x_type)
+                       : with_int<32, 64, 128, 256>(tx, [&](auto t) {
+                             return with_bool(x_type == CALM_ST_BF16, [&](auto x16) {
+                                 return calm_launch(colsum_vec_kernel<decltype(t)::value, decltype(x16)::value>, g, CS_NT, 0,
+                                                    stream, x, partials, rows, cols);
+                             });
+                         });
+    return e ? e : calm_reduce_partials(partials, g, cols, out, stream);
 }
 
 /* floats of `partials` scratch an entry point with a cross-workgroup reduction needs (upper bound over its kernel
- * variants); op = CALM_RED_*; (rows, cols) as documented at the enum */
+ * variants); op = CALM_RED_*; (rows, cols) as documented at the enum.  Rows of partials = the cap of the grid function the
+ * launch uses (the reduction plan in common.h), or that grid function itself. */
 int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols) {
     if (rows <= 0 || cols <= 0) return 0;
     switch (op) {
         case CALM_RED_LAYERNORM_BWD: return (int64_t)ln_bwd_grid(rows) * cols;
-        case CALM_RED_ROPE_BWD: return (int64_t)4096 * (cols / 2);
+        case CALM_RED_ROPE_BWD: return (int64_t)ROPE_SCRATCH_ROWS * (cols / 2);
         case CALM_RED_LATENT_FWD: return latent_grid(rows, cols);
         case CALM_RED_COLSUM: {
             const int64_t a = (int64_t)colsum_grid(rows, cols, false, nullptr) * cols;
             const int64_t b = (cols & 3) == 0 && rows >= 64 ? (int64_t)colsum_grid(rows, cols, true, nullptr) * cols : 0;
             return a > b ? a : b;
         }
-        case CALM_RED_CNN_BWD: return (int64_t)256 * 560;       // cnn_fused.hip: grid <= 256 rows of CNN_PART_STRIDE
-        case CALM_RED_SOFT_CE: return 2 * rows;                 // loss.hip: the B row losses, then the B agreement flags
-        case CALM_RED_HUBER: return 2048;                       // loss.hip: grid <= HUBER_MAX_GRID block sums
+        case CALM_RED_CNN_BWD: return (int64_t)CNN_BWD_MAX_GRID * CNN_PART_STRIDE;
+        case CALM_RED_SOFT_CE: return SOFT_CE_PART_ROWS * rows;
+        case CALM_RED_HUBER: return HUBER_MAX_GRID;
         default: return 0;
     }
 }
@@ -1119,28 +1033,21 @@ int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols) {
 int calm_row_scale(const float* x, const float* s, void* out, int32_t rows, int32_t cols, int32_t out_type,
                    void* stream) {
     if (!x || !s || !out || rows <= 0 || cols <= 0) return CALM_E_INVAL;
-    if (out_type != CALM_ST_F32 && out_type != CALM_ST_BF16) return CALM_E_INVAL;
-    const dim3 g(grid_for((int64_t)rows * cols, NT)), b(NT);
-    if (out_type == CALM_ST_BF16) hipLaunchKernelGGL(row_scale_kernel<true>, g, b, 0, as_stream(stream), x, s, out, rows, cols);
-    else hipLaunchKernelGGL(row_scale_kernel<false>, g, b, 0, as_stream(stream), x, s, out, rows, cols);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    if (!st_ok(out_type)) return CALM_E_INVAL;
+    return with_bool(out_type == CALM_ST_BF16, [&](auto o16) {
+        return calm_launch(row_scale_kernel<decltype(o16)::value>, grid_for((int64_t)rows * cols, NT), NT, 0, stream, x, s,
+                           out, rows, cols);
+    });
 }
 
 int calm_mean_seq_fwd(const float* x, float* y, int32_t B, int32_t S, int32_t D, void* stream) {
     if (!x || !y || B <= 0 || S <= 0 || D <= 0) return CALM_E_INVAL;
-    hipLaunchKernelGGL(mean_seq_fwd_kernel, dim3(grid_for((int64_t)B * D, NT)), dim3(NT), 0, as_stream(stream), x, y,
-                       B, S, D);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(mean_seq_fwd_kernel, grid_for((int64_t)B * D, NT), NT, 0, stream, x, y, B, S, D);
 }
 
 int calm_mean_seq_bwd(const float* dy, float* dx, int32_t B, int32_t S, int32_t D, void* stream) {
     if (!dy || !dx || B <= 0 || S <= 0 || D <= 0) return CALM_E_INVAL;
-    hipLaunchKernelGGL(mean_seq_bwd_kernel, dim3(grid_for((int64_t)B * S * D, NT)), dim3(NT), 0, as_stream(stream),
-                       dy, dx, B, S, D);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(mean_seq_bwd_kernel, grid_for((int64_t)B * S * D, NT), NT, 0, stream, dy, dx, B, S, D);
 }
 
 }  // extern "C"

@@ -158,21 +158,16 @@ int calm_optim_step(const calm_optim_tensor* tensors_dev, int32_t n_tensors, con
         return CALM_E_INVAL;
     if ((!step_dev && hp->step < 1) || hp->lr < 0.f || hp->beta1 < 0.f || hp->beta1 >= 1.f || hp->beta2 < 0.f || hp->beta2 >= 1.f)
         return CALM_E_INVAL;
-    hipStream_t s = as_stream(stream);
     const size_t scratch_bytes = sizeof(float) * ST * (size_t)n_tensors + sizeof(Globals);
-    hipError_t e = hipMemsetAsync(scratch, 0, scratch_bytes, s);
-    if (e != hipSuccess) return (int)e;
+    if (hipError_t e = hipMemsetAsync(scratch, 0, scratch_bytes, as_stream(stream))) return (int)e;
     Globals* G = reinterpret_cast<Globals*>(scratch + ST * (size_t)n_tensors);
     float* chunk_part = scratch + ST * (size_t)n_tensors + sizeof(Globals) / sizeof(float);     // every entry is written
-    hipLaunchKernelGGL(optim_stats, dim3(n_chunks), dim3(NT), 0, s, tensors_dev, chunk_tensor_dev, scratch, G, chunk_part);
-    CALM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(optim_finalize, dim3(1), dim3(NT), 0, s, tensors_dev, n_tensors, scratch, G, hp->max_norm,
-                       grad_scale, stats_out, (const float*)chunk_part, step_dev);
-    CALM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(optim_update, dim3(n_chunks), dim3(NT), 0, s, tensors_dev, chunk_tensor_dev,
-                       (const float*)scratch, (const Globals*)G, *hp, (const int*)step_dev, lr_dev);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    if (int e = calm_launch(optim_stats, n_chunks, NT, 0, stream, tensors_dev, chunk_tensor_dev, scratch, G, chunk_part))
+        return e;
+    if (int e = calm_launch(optim_finalize, 1, NT, 0, stream, tensors_dev, n_tensors, scratch, G, hp->max_norm, grad_scale,
+                            stats_out, chunk_part, step_dev))
+        return e;
+    return calm_launch(optim_update, n_chunks, NT, 0, stream, tensors_dev, chunk_tensor_dev, scratch, G, *hp, step_dev, lr_dev);
 }
 
 }  // extern "C"

@@ -186,10 +186,7 @@ int calm_cast_f32_one(const void* src, float* dst, int64_t n, void* stream) {
     if (!src || !dst || n <= 0) return CALM_E_INVAL;
     long g = (n + NT - 1) / NT;
     if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(cast_f32_kernel, dim3((int)g), dim3(NT), 0, as_stream(stream), reinterpret_cast<const __bf16*>(src), dst,
-                       (long)n);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(cast_f32_kernel, (int)g, NT, 0, stream, reinterpret_cast<const __bf16*>(src), dst, n);
 }
 
 int calm_cast_bf16_one(const float* src, void* dst, int64_t n, void* stream) {
@@ -199,17 +196,12 @@ int calm_cast_bf16_one(const float* src, void* dst, int64_t n, void* stream) {
     long g = (n / 8 + NT - 1) / NT;
     if (g > 4096) g = 4096;
     if (g < 1) g = 1;
-    hipLaunchKernelGGL(cast_one_kernel, dim3((int)g), dim3(NT), 0, as_stream(stream), src, reinterpret_cast<__bf16*>(dst), n8,
-                       (long)n);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(cast_one_kernel, (int)g, NT, 0, stream, src, reinterpret_cast<__bf16*>(dst), n8, n);
 }
 
 int calm_cast_bf16(const calm_cast_entry* entries_dev, const int32_t* chunk_entry_dev, int32_t n_chunks, void* stream) {
     if (!entries_dev || !chunk_entry_dev || n_chunks <= 0) return CALM_E_INVAL;
-    hipLaunchKernelGGL(cast_bf16_kernel, dim3(n_chunks), dim3(NT), 0, as_stream(stream), entries_dev, chunk_entry_dev);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(cast_bf16_kernel, n_chunks, NT, 0, stream, entries_dev, chunk_entry_dev);
 }
 
 int calm_sn_plan(const calm_sn_layer* layers, int32_t n, void* blob_host, calm_sn_plan_info* info) {
@@ -260,38 +252,28 @@ int calm_sn_power_iter(const void* plan_dev, const calm_sn_plan_info* info, int3
                        float* scratch, void* stream) {
     if (!plan_dev || !info || !scratch || info->n_layers <= 0 || info->n_work <= 0 || info->n_work_a <= 0)
         return CALM_E_INVAL;
-    hipStream_t s = as_stream(stream);
     const SnLayerDev* L = reinterpret_cast<const SnLayerDev*>(plan_dev);
     const SnWork* W = reinterpret_cast<const SnWork*>(L + info->n_layers);
     if (training) {
         const SnWorkA* WA = reinterpret_cast<const SnWorkA*>(W + info->n_work);
-        hipLaunchKernelGGL(sn_phase_a, dim3(info->n_work_a), dim3(NT), 0, s, L, WA, scratch);
-        CALM_LAUNCH_CHECK();
+        if (int e = calm_launch(sn_phase_a, info->n_work_a, NT, 0, stream, L, WA, scratch)) return e;
     }
-    hipLaunchKernelGGL(sn_phase_b, dim3(info->n_work), dim3(NT), 0, s, L, W, scratch, training, eps);
-    CALM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sn_phase_c, dim3(info->n_layers), dim3(NT), 0, s, L, (const float*)scratch, training, eps);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    if (int e = calm_launch(sn_phase_b, info->n_work, NT, 0, stream, L, W, scratch, training, eps)) return e;
+    return calm_launch(sn_phase_c, info->n_layers, NT, 0, stream, L, scratch, training, eps);
 }
 
 int calm_sn_weight_bwd(const float* G, const float* w_orig, const float* u, const float* v, const float* sigma,
                        const float* ls, float* d_w_orig, float* d_ls, int32_t rows, int32_t cols, float* scratch,
                        void* stream) {
     if (!G || !w_orig || !u || !v || !sigma || !d_w_orig || !scratch || rows <= 0 || cols <= 0) return CALM_E_INVAL;
-    hipStream_t s = as_stream(stream);
     int g1 = (rows + 3) / 4;
     if (g1 > 1024) g1 = 1024;
-    hipLaunchKernelGGL(sn_bwd_rowdot, dim3(g1), dim3(NT), 0, s, G, w_orig, sigma, scratch, rows, cols);
-    CALM_LAUNCH_CHECK();
+    if (int e = calm_launch(sn_bwd_rowdot, g1, NT, 0, stream, G, w_orig, sigma, scratch, rows, cols)) return e;
     long total = (long)rows * cols;
     int g2 = (int)((total + NT * 4 - 1) / (NT * 4));
     if (g2 > 1024) g2 = 1024;
     if (g2 < 1) g2 = 1;
-    hipLaunchKernelGGL(sn_bwd_apply, dim3(g2), dim3(NT), 0, s, G, u, v, sigma, ls, (const float*)scratch, d_w_orig,
-                       d_ls, rows, cols);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(sn_bwd_apply, g2, NT, 0, stream, G, u, v, sigma, ls, scratch, d_w_orig, d_ls, rows, cols);
 }
 
 }  // extern "C"

@@ -257,14 +257,11 @@ int calm_collate_crop_mix(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const i
     if (!crop_yx && (Hs != H || Ws != W)) return CALM_E_INVAL;
     int g = grid_for((int64_t)B * 3 * H * W, NT * 4);
     const int y1 = box ? box[0] : 0, y2 = box ? box[1] : 0, x1 = box ? box[2] : 0, x2 = box ? box[3] : 0;
-    if (out_tokens)
-        hipLaunchKernelGGL(collate_mix_kernel<true>, dim3(g), dim3(NT), 0, as_stream(stream), img_u8, Hs, Ws, crop_yx, flip, out, B, H,
-                           W, mode, lam, y1, y2, x1, x2, mean[0], mean[1], mean[2], 1.0f / std[0], 1.0f / std[1], 1.0f / std[2]);
-    else
-        hipLaunchKernelGGL(collate_mix_kernel<false>, dim3(g), dim3(NT), 0, as_stream(stream), img_u8, Hs, Ws, crop_yx, flip, out, B, H,
-                           W, mode, lam, y1, y2, x1, x2, mean[0], mean[1], mean[2], 1.0f / std[0], 1.0f / std[1], 1.0f / std[2]);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return with_bool(out_tokens != 0, [&](auto tokens) {
+        return calm_launch(collate_mix_kernel<decltype(tokens)::value>, g, NT, 0, stream, img_u8, Hs, Ws, crop_yx, flip, out, B,
+                           H, W, mode, lam, y1, y2, x1, x2, mean[0], mean[1], mean[2], 1.0f / std[0], 1.0f / std[1],
+                           1.0f / std[2]);
+    });
 }
 
 int calm_collate_mix(const uint8_t* img_u8, const uint8_t* flip, float* out, int32_t B, int32_t H, int32_t W,
@@ -274,18 +271,12 @@ int calm_collate_mix(const uint8_t* img_u8, const uint8_t* flip, float* out, int
 
 int calm_image_to_rows(const float* img, float* rows, int32_t B, int32_t S, void* stream) {
     if (!img || !rows || B <= 0 || S <= 0) return CALM_E_INVAL;
-    hipLaunchKernelGGL(image_to_rows_kernel, dim3(grid_for((int64_t)B * S * S * 3, NT * 4)), dim3(NT), 0,
-                       as_stream(stream), img, rows, B, S);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(image_to_rows_kernel, grid_for((int64_t)B * S * S * 3, NT * 4), NT, 0, stream, img, rows, B, S);
 }
 
 int calm_rows_to_image(const float* rows, float* img, int32_t B, int32_t S, void* stream) {
     if (!img || !rows || B <= 0 || S <= 0) return CALM_E_INVAL;
-    hipLaunchKernelGGL(rows_to_image_kernel, dim3(grid_for((int64_t)B * S * S * 3, NT * 4)), dim3(NT), 0,
-                       as_stream(stream), rows, img, B, S);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(rows_to_image_kernel, grid_for((int64_t)B * S * S * 3, NT * 4), NT, 0, stream, rows, img, B, S);
 }
 
 int calm_grid_transpose(const float* in, float* out, int32_t B, int32_t S, void* stream) {
@@ -293,22 +284,16 @@ int calm_grid_transpose(const float* in, float* out, int32_t B, int32_t S, void*
     if (B > 65535) return CALM_E_UNSUPP;
     const int t = (S + 31) / 32;
     static_assert((32 * 24) % NT == 0, "vector tile map");
-    if ((S & 3) == 0 && aligned16(in) && aligned16(out))
-        hipLaunchKernelGGL(grid_transpose_vec_kernel, dim3(t, t, B), dim3(NT), 0, as_stream(stream), in, out, S);
-    else
-        hipLaunchKernelGGL(grid_transpose_kernel, dim3(t, t, B), dim3(NT), 0, as_stream(stream), in, out, S);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    const bool vec = (S & 3) == 0 && aligned16(in) && aligned16(out);
+    return calm_launch(vec ? grid_transpose_vec_kernel : grid_transpose_kernel, dim3(t, t, B), NT, 0, stream, in, out, S);
 }
 
 int calm_dwconv3x3_fwd(const float* x, const float* w, const float* inv_scale, const float* bias, float* y,
                        float* y_pre, int32_t act, int32_t B, int32_t S, int32_t C, void* stream) {
     if (!x || !w || !y || B <= 0 || S <= 0 || C <= 0) return CALM_E_INVAL;
     if (act != CALM_ACT_NONE && act != CALM_ACT_GELU) return CALM_E_UNSUPP;
-    hipLaunchKernelGGL(dwconv_fwd_kernel, dim3(grid_for((int64_t)B * S * S * C, NT * 2)), dim3(NT), 0,
-                       as_stream(stream), x, w, inv_scale, bias, y, y_pre, act, B, S, C);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(dwconv_fwd_kernel, grid_for((int64_t)B * S * S * C, NT * 2), NT, 0, stream, x, w, inv_scale, bias, y,
+                       y_pre, act, B, S, C);
 }
 
 int calm_dwconv3x3_bwd(const float* dz, const float* x, const float* w, const float* inv_scale, float* dx,
@@ -317,10 +302,7 @@ int calm_dwconv3x3_bwd(const float* dz, const float* x, const float* w, const fl
     if (C > DW_MAXC || NT % C != 0) return CALM_E_UNSUPP;
     int g = grid_for((int64_t)B * S * S * C, NT * 8);
     if (g > 1024) g = 1024;
-    hipLaunchKernelGGL(dwconv_bwd_kernel, dim3(g), dim3(NT), 0, as_stream(stream), dz, x, w, inv_scale, dx, dw, db, B,
-                       S, C);
-    CALM_LAUNCH_CHECK();
-    return 0;
+    return calm_launch(dwconv_bwd_kernel, g, NT, 0, stream, dz, x, w, inv_scale, dx, dw, db, B, S, C);
 }
 
 int calm_abi_version(void) { return CALM_ABI_VERSION; }

@@ -167,3 +167,103 @@ def test_gemm_workspace_bytes_and_describe_report_one_plan():
         for o, v in zip((opt_pipe, opt_pipe32, opt_det), saved):
             lib.calm_gemm_set_option(o, v)
     assert families == {0, 1, 2, 3, 4, 5} and with_ws > 100, (families, with_ws)        # the sweep reaches every case
+
+
+# ---- what the streaming entry points refuse before they launch anything ----------------------------------------------
+# name -> (a valid argument list with fake, 16-byte aligned device addresses; indices of the pointers that are required).
+# The valid list itself is never passed: every call below changes it into one the entry point has to turn down in its
+# argument checks, so no kernel is launched and nothing is dereferenced.
+_P = 0x7f0000010000
+_STREAMING = {
+    "calm_layernorm_fwd": ([_P, _P, _P, _P, _P, 64, 672, 1e-5, 0, None], (0, 1, 2, 3, 4)),
+    "calm_layernorm_bwd": ([_P, _P, _P, _P, _P, _P, _P, None, 64, 672, 0, _P, None], (0, 1, 2, 3, 4, 5, 6, 11)),
+    "calm_rope_fwd": ([_P, _P, _P, _P, _P, 2, 16, 4, 24, 8, 0, 0, 0, None], (0, 1, 2, 3, 4)),
+    "calm_rope_bwd": ([_P, _P, _P, _P, _P, _P, 2, 16, 4, 24, 8, 0, 0, 0, 0, _P, None], (0, 1, 2, 3, 4, 5, 15)),
+    "calm_softmax_fwd": ([_P, 64, 224, None], (0,)),
+    "calm_softmax_bwd": ([_P, _P, 64, 224, None], (0, 1)),
+    "calm_softmax_bwd_heads": ([_P, _P, _P, 2, 4, 16, 224, None], (0, 1, 2)),
+    "calm_sum_heads": ([_P, _P, 2, 4, 256, None], (0, 1)),
+    "calm_latent_fwd": ([_P, None, _P, _P, _P, 64, 240, _P, None], (0, 2, 3, 4, 7)),
+    "calm_latent_bwd": ([None, None, _P, None, _P, _P, 64, 240, None], (2, 4, 5)),
+    "calm_add": ([_P, _P, _P, 1024, None], (0, 1, 2)),
+    "calm_gelu_fwd": ([_P, _P, 1024, None], (0, 1)),
+    "calm_gelu_bwd": ([_P, _P, _P, 1024, None], (0, 1, 2)),
+    "calm_colsum": ([_P, _P, 64, 672, 0, _P, None], (0, 1, 5)),
+    "calm_row_scale": ([_P, _P, _P, 64, 672, 0, None], (0, 1, 2)),
+    "calm_mean_seq_fwd": ([_P, _P, 2, 16, 64, None], (0, 1)),
+    "calm_mean_seq_bwd": ([_P, _P, 2, 16, 64, None], (0, 1)),
+    "calm_cnn_residual_fwd": ([_P] * 11 + [2, 32, 32, 1, None], tuple(range(11))),
+    "calm_cnn_residual_bwd": ([_P] * 18 + [2, 32, 32, 1, _P, None], tuple(range(18)) + (22,)),
+    "calm_soft_ce_fwd": ([_P, 1000, _P, 1000, _P, _P, None, 8, 1000, _P, None], (0, 2, 4, 5, 9)),
+    "calm_soft_ce_bwd": ([_P, 1000, _P, 1000, _P, _P, _P, 8, 1000, None], (0, 2, 4, 5, 6)),
+    "calm_huber_tokens_fwd": ([_P, _P, 1.0, _P, 2, 32, _P, None], (0, 1, 3, 6)),
+    "calm_huber_tokens_bwd": ([_P, _P, 1.0, _P, _P, 2, 32, None], (0, 1, 3, 4)),
+    "calm_top1_count": ([_P, 1000, _P, _P, 8, 1000, None], (0, 2, 3)),
+}
+# (name, {argument index: value}, expected code, what it is)
+_REFUSED = [
+    ("calm_layernorm_fwd", {8: 2}, "E_INVAL", "y_type fp8"),
+    ("calm_layernorm_fwd", {8: -1}, "E_INVAL", "y_type negative"),
+    ("calm_layernorm_bwd", {10: 3}, "E_INVAL", "dy_type fp8"),
+    ("calm_layernorm_bwd", {9: 2049}, "E_UNSUPP", "D above 2048"),
+    ("calm_layernorm_bwd", {9: 4096}, "E_UNSUPP", "D above 2048"),
+    ("calm_rope_fwd", {10: 2}, "E_INVAL", "content_type fp8"),
+    ("calm_rope_fwd", {11: 2}, "E_INVAL", "xr_type fp8"),
+    ("calm_rope_fwd", {12: 7}, "E_INVAL", "out_type unknown"),
+    ("calm_rope_fwd", {9: 7}, "E_INVAL", "odd dr"),
+    ("calm_rope_bwd", {11: 2}, "E_INVAL", "dout_type fp8"),
+    ("calm_rope_bwd", {12: 2}, "E_INVAL", "xr_type fp8"),
+    ("calm_rope_bwd", {13: 2}, "E_INVAL", "dcontent_type fp8"),
+    ("calm_rope_bwd", {14: 2}, "E_INVAL", "dxr_type fp8"),
+    ("calm_rope_bwd", {10: 7}, "E_INVAL", "odd dr"),
+    ("calm_rope_bwd", {10: 514}, "E_UNSUPP", "257 rotation pairs"),
+    ("calm_rope_bwd", {10: 1024}, "E_UNSUPP", "512 rotation pairs"),
+    ("calm_rope_bwd", {6: 1 << 15, 7: 1 << 10, 8: 2, 9: 24, 10: 8}, "E_UNSUPP", "2^31 elements"),
+    ("calm_rope_bwd", {6: 1 << 16, 7: 1 << 10, 8: 4, 9: 0, 10: 8}, "E_UNSUPP", "2^31 elements, no content"),
+    ("calm_softmax_fwd", {2: 1025}, "E_UNSUPP", "cols above 1024"),
+    ("calm_softmax_bwd", {3: 1025}, "E_UNSUPP", "cols above 1024"),
+    ("calm_softmax_bwd_heads", {6: 1025}, "E_UNSUPP", "cols above 1024"),
+    ("calm_colsum", {4: 2}, "E_INVAL", "x_type fp8"),
+    ("calm_colsum", {3: 4097}, "E_UNSUPP", "cols above 4096"),
+    ("calm_colsum", {3: 8192}, "E_UNSUPP", "cols above 4096"),
+    ("calm_row_scale", {5: 2}, "E_INVAL", "out_type fp8"),
+    ("calm_cnn_residual_fwd", {13: 16}, "E_UNSUPP", "hidden 16"),
+    ("calm_cnn_residual_fwd", {13: 64}, "E_UNSUPP", "hidden 64"),
+    ("calm_cnn_residual_bwd", {20: 16}, "E_UNSUPP", "hidden 16"),
+    ("calm_cnn_residual_bwd", {20: 64}, "E_UNSUPP", "hidden 64"),
+    ("calm_huber_tokens_fwd", {5: 30}, "E_UNSUPP", "S % 4 != 0"),
+    ("calm_huber_tokens_fwd", {5: 223}, "E_UNSUPP", "S % 4 != 0"),
+    ("calm_huber_tokens_bwd", {6: 30}, "E_UNSUPP", "S % 4 != 0"),
+    ("calm_huber_tokens_bwd", {6: 223}, "E_UNSUPP", "S % 4 != 0"),
+]
+
+
+def test_streaming_entry_points_refuse_bad_arguments_before_any_launch():
+    """The argument checks of the streaming entry points (csrc/norm_act.hip, cnn_fused.hip, loss.hip) on a host without a
+    GPU: a null required pointer, a storage type other than fp32 / bf16 and an odd rotation width are CALM_E_INVAL; a
+    shape no kernel is compiled for is CALM_E_UNSUPP (softmax rows above 1024, LayerNorm backward rows above 2048, column
+    sums above 4096 columns, a RoPE backward with more than 256 rotation pairs or 2^31 elements, a CNN tail whose hidden
+    width is not 32, a Huber loss on an image side that is not a multiple of 4).  The expected codes are those of the
+    library before its launch code was rewritten (one launch helper, typed dispatch): they are part of the C-ABI."""
+    sys.path.insert(0, ROOT)
+    from importlib import import_module
+    binding = import_module("calm_vit_dte_amd._lib")
+    lib = binding.load()
+    assert sorted(n for n in binding.SIGNATURES if re.match(
+        r"calm_(layernorm|rope|softmax|sum_heads|latent|add$|gelu|colsum|row_scale|mean_seq|cnn_residual|soft_ce|huber|top1)", n)
+    ) == sorted(_STREAMING)                                        # the table names every streaming entry point
+    calls = 0
+    for name, (valid, required) in _STREAMING.items():
+        assert len(valid) == len(binding.SIGNATURES[name][1]), name
+        for i in required:                                          # one null pointer at a time
+            args = list(valid)
+            args[i] = None
+            assert getattr(lib, name)(*args) == binding.E_INVAL, (name, "null pointer", i)
+            calls += 1
+    for name, change, code, what in _REFUSED:
+        args = list(_STREAMING[name][0])
+        for i, v in change.items():
+            args[i] = v
+        assert getattr(lib, name)(*args) == getattr(binding, code), (name, what)
+        calls += 1
+    assert calls > 120

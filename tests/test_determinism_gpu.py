@@ -143,6 +143,33 @@ def test_reduction_scratch_contract(monkeypatch):
             assert torch.equal(g, w), i
 
 
+def test_partials_buffer_outlives_its_replacement():
+    """HipBackend._partials hands kernels a raw address, and a captured graph keeps it.  When a call on the same stream
+    needs more than the cached buffer holds, the larger buffer takes its place in the cache, but the earlier one stays
+    referenced by the backend: the address handed out for the earlier, smaller shape still points at storage nobody else
+    can be given.  Calls that fit the cached buffer keep getting the cached buffer."""
+    lib_mod = import_module("calm_vit_dte_amd._lib")
+    be = calm.backend.HipBackend()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    small, large = (lib_mod.RED_LAYERNORM_BWD, 57344, 672), (lib_mod.RED_ROPE_BWD, 64 * 224 * 12, 1024)
+    assert int(be.lib.calm_reduce_scratch_floats(*small)) <= (1 << 20) < int(be.lib.calm_reduce_scratch_floats(*large))
+    with torch.cuda.stream(torch.cuda.Stream()):
+        p_small = be._partials(*small, dev)
+        assert be._partials(*small, dev) == p_small
+        (first,) = be._scratch_bufs.values()
+        assert first.data_ptr() == p_small
+        del first
+        p_large = be._partials(*large, dev)
+        assert p_large != p_small
+        held = [t for t in be._scratch_retired if t.data_ptr() == p_small]
+        assert len(held) == 1 and held[0].numel() == 1 << 20          # the same storage, still owned by the backend
+        fresh = [torch.empty(1 << 20, device=dev) for _ in range(8)]   # the allocator cannot hand that block out again
+        assert all(not (t.data_ptr() <= p_small < t.data_ptr() + 4 * t.numel()) for t in fresh)
+        assert be._partials(*small, dev) == p_large                  # no growth: the cached buffer, as before
+        assert be._partials(*large, dev) == p_large
+        assert len(be._scratch_retired) == 1 and len(be._scratch_bufs) == 1
+
+
 def test_split_k_weight_gradient_is_reproducible_in_deterministic_mode(deterministic_gemm):
     be = deterministic_gemm
     calm.backend.set_matmul_precision("bf16")
