@@ -577,10 +577,15 @@ int launch_fwd16_t(const Attn16P& p0, hipStream_t s) {
     void (*k1)(const Attn16P) = nullptr;
     void (*k3)(const Attn16P) = nullptr;
     int lds1 = G2::LDS;
+    // Phase 1 of the pipelined forward brings rows of all D = H hd columns of q and k into LDS in 16-byte chunks, on BOTH
+    // sides of the product R = q k^T.  With D % 8 == 4 the last chunk of a row would carry the next row's first four
+    // elements into R on either side (and, at the last row of the tensor, read 8 bytes past its end): those shapes take
+    // the register-staged forward, which stages 8-byte vectors.  (Every model config has D % 8 == 0.)
+    const bool rows16 = (p.H * p.hd) % 8 == 0;
     if constexpr (G2::OK) {
-        if (env.fwd2) k1 = &attn16_fwd2_kernel<NP, HDP>;
+        if (env.fwd2 && rows16) k1 = &attn16_fwd2_kernel<NP, HDP>;
         if constexpr (G3::OK) {
-            if (env.fwd2 && env.fwd3) {
+            if (env.fwd2 && rows16 && env.fwd3) {
                 k1 = &attn16_fwd2_kernel<NP, HDP, true>;
                 k3 = p.S == 32 * NP ? &attn16_fwd3_core_kernel<NP, HDP, true> : &attn16_fwd3_core_kernel<NP, HDP, false>;
                 p.stagger = env.stagger;

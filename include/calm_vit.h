@@ -300,7 +300,8 @@ int calm_attention_bwd_lse(const float* q, const float* k, const float* v, const
  *   pass, read by the key-side pass); out = the forward's output.
  * Two kernel generations sit behind these entry points, chosen by shape (same arithmetic, same rounding points):
  * S <= 224 with hd <= 64 (every stage of Base-224) runs the LDS-DMA pipelined kernels of round 3
- * (csrc/attention_bf16_fwd2.h, csrc/attention_bf16_bwd2.h), everything else the register-staged ones.  No entry point
+ * (csrc/attention_bf16_fwd2.h, csrc/attention_bf16_bwd2.h; the forward only when H * hd % 8 == 0, i.e. rows of q / k
+ * are whole 16-byte chunks), everything else the register-staged ones.  No entry point
  * uses atomics: results repeat bit for bit.  With B % 8 == 0 the workgroups of one image are dealt to one XCD (L2 reuse
  * of its K / V); any B is valid.
  * ------------------------------------------------------------------------------------- */

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 import calm_vit_dte_amd as calm
+from attn16_f64 import FILL, GELU_FWD_ERR, assert_bf16_rounding_of, bf16_ord  # shared with the attention checker
 from helpers import rel_err_elem
 
 pytestmark = pytest.mark.gpu
@@ -31,8 +32,6 @@ DEV = "cuda"
 U = 2.0 ** -24                     # unit roundoff of fp32
 EPS = 1e-6                         # the model's LayerNorm eps (oracle LN_EPS)
 GUARD = 40                         # guard elements on either side of every output
-FILL = {torch.float32: 0x7FC0DEAD, torch.bfloat16: 0x7FDE}   # quiet NaNs with payloads no arithmetic yields
-GELU_FWD_ERR = 1.39e-7             # measured, see the module docstring
 GELU_BWD_ERR = 2.85e-7
 
 
@@ -139,24 +138,6 @@ def latent_depth(rows, mvh, vec):
     g = grid_for(n, 1024)
     per = 4 * cdiv(n // 4, g * 256) if vec else cdiv(n, g * 256)
     return per + 9 + partials_depth(g)
-
-
-def bf16_ord(t):
-    """bf16 values as integers ordered like the values, adjacent representables one apart (+0 and -0 both 0)."""
-    b = t.contiguous().view(torch.int16).to(torch.int32)
-    return torch.where(b < 0, -(b & 0x7FFF), b)
-
-
-def assert_bf16_rounding_of(got, ref64, fp32_bound, min_equal=0.99):
-    """bf16 result of an fp32 computation whose own error is <= fp32_bound: at least `min_equal` of the elements are
-    the float64 reference rounded once (RNE), the rest one bf16 ulp away — or, where the fp32 bound exceeds a bf16 ulp
-    (values near 0, cancellation), within that bound plus the rounding.  An fp32 error of a few u moves a value across
-    a bf16 rounding boundary with probability ~ (few u) / 2^-8 < 1e-4 per element."""
-    r = ref64.to(torch.bfloat16)
-    d = (bf16_ord(got) - bf16_ord(r)).abs()
-    near = (got.double() - ref64).abs() <= fp32_bound + 2.0 ** -8 * ref64.abs()
-    assert bool(((d <= 1) | near).all()), f"bf16 output {int(d[~near].max())} ulps from the rounded reference"
-    assert float((d == 0).double().mean()) >= min_equal
 
 
 # ================================================================================================= 1. LayerNorm
