@@ -160,8 +160,8 @@ class VMLA_Block(torch.nn.Module):
         norm_layer: Callable[..., torch.nn.Module] = _default_norm,
     ):
         super().__init__()
-        if dropout != 0.0:
-            raise NotImplementedError("dropout > 0 is not on the reference's training path (always 0.0)")
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"dropout must be in the range 0 <= dropout < 1, got {dropout}")
         self.ls_att = torch.nn.Parameter(torch.ones(dim2), requires_grad=True)
         self.ls_mlp = torch.nn.Parameter(torch.ones(dim2), requires_grad=True) if use_mlp else None
         self.training = training
@@ -313,13 +313,24 @@ class VMLA_Block(torch.nn.Module):
                 residual = self._seq(self.input_t_proj, residual)
             if self.input_proj is not None:
                 residual = self.input_proj(residual)
-        x = self.out_proj(x, ls=self.ls_att, residual=residual)          # 300, 309
+        # the two nn.Dropout modules only carry p (read at call time, so setting `.p` on them works); the dropout itself is
+        # ops.DropoutAddFn / inside ops.MlpFn.  Keys in the reference's call order: attention site (301), then the MLP (203)
+        p_att = self.dropout.p if self.training else 0.0
+        if p_att > 0:
+            x = self.out_proj(x, ls=self.ls_att)                         # 300
+            x = ops.DropoutAddFn.apply(x, residual, p_att, ops.draw_dropout_key(x.device))   # 301, 309
+        else:
+            x = self.out_proj(x, ls=self.ls_att, residual=residual)      # 300, 309
         if self.mlp is None:                                             # 310-315
             return self.ln_2(x)                                          # block output: stays fp32
         y, x = self.ln_2.with_skip(x)
         l0, l3 = self.mlp[0], self.mlp[3]
-        return ops.MlpFn.apply(y, l0.weight_orig, None, l3.weight_orig, None, self.ls_mlp, x,
-                               l0.weight_u, l0.weight_v, l0.sigma(), l3.weight_u, l3.weight_v, l3.sigma())
+        mlp_args = (y, l0.weight_orig, None, l3.weight_orig, None, self.ls_mlp, x,
+                    l0.weight_u, l0.weight_v, l0.sigma(), l3.weight_u, l3.weight_v, l3.sigma())
+        p_mlp = self.mlp[2].p if self.training else 0.0
+        if p_mlp > 0:
+            return ops.MlpFn.apply(*mlp_args, p_mlp, ops.draw_dropout_key(y.device))
+        return ops.MlpFn.apply(*mlp_args)
 
 
 class CnnResidual(torch.nn.Sequential):

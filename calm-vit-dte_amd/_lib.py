@@ -143,6 +143,7 @@ SIGNATURES = {
     "calm_huber_tokens_fwd": (_i32, [_p, _p, _f32, _p, _i32, _i32, _p, _p]),
     "calm_huber_tokens_bwd": (_i32, [_p, _p, _f32, _p, _p, _i32, _i32, _p]),
     "calm_top1_count": (_i32, [_p, _i64, _p, _p, _i32, _i32, _p]),
+    "calm_dropout": (_i32, [_p, _p, _p, _i64, _i64, _f32, _p, _i32, _i32, _i32, _p]),
 }
 
 _lib = None

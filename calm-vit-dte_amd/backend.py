@@ -755,6 +755,16 @@ class HipBackend:
         _lib.check(self.lib.calm_top1_count(_ptr(logits), logits.stride(0), labels.data_ptr(), _ptr(metrics), B, C,
                                             _stream()), "calm_top1_count")
 
+    # ---- dropout (csrc/dropout.hip) -----------------------------------------------------
+    def dropout(self, x, residual, y, n, p, key, e0=0):
+        """y[j] = x[j] * mask(e0 + j) / (1 - p) + residual[j] with the Philox mask of `key` (device int64 [2] = seed, offset,
+        read by the kernel); x / residual / y fp32 or bf16 independently, residual may be None, y may be x."""
+        if key is None or not key.is_cuda or key.dtype != torch.int64 or key.numel() != 2 or not key.is_contiguous():
+            raise TypeError("dropout expects its key as a contiguous int64 CUDA tensor of two elements (seed, offset)")
+        _lib.check(self.lib.calm_dropout(_ptr(x, bf16_ok=True), _ptr(residual, True, bf16_ok=True), _ptr(y, bf16_ok=True),
+                                         n, e0, float(p), key.data_ptr(), _st(x), _st(residual), _st(y), _stream()),
+                   "calm_dropout")
+
     # ---- helpers ----------------------------------------------------------------------
     def add(self, a, b, out, n):
         _lib.check(self.lib.calm_add(_ptr(a), _ptr(b), _ptr(out), n, _stream()), "calm_add")

@@ -43,6 +43,24 @@ def draw_noise(like):
     return _noise_override(like) if _noise_override is not None else torch.randn_like(like)
 
 
+_dropout_key_override = None
+
+
+def set_dropout_key_override(fn):
+    """Tests inject the dropout keys (`fn(device) -> int64 tensor [2] = seed, offset`); None restores the default."""
+    global _dropout_key_override
+    _dropout_key_override = fn
+
+
+def draw_dropout_key(device):
+    """The (seed, offset) of one dropout site of one forward: 2 x 63 random bits from torch's generator of `device` —
+    reproducible under torch.manual_seed, and drawn by a device kernel, so a captured graph draws new keys on every
+    replay (as it draws new latent noise).  The kernel reads the int64 bit patterns as its uint64 key."""
+    if _dropout_key_override is not None:
+        return _dropout_key_override(device)
+    return torch.randint(0, 2 ** 63 - 1, (2,), dtype=torch.int64, device=device)
+
+
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
@@ -410,12 +428,14 @@ class SNLinearGroupFn(Function):
 
 
 class MlpFn(Function):
-    """out = (gelu(x W1^T/s1 + b1) W2^T/s2 + b2) * ls + residual  (Vi_Tools:199-205,310-315 block MLP;
-    CALM_ViT_V2.py:49-53,76 cls head).  The GELU backward is fused into the dgrad GEMM epilogue."""
+    """out = (drop(gelu(x W1^T/s1 + b1)) W2^T/s2 + b2) * ls + residual  (Vi_Tools:199-205,310-315 block MLP;
+    CALM_ViT_V2.py:49-53,76 cls head).  The GELU backward is fused into the dgrad GEMM epilogue.  p > 0 (with `key`,
+    draw_dropout_key): the hidden state is dropped in place, in its storage type, before the second product — that product
+    and the W2 weight gradient read the dropped tensor — and the backward applies the same key to its gradient."""
 
     @staticmethod
     @_amp_fwd
-    def forward(ctx, x, w1, b1, w2, b2, ls, residual, u1, v1, s1, u2, v2, s2):
+    def forward(ctx, x, w1, b1, w2, b2, ls, residual, u1, v1, s1, u2, v2, s2, p=0.0, key=None):
         be = get_backend()
         x = _c(x)
         K = x.shape[-1]
@@ -430,18 +450,25 @@ class MlpFn(Function):
         out = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
         res2 = _c(residual).reshape(-1, N) if residual is not None else None
         ctx.fp8 = _fp8_ok(K, Hd, N)
+        ctx.p = float(p)
+        if ctx.p > 0 and key is None:
+            raise ValueError("MlpFn: p > 0 needs a key (ops.draw_dropout_key)")
         if ctx.fp8:                      # both products on fp8 operands; hidden state / pre-activation stay bf16 tensors
             _lin_fwd8(be, x2, w1, s1, hg, bias=b1, act=ACT_GELU, C_pre=hp)
-            _lin_fwd8(be, hg, w2, s2, out.view(-1, N), bias=b2, col_scale=ls, residual=res2)
         else:
             _lin_fwd(be, x2, wop1, s1, hg, bias=b1, act=ACT_GELU, pre=hp)
+        if ctx.p > 0:
+            be.dropout(hg, None, hg, hg.numel(), ctx.p, key)
+        if ctx.fp8:
+            _lin_fwd8(be, hg, w2, s2, out.view(-1, N), bias=b2, col_scale=ls, residual=res2)
+        else:
             _lin_fwd(be, hg, wop2, s2, out.view(-1, N), bias=b2, col_scale=ls, residual=res2)
         ctx.wops = (wop1, wop2)
         ctx.wgen = _wgen(w1, w2)
         ctx.has_b1, ctx.has_b2, ctx.has_res = b1 is not None, b2 is not None, residual is not None
         ctx.defer = (_deferred(w1), _deferred(w2))
         ctx.xshape = x.shape
-        ctx.save_for_backward(x2, hp, hg, w1, w2, ls, u1, v1, s1, u2, v2, s2)
+        ctx.save_for_backward(x2, hp, hg, w1, w2, ls, u1, v1, s1, u2, v2, s2, key if ctx.p > 0 else None)
         return out
 
     @staticmethod
@@ -449,7 +476,7 @@ class MlpFn(Function):
     @_amp_bwd
     def backward(ctx, dout):
         be = get_backend()
-        x2, hp, hg, w1, w2, ls, u1, v1, s1, u2, v2, s2 = ctx.saved_tensors
+        x2, hp, hg, w1, w2, ls, u1, v1, s1, u2, v2, s2, key = ctx.saved_tensors
         _check_wgen(ctx.wgen, w1, w2)
         N, Hd = w2.shape
         K = w1.shape[1]
@@ -470,6 +497,8 @@ class MlpFn(Function):
             _lin_dgrad8(be, do2, w2l, s2, dhp, act=ACT_GELU_BWD, aux=hp)
         else:
             _lin_dgrad(be, do2g, w2l, s2, dhp, act=ACT_GELU_BWD, aux=hp)
+        if ctx.p > 0:                    # the mask and gelu' are both element-wise factors: either order gives d(pre-activation)
+            be.dropout(dhp, None, dhp, dhp.numel(), ctx.p, key)
         G1 = _zeros_big(w1.shape, w1)
         _lin_wgrad(be, dhp, x2, G1)
         dW1, _ = _sn_wbwd(be, G1, w1, u1, v1, s1, defer=ctx.defer[0])
@@ -483,7 +512,7 @@ class MlpFn(Function):
                 _lin_dgrad(be, dhp, wop1, s1, dx)
             dx = dx.view(ctx.xshape)
         dres = dout if ctx.has_res else None
-        return dx, dW1, db1, dW2, db2, d_ls, dres, None, None, None, None, None, None
+        return dx, dW1, db1, dW2, db2, d_ls, dres, None, None, None, None, None, None, None, None
 
 
 class SeqLinearFn(Function):
@@ -910,6 +939,37 @@ class AddFn(Function):
     @staticmethod
     def backward(ctx, g):
         return g, g
+
+
+class DropoutAddFn(Function):
+    """y = dropout(x) + residual (Vi_Tools:301,309: the attention branch behind out_proj * ls_att joins the skip path).
+    apply(x, residual, p, key); key from draw_dropout_key.  Only the 16-byte key is kept for the backward, which
+    regenerates the mask: dx = dropout(dy), dresidual = dy."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, x, residual, p, key):
+        be = get_backend()
+        x, residual = _c(x), _c(residual)
+        if x.shape != residual.shape:
+            raise ValueError("DropoutAddFn: x and residual must have one shape")
+        y = torch.empty_like(x)
+        be.dropout(x, residual, y, x.numel(), p, key)
+        ctx.p = float(p)
+        ctx.save_for_backward(key)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    @_amp_bwd
+    def backward(ctx, dy):
+        key, = ctx.saved_tensors
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dy_c = _c(dy)
+            dx = torch.empty_like(dy_c)
+            get_backend().dropout(dy_c, None, dx, dy_c.numel(), ctx.p, key)
+        return dx, dy, None, None
 
 
 class RowsToImageFn(Function):

@@ -519,6 +519,26 @@ int calm_mean_seq_fwd(const float* x, float* y, int32_t B, int32_t S, int32_t D,
 int calm_mean_seq_bwd(const float* dy, float* dx, int32_t B, int32_t S, int32_t D, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Dropout with a counter-based mask (an addition to ABI v7; nn.Dropout at Vi_Tools:301 and inside the MLP, Vi_Tools:203).
+ * For j in [0, n), e = e0 + j:
+ *     y[j] = x[j] * (word(e) >= thr ? scale : 0) + (residual ? residual[j] : 0)
+ *   word(e) = output word (e & 3) of Philox4x32-10 with counter (lo32(e >> 2), hi32(e >> 2), lo32(offset), hi32(offset)),
+ *             key (lo32(seed), hi32(seed)), multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85;
+ *   thr = (uint32_t)((double)p * 2^32),  scale = 1.0f / (1.0f - p)   (fp32; computed by the entry point).
+ * key: DEVICE uint64[2] = (seed, offset), read by the kernel — no host synchronisation, valid inside a captured graph.  The
+ * mask depends on (seed, offset, e) only: the backward passes the forward's key and gets the forward's mask, so no mask is
+ * ever stored.  e0 (a multiple of 4) lets a caller cover one logical tensor with several calls.
+ * One fp32 multiply and one fp32 add, each rounded on its own (the add is skipped without a residual); bf16 inputs widen
+ * exactly, a bf16 output is one round-to-nearest-even of the fp32 result.  A multiply, not a select: a dropped NaN / inf
+ * yields NaN (torch.nn.functional.dropout does the same).  y may alias x.  x_type / r_type / y_type: CALM_ST_F32 or
+ * CALM_ST_BF16.  CALM_E_INVAL: null x / y / key, n < 0, p outside [0, 1), e0 < 0 or e0 % 4 != 0, another storage type.
+ * n == 0 returns 0 without a launch.
+ * ------------------------------------------------------------------------------------- */
+int calm_dropout(const void* x, const void* residual /* nullable */, void* y, int64_t n, int64_t e0, float p,
+                 const uint64_t* key /* device, [2] = seed, offset */, int32_t x_type, int32_t r_type, int32_t y_type,
+                 void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * The loss end of the step (additions to ABI v7 — no existing signature or struct changes, so the version number
  * stays): logits -> loss and loss -> dL/dlogits as entry points, so that a host driving this boundary without torch can
  * train (forward, one of these, backward, calm_optim_step).  Logits are fp32 (module outputs stay fp32 in every
