@@ -28,6 +28,7 @@ COUNT_ULP_FRACTION = 32   # counted: elements whose fp32 bound is <= 1/32 of a b
 
 FILL = {torch.float32: 0x7FC0DEAD, torch.bfloat16: 0x7FDE}   # quiet NaNs with payloads no arithmetic yields
 GELU_FWD_ERR = 1.39e-7    # gelu_erf_f of common.h against float64, measured: see the docstring of test_rowwise_f64_gpu.py
+GELU_BWD_ERR = 2.85e-7    # gelu_erf_grad_f of common.h against float64, measured there as well
 
 FWD_NAMES = ("out", "R", "hp", "hg", "Mk", "MkT", "lse")
 BWD_NAMES = ("delta", "dq", "dk", "dv", "dM")

@@ -7,11 +7,10 @@ import pytest
 import torch
 
 import calm_vit_dte_amd as calm
+from gemm_f64 import GUARD_ROWS, Guarded      # C inside a NaN-filled guard band: shared with the per-instance checker
 from helpers import rel_err
 
 pytestmark = pytest.mark.gpu
-
-GUARD_ROWS, GUARD_COLS = 3, 12        # NaN rows above and below every C matrix, NaN columns beside it (4 left, 8 right)
 
 
 def rnd(*shape, seed=0):
@@ -29,28 +28,6 @@ def _product(A, B, akc, bkc):
     a = A.double() if akc else A.double().transpose(-1, -2)
     b = B.double() if bkc else B.double().transpose(-1, -2)
     return a @ b.transpose(-1, -2)
-
-
-class Guarded:
-    """A [b0, b1, M, N] fp32 matrix inside a NaN-filled buffer (row stride N + GUARD_COLS, GUARD_ROWS rows above and
-    below each matrix); `shift` moves it off 16-byte alignment (one-element epilogue)."""
-
-    def __init__(self, b0, b1, M, N, shift=0, init=None):
-        self.ld = N + GUARD_COLS
-        rows = M + 2 * GUARD_ROWS
-        self.buf = torch.full((b0 * b1 * rows * self.ld + 8,), float("nan"), device="cuda")
-        self.strides = (self.ld, b1 * rows * self.ld, rows * self.ld)
-        size, st = (b0, b1, M, N), (b1 * rows * self.ld, rows * self.ld, self.ld, 1)
-        self.t = self.buf.as_strided(size, st, GUARD_ROWS * self.ld + 4 + shift)
-        self.mask = torch.zeros(self.buf.numel(), dtype=torch.bool, device="cuda")
-        self.mask.as_strided(size, st, GUARD_ROWS * self.ld + 4 + shift).fill_(True)
-        if init is not None:
-            self.t.copy_(init)
-
-    def check(self):
-        assert torch.isnan(self.buf[~self.mask]).all(), "a store landed outside C"
-        assert torch.isfinite(self.buf[self.mask]).all(), "an element of C was not written"
-        return self.t.cpu().double()
 
 
 def _plan64(hip, *args, **kw):

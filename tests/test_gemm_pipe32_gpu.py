@@ -2,9 +2,15 @@
 gemm_f32p_kernel, LDS-DMA staging of 128-byte k-rows = 32 values, v_mfma_f32_16x16x4_f32) against a float64 product.
 The products are exact fp32 multiplies accumulated in fp32 (only the order of the reduction differs from the 128 x 128
 kernels), so the tolerance is fp32 rounding: 2e-6 x sqrt(K / 1024) of the largest output.  Cases: every operand-layout
-pair (k/k forward, k/row data gradient, row/row weight gradient — the [k][row] image is read with ds_read_b32), every tile
-width, ragged M / N / K (K tails of 4 ... 28), batches, grouped launches, k-split through atomics and through the
-workspace, the fused epilogue, and equivalence with the 128 x 128 family through calm_gemm_set_option."""
+pair (k/k forward, k/row data gradient, row/row weight gradient — the [k][row] image is read with ds_read_b32), ragged
+M / N / K (K tails of 4 ... 28), batches, grouped launches, k-split through atomics and through the workspace, the fused
+epilogue, and equivalence with the 128 x 128 family through calm_gemm_set_option.
+
+What the cases plan (calm_gemm_describe; the tile is chosen by the cost model of plan_pipe): the `plain` shapes reach 7 of
+the family's 42 instances — 128 x 128 in all three layouts, 128 x 192 (k/row), 128 x 224, 192 x 128 and 192 x 160
+(row/row).  Every `full` case passes GELU' together with a residual, which plan_pipe declines (one C-shaped epilogue
+operand): they run on the 64-row tiles of family 0.  All 42 instances and the epilogue forms plan_pipe accepts are
+launched by test_gemm_f64_gpu.py (tables: tests/gemm_f64.py)."""
 import pytest
 import torch
 
@@ -43,21 +49,21 @@ def _product(A, B, akc, bkc):
 
 CASES = [
     # M, N, K, batch, a_kcontig, b_kcontig
-    (4096, 672, 672, (1, 1), True, True),       # NT 7, K = 21 k-tiles
-    (4096, 528, 528, (1, 1), True, True),       # NT 6 (576 padded), K tail of 16
+    (4096, 672, 672, (1, 1), True, True),       # 128 x 128 tiles, K = 21 k-tiles
+    (4096, 528, 528, (1, 1), True, True),       # 128 x 128 tiles (640 padded), K tail of 16
     (4096, 384, 388, (1, 1), True, True),       # K tail of 4
-    (4096, 480, 240, (1, 1), True, True),       # NT 5, K tail of 16
-    (4096, 768, 96, (1, 1), True, True),        # NT 8, three k-tiles
-    (2056, 240, 476, (1, 1), True, True),       # ragged M (rows clamped), N 240 in a 256 tile, K tail of 28
+    (4096, 480, 240, (1, 1), True, True),       # 128 x 128 tiles (512 padded), K tail of 16
+    (4096, 768, 96, (1, 1), True, True),        # 128 x 128 tiles, three k-tiles
+    (2056, 240, 476, (1, 1), True, True),       # ragged M (rows clamped), N 240 in two 128 tiles, K tail of 28
     (1000, 136, 72, (2, 3), True, True),        # batches, ragged everything
-    (4096, 672, 1344, (1, 1), True, False),     # data gradient: weight in the [k][row] image
+    (4096, 672, 1344, (1, 1), True, False),     # data gradient: weight in the [k][row] image; 128 x 192 tiles, 2 k-slices
     (3000, 528, 1056, (1, 1), True, False),
     (2048, 240, 264, (1, 2), True, False),
     (1024, 352, 176, (3, 1), True, False),
     (224, 112, 224, (4, 6), False, False),      # per-image, per-head products of the composed attention backward
-    (672, 672, 8192, (1, 1), False, False),     # weight gradient: k-split, both operands row-contiguous
-    (1344, 672, 4096, (1, 1), False, False),
-    (528, 1056, 4108, (1, 1), False, False),    # K tail of 12
+    (672, 672, 8192, (1, 1), False, False),     # weight gradient: k-split, both operands row-contiguous; 128 x 224 tiles
+    (1344, 672, 4096, (1, 1), False, False),    # 192 x 128 tiles
+    (528, 1056, 4108, (1, 1), False, False),    # K tail of 12; 192 x 160 tiles
     (240, 480, 20480, (1, 1), False, False),    # many slices: workspace reduction
     (384, 384, 2048, (2, 1), False, False),     # row/row batches without split
     (136, 264, 640, (1, 1), False, False),

@@ -1,9 +1,16 @@
 """Pipelined persistent bf16-tensor GEMM family of calm_gemm (csrc/gemm_bf16p.h: LDS-DMA staging, (64 MT) x (32 NT) x 64
 tiles, swapped-operand accumulators) against the emulation of exactly its arithmetic: bf16 operands are exact in fp32,
 accumulation is fp32, the output is rounded once when stored.  The cases walk every operand-layout pair the family
-instantiates (k/k: forward, k/row: data gradient, row/row: weight gradient), every tile width (N picks NT, M x N picks
-MT), ragged M / N / K tails (rows clamped, columns masked, the k tail fed from the zero block), batches, independent
-groups, k-split launches through atomics and through the workspace, and the full fused epilogue."""
+instantiates (k/k: forward, k/row: data gradient, row/row: weight gradient), ragged M / N / K tails (rows clamped, columns
+masked, the k tail fed from the zero block), batches, independent groups, k-split launches through atomics and through
+the workspace, and the full fused epilogue.
+
+What the cases plan (calm_gemm_describe; the tile is chosen by the cost model of plan_pipe, not by N alone): of the 17
+`plain` shapes 14 run the 128 x 128 tile (MT 2, NT 4), 1344 x 672 x 4096 the 128 x 160 one, and two are declined by the
+pipelined family (K = 96 and K = 72 are below its 160) and run on the bf16-operand 128 x 96 kernels (family 1).  Every
+`full_bf16_out` case passes GELU' together with a residual, which plan_pipe declines (one C-shaped epilogue operand): all
+17 run on family 1, 128 x 96.  The other tiles of the family, and its epilogue with each operand plan_pipe accepts, are
+launched per compiled instance by test_gemm_f64_gpu.py (tables: tests/gemm_f64.py)."""
 import pytest
 import torch
 
@@ -35,19 +42,19 @@ def _operand(rows, K, batch, kcontig, seed):
 
 CASES = [
     # M, N, K, batch, a_kcontig, b_kcontig
-    (4096, 672, 672, (1, 1), True, True),       # NT 7, K tail of 32
-    (4096, 528, 528, (1, 1), True, True),       # NT 6 (576 padded), K tail of 16
-    (4096, 384, 384, (1, 1), True, True),       # NT 6 exact, K multiple of 64
-    (4096, 480, 240, (1, 1), True, True),       # NT 5
-    (4096, 768, 96, (1, 1), True, True),        # NT 8, two k-tiles
-    (2056, 240, 480, (1, 1), True, True),       # ragged M (rows clamped), N 240 in a 256 tile
-    (1000, 136, 72, (2, 3), True, True),        # batches, ragged everything
+    (4096, 672, 672, (1, 1), True, True),       # 128 x 128 tiles (672 = 5.25 of them), K tail of 32
+    (4096, 528, 528, (1, 1), True, True),       # 128 x 128 tiles (640 padded), K tail of 16
+    (4096, 384, 384, (1, 1), True, True),       # 128 x 128 tiles exact, K multiple of 64
+    (4096, 480, 240, (1, 1), True, True),       # 128 x 128 tiles (512 padded)
+    (4096, 768, 96, (1, 1), True, True),        # K = 96 < 160: declined, family 1 (128 x 96)
+    (2056, 240, 480, (1, 1), True, True),       # ragged M (rows clamped), N 240 in two 128 tiles
+    (1000, 136, 72, (2, 3), True, True),        # batches, ragged everything; K = 72 < 160: declined, family 1 (128 x 96)
     (4096, 672, 1344, (1, 1), True, False),     # data gradient: weight read through the transposing LDS reads
     (3000, 528, 1056, (1, 1), True, False),
     (2048, 240, 264, (1, 2), True, False),
     (1024, 352, 176, (3, 1), True, False),
     (672, 672, 8192, (1, 1), False, False),     # weight gradient: k-split, both operands row-contiguous
-    (1344, 672, 4096, (1, 1), False, False),
+    (1344, 672, 4096, (1, 1), False, False),    # the one 128 x 160 tile (NT 5) of this table
     (528, 1056, 4104, (1, 1), False, False),    # K tail of 8
     (240, 480, 20480, (1, 1), False, False),    # many slices: workspace reduction
     (384, 384, 2048, (2, 1), False, False),     # row/row batches without split

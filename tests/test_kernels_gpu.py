@@ -64,6 +64,9 @@ def _operand(rows, K, batch, kcontig, seed):
     return t, strides
 
 
+# These shapes name layouts and epilogues, not kernels: which instance a shape runs is the cost model's choice (today the
+# 64-row tiles for 7 of the 9, the one-element 128 x 96 kernel for the rest).  The case table per compiled kernel instance
+# is launched by test_gemm_f64_gpu.py (tables in tests/gemm_f64.py, proven on the host by test_gemm_f64_cpu.py).
 @pytest.mark.parametrize("M,N,K,batch,akc,bkc", GEMM_CASES)
 @pytest.mark.parametrize("epi", ["plain", "full", "gelu_bwd", "accumulate"])
 def test_gemm_layouts_and_epilogues(hip, emu, M, N, K, batch, akc, bkc, epi):

@@ -33,6 +33,9 @@ def _operand(rows, K, batch, kcontig, seed):
     return rnd(b0, b1, K, rows, seed=seed), (1, rows, b1 * rows * K, rows * K)
 
 
+# These shapes all plan the 128 x 96 tile of the bf16-operand kernels (family 1); coverage per compiled kernel instance
+# (BN 128, the storage pairs, the 256 x 128 and pipelined families) is launched by test_gemm_f64_gpu.py (tables in
+# tests/gemm_f64.py, proven on the host by test_gemm_f64_cpu.py).
 CASES = [
     # M, N, K, batch, a_kcontig, b_kcontig  (all multiples of 4: the 16-byte staging path)
     (256, 384, 128, (1, 1), True, True),      # forward linear

@@ -23,7 +23,7 @@ import torch
 import torch.nn.functional as F
 
 import calm_vit_dte_amd as calm
-from attn16_f64 import FILL, GELU_FWD_ERR, assert_bf16_rounding_of, bf16_ord  # shared with the attention checker
+from attn16_f64 import FILL, GELU_BWD_ERR, GELU_FWD_ERR, assert_bf16_rounding_of, bf16_ord  # shared with the attention checker
 from helpers import rel_err_elem
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +32,6 @@ DEV = "cuda"
 U = 2.0 ** -24                     # unit roundoff of fp32
 EPS = 1e-6                         # the model's LayerNorm eps (oracle LN_EPS)
 GUARD = 40                         # guard elements on either side of every output
-GELU_BWD_ERR = 2.85e-7
 
 
 @pytest.fixture(scope="module")
