@@ -9,6 +9,7 @@ import torch
 
 from . import Vi_Tools_CNN_less_V2 as vt
 from . import ops
+from .backend import lean_forward
 from .spectral_norm import SNLinear, sn_scope
 
 
@@ -59,7 +60,8 @@ class ViT(torch.nn.Module):
                 x = self.pool(x)
                 h0, h2 = self.head[0], self.head[2]
                 x = ops.MlpFn.apply(x, h0.weight_orig, None, h2.weight_orig, None, None, None,
-                                    h0.weight_u, h0.weight_v, h0.sigma(), h2.weight_u, h2.weight_v, h2.sigma())
+                                    h0.weight_u, h0.weight_v, h0.sigma(), h2.weight_u, h2.weight_v, h2.sigma(), 0.0, None,
+                                    lean_forward())
             else:                                                         # 78-83
                 x = self.proj.residual_forward(x)
             return x, kl_loss

@@ -11,7 +11,7 @@ from typing import Callable
 import torch
 
 from . import ops
-from .backend import ACT_GELU, ACT_NONE  # noqa: F401
+from .backend import ACT_GELU, ACT_NONE, lean_forward  # noqa: F401
 from .spectral_norm import SNConv2d, SNLinear, sn_scope
 
 
@@ -305,9 +305,14 @@ class VMLA_Block(torch.nn.Module):
         attention = ops.LatentMaskAttention16Fn if a16 else ops.LatentMaskAttentionFn
         if not a16 and ops.use_attention_lse(q.shape[1], k.shape[1], H, self.head_dim):
             attention = ops.LatentMaskAttentionLseFn                     # row-LSE mode: no saved probabilities
-        x = attention.apply(                                             # 288-299
-            q, k, v, m0.weight_orig, m0.bias, m2.weight_orig, m2.bias,
-            m0.weight_u, m0.weight_v, m0.sigma(), m2.weight_u, m2.weight_v, m2.sigma(), H)
+        if lean_forward():
+            # backend.set_lean_inference under no_grad: nothing is kept for a backward (out and the mask scratch only)
+            x = ops.latent_mask_attention_infer(q, k, v, m0.weight_orig, m0.bias, m2.weight_orig, m2.bias,
+                                                m0.sigma(), m2.sigma(), H)
+        else:
+            x = attention.apply(                                         # 288-299
+                q, k, v, m0.weight_orig, m0.bias, m2.weight_orig, m2.bias,
+                m0.weight_u, m0.weight_v, m0.sigma(), m2.weight_u, m2.weight_v, m2.sigma(), H)
         if residual.shape != (x.shape[0], x.shape[1], self.out_proj.out_features):   # 302-308
             if self.input_t_proj is not None:
                 residual = self._seq(self.input_t_proj, residual)
@@ -330,7 +335,7 @@ class VMLA_Block(torch.nn.Module):
         p_mlp = self.mlp[2].p if self.training else 0.0
         if p_mlp > 0:
             return ops.MlpFn.apply(*mlp_args, p_mlp, ops.draw_dropout_key(y.device))
-        return ops.MlpFn.apply(*mlp_args)
+        return ops.MlpFn.apply(*mlp_args, 0.0, None, lean_forward())
 
 
 class CnnResidual(torch.nn.Sequential):

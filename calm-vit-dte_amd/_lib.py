@@ -112,9 +112,11 @@ SIGNATURES = {
     "calm_attention_fwd_lse": (_i32, [_p] * 15 + [_i32] * 5 + [_p]),
     "calm_attention_bwd_lse_scratch_bytes": (_i64, [_i32] * 5),
     "calm_attention_bwd_lse": (_i32, [_p] * 7 + [_i64] + [_p] * 4 + [_i32] * 5 + [_p]),
+    "calm_attention_infer": (_i32, [_p] * 11 + [_i32] * 5 + [_p]),
     "calm_attention16_supported": (_i32, [_i32, _i32, _i32]),
     "calm_attention16_fwd": (_i32, [_p] * 16 + [_i32] * 4 + [_p]),
     "calm_attention16_bwd": (_i32, [_p] * 13 + [_i32] * 4 + [_p]),
+    "calm_attention16_infer": (_i32, [_p] * 11 + [_i32] * 4 + [_p]),
     "calm_latent_fwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i32, _p, _p]),
     "calm_latent_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p]),
     "calm_sn_plan": (_i32, [C.POINTER(SnLayer), _i32, _p, C.POINTER(SnPlanInfo)]),

@@ -72,6 +72,28 @@ def get_attention_storage():
     return _attention_storage
 
 
+# Lean inference forward: under torch.no_grad() the attention stores nothing for a backward that will not run
+# (calm_attention_infer / calm_attention16_infer) and the GELU GEMMs request no pre-activation.  Off by default.
+_lean_inference = os.environ.get("CALM_LEAN_INFERENCE", "0") not in ("", "0")    # read once, at import
+
+
+def set_lean_inference(on):
+    """True: forwards that run with grad disabled take the lean kernels (ops.latent_mask_attention_infer; MlpFn and
+    SNLinearFn without C_pre): same outputs bit for bit, none of the tensors only a backward reads.  With grad enabled
+    nothing changes, whatever the switch says.  False (default): every forward is the training forward."""
+    global _lean_inference
+    _lean_inference = bool(on)
+
+
+def get_lean_inference():
+    return _lean_inference
+
+
+def lean_forward():
+    """Whether a forward issued now is a lean one: the switch is on and autograd records nothing."""
+    return _lean_inference and not torch.is_grad_enabled()
+
+
 # The loss end of the step on the library's own kernels (csrc/loss.hip) instead of stock torch: off by default.
 _loss_kernels = os.environ.get("CALM_LOSS_KERNELS", "0") not in ("", "0")        # read once, at import
 
@@ -257,6 +279,7 @@ class HipBackend:
         self._scratch_bufs = {}
         self._scratch_retired = []      # buffers a larger one replaced: a captured graph may hold their addresses
         self._scratch_need = {}
+        self.plan_epoch = 0
         self.upcast_launches = 0        # calm_gemm launches re-run on fp32 copies (CALM_E_LAYOUT with bf16 tensors)
 
     def _partials(self, op, rows, cols, device):
@@ -286,6 +309,7 @@ class HipBackend:
         prev = self.lib.calm_gemm_set_option(int(option), int(value))
         if prev < 0:
             raise ValueError(f"calm_gemm_set_option({option}, {value}) -> {prev}")
+        self.plan_epoch += 1            # answers of gemm_describe cached before this call are stale
         return prev
 
     def selfcheck_bf16_gemm(self, rows=57344, on_mismatch="raise"):
@@ -638,6 +662,11 @@ class HipBackend:
                                                    _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dM), B, Sq, Skv, H, hd, _stream()),
                    "calm_attention_bwd_lse")
 
+    def attn_infer(self, q, k, v, w1, b1, s1, w2, b2, s2, out, Mk, B, Sq, Skv, H, hd):
+        _lib.check(self.lib.calm_attention_infer(_ptr(q), _ptr(k), _ptr(v), _ptr(w1), _ptr(b1), _ptr(s1), _ptr(w2),
+                                                 _ptr(b2), _ptr(s2), _ptr(out), _ptr(Mk), B, Sq, Skv, H, hd, _stream()),
+                   "calm_attention_infer")
+
     # ---- the same attention on the bf16 matrix pipe (bf16 pipeline) ----------------------
     def attn16_supported(self, S, H, hd):
         return bool(self.lib.calm_attention16_supported(S, H, hd))
@@ -647,6 +676,11 @@ class HipBackend:
         _lib.check(self.lib.calm_attention16_fwd(h(q), h(k), h(v), h(w1), _ptr(b1), _ptr(s1), h(w2), _ptr(b2), _ptr(s2),
                                                  h(out), h(R), h(hp), h(hg), h(Mk), h(MkT), _ptr(lse), B, S, H, hd,
                                                  _stream()), "calm_attention16_fwd")
+
+    def attn16_infer(self, q, k, v, w1, b1, s1, w2, b2, s2, out, Mk, B, S, H, hd):
+        h = lambda t: _ptr16(t)
+        _lib.check(self.lib.calm_attention16_infer(h(q), h(k), h(v), h(w1), _ptr(b1), _ptr(s1), h(w2), _ptr(b2), _ptr(s2),
+                                                   h(out), h(Mk), B, S, H, hd, _stream()), "calm_attention16_infer")
 
     def attn16_bwd(self, q, k, v, out, dout, Mk, MkT, lse, delta, dq, dk, dv, dM, B, S, H, hd):
         h = lambda t: _ptr16(t)

@@ -183,7 +183,13 @@ struct Fwd1Geo {
     static_assert(LD1 * 2 % 32 == 16 && LD2 * 2 % 32 == 16, "paired-tile order reads: stride = 16 (mod 32) bytes");
 };
 
-template <int NP, int HDP>
+// LEAN (calm_attention16_infer): the forward of a model that will run no backward — R, hp, hg and lse are absent (null), and
+// their stores, with the packs and addresses that only feed them, sit behind the wave-uniform test of those pointers.
+// out and Mk go through the same instructions as in the stored form and are bit-identical to it.  The template flag only
+// keeps the stored instantiation what it was (its tests fold away); the stores of the lean one are skipped at run time
+// and not compiled out, because without them — without the lse store's basic-block boundary in the head loop above all —
+// the register allocator did worse on five instances (<7,64>: 211 -> 256 VGPRs and 12 bytes of scratch).
+template <int NP, int HDP, bool LEAN = false>
 __global__ __launch_bounds__(64 * waves_for(NP), fwd_waves_per_simd(NP)) void attn16_fwd_kernel(const Attn16P p) {
     typedef Fwd1Geo<NP, HDP> G;
     constexpr int NJ = 2 * NP, SP = G::SP, NW = G::NW, NTH = 64 * NW;
@@ -249,7 +255,7 @@ __global__ __launch_bounds__(64 * waves_for(NP), fwd_waves_per_simd(NP)) void at
         for (int t = 0; t < NJ; ++t) {
             const int j = 16 * t + 4 * g;
             const bf16x4 r4 = pack4(acc[t]);
-            if (q_ok && j < S) *reinterpret_cast<bf16x4*>(Rrow + j) = r4;
+            if (q_ok && j < S && (!LEAN || p.R)) *reinterpret_cast<bf16x4*>(Rrow + j) = r4;
             if (t & 1) Rf[t >> 1] = cat8(pack4(acc[t - 1]), r4);
         }
     }
@@ -301,7 +307,7 @@ __global__ __launch_bounds__(64 * waves_for(NP), fwd_waves_per_simd(NP)) void at
                 pb[r] = h1[r] * inv1 + bb[r]; gb[r] = gelu_erf_f(pb[r]);
             }
             const bf16x4 ga4 = pack4(ga), gb4 = pack4(gb);
-            if (q_ok) {
+            if (q_ok && (!LEAN || p.hp)) {
                 const long ho = ((long)b * S + q_lane) * NH;
                 if (na < NH) {
                     *reinterpret_cast<bf16x4*>(p.hp + ho + na) = pack4(pa);
@@ -448,7 +454,7 @@ __global__ __launch_bounds__(64 * waves_for(NP), fwd_waves_per_simd(NP)) void at
         sum += __shfl_xor(sum, 16, 64);
         sum += __shfl_xor(sum, 32, 64);
         const float inv = 1.0f / sum;
-        if (q_ok && g == 0) p.lse[((long)b * p.H + h) * S + q_lane] = mx + __logf(sum);
+        if (q_ok && g == 0 && (!LEAN || p.lse)) p.lse[((long)b * p.H + h) * S + q_lane] = mx + __logf(sum);
         // O^T[d,i] = sum_j V_h[j,d] P^T[j,i]: V^T fragments by transposed reads of the row-major [key][d] image.
         // One output tile at a time (rolled loop): unrolled over the tiles the compiler hoists all NP x ndt transposed
         // reads ahead of the products (+100 VGPRs, scratch).
@@ -472,7 +478,7 @@ __global__ __launch_bounds__(64 * waves_for(NP), fwd_waves_per_simd(NP)) void at
     }
 #ifdef ATT16_STAMP
     __syncthreads();
-    if (tid == 0 && qg == 0) {       // diagnostic build only: phase cycles over the lse of the first queries of head 0
+    if (!LEAN && tid == 0 && qg == 0) {       // diagnostic build only: phase cycles over the lse of the first queries of head 0
         const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
         float* d = p.lse + (long)b * p.H * S;
         d[0] = (float)(ts1 - ts0); d[1] = (float)(ts2 - ts1); d[2] = (float)(ts3 - ts2);
@@ -564,7 +570,9 @@ int with_shape16(int S, int hd, F&& f) {
     return CALM_E_UNSUPP;
 }
 
-template <int NP, int HDP>
+// LEAN: the same dispatch rule between the pipelined and the register-staged kernel, never the experimental v3 pair, and
+// no mask_transpose_kernel pass (MkT is read by the key-side backward alone).
+template <int NP, int HDP, bool LEAN>
 int launch_fwd16_t(const Attn16P& p0, hipStream_t s) {
     typedef Fwd2Geo<NP, HDP> G2;
     typedef Fwd3Geo<NP, HDP> G3;
@@ -583,8 +591,8 @@ int launch_fwd16_t(const Attn16P& p0, hipStream_t s) {
     // the register-staged forward, which stages 8-byte vectors.  (Every model config has D % 8 == 0.)
     const bool rows16 = (p.H * p.hd) % 8 == 0;
     if constexpr (G2::OK) {
-        if (env.fwd2 && rows16) k1 = &attn16_fwd2_kernel<NP, HDP>;
-        if constexpr (G3::OK) {
+        if (env.fwd2 && rows16) k1 = &attn16_fwd2_kernel<NP, HDP, false, LEAN>;
+        if constexpr (G3::OK && !LEAN) {
             if (env.fwd2 && rows16 && env.fwd3) {
                 k1 = &attn16_fwd2_kernel<NP, HDP, true>;
                 k3 = p.S == 32 * NP ? &attn16_fwd3_core_kernel<NP, HDP, true> : &attn16_fwd3_core_kernel<NP, HDP, false>;
@@ -593,7 +601,7 @@ int launch_fwd16_t(const Attn16P& p0, hipStream_t s) {
         }
     }
     if (!k1) {
-        k1 = &attn16_fwd_kernel<NP, HDP>;
+        k1 = &attn16_fwd_kernel<NP, HDP, LEAN>;
         lds1 = Fwd1Geo<NP, HDP>::LDS;
     }
     int e = launch(k1, dim3(p.groups * p.B), 64 * nw, lds1, s, p);
@@ -605,6 +613,7 @@ int launch_fwd16_t(const Attn16P& p0, hipStream_t s) {
         e = launch(k3, dim3(p.B < slots3 ? p.B : slots3), 64 * G3::NW, G3::LDS, s, p);
         if (e) return e;
     }
+    if constexpr (LEAN) return 0;
     const int t32 = (p.S + 31) / 32;
     hipLaunchKernelGGL(mask_transpose_kernel, dim3(t32, t32, p.B), dim3(256), 0, s, (const __bf16*)p.Mk, p.MkT, p.S);
     CALM_LAUNCH_CHECK();
@@ -968,7 +977,22 @@ int calm_attention16_fwd(const void* q, const void* k, const void* v, const void
               (__bf16*)out, (__bf16*)R, (__bf16*)hp, (__bf16*)hg, (__bf16*)Mk, (__bf16*)MkT, lse, B, S, H, hd,
               1.0f / sqrtf((float)hd), 0, 0};
     hipStream_t s = as_stream(stream);
-    return with_shape16(S, hd, [&](auto np, auto hdp) -> int { return launch_fwd16_t<decltype(np)::value, decltype(hdp)::value>(p, s); });
+    return with_shape16(S, hd, [&](auto np, auto hdp) -> int { return launch_fwd16_t<decltype(np)::value, decltype(hdp)::value, false>(p, s); });
+}
+
+// Lean inference forward: calm_attention16_fwd with R, hp, hg, MkT and lse absent and no transpose pass.  Mk stays the
+// caller's scratch (the long-row kernels re-read it per head).  out and Mk are bit-identical to calm_attention16_fwd's.
+int calm_attention16_infer(const void* q, const void* k, const void* v, const void* w1, const float* b1, const float* s1,
+                           const void* w2, const float* b2, const float* s2, void* out, void* Mk, int32_t B, int32_t S,
+                           int32_t H, int32_t hd, void* stream) {
+    if (!q || !k || !v || !w1 || !b1 || !s1 || !w2 || !b2 || !s2 || !out || !Mk || B <= 0) return CALM_E_INVAL;
+    if (!calm_attention16_supported(S, H, hd)) return CALM_E_UNSUPP;
+    if (B > 65535) return CALM_E_UNSUPP;                    // the batch limit of calm_attention16_fwd
+    Attn16P p{(const __bf16*)q, (const __bf16*)k, (const __bf16*)v, (const __bf16*)w1, b1, s1, (const __bf16*)w2, b2, s2,
+              (__bf16*)out, nullptr, nullptr, nullptr, (__bf16*)Mk, nullptr, nullptr, B, S, H, hd,
+              1.0f / sqrtf((float)hd), 0, 0};
+    hipStream_t s = as_stream(stream);
+    return with_shape16(S, hd, [&](auto np, auto hdp) -> int { return launch_fwd16_t<decltype(np)::value, decltype(hdp)::value, true>(p, s); });
 }
 
 int calm_attention16_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* Mk,

@@ -141,8 +141,11 @@ struct Fwd2Geo {
 
 // MASK_ONLY (round 4): phases 1 and 2 alone — R, the hidden states and the mask M are written out and the kernel ends;
 // the per-head core then runs as attn16_fwd3_core_kernel (attention_bf16_fwd3.h), one workgroup per (image, head).
-template <int NP, int HDP, bool MASK_ONLY = false>
+// LEAN (calm_attention16_infer): R, hp, hg and lse are absent.  Their buffer stores, descriptors and packs are compiled
+// out TOGETHER WITH their entries in the vm_seq ledger, which must count exactly the vector-memory instructions issued.
+template <int NP, int HDP, bool MASK_ONLY = false, bool LEAN = false>
 __global__ __launch_bounds__(64 * waves_for(NP), 2) void attn16_fwd2_kernel(const Attn16P p) {
+    static_assert(!(MASK_ONLY && LEAN), "the v3 pair has no lean form");
     typedef Fwd2Geo<NP, HDP> G;
     constexpr int NJ = 2 * NP, SP = G::SP, NW = G::NW;
     extern __shared__ __attribute__((aligned(1024))) char smem2[];
@@ -327,23 +330,23 @@ __global__ __launch_bounds__(64 * waves_for(NP), 2) void attn16_fwd2_kernel(cons
             mark[s] = vm_seq;
         }
         {   // phase 1's result: R (saved for the backward) and the packed B fragments of the mask MLP
-            const __amdgpu_buffer_rsrc_t rs_r = make_rsrc(p.R + (long)b * S * S, (long)S * S * 2);
+            const __amdgpu_buffer_rsrc_t rs_r = make_rsrc(p.R + (long)b * S * S, (long)S * S * 2);   // (unused when LEAN)
 #pragma unroll
             for (int t = 0; t < NJ; ++t) {
                 const int j = 16 * t + 4 * g;
                 // (pad keys: zero — the W1 image holds re-read valid columns there, not zeros)
                 const bf16x4 r4 = j < S ? pack4(acc[t]) : (bf16x4){(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-                buf_store4(rs_r, (q_ok && j < S) ? (unsigned)((q_lane * S + j) * 2) : 0xFFFFFFFFu, r4);
+                if constexpr (!LEAN) buf_store4(rs_r, (q_ok && j < S) ? (unsigned)((q_lane * S + j) * 2) : 0xFFFFFFFFu, r4);
                 if (t & 1) {
                     const bf16x4 r3 = j - 16 < S ? pack4(acc[t - 1]) : (bf16x4){(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
                     Rf[t >> 1] = cat8(r3, r4);
                 }
             }
-            vm_seq += NJ;
+            if constexpr (!LEAN) vm_seq += NJ;
         }
 #pragma unroll
         for (int t = 0; t < NJ; ++t) acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
-        const __amdgpu_buffer_rsrc_t rs_hp = make_rsrc(p.hp + (long)b * S * NH, (long)S * NH * 2);
+        const __amdgpu_buffer_rsrc_t rs_hp = make_rsrc(p.hp + (long)b * S * NH, (long)S * NH * 2);   // (both unused when LEAN)
         const __amdgpu_buffer_rsrc_t rs_hg = make_rsrc(p.hg + (long)b * S * NH, (long)S * NH * 2);
 #pragma unroll 1
         for (int c = 0; c < nch; ++c) {
@@ -409,13 +412,15 @@ __global__ __launch_bounds__(64 * waves_for(NP), 2) void attn16_fwd2_kernel(cons
             const bf16x4 ga4 = pack4(ga), gb4 = pack4(gb);
             __builtin_amdgcn_sched_barrier(0);
             slot2(2);
-            const unsigned oa = (q_ok && na < NH) ? (unsigned)((q_lane * NH + na) * 2) : 0xFFFFFFFFu;
-            const unsigned ob = (q_ok && nb < NH) ? (unsigned)((q_lane * NH + nb) * 2) : 0xFFFFFFFFu;
-            buf_store4(rs_hp, oa, pack4(pa));
-            buf_store4(rs_hg, oa, ga4);
-            buf_store4(rs_hp, ob, pack4(pb));
-            buf_store4(rs_hg, ob, gb4);
-            vm_seq += 4;
+            if constexpr (!LEAN) {
+                const unsigned oa = (q_ok && na < NH) ? (unsigned)((q_lane * NH + na) * 2) : 0xFFFFFFFFu;
+                const unsigned ob = (q_ok && nb < NH) ? (unsigned)((q_lane * NH + nb) * 2) : 0xFFFFFFFFu;
+                buf_store4(rs_hp, oa, pack4(pa));
+                buf_store4(rs_hg, oa, ga4);
+                buf_store4(rs_hp, ob, pack4(pb));
+                buf_store4(rs_hg, ob, gb4);
+                vm_seq += 4;
+            }
             const bf16x8 hf = cat8(ga4, gb4);        // hidden columns >= NH meet zero columns of the W2 image
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -515,7 +520,7 @@ __global__ __launch_bounds__(64 * waves_for(NP), 2) void attn16_fwd2_kernel(cons
     }
     const float sc2 = p.scale * 1.4426950408889634f;
     const __amdgpu_buffer_rsrc_t rs_o = make_rsrc(p.out + (long)b * S * D, (long)S * D * 2);
-    const __amdgpu_buffer_rsrc_t rs_l = make_rsrc(p.lse + (long)b * p.H * S, (long)p.H * S * 4);
+    const __amdgpu_buffer_rsrc_t rs_l = make_rsrc(p.lse + (long)b * p.H * S, (long)p.H * S * 4);       // (unused when LEAN)
 #pragma unroll 1
     for (int h = 0; h < p.H; ++h) {
         F2_T(t_a);
@@ -590,8 +595,9 @@ __global__ __launch_bounds__(64 * waves_for(NP), 2) void attn16_fwd2_kernel(cons
         sum += __shfl_xor(sum, 16, 64);
         sum += __shfl_xor(sum, 32, 64);
         const float inv = 1.0f / sum;
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (mx + __builtin_amdgcn_logf(sum)) * 0.6931471805599453f),
-                                              rs_l, (q_ok && g == 0) ? (unsigned)((h * S + q_lane) * 4) : 0xFFFFFFFFu, 0, 0);
+        if constexpr (!LEAN)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (mx + __builtin_amdgcn_logf(sum)) * 0.6931471805599453f),
+                                                  rs_l, (q_ok && g == 0) ? (unsigned)((h * S + q_lane) * 4) : 0xFFFFFFFFu, 0, 0);
         bf16x8 Pf[NP];
 #pragma unroll
         for (int pr = 0; pr < NP; ++pr) Pf[pr] = cat8(pack4(acc[2 * pr] * inv), pack4(acc[2 * pr + 1] * inv));
@@ -618,14 +624,14 @@ __global__ __launch_bounds__(64 * waves_for(NP), 2) void attn16_fwd2_kernel(cons
                 for (int pr = 0; pr < NP; ++pr) vc[pr] = vn[pr];
             }
         }
-        vm_seq += ndt + 1;
+        vm_seq += ndt + (LEAN ? 0 : 1);      // the output tiles, and the lse store above
         asm volatile("" ::: "memory");
         F2_T(t_d);
         F2_ADD(tc[2], t_c, t_d);
     }
 #ifdef ATT16_STAMP
     __builtin_amdgcn_s_barrier();
-    if (tid == 0 && qg == 0) {
+    if (!LEAN && tid == 0 && qg == 0) {
         const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         float* d = p.lse + (long)b * p.H * S;

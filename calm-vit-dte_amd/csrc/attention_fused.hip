@@ -150,7 +150,10 @@ struct AttGeo {
     static constexpr size_t bwd_kv_bytes(int hd) { return sizeof(float) * (size_t)at(hd).stripe; }
 };
 
-template <int NJ, int NW>
+// LEAN (calm_attention_infer): the forward of a model that will run no backward.  R, hp, hg, P and lse are absent — their
+// stores, and the address arithmetic that only feeds them, are compiled out; every value that reaches out or Mk goes
+// through the same instructions in the same order, so both are bit-identical to the stored form's.
+template <int NJ, int NW, bool LEAN>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
     constexpr int NTH = 64 * NW;
     constexpr int NV_K = (NJ + NW - 1) / NW;   // float4 per thread for a [16*NJ x 16] chunk
@@ -212,7 +215,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
             __syncthreads();
         }
     }
-    if (active) {   // save R[b,i,j] (4 consecutive keys per register group)
+    if (!LEAN && active) {   // save R[b,i,j] (4 consecutive keys per register group)
         float* Rrow = p.R + ((long)b * p.Sq + iq) * p.Skv;
 #pragma unroll
         for (int t = 0; t < NJ; ++t) *reinterpret_cast<f32x4v*>(Rrow + 16 * t + 4 * g) = accR[t];
@@ -256,9 +259,11 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
                 f32x4v pre, act;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { pre[r] = hid[r] * inv1 + bb[r]; act[r] = gelu_erf_f(pre[r]); }
-                const long ho = ((long)b * p.Sq + iq) * (2 * SKV) + n0 + 4 * g;
-                *reinterpret_cast<f32x4v*>(p.hp + ho) = pre;
-                *reinterpret_cast<f32x4v*>(p.hg + ho) = act;
+                if constexpr (!LEAN) {
+                    const long ho = ((long)b * p.Sq + iq) * (2 * SKV) + n0 + 4 * g;
+                    *reinterpret_cast<f32x4v*>(p.hp + ho) = pre;
+                    *reinterpret_cast<f32x4v*>(p.hg + ho) = act;
+                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
 #pragma unroll
@@ -399,10 +404,10 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
         sum += __shfl_xor(sum, 32, 64);
         const float inv = 1.0f / sum;
         // row-LSE mode: what the backward needs to rebuild this row's probabilities (one lane group per query)
-        if (active && p.lse && g == 0) p.lse[((long)b * p.H + h) * p.Sq + iq] = mx + logf(sum);
+        if (!LEAN && active && p.lse && g == 0) p.lse[((long)b * p.H + h) * p.Sq + iq] = mx + logf(sum);
 #pragma unroll
         for (int t = 0; t < NJ; ++t) accS[t] = accS[t] * inv;
-        if (active && p.P) {
+        if (!LEAN && active && p.P) {
             float* Prow = p.P + (((long)b * p.H + h) * p.Sq + iq) * p.Skv;
 #pragma unroll
             for (int t = 0; t < NJ; ++t) *reinterpret_cast<f32x4v*>(Prow + 16 * t + 4 * g) = accS[t];
@@ -799,7 +804,7 @@ int launch_bwd(const AttnBwdP& p, hipStream_t s) {
     return launch(&attn_bwd_kv_kernel<NJ, NW>, grid, 64 * NW, G::bwd_kv_bytes(p.hd), s, p);
 }
 
-template <class G>
+template <class G, bool LEAN>
 int launch_fwd(const AttnFwdP& p, hipStream_t s) {
     static_assert(G::fwd_bytes(4) <= LDS_MAX, "fits at the smallest head dim; larger ones are checked per launch");
     constexpr int NJ = G::NJ, NW = G::NW;
@@ -807,7 +812,7 @@ int launch_fwd(const AttnFwdP& p, hipStream_t s) {
     const size_t lds = G::fwd_bytes(p.hd);
     if (lds > LDS_MAX) return CALM_E_UNSUPP;
     dim3 grid((tiles + NW - 1) / NW, p.B);
-    return launch(&attn_fwd_kernel<NJ, NW>, grid, 64 * NW, lds, s, p);
+    return launch(&attn_fwd_kernel<NJ, NW, LEAN>, grid, 64 * NW, lds, s, p);
 }
 
 #ifndef ATT_NW11
@@ -860,7 +865,7 @@ int attention_fwd(const float* q, const float* k, const float* v, const float* w
     if (B > 65535) return CALM_E_UNSUPP;
     AttnFwdP p{q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, P, B, Sq, Skv, H, hd, 1.0f / sqrtf((float)hd), lse};
     hipStream_t s = as_stream(stream);
-    return with_geo(Skv / 16, [&](auto g) -> int { return launch_fwd<decltype(g)>(p, s); });
+    return with_geo(Skv / 16, [&](auto g) -> int { return launch_fwd<decltype(g), false>(p, s); });
 }
 }  // namespace
 
@@ -878,6 +883,20 @@ int calm_attention_fwd_lse(const float* q, const float* k, const float* v, const
                            int32_t hd, void* stream) {
     if (!lse) return CALM_E_INVAL;
     return attention_fwd(q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, nullptr, lse, B, Sq, Skv, H, hd, stream);
+}
+
+// Lean inference forward: calm_attention_fwd with R, hp, hg, P and lse absent (attn_fwd_kernel<.., LEAN = true>).  Mk stays
+// the caller's scratch — the kernel re-reads it per head.  out and Mk are bit-identical to calm_attention_fwd's.
+int calm_attention_infer(const float* q, const float* k, const float* v, const float* w1, const float* b1,
+                         const float* s1, const float* w2, const float* b2, const float* s2, float* out, float* Mk,
+                         int32_t B, int32_t Sq, int32_t Skv, int32_t H, int32_t hd, void* stream) {
+    if (!q || !k || !v || !w1 || !b1 || !s1 || !w2 || !b2 || !s2 || !out || !Mk || B <= 0) return CALM_E_INVAL;
+    if (!calm_attention_fwd_supported(Sq, Skv, H, hd)) return CALM_E_UNSUPP;
+    if (B > 65535) return CALM_E_UNSUPP;
+    AttnFwdP p{q, k, v, w1, b1, s1, w2, b2, s2, out, nullptr, nullptr, nullptr, Mk, nullptr, B, Sq, Skv, H, hd,
+               1.0f / sqrtf((float)hd), nullptr};
+    hipStream_t s = as_stream(stream);
+    return with_geo(Skv / 16, [&](auto g) -> int { return launch_fwd<decltype(g), true>(p, s); });
 }
 
 // Measured on MI355X (scripts/ab_attn_bwd.py, same process): the two fused launches beat the GEMM composition

@@ -14,8 +14,8 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from .backend import (ACT_GELU, ACT_GELU_BWD, ACT_NONE, act_dtype, bf16_pipeline, fp8_linears, get_attention_storage,
-                      get_backend)
+from .backend import (ACT_GELU, ACT_GELU_BWD, ACT_NONE, act_dtype, bf16_pipeline, effective_precision, fp8_linears,
+                      get_attention_storage, get_backend)
 from .spectral_norm import W16_ATTR, W16_GEN_ATTR
 
 # The reference calls the model under autocast(bfloat16) (distributed_trainer_cls.py:84): custom_fwd records the
@@ -131,6 +131,31 @@ def _lin_fwd(be, x2, w, sigma, out, bias=None, act=ACT_NONE, col_scale=None, res
     N = w.shape[0]
     be.gemm(x2, w, out, M, N, K, (K, 1, 0, 0), (K, 1, 0, 0), (N, 0, 0), inv_scale=sigma, bias=bias, act=act,
             col_scale=col_scale, residual=residual, r=(N, 0, 0), C_pre=pre, split_k=1)
+
+
+_pre_droppable = {}
+
+
+def _gelu_pre(be, x2, w, sigma, out, bias, lean):
+    """The pre-activation tensor (C_pre) for the GELU launch `_lin_fwd(be, x2, w, sigma, out, bias=bias, act=ACT_GELU)`.
+    Only the GELU backward reads it, so a lean forward passes none — where calm_gemm_describe plans the same kernel
+    instance with and without it, which keeps `out` bit-identical; where it does not, or on a backend that cannot tell,
+    the tensor is kept as scratch rather than change the plan.
+    `lean` is backend.lean_forward() AS THE CALLER OF Function.apply SAW IT: inside Function.forward grad mode is always
+    off, so the forward of a Function cannot ask for itself whether autograd records it."""
+    if not lean:
+        return torch.empty_like(out)
+    describe = getattr(be, "gemm_describe", None)
+    if describe is None:
+        return torch.empty_like(out)
+    (M, K), N = x2.shape, w.shape[0]
+    key = (M, N, K, x2.dtype, w.dtype, out.dtype, bias is None, effective_precision(), getattr(be, "plan_epoch", 0))
+    drop = _pre_droppable.get(key)
+    if drop is None:
+        args = (x2, w, out, M, N, K, (K, 1, 0, 0), (K, 1, 0, 0), (N, 0, 0))
+        kw = dict(inv_scale=sigma, bias=bias, act=ACT_GELU, r=(N, 0, 0), split_k=1)
+        drop = _pre_droppable[key] = describe(*args, C_pre=out, **kw) == describe(*args, **kw)   # (out: a stand-in address)
+    return None if drop else torch.empty_like(out)
 
 
 def _lin_dgrad(be, dy2, w, sigma, dx, act=ACT_NONE, aux=None, residual=None, accumulate=False):
@@ -300,7 +325,8 @@ class SNLinearFn(Function):
 
     @staticmethod
     @_amp_fwd
-    def forward(ctx, x, w, bias, ls, residual, u, v, sigma, act, out16=False):
+    def forward(ctx, x, w, bias, ls, residual, u, v, sigma, act, out16=False, lean=False):
+        """lean: the caller's backend.lean_forward() — no pre-activation is kept for the GELU backward."""
         be = get_backend()
         x = _c(x)
         K = x.shape[-1]
@@ -311,9 +337,11 @@ class SNLinearFn(Function):
         if out16 and (act != ACT_NONE or ls is not None or residual is not None):
             raise ValueError("a bf16 projection output takes no activation / LayerScale / residual epilogue")
         out = torch.empty(x.shape[:-1] + (N,), dtype=act_dtype(N) if out16 else torch.float32, device=x.device)
-        pre = torch.empty_like(out) if act == ACT_GELU else None
         res2 = _c(residual).reshape(-1, N) if residual is not None else None
         ctx.fp8 = _fp8_ok(K, N) and x2.shape[0] >= 1024          # the large token-axis linears only
+        pre = None
+        if act == ACT_GELU:
+            pre = torch.empty_like(out) if ctx.fp8 else _gelu_pre(be, x2, wop, sigma, out.view(-1, N), bias, lean)
         if ctx.fp8:
             _lin_fwd8(be, x2, w, sigma, out.view(-1, N), bias=bias, act=act, col_scale=ls, residual=res2,
                       C_pre=pre.view(-1, N) if pre is not None else None)
@@ -363,7 +391,7 @@ class SNLinearFn(Function):
             dx = dx.view(ctx.xshape)
         db = _colsum(be, dz) if ctx.has_bias else None
         dres = dy if ctx.has_res else None
-        return dx, dW, db, d_ls, dres, None, None, None, None, None
+        return dx, dW, db, d_ls, dres, None, None, None, None, None, None
 
 
 class SNLinearGroupFn(Function):
@@ -435,7 +463,8 @@ class MlpFn(Function):
 
     @staticmethod
     @_amp_fwd
-    def forward(ctx, x, w1, b1, w2, b2, ls, residual, u1, v1, s1, u2, v2, s2, p=0.0, key=None):
+    def forward(ctx, x, w1, b1, w2, b2, ls, residual, u1, v1, s1, u2, v2, s2, p=0.0, key=None, lean=False):
+        """lean: the caller's backend.lean_forward() — no pre-activation is kept for the GELU backward."""
         be = get_backend()
         x = _c(x)
         K = x.shape[-1]
@@ -445,11 +474,11 @@ class MlpFn(Function):
         M = x2.shape[0]
         wop1, wop2 = _wop(w1), _wop(w2)
         # hidden state and pre-activation feed GEMMs / the GELU' epilogue only: bf16 tensors in the bf16 pipeline
-        hp = torch.empty(M, Hd, dtype=act_dtype(Hd), device=x.device)
-        hg = torch.empty_like(hp)
+        hg = torch.empty(M, Hd, dtype=act_dtype(Hd), device=x.device)
         out = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
         res2 = _c(residual).reshape(-1, N) if residual is not None else None
         ctx.fp8 = _fp8_ok(K, Hd, N)
+        hp = torch.empty_like(hg) if ctx.fp8 else _gelu_pre(be, x2, wop1, s1, hg, b1, lean)
         ctx.p = float(p)
         if ctx.p > 0 and key is None:
             raise ValueError("MlpFn: p > 0 needs a key (ops.draw_dropout_key)")
@@ -512,7 +541,7 @@ class MlpFn(Function):
                 _lin_dgrad(be, dhp, wop1, s1, dx)
             dx = dx.view(ctx.xshape)
         dres = dout if ctx.has_res else None
-        return dx, dW1, db1, dW2, db2, d_ls, dres, None, None, None, None, None, None, None, None
+        return dx, dW1, db1, dW2, db2, d_ls, dres, None, None, None, None, None, None, None, None, None
 
 
 class SeqLinearFn(Function):
@@ -801,6 +830,49 @@ class LatentMaskAttention16Fn(Function):
         dW1, db1, dW2, db2 = _attn_mask_bwd(be, ctx.defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2,
                                             w1o=w1o, w2o=w2o)
         return dq, dk, dv, dW1, db1, dW2, db2, None, None, None, None, None, None, None
+
+
+def latent_mask_attention_infer(q, k, v, w1, b1, w2, b2, s1, s2, H):
+    """The attention of LatentMaskAttentionFn / LatentMaskAttention16Fn for a forward that no backward follows (no
+    autograd Function, call it under torch.no_grad()): calm_attention_infer / calm_attention16_infer, which allocate and
+    write the output and the mask scratch Mk only — no R, hp, hg, P, MkT, lse.  The result equals the training forward's
+    bit for bit.  bf16 q / k / v (the bf16 pipeline) take the bf16 kernels; fp32 shapes without a fused instantiation
+    keep the composed path, minus the pre-activation."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, w1, w2) if t is not None):
+        raise RuntimeError("latent_mask_attention_infer records nothing for a backward: call it under torch.no_grad()")
+    be = get_backend()
+    q, k, v = _c(q), _c(k), _c(v)
+    B, Sq, D = q.shape
+    Skv = k.shape[1]
+    hd = D // H
+    dev, dt = q.device, q.dtype
+    out = torch.empty(B, Sq, D, dtype=dt, device=dev)
+    Mk = torch.empty(B * Sq, Skv, dtype=dt, device=dev)
+    if dt == torch.bfloat16:
+        w1o, w2o = _wop(w1), _wop(w2)
+        if w1o.dtype != torch.bfloat16 or w2o.dtype != torch.bfloat16:
+            raise RuntimeError("bf16 attention needs the step's bf16 weight copies (spectral_norm._refresh_bf16_weights)")
+        if Sq != Skv or not be.attn16_supported(Sq, H, hd):
+            raise RuntimeError(f"bf16 attention: no kernel for Sq={Sq} Skv={Skv} H={H} hd={hd}")
+        be.attn16_infer(q, k, v, w1o, b1, s1, w2o, b2, s2, out, Mk, B, Sq, H, hd)
+    elif be.attn_fwd_supported(Sq, Skv, H, hd):
+        be.attn_infer(q, k, v, w1, b1, s1, w2, b2, s2, out, Mk, B, Sq, Skv, H, hd)
+    else:
+        # LatentMaskAttentionFn's composition; R, the hidden state and P are operands of the next product here
+        R = torch.empty(B, Sq, Skv, dtype=dt, device=dev)
+        be.gemm(q, k, R, Sq, Skv, D, (D, 1, Sq * D, 0), (D, 1, Skv * D, 0), (Skv, Sq * Skv, 0), batch=(B, 1))
+        R2 = R.view(B * Sq, Skv)
+        hg = torch.empty(B * Sq, w1.shape[0], dtype=dt, device=dev)
+        _lin_fwd(be, R2, w1, s1, hg, bias=b1, act=ACT_GELU, pre=_gelu_pre(be, R2, w1, s1, hg, b1, True))
+        _lin_fwd(be, hg, w2, s2, Mk, bias=b2)
+        del R, R2, hg
+        P = torch.empty(B, H, Sq, Skv, dtype=dt, device=dev)
+        be.gemm(q, k, P, Sq, Skv, hd, (D, 1, Sq * D, hd), (D, 1, Skv * D, hd), (Skv, H * Sq * Skv, Sq * Skv),
+                batch=(B, H), alpha=1.0 / math.sqrt(hd), residual=Mk, r=(Skv, Sq * Skv, 0))
+        be.softmax_fwd(P, B * H * Sq, Skv)
+        be.gemm(P, v, out, Sq, hd, Skv, (Skv, 1, H * Sq * Skv, Sq * Skv), (1, D, Skv * D, hd), (D, Sq * D, hd),
+                batch=(B, H))
+    return out
 
 
 def use_attention16(S, H, hd):

@@ -73,9 +73,10 @@ class SNLinear(SpectralWeight):
         self.in_features, self.out_features = in_features, out_features
 
     def forward(self, x, act=0, ls=None, residual=None, out16=False):
+        from .backend import lean_forward
         from .ops import SNLinearFn
         return SNLinearFn.apply(x, self.weight_orig, self.bias, ls, residual, self.weight_u, self.weight_v,
-                                self.sigma(), act, out16)
+                                self.sigma(), act, out16, lean_forward())
 
     def extra_repr(self):
         return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"

@@ -372,18 +372,107 @@ class DeviceCollate:
         return out, y
 
 
-def evaluate(model, batches):
+def _map_tensors(out, fn):
+    """fn over the tensors of a model output (a tensor, or a tuple / list of tensors and None)."""
+    if isinstance(out, torch.Tensor):
+        return fn(out)
+    if isinstance(out, (tuple, list)):
+        return type(out)(_map_tensors(o, fn) for o in out)
+    return out
+
+
+class Predictor:
+    """Inference front of a model: `predictor(x)` returns what `model(x)` returns, computed in eval mode under
+    torch.no_grad() with the lean forward (backend.set_lean_inference: the attention keeps nothing for a backward, the
+    GELU GEMMs write no pre-activation) whatever the global switch says; the model's training flag and the switch are
+    put back before the call returns.  The results equal the training forward's in eval mode bit for bit.
+
+    graph=True (needs example_x) follows GraphedTrainStep: the forward is warmed up on a side stream, captured once into a
+    hipGraph at example_x's shape and dtype and replayed, inputs copied into a static buffer — one graph launch instead
+    of the host enqueueing every kernel.  The spectral-norm sigma products of eval mode and the bf16 weight copies are part
+    of the captured region and read the parameters where they live, so an in-place update of the weights (an optimizer
+    step, load_state_dict) is seen by the next replay.  A batch of any other shape or dtype (a ragged last batch) runs
+    eagerly, lean.  Outputs of a replay are copies: they stay valid across later calls.  close() releases the graph."""
+
+    def __init__(self, model, example_x=None, autocast_dtype=None, graph=False, warmup=2):
+        self.model = model
+        self.autocast_dtype = autocast_dtype
+        self.graph = None
+        self.x = self.out = None
+        if graph:
+            if example_x is None or not example_x.is_cuda:
+                raise ValueError("Predictor(graph=True) needs a CUDA example_x to capture the forward at")
+            self.x = example_x.detach().clone()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):                 # warm-up on a side stream (allocator + lazy plans)
+                for _ in range(max(int(warmup), 1)):
+                    self._eager(self.x)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            graph_obj = torch.cuda.CUDAGraph()
+
+            def capture(x):
+                with torch.cuda.graph(graph_obj):
+                    return self._forward(x)
+            self.out = self._lean(capture, self.x)
+            self.graph = graph_obj
+
+    def _forward(self, x):
+        with torch.autocast(device_type="cuda", dtype=self.autocast_dtype or torch.bfloat16,
+                            enabled=self.autocast_dtype is not None and x.is_cuda):
+            return self.model(x)
+
+    def _lean(self, fn, x):
+        """fn(x) in eval mode, without grad, with the lean switch on; flag and switch restored."""
+        from . import backend
+        was_training, was_lean = self.model.training, backend.get_lean_inference()
+        self.model.eval()
+        backend.set_lean_inference(True)
+        try:
+            with torch.no_grad():
+                return fn(x)
+        finally:
+            backend.set_lean_inference(was_lean)
+            self.model.train(was_training)
+
+    def _eager(self, x):
+        return self._lean(self._forward, x)
+
+    def __call__(self, x):
+        if self.graph is None or x.shape != self.x.shape or x.dtype != self.x.dtype or x.device != self.x.device:
+            return self._eager(x)
+        self.x.copy_(x, non_blocking=True)
+        self.graph.replay()
+        return _map_tensors(self.out, torch.clone)
+
+    def close(self):
+        """Release the captured graph and its static tensors; later calls run eagerly."""
+        if self.graph is not None:
+            self.graph.reset()
+        self.graph = self.x = self.out = None
+
+
+def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None):
     """Top-1 accuracy over (x, labels) batches in eval mode (CALM_ViT_V2.py:228-239).  With the loss kernels switched on
     the hits are counted on the device (calm_top1_count into a StepMetrics) and read once after the last batch instead of
-    once per batch."""
+    once per batch.  lean / graph: the forward goes through a Predictor (lean kernels; graph=True captures it at the first
+    batch's shape and replays it, other shapes run eagerly) under autocast_dtype if one is given; without either flag the
+    model is called as before."""
     from . import backend
     was_training = model.training
     model.eval()
     correct = total = 0
     metrics = None
+    predictor = None
     with torch.no_grad():
         for x, labels in batches:
-            y_hat, _ = model(x)
+            if lean or graph:
+                if predictor is None:
+                    predictor = Predictor(model, example_x=x if graph else None, autocast_dtype=autocast_dtype, graph=graph)
+                y_hat, _ = predictor(x)
+            else:
+                y_hat, _ = model(x)
             logits = y_hat.reshape(x.shape[0], -1)
             if backend.get_loss_kernels() and labels.dim() == 1 and backend.loss_kernels_take(logits):
                 if metrics is None:
@@ -397,6 +486,8 @@ def evaluate(model, batches):
     if metrics is not None:
         _, hits, rows, _ = metrics.read()
         correct, total = correct + hits, total + rows
+    if predictor is not None:
+        predictor.close()
     model.train(was_training)
     return correct / max(total, 1)
 

@@ -287,6 +287,15 @@ int calm_attention_bwd_lse(const float* q, const float* k, const float* v, const
                            const float* lse, void* scratch, int64_t scratch_bytes, float* dq, float* dk, float* dv,
                            float* dM, int32_t B, int32_t Sq, int32_t Skv, int32_t H, int32_t hd, void* stream);
 
+/* Lean inference forward of the fp32 attention (addition to ABI v7, as the row-LSE entries were): calm_attention_fwd
+ * with R, hp, hg, P and lse absent — the forward of a model that will run no backward.  Mk [B,Sq,Skv] stays: it is the
+ * caller's scratch, written once and re-read by the kernel per head.  Same kernel, same supported shapes
+ * (calm_attention_fwd_supported), same launch geometry; the stores of the absent tensors are compiled out.  out and Mk
+ * are bit-identical to calm_attention_fwd's. */
+int calm_attention_infer(const float* q, const float* k, const float* v, const float* w1, const float* b1,
+                         const float* s1, const float* w2, const float* b2, const float* s2, float* out, float* Mk,
+                         int32_t B, int32_t Sq, int32_t Skv, int32_t H, int32_t hd, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * The same attention on the bf16 matrix pipe (ABI v4; the bf16 pipeline — what autocast(bfloat16) makes of
  * Vi_Tools:288-299): q, k, v, out and the saved R / hp / hg / Mk are bf16 tensors; w1 [2S,S] / w2 [S,2S] are the
@@ -312,6 +321,13 @@ int calm_attention16_fwd(const void* q, const void* k, const void* v, const void
 int calm_attention16_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* Mk,
                          const void* MkT, const float* lse, float* delta, void* dq, void* dk, void* dv, void* dM,
                          int32_t B, int32_t S, int32_t H, int32_t hd, void* stream);
+/* Lean inference forward of the bf16 attention (addition to ABI v7): calm_attention16_fwd without R, hp, hg, MkT and lse
+ * and without the transpose pass that writes MkT.  Mk [B,S,S] (bf16) stays as the caller's scratch.  Both kernel
+ * generations, chosen by the same rule as in calm_attention16_fwd; never the experimental CALM_ATTN16_V3 pair.  out and
+ * Mk are bit-identical to calm_attention16_fwd's. */
+int calm_attention16_infer(const void* q, const void* k, const void* v, const void* w1, const float* b1, const float* s1,
+                           const void* w2, const float* b2, const float* s2, void* out, void* Mk, int32_t B, int32_t S,
+                           int32_t H, int32_t hd, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Latent bottleneck sampling (Vi_Tools:232-242) + KL partial sum (Vi_Tools:24-25).
