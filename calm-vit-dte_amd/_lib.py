@@ -82,6 +82,17 @@ class SnPlanInfo(C.Structure):
                 ("n_work_a", _i32), ("reserved", _i32)]
 
 
+AUG_FLIP, AUG_SOLARIZE, AUG_GRAYSCALE, AUG_BLUR = 1, 2, 4, 8                       # calm_aug_sample.flags (CALM_AUG_*)
+AUG_OP_BRIGHTNESS, AUG_OP_CONTRAST, AUG_OP_SATURATION, AUG_OP_HUE, AUG_OP_NONE = 0, 1, 2, 3, 255
+
+
+class AugSample(C.Structure):
+    """struct calm_aug_sample (48 bytes, one per sample of calm_augment_collate)."""
+    _fields_ = [("y0", _i32), ("x0", _i32), ("flags", C.c_uint32), ("order", C.c_uint8 * 4),
+                ("brightness", _f32), ("contrast", _f32), ("saturation", _f32), ("hue", _f32),
+                ("solarize_thr", _f32), ("blur_sigma", _f32), ("reserved", _f32 * 2)]
+
+
 # name -> (restype, argtypes); every symbol include/calm_vit.h declares
 SIGNATURES = {
     "calm_abi_version": (_i32, []),
@@ -126,6 +137,7 @@ SIGNATURES = {
     "calm_optim_step": (_i32, [_p, _i32, _p, _i32, _p, C.POINTER(OptimHparams), _p, _p, _p, _p, _p]),
     "calm_collate_mix": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_collate_crop_mix": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
+    "calm_augment_collate": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_image_to_rows": (_i32, [_p, _p, _i32, _i32, _p]),
     "calm_rows_to_image": (_i32, [_p, _p, _i32, _i32, _p]),
     "calm_grid_transpose": (_i32, [_p, _p, _i32, _i32, _p]),

@@ -525,6 +525,32 @@ class HipBackend:
                                                   int(tokens), mode, float(lam), cbox, cm, cs, _stream()),
                    "calm_collate_crop_mix")
 
+    def augment_collate(self, img_u8, samples, gray_mean, out, mode, lam, box, mean, std, tokens=False):
+        """collate_crop_mix with ColorJitter / solarize / flip / grayscale / 3x3 Gaussian blur per sample in front of
+        Normalize (calm_augment_collate).  img_u8 [B,3,Hs,Ws] uint8; samples: the device array of B calm_aug_sample
+        records as a contiguous uint8 CUDA tensor [B,48] (trainer.DeviceAugment.pack: crop corners and flips are in it);
+        gray_mean [B] fp32 CUDA, written (the contrast means); out [B,3,H,W] or, tokens=True, [B,H,3W] fp32."""
+        if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or not img_u8.is_contiguous():
+            raise TypeError("augment_collate expects a contiguous uint8 CUDA image batch")
+        B, _, Hs, Ws = img_u8.shape
+        if tokens:
+            H, W = out.shape[1], out.shape[2] // 3
+        else:
+            H, W = out.shape[2], out.shape[3]
+        if out.shape[0] != B or out.numel() != B * 3 * H * W or not out.is_contiguous():
+            raise TypeError("augment_collate: out must be contiguous [B,3,H,W] or, tokens=True, [B,H,3W]")
+        if (samples.dtype != torch.uint8 or not samples.is_cuda or not samples.is_contiguous()
+                or tuple(samples.shape) != (B, C.sizeof(_lib.AugSample))):
+            raise TypeError("augment_collate: samples must be a contiguous uint8 CUDA tensor [B,48] (calm_aug_sample records)")
+        if (gray_mean.dtype != torch.float32 or not gray_mean.is_cuda or not gray_mean.is_contiguous()
+                or gray_mean.numel() != B):
+            raise TypeError("augment_collate: gray_mean must be a contiguous fp32 CUDA tensor [B]")
+        cbox = (C.c_int32 * 4)(*box) if box is not None else None
+        cm, cs = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+        _lib.check(self.lib.calm_augment_collate(img_u8.data_ptr(), Hs, Ws, samples.data_ptr(), gray_mean.data_ptr(),
+                                                 _ptr(out), B, H, W, int(tokens), mode, float(lam), cbox, cm, cs, _stream()),
+                   "calm_augment_collate")
+
     # ---- optimizer-side step ------------------------------------------------------------
     def optim_plan(self, records):
         """records: one dict per parameter — param, exp_avg, exp_avg_sq, sn (None or (u, v, sigma, rows, cols))."""

@@ -325,7 +325,8 @@ class DeviceCollate:
     ToDtype(scale=True) + Normalize + RandomHorizontalFlip + RandomChoice([CutMix(alpha=1.0), MixUp(alpha=0.8)])
     with 1000-way soft labels (distributed_trainer_cls.py:58-61,128-139, torchvision.transforms.v2 semantics), one kernel
     pass over the uint8 batch (calm_collate_mix).  The decode / resize / colour augmentations stay with the loader.
-    torchvision is not installed in the build image, so the semantics are restated from its documentation."""
+    torchvision is not installed in the build image, so the semantics are restated from its documentation.
+    (With an `augment=DeviceAugment(...)` argument the call also runs the colour augmentations on the device.)"""
 
     MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
@@ -346,22 +347,34 @@ class DeviceCollate:
         flips = torch.from_numpy((rng.random(B) < self.flip_p).astype("uint8"))
         return mode, lam, box, flips
 
-    def __call__(self, img_u8, labels, decisions=None, crop=None, tokens=False):
+    def __call__(self, img_u8, labels, decisions=None, crop=None, tokens=False, augment=None, aug_table=None):
         """crop=(H, W): RandomCrop of every sample to H x W inside the (resized) source, corners drawn uniformly as
         torchvision's RandomCrop.get_params does (cls:130); tokens=True: the batch comes out as the row tokens
         [B, H, 3W] of the first Block (Vi_Tools_CNN_less_V2.py:389-391) — feed it to `model.autoencoder` / a ViT whose
-        first Block skips the tokenisation — instead of the image [B,3,H,W]."""
+        first Block skips the tokenisation — instead of the image [B,3,H,W].
+        augment: a DeviceAugment — ColorJitter / solarize / grayscale / blur of cls:131-135 run in the same pass
+        (calm_augment_collate) with parameters from the augment object's own generator, so the draws made here (mode,
+        lam, box, flips, corners) are the ones made without it; aug_table: that per-sample table given instead of drawn
+        (DeviceAugment.draw's format).  None (the default) is the plain collate."""
         from .backend import get_backend
         B, _, Hs, Ws = img_u8.shape
         H, W = crop if crop is not None else (Hs, Ws)
         mode, lam, box, flips = decisions if decisions is not None else self.draw(B, H, W)
-        corners = None
+        corners = corners_host = None
         if crop is not None:
             import numpy as np
-            corners = torch.from_numpy(np.stack([self.rng.integers(0, Hs - H + 1, B), self.rng.integers(0, Ws - W + 1, B)],
-                                                axis=1).astype("int32")).to(img_u8.device)
+            corners_host = np.stack([self.rng.integers(0, Hs - H + 1, B), self.rng.integers(0, Ws - W + 1, B)],
+                                    axis=1).astype("int32")
+            corners = torch.from_numpy(corners_host).to(img_u8.device)
         out = torch.empty((B, H, 3 * W) if tokens else (B, 3, H, W), dtype=torch.float32, device=img_u8.device)
-        if crop is None and not tokens:
+        if augment is not None or aug_table is not None:
+            table = aug_table if aug_table is not None else augment.draw(B)
+            DeviceAugment.check_window(table, H, W)
+            samples = DeviceAugment.pack(table, corners_host, flips, device=img_u8.device)
+            self.last_gray_mean = torch.empty(B, dtype=torch.float32, device=img_u8.device)
+            get_backend().augment_collate(img_u8, samples, self.last_gray_mean, out, mode, lam, box, self.MEAN, self.STD,
+                                          tokens=tokens)
+        elif crop is None and not tokens:
             get_backend().collate_mix(img_u8, flips.to(img_u8.device), out, mode, lam, box, self.MEAN, self.STD)
         else:
             get_backend().collate_crop_mix(img_u8, corners, flips.to(img_u8.device), out, mode, lam, box, self.MEAN, self.STD,
@@ -370,6 +383,92 @@ class DeviceCollate:
         y = onehot * lam + onehot.roll(1, 0) * (1.0 - lam)
         self.last_corners = corners
         return out, y
+
+
+class DeviceAugment:
+    """The per-sample random parameters of the reference's colour augmentations (distributed_trainer_cls.py:131-135,
+    defaults from there) for the device pass calm_augment_collate:
+      ColorJitter(brightness, contrast, saturation, hue): a factor drawn uniformly from each range and a random order of
+        the four operations per sample, as torchvision's ColorJitter draws them (a range of None leaves the operation out);
+      RandomSolarize(solarize_threshold, p=solarize_p); RandomGrayscale(p=grayscale_p);
+      GaussianBlur(3, sigma=blur_sigma): sigma uniform in the range (None: no blur).
+    Deviation from the reference, stated: it applies these operations to 8-bit PIL images and rounds after each one; the
+    device pass keeps fp32 on [0, 1] throughout and quantises nowhere (tests/test_augment_cpu.py bounds the difference
+    per operation).  The 8-bit comparison `level >= solarize_threshold` becomes `v >= (solarize_threshold - 0.5) / 255`.
+    The object owns its generator: the draws of DeviceCollate do not shift when it is used."""
+
+    def __init__(self, seed=None, brightness=(0.5, 1), contrast=(0.5, 1), saturation=(0.5, 1), hue=(-0.125, 0.125),
+                 solarize_p=0.5, solarize_threshold=224, grayscale_p=0.1, blur_sigma=(0.1, 2.0)):
+        import numpy as np
+        self.ranges = (brightness, contrast, saturation, hue)              # indexed by the operation id
+        self.solarize_p, self.solarize_threshold, self.grayscale_p = solarize_p, solarize_threshold, grayscale_p
+        self.blur_sigma = blur_sigma
+        self.rng = np.random.default_rng(seed)
+
+    @staticmethod
+    def dtype():
+        """The numpy record of struct calm_aug_sample."""
+        import numpy as np
+        from . import _lib
+        return np.dtype(_lib.AugSample)
+
+    @classmethod
+    def identity(cls, B):
+        """A table of B samples with no operation and no flag."""
+        import numpy as np
+        from . import _lib
+        t = np.zeros(B, dtype=cls.dtype())
+        t["order"] = _lib.AUG_OP_NONE
+        t["brightness"] = t["contrast"] = t["saturation"] = 1.0
+        return t
+
+    def draw(self, B):
+        """The per-sample table of one batch (a numpy record array of calm_aug_sample; corners and the flip bit are
+        DeviceCollate's and are filled in by pack)."""
+        import numpy as np
+        from . import _lib
+        rng = self.rng
+        t = self.identity(B)
+        perm = rng.permuted(np.tile(np.arange(4, dtype=np.uint8), (B, 1)), axis=1)
+        names = ("brightness", "contrast", "saturation", "hue")
+        for op, (name, rg) in enumerate(zip(names, self.ranges)):
+            if rg is None:
+                perm[perm == op] = _lib.AUG_OP_NONE
+            else:
+                t[name] = rng.uniform(rg[0], rg[1], B).astype(np.float32)
+        # the operations left out move to the end of the order (they are skipped wherever they stand)
+        t["order"] = np.take_along_axis(perm, np.argsort(perm == _lib.AUG_OP_NONE, axis=1, kind="stable"), axis=1)
+        flags = np.zeros(B, dtype=np.uint32)
+        flags |= np.where(rng.random(B) < self.solarize_p, _lib.AUG_SOLARIZE, 0).astype(np.uint32)
+        flags |= np.where(rng.random(B) < self.grayscale_p, _lib.AUG_GRAYSCALE, 0).astype(np.uint32)
+        t["solarize_thr"] = np.float32((self.solarize_threshold - 0.5) / 255.0)
+        if self.blur_sigma is not None:
+            flags |= np.uint32(_lib.AUG_BLUR)
+            t["blur_sigma"] = rng.uniform(self.blur_sigma[0], self.blur_sigma[1], B).astype(np.float32)
+        t["flags"] = flags
+        return t
+
+    @staticmethod
+    def check_window(table, H, W):
+        from . import _lib
+        if (H < 2 or W < 2) and bool((table["flags"] & _lib.AUG_BLUR).any()):
+            raise ValueError(f"the 3x3 blur reflects at the window's edge: it needs a window of at least 2 x 2, got {H} x {W}")
+
+    @staticmethod
+    def pack(table, corners=None, flips=None, device="cuda"):
+        """The device array of calm_aug_sample records, [B,48] uint8, in one host-to-device copy: `table` with the crop
+        corners ([B,2] integers, None = (0, 0)) and the flip decisions ([B], None = keep the table's bits) filled in."""
+        import numpy as np
+        from . import _lib
+        t = np.array(table, dtype=DeviceAugment.dtype(), copy=True)
+        if corners is not None:
+            c = np.asarray(corners)
+            t["y0"], t["x0"] = c[:, 0], c[:, 1]
+        if flips is not None:
+            f = np.asarray(flips).astype(bool)
+            t["flags"] = (t["flags"] & ~np.uint32(_lib.AUG_FLIP)) | np.where(f, _lib.AUG_FLIP, 0).astype(np.uint32)
+        host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
+        return host.to(device)
 
 
 def _map_tensors(out, fn):
@@ -820,7 +919,7 @@ class SoftMixCollate:
 def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, epochs=15, batch_size=128,
           checkpoint_path=None, num_classes=1000, num_workers=0, collate_fn="mix", log_every=100, max_steps=None,
           destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
-          device_metrics=False):
+          device_metrics=False, device_augment=False):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -848,6 +947,10 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     first Block's row tokens [B,S,3S] directly — the model's first Block takes them without the image_to_rows pass
     (cls:58-62,128-139; Vi_Tools:389-391).
 
+    device_augment=True (needs device_collate=True): the colour augmentations of cls:131-135 — ColorJitter, RandomSolarize,
+    RandomGrayscale, GaussianBlur — run in that same pass (`DeviceAugment`, seeded 2006 + rank, with the reference's
+    ranges) instead of in DataLoader workers; the dataset then yields the resized uint8 images unaugmented.
+
     selfcheck ("raise" | "fallback" | None; GPU only, once per process): before the first step the box is asked whether
     the two bf16 GEMM families agree on it (HipBackend.selfcheck_bf16_gemm — round 3 saw one box of the pool on which the
     default pipelined family returned a deterministic wrong gradient); "raise" stops the job with the pattern of the
@@ -870,6 +973,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                          "(backend.set_loss_kernels(True) or CALM_LOSS_KERNELS=1)")
     if device_collate and not use_gpu:                     # (argument errors before any process group exists)
         raise ValueError("device_collate=True needs use_gpu=True (the collate is a HIP kernel)")
+    if device_augment and not device_collate:
+        raise ValueError("device_augment=True needs device_collate=True (the augmentation is part of the collate kernel)")
     if graph and not (use_gpu and (optimizer == "fused" or isinstance(optimizer, FusedClipAdamW))):
         raise ValueError('graph=True needs use_gpu=True and optimizer="fused" (FusedClipAdamW)')
     rank, local_rank, world = init_distributed(use_gpu)
@@ -902,6 +1007,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         if not use_gpu:
             raise ValueError("device_collate=True needs use_gpu=True (the collate is a HIP kernel)")
         dcoll = DeviceCollate(num_classes=num_classes, seed=2006 + rank)
+        daug = DeviceAugment(seed=2006 + rank) if device_augment else None
         collate_fn = None                                   # default_collate: stack uint8 images and labels
     elif collate_fn == "mix":
         collate_fn = SoftMixCollate(num_classes=num_classes, seed=2006 + rank)
@@ -922,7 +1028,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             for i, (x, y) in enumerate(loader):
                 x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
                 if dcoll is not None:
-                    x, y = dcoll(x, y.long(), crop=crop, tokens=True)   # uint8 batch -> row tokens + soft labels
+                    x, y = dcoll(x, y.long(), crop=crop, tokens=True, augment=daug)   # uint8 batch -> row tokens + soft labels
                 if graph and gstep is None:
                     gstep = GraphedTrainStep(model, optimizer, x, y, max_norm=1.0, scaler=scaler,
                                              autocast_dtype=torch.bfloat16, reducer=reducer, restore_after_warmup=True,

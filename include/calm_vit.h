@@ -477,6 +477,49 @@ int calm_collate_crop_mix(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const i
                           const int32_t* box, const float* mean, const float* std, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Photometric augmentation fused into the collate (an addition to ABI v7 — no existing signature or struct changes, so
+ * the version number stays).  calm_collate_crop_mix with the per-pixel transforms of distributed_trainer_cls.py:131-135
+ * between the crop and Normalize, which the reference runs on PIL images in its DataLoader workers:
+ *   ColorJitter(brightness, contrast, saturation, hue) cls:131, RandomSolarize cls:132, RandomHorizontalFlip cls:133,
+ *   RandomGrayscale cls:134, GaussianBlur(3, sigma) cls:135.
+ * Per sample, on the cropped H x W window in fp32 on [0, 1] from v = (float)u8 / 255.0f, in this order:
+ *   1. the jitter operations order[0..3] (ids below; 255 or any other value = none, skipped; an id appears at most once),
+ *      each blend(a, b, r) = clamp(r a + (1 - r) b, 0, 1) with gray = 0.2989 R + 0.587 G + 0.114 B:
+ *        0 brightness: blend(x, 0, f)     1 contrast: blend(x, m, f), m = mean of gray over the window as the image stands
+ *        2 saturation: blend(x, gray, f)    when contrast runs (after the operations in front of it in this order)
+ *        3 hue: RGB -> HSV, h = (h + f) mod 1, HSV -> RGB (the hexcone formulas of Python's colorsys)
+ *   2. solarize (flag): a channel value v >= solarize_thr becomes 1 - v
+ *   3. horizontal flip (flag)             4. grayscale (flag): R = G = B = gray
+ *   5. 3 x 3 Gaussian blur (flag), separable, w1 = exp(-0.5 / sigma^2), centre 1 / (1 + 2 w1), edge w1 / (1 + 2 w1),
+ *      reflect padding at the edges of the WINDOW (-1 -> 1, H -> H - 2), never of the source image
+ *   6. Normalize, then MixUp / CutMix with the partner (b - 1) mod B as calm_collate_crop_mix does — the partner goes
+ *      through steps 1-5 with its own parameters, crop corner and contrast mean.
+ * Nothing is rounded to 8 bits between the operations (the reference's PIL images are after each one).
+ * samples_dev: DEVICE array [B].  Corners outside [0, Hs-H] x [0, Ws-W] are clamped into that range.  A blur flag needs
+ * H >= 2 and W >= 2 (the flags live on the device: the caller checks).  gray_mean: DEVICE float [B], written by the first
+ * of the two launches (one workgroup per sample, fixed summation order: repeats bit for bit; 0 for a sample without a
+ * contrast operation) and read by the second.  out, out_tokens, mode, lam, box, mean, std: as calm_collate_crop_mix.
+ * CALM_E_INVAL as calm_collate_crop_mix, and for a null samples_dev / gray_mean; CALM_E_UNSUPP for B > 65535 or
+ * H * W > 2^30.
+ * ------------------------------------------------------------------------------------- */
+enum { CALM_AUG_FLIP = 1, CALM_AUG_SOLARIZE = 2, CALM_AUG_GRAYSCALE = 4, CALM_AUG_BLUR = 8 };          /* calm_aug_sample.flags */
+enum { CALM_AUG_OP_BRIGHTNESS = 0, CALM_AUG_OP_CONTRAST = 1, CALM_AUG_OP_SATURATION = 2, CALM_AUG_OP_HUE = 3,
+       CALM_AUG_OP_NONE = 255 };                                                                         /* .order[k]   */
+typedef struct calm_aug_sample {   /* 48 bytes */
+    int32_t  y0, x0;               /* crop corner */
+    uint32_t flags;                /* CALM_AUG_* */
+    uint8_t  order[4];             /* jitter operation ids in application order */
+    float    brightness, contrast, saturation, hue;
+    float    solarize_thr, blur_sigma;
+    float    reserved[2];
+} calm_aug_sample;
+
+int calm_augment_collate(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const calm_aug_sample* samples_dev,
+                         float* gray_mean /* DEVICE [B], written */, float* out, int32_t B, int32_t H, int32_t W,
+                         int32_t out_tokens, int32_t mode, float lam, const int32_t* box, const float* mean,
+                         const float* std, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Tokenisation (bit-exact index work).
  * image_to_rows : rows[b,i,3j+c] = img[b,c,i,j]           (Vi_Tools:389-391); rows_to_image inverse.
  * grid_transpose: out[b,j,3i+c]  = in[b,i,3j+c]           (Vi_Tools:394-395,397-398; self-inverse)
