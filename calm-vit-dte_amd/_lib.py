@@ -93,6 +93,11 @@ class AugSample(C.Structure):
                 ("solarize_thr", _f32), ("blur_sigma", _f32), ("reserved", _f32 * 2)]
 
 
+class ResizeSample(C.Structure):
+    """struct calm_resize_sample (16 bytes, one per image of calm_resize_u8)."""
+    _fields_ = [("offset", _i64), ("h", _i32), ("w", _i32)]
+
+
 # name -> (restype, argtypes); every symbol include/calm_vit.h declares
 SIGNATURES = {
     "calm_abi_version": (_i32, []),
@@ -138,6 +143,8 @@ SIGNATURES = {
     "calm_collate_mix": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_collate_crop_mix": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_augment_collate": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
+    "calm_resize_coeffs": (_i32, [_i32, _i32, _p, _p, _i32]),
+    "calm_resize_u8": (_i32, [_p, _i64, _p, _p, _i32, _i32, _i32, _p]),
     "calm_image_to_rows": (_i32, [_p, _p, _i32, _i32, _p]),
     "calm_rows_to_image": (_i32, [_p, _p, _i32, _i32, _p]),
     "calm_grid_transpose": (_i32, [_p, _p, _i32, _i32, _p]),

@@ -551,6 +551,22 @@ class HipBackend:
                                                  _ptr(out), B, H, W, int(tokens), mode, float(lam), cbox, cm, cs, _stream()),
                    "calm_augment_collate")
 
+    def resize_u8(self, packed, samples, out):
+        """PIL's antialiased bilinear Image.resize over a ragged batch, bit for bit (calm_resize_u8).  packed: 1-D uint8
+        CUDA tensor holding B images as h x w x 3 interleaved bytes; samples: the device array of B calm_resize_sample
+        records (offset, h, w) as a contiguous uint8 CUDA tensor [B,16] (trainer.DeviceResize.pack); out [B,3,oh,ow]
+        uint8 CUDA, written."""
+        if not packed.is_cuda or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+            raise TypeError("resize_u8 expects a contiguous 1-D uint8 CUDA buffer")
+        if not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 4 or out.shape[1] != 3 or not out.is_contiguous():
+            raise TypeError("resize_u8: out must be a contiguous uint8 CUDA tensor [B,3,oh,ow]")
+        B, _, oh, ow = out.shape
+        if (samples.dtype != torch.uint8 or not samples.is_cuda or not samples.is_contiguous()
+                or tuple(samples.shape) != (B, C.sizeof(_lib.ResizeSample))):
+            raise TypeError("resize_u8: samples must be a contiguous uint8 CUDA tensor [B,16] (calm_resize_sample records)")
+        _lib.check(self.lib.calm_resize_u8(packed.data_ptr(), packed.numel(), samples.data_ptr(), out.data_ptr(), B, oh, ow,
+                                           _stream()), "calm_resize_u8")
+
     # ---- optimizer-side step ------------------------------------------------------------
     def optim_plan(self, records):
         """records: one dict per parameter — param, exp_avg, exp_avg_sq, sn (None or (u, v, sigma, rows, cols))."""

@@ -326,7 +326,9 @@ class DeviceCollate:
     with 1000-way soft labels (distributed_trainer_cls.py:58-61,128-139, torchvision.transforms.v2 semantics), one kernel
     pass over the uint8 batch (calm_collate_mix).  The decode / resize / colour augmentations stay with the loader.
     torchvision is not installed in the build image, so the semantics are restated from its documentation.
-    (With an `augment=DeviceAugment(...)` argument the call also runs the colour augmentations on the device.)"""
+    (With an `augment=DeviceAugment(...)` argument the call also runs the colour augmentations on the device, and
+    `DeviceResize` in front of the call runs the resize there: the batch it returns is the [B,3,Hs,Ws] uint8 input of
+    this call, so the draws made here are the same with and without it.)"""
 
     MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
@@ -469,6 +471,92 @@ class DeviceAugment:
             t["flags"] = (t["flags"] & ~np.uint32(_lib.AUG_FLIP)) | np.where(f, _lib.AUG_FLIP, 0).astype(np.uint32)
         host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
         return host.to(device)
+
+
+class RaggedU8Collate:
+    """DataLoader collate_fn for decoded images of different sizes: samples `(uint8 [h, w, 3], label)` — the array
+    np.asarray(pil_image) gives, or a tensor of that shape — become
+      packed  uint8 [N]     the images' bytes one after the other, each starting at a multiple of ALIGN = 16 bytes,
+      meta    int64 [B, 3]  (byte offset, h, w) per image,
+      labels  int64 [B].
+    One host-to-device copy per batch then moves every image, whatever its size, and `DeviceResize` turns the packed
+    buffer into the [B,3,oh,ow] uint8 batch `DeviceCollate` reads.  The object holds no state: it pickles into worker
+    processes, and the three tensors go through the loader's pin_memory like any other batch."""
+
+    ALIGN = 16
+
+    def __call__(self, batch):
+        import numpy as np
+        imgs = [np.ascontiguousarray(np.asarray(img)) for img, _ in batch]
+        meta = np.empty((len(imgs), 3), dtype=np.int64)
+        end = 0
+        for b, a in enumerate(imgs):
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise TypeError(f"RaggedU8Collate expects uint8 images [h, w, 3], got {a.dtype} {a.shape}")
+            off = -(-end // self.ALIGN) * self.ALIGN
+            meta[b] = off, a.shape[0], a.shape[1]
+            end = off + a.size
+        packed = np.zeros(end, dtype=np.uint8)
+        for (off, _, _), a in zip(meta, imgs):
+            packed[off:off + a.size] = a.reshape(-1)
+        labels = torch.as_tensor([int(label) for _, label in batch], dtype=torch.int64)
+        return torch.from_numpy(packed), torch.from_numpy(meta), labels
+
+
+class DeviceResize:
+    """transforms.Resize(size) of the reference's list (distributed_trainer_cls.py:129) on the device: on a PIL image that
+    is Image.resize(size, BILINEAR) — antialiased, two passes, 22-bit fixed point — and calm_resize_u8 computes the same
+    bytes.  `size` is (oh, ow).  __call__(packed_dev, meta): the packed uint8 device buffer and the host int64 [B,3] table
+    of (offset, h, w) a RaggedU8Collate returns -> uint8 [B,3,oh,ow] on the device.  Source sides 1 .. 16384."""
+
+    MAX_SIDE = 16384
+
+    def __init__(self, size=(256, 256)):
+        try:
+            oh, ow = (int(v) for v in size)
+        except TypeError:
+            raise ValueError(f"DeviceResize takes size=(oh, ow), got {size!r}") from None
+        if not (1 <= oh <= self.MAX_SIDE and 1 <= ow <= self.MAX_SIDE):
+            raise ValueError(f"DeviceResize: output sides must be within 1 .. {self.MAX_SIDE}, got {(oh, ow)}")
+        self.size = (oh, ow)
+
+    @staticmethod
+    def dtype():
+        """The numpy record of struct calm_resize_sample."""
+        import numpy as np
+        from . import _lib
+        return np.dtype(_lib.ResizeSample)
+
+    @classmethod
+    def records(cls, meta, nbytes):
+        """The host array of calm_resize_sample records for a meta table, checked against a buffer of nbytes bytes (the
+        kernel would write zeros for a record it cannot read; here it is an error)."""
+        import numpy as np
+        m = np.asarray(meta.cpu() if isinstance(meta, torch.Tensor) else meta, dtype=np.int64)
+        if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] < 1:
+            raise ValueError(f"DeviceResize: meta must be [B, 3] (offset, h, w), got shape {m.shape}")
+        off, h, w = m[:, 0], m[:, 1], m[:, 2]
+        if (h < 1).any() or (w < 1).any() or (h > cls.MAX_SIDE).any() or (w > cls.MAX_SIDE).any():
+            raise ValueError(f"DeviceResize: source sides must be within 1 .. {cls.MAX_SIDE}")
+        if (off < 0).any() or (off + 3 * h * w > nbytes).any():
+            raise ValueError("DeviceResize: an image lies outside the packed buffer")
+        t = np.zeros(len(m), dtype=cls.dtype())
+        t["offset"], t["h"], t["w"] = off, h, w
+        return t
+
+    @classmethod
+    def pack(cls, meta, nbytes, device="cuda"):
+        """The device array of calm_resize_sample records, [B,16] uint8, in one host-to-device copy."""
+        import numpy as np
+        t = cls.records(meta, nbytes)
+        return torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize)).to(device)
+
+    def __call__(self, packed_dev, meta):
+        from .backend import get_backend
+        samples = self.pack(meta, packed_dev.numel(), device=packed_dev.device)
+        out = torch.empty((samples.shape[0], 3) + self.size, dtype=torch.uint8, device=packed_dev.device)
+        get_backend().resize_u8(packed_dev, samples, out)
+        return out
 
 
 def _map_tensors(out, fn):
@@ -919,7 +1007,7 @@ class SoftMixCollate:
 def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, epochs=15, batch_size=128,
           checkpoint_path=None, num_classes=1000, num_workers=0, collate_fn="mix", log_every=100, max_steps=None,
           destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
-          device_metrics=False, device_augment=False):
+          device_metrics=False, device_augment=False, device_resize=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -951,6 +1039,12 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     RandomGrayscale, GaussianBlur — run in that same pass (`DeviceAugment`, seeded 2006 + rank, with the reference's
     ranges) instead of in DataLoader workers; the dataset then yields the resized uint8 images unaugmented.
 
+    device_resize=(oh, ow) (needs device_collate=True): the Resize of cls:129 runs on the device as well.  The dataset
+    yields the decoded images as they are, `(uint8 [h, w, 3], label)` of any size; the loader packs a batch into one
+    byte buffer (`RaggedU8Collate`), and `DeviceResize` resamples it to [B,3,oh,ow] uint8 with PIL's antialiased
+    bilinear arithmetic, bit for bit, in front of the unchanged `DeviceCollate` call.  The run equals the one without
+    device_resize on the same images resized by PIL.  None (the default): the dataset yields the resized images.
+
     selfcheck ("raise" | "fallback" | None; GPU only, once per process): before the first step the box is asked whether
     the two bf16 GEMM families agree on it (HipBackend.selfcheck_bf16_gemm — round 3 saw one box of the pool on which the
     default pipelined family returned a deterministic wrong gradient); "raise" stops the job with the pattern of the
@@ -975,6 +1069,10 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         raise ValueError("device_collate=True needs use_gpu=True (the collate is a HIP kernel)")
     if device_augment and not device_collate:
         raise ValueError("device_augment=True needs device_collate=True (the augmentation is part of the collate kernel)")
+    if device_resize is not None:
+        if not device_collate:
+            raise ValueError("device_resize=(oh, ow) needs device_collate=True (the resized uint8 batch feeds the collate kernel)")
+        dres = DeviceResize(device_resize)                 # (refuses a size that is not a pair of sides within 1 .. 16384)
     if graph and not (use_gpu and (optimizer == "fused" or isinstance(optimizer, FusedClipAdamW))):
         raise ValueError('graph=True needs use_gpu=True and optimizer="fused" (FusedClipAdamW)')
     rank, local_rank, world = init_distributed(use_gpu)
@@ -1009,6 +1107,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         dcoll = DeviceCollate(num_classes=num_classes, seed=2006 + rank)
         daug = DeviceAugment(seed=2006 + rank) if device_augment else None
         collate_fn = None                                   # default_collate: stack uint8 images and labels
+        if device_resize is not None:
+            collate_fn = RaggedU8Collate()                  # images of any size: one packed buffer and its table
     elif collate_fn == "mix":
         collate_fn = SoftMixCollate(num_classes=num_classes, seed=2006 + rank)
     loader = DataLoader(dataset, batch_size=batch_size, sampler=sampler, collate_fn=collate_fn, num_workers=num_workers,
@@ -1025,8 +1125,14 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             sampler.set_epoch(epoch)
             model.train()
             epoch_loss = 0.0
-            for i, (x, y) in enumerate(loader):
-                x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
+            for i, batch in enumerate(loader):
+                if device_resize is not None:
+                    packed, meta, y = batch
+                    x = dres(packed.to(device, non_blocking=True), meta)   # packed originals -> [B,3,oh,ow] uint8
+                else:
+                    x, y = batch
+                    x = x.to(device, non_blocking=True)
+                y = y.to(device, non_blocking=True)
                 if dcoll is not None:
                     x, y = dcoll(x, y.long(), crop=crop, tokens=True, augment=daug)   # uint8 batch -> row tokens + soft labels
                 if graph and gstep is None:

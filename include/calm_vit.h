@@ -520,6 +520,46 @@ int calm_augment_collate(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const ca
                          const float* std, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Device resize over a ragged uint8 batch (an addition to ABI v7 — no existing signature or struct changes, so the
+ * version number stays).  The first transform of the reference's list, transforms.Resize((256, 256)) on a PIL image
+ * (distributed_trainer_cls.py:129), is Image.resize((ow, oh), BILINEAR): antialiased, a horizontal pass and then a
+ * vertical pass, the intermediate rounded to uint8, coefficients computed per axis in double and converted to 22-bit
+ * fixed point.  Per axis, with `in` source and `out` output pixels:
+ *   scale = (double)in / out;  fs = max(scale, 1.0);  support = fs;  ss = 1.0 / fs
+ *   output o:  center = (o + 0.5) * scale
+ *              lo = max((int)(center - support + 0.5), 0);  hi = min((int)(center + support + 0.5), in);  n = hi - lo
+ *              w[j] = tri((j + lo - center + 0.5) * ss) for j < n,  tri(t) = max(1 - |t|, 0)
+ *              ww = w[0] + w[1] + ... (in this order);  w[j] /= ww when ww != 0
+ *              k[j] = (int)(0.5 + w[j] * 4194304.0)                                            (1 << 22)
+ *   pixel:     acc = (1 << 21) + sum_j src[lo + j] * k[j];  result = clamp(acc >> 22, 0, 255)
+ * every floating-point operation a single IEEE double operation (no fused multiply-add).  From the coefficients on the
+ * arithmetic is integer, so the output equals PIL's byte for byte; a source of the output's size comes back unchanged.
+ *
+ * calm_resize_coeffs: the definition of those coefficients, on the host (no GPU, no launch).  bounds[2 o], bounds[2 o + 1]
+ *   = lo, n of output pixel o; kk[o * ksize + j] = k[j], zero for n <= j < ksize.  ksize >= 2 * ceil(max(in / out, 1)) + 1
+ *   always holds every pixel's taps.  CALM_E_INVAL: a null pointer, in / out / ksize <= 0, a pixel with more than ksize
+ *   taps (nothing is written then); CALM_E_UNSUPP: in or out above 16384.
+ * calm_resize_u8: one launch.  packed: DEVICE byte buffer of nbytes bytes holding B images, image b as h x w x 3 uint8,
+ *   interleaved (the bytes of np.asarray(pil_image)), at byte offset samples_dev[b].offset — any offset, any base
+ *   alignment.  samples_dev: DEVICE array [B].  out: DEVICE uint8 [B, 3, oh, ow], planar, the layout
+ *   calm_collate_crop_mix and calm_augment_collate read.  Source sides from 1 to 16384, up- and downscaling.  The records
+ *   live on the device, so the launch cannot refuse one: a record with h or w outside [1, 16384] or with
+ *   offset + 3 h w > nbytes is not read and its output is zeros (the caller that holds the sizes on the host checks them;
+ *   trainer.DeviceResize does).  Deterministic: no atomics, every output byte written once.
+ *   CALM_E_INVAL: a null packed / samples_dev / out, nbytes <= 0, B <= 0, oh <= 0 or ow <= 0;
+ *   CALM_E_UNSUPP: B > 65535, oh or ow above 16384.  All of them before any launch.
+ * ------------------------------------------------------------------------------------- */
+typedef struct calm_resize_sample {   /* 16 bytes */
+    int64_t offset;                   /* of the image's first byte in `packed` */
+    int32_t h, w;                     /* source rows, columns */
+} calm_resize_sample;
+
+int calm_resize_coeffs(int32_t in, int32_t out, int32_t* bounds /* [2 * out] */, int32_t* kk /* [out * ksize] */,
+                       int32_t ksize);
+int calm_resize_u8(const uint8_t* packed, int64_t nbytes, const calm_resize_sample* samples_dev, uint8_t* out /* [B,3,oh,ow] */,
+                   int32_t B, int32_t oh, int32_t ow, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Tokenisation (bit-exact index work).
  * image_to_rows : rows[b,i,3j+c] = img[b,c,i,j]           (Vi_Tools:389-391); rows_to_image inverse.
  * grid_transpose: out[b,j,3i+c]  = in[b,i,3j+c]           (Vi_Tools:394-395,397-398; self-inverse)
