@@ -98,6 +98,15 @@ class ResizeSample(C.Structure):
     _fields_ = [("offset", _i64), ("h", _i32), ("w", _i32)]
 
 
+RCROP_U8, RCROP_IMAGE, RCROP_TOKENS = 0, 1, 2                                      # calm_resized_crop's out_kind
+
+
+class RCropSample(C.Structure):
+    """struct calm_rcrop_sample (48 bytes, one per image of calm_resized_crop)."""
+    _fields_ = [("offset", _i64), ("h", _i32), ("w", _i32), ("by0", _i32), ("bx0", _i32), ("bh", _i32), ("bw", _i32),
+                ("vh", _i32), ("vw", _i32), ("wy0", _i32), ("wx0", _i32)]
+
+
 # name -> (restype, argtypes); every symbol include/calm_vit.h declares
 SIGNATURES = {
     "calm_abi_version": (_i32, []),
@@ -145,6 +154,8 @@ SIGNATURES = {
     "calm_augment_collate": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_resize_coeffs": (_i32, [_i32, _i32, _p, _p, _i32]),
     "calm_resize_u8": (_i32, [_p, _i64, _p, _p, _i32, _i32, _i32, _p]),
+    "calm_resized_crop": (_i32, [_p, _i64, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),
+    "calm_resized_crop_check": (_i32, [C.POINTER(RCropSample), _i64, _i32, _i32]),
     "calm_image_to_rows": (_i32, [_p, _p, _i32, _i32, _p]),
     "calm_rows_to_image": (_i32, [_p, _p, _i32, _i32, _p]),
     "calm_grid_transpose": (_i32, [_p, _p, _i32, _i32, _p]),

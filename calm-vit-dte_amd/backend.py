@@ -567,6 +567,35 @@ class HipBackend:
         _lib.check(self.lib.calm_resize_u8(packed.data_ptr(), packed.numel(), samples.data_ptr(), out.data_ptr(), B, oh, ow,
                                            _stream()), "calm_resize_u8")
 
+    def resized_crop(self, packed, samples, out, mean=None, std=None, tokens=False):
+        """PIL's crop(box).resize(size, BILINEAR) over a ragged batch, of which only a window is computed
+        (calm_resized_crop).  packed: 1-D uint8 CUDA tensor holding B images as h x w x 3 interleaved bytes; samples: the
+        device array of B calm_rcrop_sample records as a contiguous uint8 CUDA tensor [B,48]
+        (trainer.DeviceResizedCrop.pack); out, written: uint8 [B,3,H,W] (the resized bytes), fp32 [B,3,H,W] (normalised
+        with mean / std, three floats each) or, tokens=True, fp32 [B,H,3W] (the first Block's row tokens)."""
+        if not packed.is_cuda or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+            raise TypeError("resized_crop expects a contiguous 1-D uint8 CUDA buffer")
+        if not out.is_cuda or not out.is_contiguous() or out.dtype not in (torch.uint8, torch.float32):
+            raise TypeError("resized_crop: out must be a contiguous uint8 or fp32 CUDA tensor")
+        if tokens:
+            if out.dtype != torch.float32 or out.dim() != 3 or out.shape[2] % 3 != 0:
+                raise TypeError("resized_crop: tokens=True writes a contiguous fp32 CUDA tensor [B,H,3W]")
+            kind, (B, H, W) = _lib.RCROP_TOKENS, (out.shape[0], out.shape[1], out.shape[2] // 3)
+        else:
+            if out.dim() != 4 or out.shape[1] != 3:
+                raise TypeError("resized_crop: out must be a contiguous uint8 or fp32 CUDA tensor [B,3,H,W]")
+            kind, (B, _, H, W) = (_lib.RCROP_U8 if out.dtype == torch.uint8 else _lib.RCROP_IMAGE), out.shape
+        if (samples.dtype != torch.uint8 or not samples.is_cuda or not samples.is_contiguous()
+                or tuple(samples.shape) != (B, C.sizeof(_lib.RCropSample))):
+            raise TypeError("resized_crop: samples must be a contiguous uint8 CUDA tensor [B,48] (calm_rcrop_sample records)")
+        cm = cs = None
+        if kind != _lib.RCROP_U8:
+            if mean is None or std is None or len(mean) != 3 or len(std) != 3:
+                raise TypeError("resized_crop: an fp32 output needs mean and std, three floats each")
+            cm, cs = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+        _lib.check(self.lib.calm_resized_crop(packed.data_ptr(), packed.numel(), samples.data_ptr(), out.data_ptr(), B, H, W,
+                                              kind, cm, cs, _stream()), "calm_resized_crop")
+
     # ---- optimizer-side step ------------------------------------------------------------
     def optim_plan(self, records):
         """records: one dict per parameter — param, exp_avg, exp_avg_sq, sn (None or (u, v, sigma, rows, cols))."""

@@ -14,6 +14,7 @@
 // with more taps — a scale above 15 — goes through them in rounds, the partial sums staying in registers) and the
 // vertical coefficients of the 32 rows in flight.  The number of chunks follows from the sample's scale, which is uniform
 // over the workgroup, so every barrier is too.
+// (resized_crop.hip restates this tile loop with a source box and an output window: a fix here has to be mirrored there.)
 #include "common.h"
 #include "resize_coeffs.h"
 

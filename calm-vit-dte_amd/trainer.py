@@ -349,6 +349,13 @@ class DeviceCollate:
         flips = torch.from_numpy((rng.random(B) < self.flip_p).astype("uint8"))
         return mode, lam, box, flips
 
+    def draw_corners(self, B, Hs, Ws, H, W):
+        """int32 [B, 2] of (y0, x0): the RandomCrop corners of an H x W window inside Hs x Ws, the draws __call__ makes
+        for crop=(H, W) after draw() — made here by a caller that needs them before the batch exists (a resize that
+        computes only the window) and then passes crop=None and its decisions."""
+        import numpy as np
+        return np.stack([self.rng.integers(0, Hs - H + 1, B), self.rng.integers(0, Ws - W + 1, B)], axis=1).astype("int32")
+
     def __call__(self, img_u8, labels, decisions=None, crop=None, tokens=False, augment=None, aug_table=None):
         """crop=(H, W): RandomCrop of every sample to H x W inside the (resized) source, corners drawn uniformly as
         torchvision's RandomCrop.get_params does (cls:130); tokens=True: the batch comes out as the row tokens
@@ -364,9 +371,7 @@ class DeviceCollate:
         mode, lam, box, flips = decisions if decisions is not None else self.draw(B, H, W)
         corners = corners_host = None
         if crop is not None:
-            import numpy as np
-            corners_host = np.stack([self.rng.integers(0, Hs - H + 1, B), self.rng.integers(0, Ws - W + 1, B)],
-                                    axis=1).astype("int32")
+            corners_host = self.draw_corners(B, Hs, Ws, H, W)
             corners = torch.from_numpy(corners_host).to(img_u8.device)
         out = torch.empty((B, H, 3 * W) if tokens else (B, 3, H, W), dtype=torch.float32, device=img_u8.device)
         if augment is not None or aug_table is not None:
@@ -559,6 +564,194 @@ class DeviceResize:
         return out
 
 
+class DeviceResizedCrop:
+    """Crop a box of every image, resize it with PIL's antialiased bilinear arithmetic and keep a window of the result, in
+    one launch over the packed originals of a RaggedU8Collate (calm_resized_crop): per sample a source box, the size
+    vh x vw the box is resized to and the top-left corner of the H x W window inside it.  The bytes are those of
+    `Image.crop(box).resize((vw, vh), BILINEAR)` — torchvision's resized_crop on a PIL image — sliced to the window.
+    torchvision is not installed in the build image, so the semantics of its transforms are restated from its
+    documentation; the draws are host-side numpy.  Three constructors:
+
+      .center(resize=256, crop=(224, 224))   Resize(int) + CenterCrop, the standard validation transform: the short side
+          goes to `resize`, the long one to int(resize * long / short); the window is the central crop, top =
+          int(round((vh - H) / 2.0)).  An image whose resized size does not hold the crop is a ValueError (torchvision
+          would pad it).
+      .random_resized(size=(224, 224), scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), seed=None)   RandomResizedCrop: per image
+          up to ten attempts at a box of area uniform in `scale` times the image's and of log-uniform aspect ratio, the
+          corner uniform; after ten failures the central box with the ratio clamped.  The box is resized to `size`.  The
+          object owns its generator: the draws of DeviceCollate do not move.
+      .window(size=(256, 256), crop=(224, 224))   Resize(size) of which only the crop window is computed; the corners
+          ([B, 2] of (y0, x0), DeviceCollate.draw_corners) are given at the call.
+
+    __call__(packed_dev, meta, corners=None, out="u8" | "image" | "tokens") -> uint8 [B,3,H,W] (what DeviceCollate
+    reads), fp32 [B,3,H,W] normalised with DeviceCollate's mean / std, or the fp32 row tokens [B,H,3W] of the first
+    Block.  The host records of the last call stay in `last_records`."""
+
+    MAX_SIDE = 16384
+    MEAN, STD = DeviceCollate.MEAN, DeviceCollate.STD
+    OUTPUTS = ("u8", "image", "tokens")
+
+    def __init__(self, kind, size, resize=None, scale=None, ratio=None, seed=None):
+        """Use the constructors .center / .random_resized / .window."""
+        import numpy as np
+        if kind not in ("center", "random_resized", "window"):
+            raise ValueError(f"DeviceResizedCrop: unknown kind {kind!r}")
+        self.kind, self.size, self.resize, self.scale, self.ratio = kind, size, resize, scale, ratio
+        self.rng = np.random.default_rng(seed) if kind == "random_resized" else None
+        self.last_records = self.last_fallback = None
+
+    @classmethod
+    def _pair(cls, what, v):
+        try:
+            a, b = (int(x) for x in v)
+        except (TypeError, ValueError):
+            raise ValueError(f"DeviceResizedCrop: {what} must be a pair of sides, got {v!r}") from None
+        if not (1 <= a <= cls.MAX_SIDE and 1 <= b <= cls.MAX_SIDE):
+            raise ValueError(f"DeviceResizedCrop: {what} must be within 1 .. {cls.MAX_SIDE}, got {(a, b)}")
+        return a, b
+
+    @classmethod
+    def center(cls, resize=256, crop=(224, 224)):
+        H, W = cls._pair("crop", crop)
+        if isinstance(resize, bool) or not isinstance(resize, int) or not 1 <= resize <= cls.MAX_SIDE:
+            raise ValueError(f"DeviceResizedCrop.center: resize is the short side, an integer within 1 .. {cls.MAX_SIDE}, "
+                             f"got {resize!r}")
+        if H > resize and W > resize:
+            raise ValueError(f"DeviceResizedCrop.center: a crop of {(H, W)} never fits a short side of {resize}")
+        return cls("center", (H, W), resize=resize)
+
+    @classmethod
+    def random_resized(cls, size=(224, 224), scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), seed=None):
+        size = cls._pair("size", size)
+        try:
+            (s0, s1), (r0, r1) = (float(v) for v in scale), (float(v) for v in ratio)
+        except (TypeError, ValueError):
+            raise ValueError("DeviceResizedCrop.random_resized: scale and ratio are (min, max) pairs") from None
+        if not (0.0 < s0 <= s1 and 0.0 < r0 <= r1):
+            raise ValueError(f"DeviceResizedCrop.random_resized: need 0 < min <= max, got scale {scale!r}, ratio {ratio!r}")
+        return cls("random_resized", size, scale=(s0, s1), ratio=(r0, r1), seed=seed)
+
+    @classmethod
+    def window(cls, size=(256, 256), crop=(224, 224)):
+        vh, vw = cls._pair("size", size)
+        H, W = cls._pair("crop", crop)
+        if H > vh or W > vw:
+            raise ValueError(f"DeviceResizedCrop.window: a crop of {(H, W)} does not fit {(vh, vw)}")
+        return cls("window", (H, W), resize=(vh, vw))
+
+    @staticmethod
+    def dtype():
+        """The numpy record of struct calm_rcrop_sample."""
+        import numpy as np
+        from . import _lib
+        return np.dtype(_lib.RCropSample)
+
+    @classmethod
+    def valid(cls, t, nbytes, H, W):
+        """bool [B]: calm_resized_crop_check over a record array (the conditions of include/calm_vit.h, in 64-bit)."""
+        import numpy as np
+        f = {n: t[n].astype(np.int64) for n in t.dtype.names}
+        ok = (f["h"] >= 1) & (f["h"] <= cls.MAX_SIDE) & (f["w"] >= 1) & (f["w"] <= cls.MAX_SIDE)
+        ok &= (f["offset"] >= 0) & (f["offset"] <= nbytes)
+        ok &= np.where(ok, 3 * f["h"] * f["w"] <= nbytes - np.where(ok, f["offset"], 0), False)
+        ok &= (f["by0"] >= 0) & (f["bx0"] >= 0) & (f["bh"] >= 1) & (f["bw"] >= 1)
+        ok &= (f["by0"] + f["bh"] <= f["h"]) & (f["bx0"] + f["bw"] <= f["w"])
+        ok &= (f["vh"] >= 1) & (f["vh"] <= cls.MAX_SIDE) & (f["vw"] >= 1) & (f["vw"] <= cls.MAX_SIDE)
+        ok &= (f["wy0"] >= 0) & (f["wx0"] >= 0) & (H >= 1) & (W >= 1) & (f["wy0"] + H <= f["vh"]) & (f["wx0"] + W <= f["vw"])
+        return ok
+
+    def _random_box(self, h, w):
+        """RandomResizedCrop.get_params for one h x w image -> (top, left, box h, box w), whether the fallback was taken."""
+        import math
+        rng, area = self.rng, h * w
+        log_ratio = (math.log(self.ratio[0]), math.log(self.ratio[1]))
+        for _ in range(10):
+            target = area * float(rng.uniform(self.scale[0], self.scale[1]))
+            aspect = math.exp(float(rng.uniform(log_ratio[0], log_ratio[1])))
+            bw, bh = int(round(math.sqrt(target * aspect))), int(round(math.sqrt(target / aspect)))
+            if 0 < bw <= w and 0 < bh <= h:
+                return (int(rng.integers(0, h - bh + 1)), int(rng.integers(0, w - bw + 1)), bh, bw), False
+        in_ratio = float(w) / float(h)                     # the central box, the ratio clamped to the range
+        if in_ratio < self.ratio[0]:
+            bw = w
+            bh = int(round(bw / self.ratio[0]))
+        elif in_ratio > self.ratio[1]:
+            bh = h
+            bw = int(round(bh * self.ratio[1]))
+        else:
+            bw, bh = w, h
+        bh, bw = min(max(bh, 1), h), min(max(bw, 1), w)
+        return ((h - bh) // 2, (w - bw) // 2, bh, bw), True
+
+    def records(self, meta, nbytes, corners=None):
+        """The host array of calm_rcrop_sample records for a meta table ([B, 3] of (offset, h, w)), checked against a
+        buffer of nbytes bytes: what the kernel would answer with zeros is an error here.  .random_resized draws here."""
+        import numpy as np
+        m = np.asarray(meta.cpu() if isinstance(meta, torch.Tensor) else meta, dtype=np.int64)
+        if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] < 1:
+            raise ValueError(f"DeviceResizedCrop: meta must be [B, 3] (offset, h, w), got shape {m.shape}")
+        B, (H, W) = len(m), self.size
+        off, h, w = m[:, 0], m[:, 1], m[:, 2]
+        if (h < 1).any() or (w < 1).any() or (h > self.MAX_SIDE).any() or (w > self.MAX_SIDE).any():
+            raise ValueError(f"DeviceResizedCrop: source sides must be within 1 .. {self.MAX_SIDE}")
+        if (corners is not None) != (self.kind == "window"):
+            raise ValueError("DeviceResizedCrop: corners ([B, 2] of (y0, x0)) are given to .window and to nothing else")
+        t = np.zeros(B, dtype=self.dtype())
+        t["offset"], t["h"], t["w"] = off, h, w
+        t["bh"], t["bw"] = h, w                             # the whole image unless a box is drawn
+        if self.kind == "center":
+            tall = w <= h                                   # the short side goes to `resize`
+            long_side = (self.resize * np.where(tall, h, w).astype(np.float64) / np.where(tall, w, h)).astype(np.int64)
+            vh, vw = np.where(tall, long_side, self.resize), np.where(tall, self.resize, long_side)
+            if (vh < H).any() or (vw < W).any() or (vh > self.MAX_SIDE).any() or (vw > self.MAX_SIDE).any():
+                b = int(np.flatnonzero((vh < H) | (vw < W) | (vh > self.MAX_SIDE) | (vw > self.MAX_SIDE))[0])
+                raise ValueError(f"DeviceResizedCrop.center: image {b} ({h[b]} x {w[b]}) resizes to {vh[b]} x {vw[b]}, "
+                                 f"which does not hold the {H} x {W} crop or exceeds {self.MAX_SIDE}")
+            t["vh"], t["vw"] = vh, vw
+            t["wy0"] = [int(round((int(v) - H) / 2.0)) for v in vh]
+            t["wx0"] = [int(round((int(v) - W) / 2.0)) for v in vw]
+        elif self.kind == "random_resized":
+            boxes = [self._random_box(int(hh), int(ww)) for hh, ww in zip(h, w)]
+            t["by0"], t["bx0"], t["bh"], t["bw"] = (np.asarray(v) for v in zip(*(bx for bx, _ in boxes)))
+            t["vh"], t["vw"] = H, W
+            self.last_fallback = np.asarray([fb for _, fb in boxes], dtype=bool)
+        else:
+            c = np.asarray(corners.cpu() if isinstance(corners, torch.Tensor) else corners)
+            if c.shape != (B, 2):
+                raise ValueError(f"DeviceResizedCrop.window: corners must be [B, 2] (y0, x0), got shape {c.shape}")
+            t["vh"], t["vw"] = self.resize
+            cc = c.astype(np.int64)
+            if (cc < 0).any() or (cc > np.iinfo(np.int32).max).any():
+                raise ValueError("DeviceResizedCrop.window: a corner lies outside the resized image")
+            t["wy0"], t["wx0"] = cc[:, 0], cc[:, 1]
+        bad = ~self.valid(t, int(nbytes), H, W)
+        if bad.any():
+            b = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"DeviceResizedCrop: record {b} {t[b]} does not lie in the buffer, its image or its resized size")
+        self.last_records = t
+        return t
+
+    def pack(self, meta, nbytes, corners=None, device="cuda"):
+        """The device array of calm_rcrop_sample records, [B,48] uint8, in one host-to-device copy."""
+        import numpy as np
+        t = self.records(meta, nbytes, corners)
+        return torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize)).to(device)
+
+    def __call__(self, packed_dev, meta, corners=None, out="u8"):
+        from .backend import get_backend
+        if out not in self.OUTPUTS:
+            raise ValueError(f"DeviceResizedCrop: out is one of {self.OUTPUTS}, got {out!r}")
+        samples = self.pack(meta, packed_dev.numel(), corners, device=packed_dev.device)
+        B, (H, W) = samples.shape[0], self.size
+        if out == "u8":
+            y = torch.empty((B, 3, H, W), dtype=torch.uint8, device=packed_dev.device)
+            get_backend().resized_crop(packed_dev, samples, y)
+        else:
+            y = torch.empty((B, H, 3 * W) if out == "tokens" else (B, 3, H, W), dtype=torch.float32, device=packed_dev.device)
+            get_backend().resized_crop(packed_dev, samples, y, self.MEAN, self.STD, tokens=out == "tokens")
+        return y
+
+
 def _map_tensors(out, fn):
     """fn over the tensors of a model output (a tensor, or a tuple / list of tensors and None)."""
     if isinstance(out, torch.Tensor):
@@ -640,13 +833,34 @@ class Predictor:
         self.graph = self.x = self.out = None
 
 
-def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None):
+def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, transform=None, transform_out="tokens"):
     """Top-1 accuracy over (x, labels) batches in eval mode (CALM_ViT_V2.py:228-239).  With the loss kernels switched on
     the hits are counted on the device (calm_top1_count into a StepMetrics) and read once after the last batch instead of
     once per batch.  lean / graph: the forward goes through a Predictor (lean kernels; graph=True captures it at the first
     batch's shape and replays it, other shapes run eagerly) under autocast_dtype if one is given; without either flag the
-    model is called as before."""
+    model is called as before.
+    transform: a DeviceResizedCrop.center (DeviceResizedCrop.center(256, (224, 224)) is Resize(256) + CenterCrop(224) +
+    Normalize).  `batches` then yield what a RaggedU8Collate returns, (packed, meta, labels) with the decoded images as
+    they are, and x is the output of one launch on the model's device: the first Block's row tokens [B,H,3W]
+    (transform_out="tokens", the form train(device_collate=True) feeds the model) or the image [B,3,H,W] ("image": for a
+    model whose first layer is not this ViT's first Block, which alone takes row tokens — the kernel has both outputs and
+    the caller has to be able to choose)."""
     from . import backend
+    if transform is not None:
+        if not isinstance(transform, DeviceResizedCrop):
+            raise TypeError(f"evaluate: transform must be a DeviceResizedCrop, got {type(transform).__name__}")
+        if transform.kind != "center":                      # no random crops in an evaluation; .window needs corners per call
+            raise ValueError("evaluate: transform takes a DeviceResizedCrop.center(...), the deterministic validation transform")
+        if transform_out not in ("tokens", "image"):
+            raise ValueError(f'evaluate: transform_out is "tokens" or "image", got {transform_out!r}')
+        device = next(model.parameters()).device
+        if device.type != "cuda":
+            raise ValueError("evaluate: transform= runs a HIP kernel, the model must be on a GPU")
+
+        def _transformed(src):
+            for packed, meta, labels in src:
+                yield transform(packed.to(device, non_blocking=True), meta, out=transform_out), labels.to(device)
+        batches = _transformed(batches)
     was_training = model.training
     model.eval()
     correct = total = 0
@@ -1007,7 +1221,7 @@ class SoftMixCollate:
 def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, epochs=15, batch_size=128,
           checkpoint_path=None, num_classes=1000, num_workers=0, collate_fn="mix", log_every=100, max_steps=None,
           destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
-          device_metrics=False, device_augment=False, device_resize=None):
+          device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -1045,6 +1259,15 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     bilinear arithmetic, bit for bit, in front of the unchanged `DeviceCollate` call.  The run equals the one without
     device_resize on the same images resized by PIL.  None (the default): the dataset yields the resized images.
 
+    resize_window=True (needs device_resize and crop): the decisions and the crop corners of a batch are drawn first, in
+    the order `DeviceCollate` draws them, and only the crop window of every resized image is computed
+    (`DeviceResizedCrop.window`) — 23 % fewer pixels at 224 of 256 — before the collate takes the batch at the crop size.
+    The run equals the one without the flag bit for bit.
+
+    random_resized_crop=DeviceResizedCrop.random_resized(...) (needs device_collate=True; excludes device_resize and
+    crop): RandomResizedCrop on the device.  The dataset yields the decoded images as for device_resize; the transform
+    draws a box per image from its own generator and hands the collate a batch already at its size.
+
     selfcheck ("raise" | "fallback" | None; GPU only, once per process): before the first step the box is asked whether
     the two bf16 GEMM families agree on it (HipBackend.selfcheck_bf16_gemm — round 3 saw one box of the pool on which the
     default pipelined family returned a deterministic wrong gradient); "raise" stops the job with the pattern of the
@@ -1073,6 +1296,17 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         if not device_collate:
             raise ValueError("device_resize=(oh, ow) needs device_collate=True (the resized uint8 batch feeds the collate kernel)")
         dres = DeviceResize(device_resize)                 # (refuses a size that is not a pair of sides within 1 .. 16384)
+    if resize_window:
+        if device_resize is None or crop is None:
+            raise ValueError("resize_window=True needs device_resize=(oh, ow) and crop=(H, W): it resizes only the crop window")
+        dwin = DeviceResizedCrop.window(dres.size, crop)    # (refuses a crop that does not fit the resized size)
+    if random_resized_crop is not None:
+        if not isinstance(random_resized_crop, DeviceResizedCrop) or random_resized_crop.kind != "random_resized":
+            raise ValueError("random_resized_crop takes a DeviceResizedCrop.random_resized(...)")
+        if not device_collate:
+            raise ValueError("random_resized_crop needs device_collate=True (the cropped uint8 batch feeds the collate kernel)")
+        if device_resize is not None or crop is not None:
+            raise ValueError("random_resized_crop excludes device_resize and crop: it is the crop and the resize")
     if graph and not (use_gpu and (optimizer == "fused" or isinstance(optimizer, FusedClipAdamW))):
         raise ValueError('graph=True needs use_gpu=True and optimizer="fused" (FusedClipAdamW)')
     rank, local_rank, world = init_distributed(use_gpu)
@@ -1107,7 +1341,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         dcoll = DeviceCollate(num_classes=num_classes, seed=2006 + rank)
         daug = DeviceAugment(seed=2006 + rank) if device_augment else None
         collate_fn = None                                   # default_collate: stack uint8 images and labels
-        if device_resize is not None:
+        if device_resize is not None or random_resized_crop is not None:
             collate_fn = RaggedU8Collate()                  # images of any size: one packed buffer and its table
     elif collate_fn == "mix":
         collate_fn = SoftMixCollate(num_classes=num_classes, seed=2006 + rank)
@@ -1126,15 +1360,25 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             model.train()
             epoch_loss = 0.0
             for i, batch in enumerate(loader):
-                if device_resize is not None:
+                decisions, window = None, crop
+                if resize_window:
+                    packed, meta, y = batch
+                    decisions = dcoll.draw(len(meta), *dwin.size)          # the order of DeviceCollate.__call__: decisions,
+                    corners = dcoll.draw_corners(len(meta), *dres.size, *dwin.size)    # then corners
+                    x = dwin(packed.to(device, non_blocking=True), meta, corners=corners)   # only the crop window, uint8
+                    window = None                                          # the batch is at the crop size already
+                elif random_resized_crop is not None:
+                    packed, meta, y = batch
+                    x = random_resized_crop(packed.to(device, non_blocking=True), meta)     # box -> [B,3,H,W] uint8
+                elif device_resize is not None:
                     packed, meta, y = batch
                     x = dres(packed.to(device, non_blocking=True), meta)   # packed originals -> [B,3,oh,ow] uint8
                 else:
                     x, y = batch
                     x = x.to(device, non_blocking=True)
                 y = y.to(device, non_blocking=True)
-                if dcoll is not None:
-                    x, y = dcoll(x, y.long(), crop=crop, tokens=True, augment=daug)   # uint8 batch -> row tokens + soft labels
+                if dcoll is not None:                                      # uint8 batch -> row tokens + soft labels
+                    x, y = dcoll(x, y.long(), decisions=decisions, crop=window, tokens=True, augment=daug)
                 if graph and gstep is None:
                     gstep = GraphedTrainStep(model, optimizer, x, y, max_norm=1.0, scaler=scaler,
                                              autocast_dtype=torch.bfloat16, reducer=reducer, restore_after_warmup=True,

@@ -560,6 +560,49 @@ int calm_resize_u8(const uint8_t* packed, int64_t nbytes, const calm_resize_samp
                    int32_t B, int32_t oh, int32_t ow, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Device resized crop (an addition to ABI v7 — no existing signature or struct changes, so the version number stays):
+ * calm_resize_u8 with a per-sample source box, a per-sample output size and an output window, i.e. what
+ * Image.crop((bx0, by0, bx0 + bw, by0 + bh)).resize((vw, vh), BILINEAR) returns — torchvision's resized_crop on a PIL
+ * image — of which only the H x W pixels from (wy0, wx0) on are computed:
+ *   out[b, :, y, x] = pixel (wy0 + y, wx0 + x) of resize(crop(image_b, box_b), (vh_b, vw_b)).
+ * One launch covers Resize(int) + CenterCrop (box = the image, vh x vw = the aspect-preserving size, the window = the
+ * central crop), RandomResizedCrop (a random box, vh x vw = H x W, window at (0, 0)) and Resize(size) + RandomCrop
+ * (box = the image, window = the crop).
+ * The contract is the per-axis formulas above — the horizontal pass, rounded to uint8, then the vertical pass — with
+ * `in` = bw / bh, `out` = vw / vh and the source indices shifted by bx0 / by0; pixels outside the box are never read
+ * (this is crop-then-resize: Image.resize(size, BILINEAR, box=box) is a different function, it reads pixels around the
+ * box).  PIL returns the same bytes for sources whose sides are within a factor of about 100 of one another; on very
+ * tall and narrow ones (w = 2 .. 6 with h above roughly 100 w, downscaled vertically) PIL 12.2.0 runs the vertical pass
+ * first and a few bytes differ.  There the contract is these formulas, as it is for calm_resize_u8.
+ * out_kind: 0  uint8 [B,3,H,W] planar, the layout calm_collate_crop_mix and calm_augment_collate read;
+ *           1  fp32 [B,3,H,W], n(v) = (v / 255 - mean[c]) / std[c];
+ *           2  fp32 row tokens [B,H,3W], out[b,i,3j+c] = n(v) of channel c at (i, j) (what the first Block consumes).
+ * mean, std: HOST float[3], required for kinds 1 and 2, ignored for kind 0.  In fp32 n(v) is evaluated as
+ *   fma((float)v, 1.0f / 255.0f, -mean[c]) * (1.0f / std[c]), three roundings, the same on every launch.
+ * A record is valid when 1 <= h, w <= 16384, the image lies inside nbytes, by0, bx0 >= 0, bh, bw >= 1, by0 + bh <= h,
+ * bx0 + bw <= w, 1 <= vh, vw <= 16384, wy0, wx0 >= 0, wy0 + H <= vh and wx0 + W <= vw, evaluated in 64-bit by one
+ * function (csrc/rcrop_check.h) that the kernel calls before it forms any address and that calm_resized_crop_check
+ * exposes on the host (no GPU, no launch; a null sample is invalid).  The records live on the device, so the launch cannot
+ * refuse one: an invalid record is never read and its output is what an all-zero source gives — zeros for kind 0, n(0)
+ * for kinds 1 and 2 (trainer.DeviceResizedCrop refuses it on the host).  packed: any offsets, any base alignment; no
+ * dword is loaded that does not hold a byte of the image.  Deterministic: no atomics, every output element written once.
+ *   CALM_E_INVAL: a null packed / samples_dev / out, nbytes <= 0, B <= 0, H <= 0 or W <= 0, an out_kind outside 0 .. 2,
+ *     a null mean or std for kinds 1 and 2;
+ *   CALM_E_UNSUPP: B > 65535, H or W above 16384.  All of them before any launch.
+ * ------------------------------------------------------------------------------------- */
+typedef struct calm_rcrop_sample {   /* 48 bytes */
+    int64_t offset;                   /* of the image's first byte in `packed`, as calm_resize_sample */
+    int32_t h, w;                     /* source rows, columns */
+    int32_t by0, bx0, bh, bw;         /* source box: PIL crop((bx0, by0, bx0 + bw, by0 + bh)) */
+    int32_t vh, vw;                   /* the size the box is resized to */
+    int32_t wy0, wx0;                 /* top-left of the output window inside vh x vw */
+} calm_rcrop_sample;
+
+int calm_resized_crop(const uint8_t* packed, int64_t nbytes, const calm_rcrop_sample* samples_dev, void* out, int32_t B,
+                      int32_t H, int32_t W, int32_t out_kind, const float* mean, const float* std, void* stream);
+int calm_resized_crop_check(const calm_rcrop_sample* sample /* HOST */, int64_t nbytes, int32_t H, int32_t W);  /* 1 valid, 0 not */
+
+/* ---------------------------------------------------------------------------------------
  * Tokenisation (bit-exact index work).
  * image_to_rows : rows[b,i,3j+c] = img[b,c,i,j]           (Vi_Tools:389-391); rows_to_image inverse.
  * grid_transpose: out[b,j,3i+c]  = in[b,i,3j+c]           (Vi_Tools:394-395,397-398; self-inverse)
