@@ -405,6 +405,7 @@ def test_tokenisation_is_bit_exact(hip, emu, B, S):
     assert torch.equal(tt, rows_hip)                    # involution
 
 
+# (element-wise against float64, C = 1 ... 64, every optional pointer, the backward's grid clamp: test_tail_f64_gpu.py)
 @pytest.mark.parametrize("B,S", [(2, 44), (1, 80)])
 def test_dwconv3x3(hip, emu, B, S):
     Cch = 32
@@ -452,7 +453,8 @@ def test_streaming_helpers(hip, emu):
 
 @pytest.mark.parametrize("B,S", [(2, 48), (1, 80), (3, 36), (2, 12), (1, 176)])
 def test_fused_cnn_residual(hip, emu, B, S):
-    """Fused conv1x1-GELU-dw3x3-GELU-conv1x1 + residual (LDS-tiled, backward recomputes) incl. ragged tiles."""
+    """Fused conv1x1-GELU-dw3x3-GELU-conv1x1 + residual (LDS-tiled, backward recomputes) incl. ragged tiles.
+    (Element-wise against float64, past both grid caps, residual = 0, onto non-zero gradients: test_tail_f64_gpu.py.)"""
     Ch = 32
     x, dy = rnd(B, S, 3 * S, seed=1), rnd(B, S, 3 * S, seed=2)
     w0, b0 = rnd(Ch, 3, seed=3) * 0.6, rnd(Ch, seed=4) * 0.1
