@@ -71,6 +71,14 @@ class CastEntry(C.Structure):
     _fields_ = [("src", _p), ("dst", _p), ("numel", _i64), ("chunk0", _i32), ("reserved", _i32)]
 
 
+EMA_CONSTANT, EMA_WARMUP = 0, 1                   # calm_ema_update's schedule (CALM_EMA_*)
+
+
+class EmaEntry(C.Structure):
+    """struct calm_ema_entry (32 bytes)."""
+    _fields_ = [("src", _p), ("ema", _p), ("numel", _i64), ("chunk0", _i32), ("reserved", _i32)]
+
+
 class SnLayer(C.Structure):
     """struct calm_sn_layer."""
     _fields_ = [("w", _p), ("u", _p), ("v", _p), ("sigma", _p), ("rows", _i32), ("cols", _i32)]
@@ -149,6 +157,9 @@ SIGNATURES = {
     "calm_sn_weight_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _p, _p]),
     "calm_optim_chunk_elems": (_i32, []),
     "calm_optim_step": (_i32, [_p, _i32, _p, _i32, _p, C.POINTER(OptimHparams), _p, _p, _p, _p, _p]),
+    "calm_ema_chunk_elems": (_i32, []),
+    "calm_ema_update": (_i32, [_p, _i32, _p, _i32, _f32, _i32, _p, _p, _p, _p]),
+    "calm_ema_swap": (_i32, [_p, _i32, _p, _i32, _p]),
     "calm_collate_mix": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_collate_crop_mix": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_augment_collate": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),

@@ -261,6 +261,46 @@ class OptimPlan:
         self.uploaded = grad_ptrs.copy()
 
 
+class EmaPlan:
+    """Device tables of calm_ema_entry records for calm_ema_update / calm_ema_swap, fixed at construction: the entry
+    table, the chunk table, the update counter `count_dev` (int32[1], advanced by the device, not on skipped updates) and
+    `weight_out` (float32[2]: the weight 1 - d of the last update, and whether it was skipped).  `src_ptrs` / `ema_ptrs`
+    record the addresses the table holds (ModelEMA checks them against the parameters before every update).  Tensors with
+    no elements have no entry."""
+
+    def __init__(self, be, pairs):
+        chunk = int(be.lib.calm_ema_chunk_elems())
+        for src, ema in pairs:
+            if not (src.is_contiguous() and ema.is_contiguous()):
+                raise TypeError("weight EMA expects contiguous parameters and averages")
+            if src.shape != ema.shape:
+                raise ValueError("weight EMA shape mismatch")
+            _ptr(src), _ptr(ema)                                   # fp32 tensors on the device, or it raises
+        pairs = [(src, ema) for src, ema in pairs if src.numel() > 0]
+        if not pairs:
+            raise ValueError("weight EMA needs at least one tensor with elements")
+        ent = np.zeros(len(pairs), dtype=np.dtype(_lib.EmaEntry))
+        chunk_entry, spans = [], []
+        for i, (src, ema) in enumerate(pairs):
+            e = ent[i]
+            e["src"], e["ema"], e["numel"] = src.data_ptr(), ema.data_ptr(), src.numel()
+            e["chunk0"] = len(chunk_entry)
+            chunk_entry += [i] * ((src.numel() + chunk - 1) // chunk)
+            spans += [(src.data_ptr(), src.data_ptr() + 4 * src.numel()), (ema.data_ptr(), ema.data_ptr() + 4 * src.numel())]
+        spans.sort()
+        if any(b[0] < a[1] for a, b in zip(spans, spans[1:])):        # an exchange of overlapping ranges is a race
+            raise ValueError("weight EMA expects parameters and averages that do not overlap in memory")
+        dev = pairs[0][0].device
+        self.n = len(pairs)
+        self.n_chunks = len(chunk_entry)
+        self.table_dev = torch.from_numpy(ent.view(np.uint8).reshape(-1).copy()).to(dev)
+        self.chunk_dev = torch.tensor(chunk_entry, dtype=torch.int32, device=dev)
+        self.count_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.weight_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.src_ptrs = ent["src"].copy()
+        self.ema_ptrs = ent["ema"].copy()
+
+
 class SnPlan:
     """Device-resident plan for the batched spectral-norm power iteration."""
 
@@ -610,6 +650,23 @@ class HipBackend:
         _lib.check(self.lib.calm_optim_step(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
                                             _ptr(plan.scratch), C.byref(h), _ptr(grad_scale, True), _ptr(stats_out),
                                             plan.step_dev.data_ptr(), _ptr(lr_dev, True), _stream()), "calm_optim_step")
+
+    # ---- weight EMA ---------------------------------------------------------------------
+    def ema_plan(self, pairs):
+        """pairs: [(fp32 parameter, its fp32 average of the same shape)] -> plan for ema_update / ema_swap."""
+        return EmaPlan(self, pairs)
+
+    def ema_update(self, plan, decay, schedule, skip=None):
+        """ema += (1 - d) * (src - ema) over the plan; d = decay (EMA_CONSTANT) or min(decay, (1 + n) / (10 + n))
+        (EMA_WARMUP) with n = plan.count_dev.  skip: device scalar; non-zero leaves averages and counter untouched."""
+        _lib.check(self.lib.calm_ema_update(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
+                                            decay, schedule, plan.count_dev.data_ptr(), _ptr(skip, True),
+                                            _ptr(plan.weight_out), _stream()), "calm_ema_update")
+
+    def ema_swap(self, plan):
+        """Exchange every parameter with its average, in place."""
+        _lib.check(self.lib.calm_ema_swap(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
+                                          _stream()), "calm_ema_swap")
 
     # ---- LayerNorm --------------------------------------------------------------------
     def layernorm_fwd(self, x, w, y, mean, rstd, rows, D, eps):

@@ -13,10 +13,14 @@ as set by torchrun):
         all-reduced (mean) on a SIDE HIP stream while the rest of backward keeps running.
   * `TrainStep`                        <- one iteration of the step loop               (cls:79-96):
         forward, CE with soft targets, backward, unscale / clip_grad_norm_(1.0), AdamW, zero_grad.
+  * `ModelEMA`                         (no counterpart: the reference keeps no weight average)
+        exponential moving average of the parameters, one kernel pass behind the optimizer step; exchanged into the
+        parameters in place for evaluation.
 
 The model also works under stock `torch.nn.parallel.DistributedDataParallel` (that is what the
 reference's train() does with it); the reducer here is the MI355X-tuned equivalent.
 """
+import contextlib
 import os
 import weakref
 
@@ -228,10 +232,14 @@ class StepMetrics:
 class TrainStep:
     """One iteration of distributed_trainer_cls.py:79-96 (per rank)."""
 
-    def __init__(self, model, optimizer, reducer=None, max_norm=1.0, scaler=None, autocast_dtype=None, metrics=None):
-        """metrics: a StepMetrics the loss kernel accumulates into (only with the loss kernels switched on)."""
+    def __init__(self, model, optimizer, reducer=None, max_norm=1.0, scaler=None, autocast_dtype=None, metrics=None,
+                 ema=None):
+        """metrics: a StepMetrics the loss kernel accumulates into (only with the loss kernels switched on).
+        ema: a ModelEMA of `model`, updated right behind the optimizer step; a step skipped for inf/NaN gradients leaves
+        the average and its update count alone."""
         self.model, self.opt, self.reducer = model, optimizer, reducer
         self.metrics = metrics
+        self.ema = ema
         self.max_norm = max_norm
         self.scaler = scaler
         self.autocast_dtype = autocast_dtype          # torch.bfloat16: the reference's `with autocast(...)` (cls:84)
@@ -264,6 +272,8 @@ class TrainStep:
                     self._one = torch.ones((), dtype=torch.float32, device=loss.device)
                 scale = sc.scale(self._one)                      # the current scale as a device tensor, no host sync
                 stats = self.opt.step(grad_scale=scale)
+                if self.ema is not None:
+                    self.ema.update(skip=stats[1:2])             # found_inf of this step, read on the device
                 bad = stats[1] > 0
                 # the counter is updated IN PLACE: a captured step (GraphedTrainStep) replays these kernels on the
                 # addresses seen at capture, so a rebound tensor would leave every replay reading the pre-capture value
@@ -275,16 +285,30 @@ class TrainStep:
                 self._clean_steps.copy_(torch.where(grow, torch.zeros_like(self._clean_steps), self._clean_steps))
                 sc.update(new_scale.detach())          # GradScaler.update(tensor) copies into its scale tensor in place
             else:
-                self.opt.step()
+                stats = self.opt.step()
+                if self.ema is not None:
+                    self.ema.update(skip=stats[1:2])
             return loss.detach(), y_hat.detach()
         if self.scaler is not None:
             self.scaler.unscale_(self.opt)                                 # cls:88
         torch.nn.utils.clip_grad_norm_(self.params, max_norm=self.max_norm, error_if_nonfinite=False)   # cls:92
+        skip = None
         if self.scaler is not None:
+            watch = self.ema is not None and self.scaler.is_enabled()
+            if watch:
+                # scaler.step() skips optimizer.step() on inf/NaN and scaler.update() then backs the scale off: the step
+                # was skipped exactly when the scale shrank.  Public API only, device arithmetic, no host sync.
+                if not hasattr(self, "_ema_one"):
+                    self._ema_one = torch.ones(1, dtype=torch.float32, device=loss.device)
+                old_scale = self.scaler.scale(self._ema_one)
             self.scaler.step(self.opt)                                     # cls:93-94
             self.scaler.update()
+            if watch:
+                skip = (self.scaler.scale(self._ema_one) < old_scale).to(torch.float32)
         else:
             self.opt.step()
+        if self.ema is not None:
+            self.ema.update(skip=skip)
         self.opt.zero_grad()                                               # cls:96
         return loss.detach(), y_hat.detach()
 
@@ -294,8 +318,9 @@ class RegTrainStep(TrainStep):
     tokens [B,S,3S]; they are viewed as the image [B,3,S,S] (:78-79), loss = HuberLoss(img, x) + 0.1 * kl_loss
     (:81,87), then the same scale / clip(1.0) / optimizer step as the classification trainer."""
 
-    def __init__(self, model, optimizer, reducer=None, max_norm=1.0, scaler=None, autocast_dtype=None, kl_weight=0.1):
-        super().__init__(model, optimizer, reducer, max_norm=max_norm, scaler=scaler, autocast_dtype=autocast_dtype)
+    def __init__(self, model, optimizer, reducer=None, max_norm=1.0, scaler=None, autocast_dtype=None, kl_weight=0.1,
+                 ema=None):
+        super().__init__(model, optimizer, reducer, max_norm=max_norm, scaler=scaler, autocast_dtype=autocast_dtype, ema=ema)
         self.kl_weight = kl_weight
 
     def __call__(self, x, _y=None):
@@ -833,7 +858,7 @@ class Predictor:
         self.graph = self.x = self.out = None
 
 
-def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, transform=None, transform_out="tokens"):
+def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, transform=None, transform_out="tokens", ema=None):
     """Top-1 accuracy over (x, labels) batches in eval mode (CALM_ViT_V2.py:228-239).  With the loss kernels switched on
     the hits are counted on the device (calm_top1_count into a StepMetrics) and read once after the last batch instead of
     once per batch.  lean / graph: the forward goes through a Predictor (lean kernels; graph=True captures it at the first
@@ -844,7 +869,15 @@ def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, trans
     they are, and x is the output of one launch on the model's device: the first Block's row tokens [B,H,3W]
     (transform_out="tokens", the form train(device_collate=True) feeds the model) or the image [B,3,H,W] ("image": for a
     model whose first layer is not this ViT's first Block, which alone takes row tokens — the kernel has both outputs and
-    the caller has to be able to choose)."""
+    the caller has to be able to choose).
+    ema: a ModelEMA of `model`.  The whole loop runs inside `ema.applied()`: the averages are exchanged into the parameters
+    in place (every cached address and captured graph stays valid) and exchanged back when the loop ends or raises."""
+    if ema is not None:
+        if ema.model is not model:
+            raise ValueError("evaluate: ema= must be the ModelEMA of the model being evaluated")
+        with ema.applied():
+            return evaluate(model, batches, lean=lean, graph=graph, autocast_dtype=autocast_dtype, transform=transform,
+                            transform_out=transform_out)
     from . import backend
     if transform is not None:
         if not isinstance(transform, DeviceResizedCrop):
@@ -1076,6 +1109,188 @@ class FusedClipAdamW(torch.optim.Optimizer):
             dst.copy_(src)
 
 
+def ema_weight(decay, schedule, n):
+    """The weight w = 1 - d of weight-EMA update number n + 1 as calm_ema_update's first launch evaluates it, in fp32:
+    d = decay (EMA_CONSTANT) or min(decay, (1 + n) / (10 + n)) (EMA_WARMUP).  numpy's float32 division is correctly
+    rounded, as the kernel's is."""
+    import numpy as np
+    from . import _lib
+    f = np.float32
+    d = f(decay)
+    if schedule == _lib.EMA_WARMUP:
+        d = min(d, (f(1.0) + f(n)) / (f(10.0) + f(n)))
+    return float(f(1.0) - d)
+
+
+class ModelEMA:
+    """Exponential moving average of a model's parameters (timm's ModelEmaV2 / torch's AveragedModel):
+    after every optimizer step  ema += (1 - d) * (p - ema),  d = decay, or min(decay, (1 + n) / (10 + n)) with warmup=True
+    (n = updates applied so far), so a short run is not dominated by the initial weights.
+
+    Every entry of `model.named_parameters()` gets an fp32 clone (the "shadow"), initialised to the current value.
+    CUDA parameters are updated by calm_ema_update — one pass over all of them, a launch of its own behind
+    calm_optim_step — and there is no torch fallback for them; CPU parameters (the gloo path of train(use_gpu=False)) take
+    the same arithmetic through Tensor.lerp_ with the host-computed fp32 weight (`ema_weight`) and a host counter.
+
+    Buffers are NOT shadowed.  The only ones this model has are the spectral-norm `weight_u` / `weight_v`: unit direction
+    vectors of the power iteration on the LIVE weight, not quantities a mean of which means anything (the average of unit
+    vectors is not a unit vector, and sigma = u^T W v is taken with them).  They stay shared: evaluating with the average
+    uses the live u / v, as a copy of the model loaded with `model_state_dict()` does.
+
+    Evaluation exchanges the averages INTO the parameters (calm_ema_swap) instead of exchanging tensor objects: the
+    optimizer plan, the spectral-norm plan, the bf16 weight-copy plan and captured graphs (Predictor, GraphedTrainStep)
+    cache raw parameter addresses, and all of them stay valid; a captured eval graph sees the averages on its next
+    replay.  `with ema.applied(): ...` swaps in and, in a finally, back."""
+
+    def __init__(self, model, decay=0.9999, warmup=True):
+        from . import _lib
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"ModelEMA: decay must be in [0, 1), got {decay}")
+        self.model = model
+        self.decay = decay
+        self.schedule = _lib.EMA_WARMUP if warmup else _lib.EMA_CONSTANT
+        named = list(model.named_parameters())
+        if not named:
+            raise ValueError("ModelEMA: the model has no parameters")
+        self.names = [n for n, _ in named]
+        self.params = [p for _, p in named]
+        for n, p in named:
+            if p.dtype != torch.float32:
+                raise TypeError(f"ModelEMA: fp32 parameters expected, {n} is {p.dtype}")
+        self.shadows = [p.detach().clone(memory_format=torch.contiguous_format) for p in self.params]
+        self._swapped = False
+        self._bind(0)
+
+    def _bind(self, count):
+        """Record the parameter addresses and, on a GPU, build the device plan; `count` = updates applied so far."""
+        import numpy as np
+        devices = {p.device for p in self.params}
+        if len(devices) != 1:
+            raise ValueError(f"ModelEMA: parameters on one device expected, got {sorted(map(str, devices))}")
+        self.device = devices.pop()
+        self._plan = None
+        self._count = int(count)
+        if self.device.type == "cuda":
+            from .backend import get_backend
+            self._be = get_backend()
+            self._plan = self._be.ema_plan([(p.data, s) for p, s in zip(self.params, self.shadows)])
+            self._plan.count_dev.fill_(int(count))
+        self._ptrs = np.fromiter((p.data_ptr() for p in self.params), dtype=np.uint64, count=len(self.params))
+
+    def rebind(self):
+        """After the model was moved on purpose (model.to(device)): move the averages to the parameters' device and
+        record the new addresses; the update count is kept."""
+        if self._swapped:
+            raise RuntimeError("ModelEMA.rebind: the averages are swapped into the model; swap() back first")
+        count = self.num_updates
+        self.shadows = [s.to(p.device) for s, p in zip(self.shadows, self.params)]
+        self._bind(count)
+
+    def _check(self):
+        """The plan caches raw addresses (as FusedClipAdamW._check_plan): refuse to read orphaned storage."""
+        import numpy as np
+        now = np.fromiter((p.data_ptr() for p in self.params), dtype=np.uint64, count=len(self.params))
+        if not np.array_equal(now, self._ptrs):
+            raise RuntimeError("ModelEMA: parameters were moved or replaced after the average was built (model.to / .float "
+                               "/ load with assign=True); build it after the model is on its final device, or rebind()")
+
+    @property
+    def is_swapped(self):
+        """True while the parameters hold the averages (and the shadows the live weights)."""
+        return self._swapped
+
+    @property
+    def num_updates(self):
+        """Updates applied (skipped ones not counted).  On a GPU the counter lives on the device: reading it synchronises."""
+        return int(self._plan.count_dev.item()) if self._plan is not None else self._count
+
+    def state_tensors(self):
+        """The tensors that are this object's state, for an in-place snapshot / restore (GraphedTrainStep)."""
+        return list(self.shadows) + ([self._plan.count_dev] if self._plan is not None else [])
+
+    @torch.no_grad()
+    def update(self, skip=None):
+        """One update from the current parameters.  skip: a one-element fp32 tensor on the parameters' device; non-zero
+        leaves the averages and the update count untouched (a step the optimizer skipped for inf/NaN gradients)."""
+        if self._swapped:
+            raise RuntimeError("ModelEMA.update: the averages are swapped into the model; swap() back before training on")
+        self._check()
+        if self._plan is not None:
+            self._be.ema_update(self._plan, self.decay, self.schedule, skip)
+            return
+        if skip is not None and float(skip.reshape(-1)[0]) != 0.0:
+            return
+        w = ema_weight(self.decay, self.schedule, self._count)
+        for p, s in zip(self.params, self.shadows):
+            s.lerp_(p.detach(), w)
+        self._count += 1
+
+    @torch.no_grad()
+    def swap(self):
+        """Exchange parameters and averages in place, element for element."""
+        self._check()
+        if self._plan is not None:
+            self._be.ema_swap(self._plan)
+        else:
+            for p, s in zip(self.params, self.shadows):
+                t = p.detach().clone()
+                p.detach().copy_(s)
+                s.copy_(t)
+        self._swapped = not self._swapped
+
+    @contextlib.contextmanager
+    def applied(self):
+        """The model holds the averages inside the block; the live weights come back when it ends or raises."""
+        if self._swapped:
+            raise RuntimeError("ModelEMA.applied: the averages are swapped in already")
+        self.swap()
+        try:
+            yield self.model
+        finally:
+            self.swap()
+
+    def _live_shadows(self, what):
+        if self._swapped:
+            raise RuntimeError(f"ModelEMA.{what}: the averages are swapped into the model; swap() back first")
+        return self.shadows
+
+    def state_dict(self):
+        from . import _lib
+        return {"decay": self.decay, "warmup": self.schedule == _lib.EMA_WARMUP, "num_updates": self.num_updates,
+                "shadow": {n: s.detach().clone() for n, s in zip(self.names, self._live_shadows("state_dict"))}}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        from . import _lib
+        shadows = self._live_shadows("load_state_dict")
+        got = sd["shadow"]
+        if set(got) != set(self.names):
+            missing, extra = sorted(set(self.names) - set(got)), sorted(set(got) - set(self.names))
+            raise KeyError(f"ModelEMA.load_state_dict: parameter names differ (missing {missing[:3]}, unexpected {extra[:3]})")
+        for n, s in zip(self.names, shadows):
+            if tuple(got[n].shape) != tuple(s.shape):
+                raise ValueError(f"ModelEMA.load_state_dict: {n} has shape {tuple(got[n].shape)}, expected {tuple(s.shape)}")
+        decay = float(sd["decay"])
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"ModelEMA.load_state_dict: decay must be in [0, 1), got {decay}")
+        for n, s in zip(self.names, shadows):
+            s.copy_(got[n])                                       # in place: the plan holds these addresses
+        self.decay = decay
+        self.schedule = _lib.EMA_WARMUP if sd["warmup"] else _lib.EMA_CONSTANT
+        self._count = int(sd["num_updates"])
+        if self._plan is not None:
+            self._plan.count_dev.fill_(self._count)
+
+    def model_state_dict(self):
+        """The model's state_dict() with every parameter replaced by a clone of its average (buffers as they are): loads
+        into a ViT — and into the reference's — under the same keys."""
+        sd = self.model.state_dict()
+        for n, s in zip(self.names, self._live_shadows("model_state_dict")):
+            sd[n] = s.detach().clone()
+        return sd
+
+
 class GraphedTrainStep:
     """The same step captured once into a hipGraph and replayed: every kernel of the library only enqueues on the
     current stream (no allocation, no host sync), so forward + loss + backward + gradient exchange + unscale / clip /
@@ -1096,8 +1311,10 @@ class GraphedTrainStep:
     capture, so that the first replay is step 1 of the run — the replayed trajectory then equals the eager one."""
 
     def __init__(self, model, optimizer, example_x, example_y, max_norm=1.0, warmup=3, scaler=None, autocast_dtype=None,
-                 reducer=None, restore_after_warmup=False, metrics=None):
-        """reducer: a BucketedGradReducer whose bucket copies and RCCL all-reduces are captured with the step (round 4:
+                 reducer=None, restore_after_warmup=False, metrics=None, ema=None):
+        """ema: a ModelEMA of `model`; calm_ema_update is captured behind the optimizer step, and restore_after_warmup puts
+        the averages and their device update count back with the rest, so the first replay is update 1.
+        reducer: a BucketedGradReducer whose bucket copies and RCCL all-reduces are captured with the step (round 4:
         the collectives are issued in the capture-compatible form, see BucketedGradReducer._launch; exercised in a world
         of one in a child process by scripts/rccl_capture_check.py — DESIGN.md section 6 records the outcome)."""
         if reducer is None and dist.is_initialized() and dist.get_world_size() > 1:
@@ -1106,7 +1323,7 @@ class GraphedTrainStep:
                                "to capture with it; with world_size > 1 pass reducer=... or use TrainStep")
         # metrics: the StepMetrics buffer's address is baked into the graph, so replays keep accumulating into it
         self.inner = TrainStep(model, optimizer, reducer, max_norm=max_norm, scaler=scaler, autocast_dtype=autocast_dtype,
-                               metrics=metrics)
+                               metrics=metrics, ema=ema)
         self.opt = optimizer
         if isinstance(optimizer, FusedClipAdamW):
             optimizer.lr_on_device = True          # replays read the learning rate from a device scalar
@@ -1117,7 +1334,8 @@ class GraphedTrainStep:
             if not isinstance(optimizer, FusedClipAdamW):
                 raise ValueError("restore_after_warmup needs FusedClipAdamW (its whole state is a known set of tensors)")
             live = list(model.parameters()) + list(model.buffers()) + optimizer.exp_avg + optimizer.exp_avg_sq + \
-                [optimizer._plan.step_dev] + ([metrics.buf] if metrics is not None else [])
+                [optimizer._plan.step_dev] + ([metrics.buf] if metrics is not None else []) + \
+                ([] if ema is None else ema.state_tensors())
             snap = ([(t, t.detach().clone()) for t in live], torch.cuda.get_rng_state(example_x.device),
                     None if scaler is None or not scaler.is_enabled() else scaler.get_scale())
         side = torch.cuda.Stream()
@@ -1221,7 +1439,8 @@ class SoftMixCollate:
 def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, epochs=15, batch_size=128,
           checkpoint_path=None, num_classes=1000, num_workers=0, collate_fn="mix", log_every=100, max_steps=None,
           destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
-          device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None):
+          device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None,
+          ema=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -1282,7 +1501,13 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     device_metrics=True (GPU, loss kernels switched on — backend.set_loss_kernels / CALM_LOSS_KERNELS=1): the per-step
     `epoch_loss += loss.item()` of cls:97 — a host sync per step whose sum nothing reads — is dropped; the loss kernel
     accumulates loss and dominant-class agreement in a StepMetrics buffer on the device and rank 0 prints one line per
-    epoch from a single read of it.  The log_every lines are unchanged (they synchronise as before)."""
+    epoch from a single read of it.  The log_every lines are unchanged (they synchronise as before).
+
+    ema: a decay (float) or {"decay": ..., "warmup": ...}: a ModelEMA of the model, built after the broadcast of rank 0's
+    parameters — every rank then holds the same average without any communication — and updated behind every optimizer
+    step (not behind one skipped for inf/NaN gradients).  With checkpoint_path, rank 0 also writes
+    `ema.model_state_dict()` beside it as `<stem>_ema<ext>` once per epoch.  The live model is what is returned; the
+    ModelEMA is `model._calm_ema` afterwards (on the CPU with the model)."""
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
     if device_metrics and not (use_gpu and _backend.get_loss_kernels()):
@@ -1309,6 +1534,10 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             raise ValueError("random_resized_crop excludes device_resize and crop: it is the crop and the resize")
     if graph and not (use_gpu and (optimizer == "fused" or isinstance(optimizer, FusedClipAdamW))):
         raise ValueError('graph=True needs use_gpu=True and optimizer="fused" (FusedClipAdamW)')
+    if ema is not None:
+        ema_kw = dict(ema) if isinstance(ema, dict) else {"decay": float(ema)}
+        if not set(ema_kw) <= {"decay", "warmup"} or not 0.0 <= float(ema_kw.get("decay", 0.9999)) < 1.0:
+            raise ValueError(f'train: ema takes a decay in [0, 1) or a dict with "decay" / "warmup", got {ema!r}')
     rank, local_rank, world = init_distributed(use_gpu)
     device = torch.device(f"cuda:{local_rank}" if use_gpu else "cpu")
     if use_gpu:
@@ -1328,6 +1557,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     elif scheduler is False:
         scheduler = None
     sync_module_states(model)
+    ema_obj = ModelEMA(model, **ema_kw) if ema is not None else None
     reducer = BucketedGradReducer(model) if world > 1 else None
     if world > 1:
         sampler = DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=True, seed=2006)       # cls:56
@@ -1350,7 +1580,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     scaler = torch.amp.GradScaler("cuda", enabled=use_gpu)                                                 # cls:64
     metrics = StepMetrics(device) if device_metrics else None
     step = TrainStep(model, optimizer, reducer, max_norm=1.0, scaler=scaler if use_gpu else None,
-                     autocast_dtype=torch.bfloat16 if use_gpu else None, metrics=metrics)
+                     autocast_dtype=torch.bfloat16 if use_gpu else None, metrics=metrics, ema=ema_obj)
     model.train()
     n_steps = 0
     gstep = None
@@ -1382,7 +1612,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                 if graph and gstep is None:
                     gstep = GraphedTrainStep(model, optimizer, x, y, max_norm=1.0, scaler=scaler,
                                              autocast_dtype=torch.bfloat16, reducer=reducer, restore_after_warmup=True,
-                                             metrics=metrics)
+                                             metrics=metrics, ema=ema_obj)
                 if gstep is not None and x.shape == gstep.x.shape and y.shape == gstep.y.shape:
                     loss, y_hat = gstep(x, y)
                 else:
@@ -1405,6 +1635,9 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             if rank == 0 and local_rank == 0 and checkpoint_path:
                 os.makedirs(os.path.dirname(os.path.abspath(checkpoint_path)), exist_ok=True)
                 torch.save(model.state_dict(), checkpoint_path)                                            # cls:105-107
+                if ema_obj is not None:
+                    stem, ext = os.path.splitext(checkpoint_path)
+                    torch.save(ema_obj.model_state_dict(), stem + "_ema" + ext)
             if scheduler is not None:
                 scheduler.step()                                                                           # cls:108-109
             if max_steps is not None and n_steps >= max_steps:
@@ -1418,6 +1651,9 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         if isinstance(optimizer, FusedClipAdamW):
             optimizer.close()
     model = model.to("cpu")                                                                                # cls:112
+    if ema_obj is not None:
+        ema_obj.rebind()                   # the averages follow the parameters to the CPU
+        model._calm_ema = ema_obj
     if destroy_process_group and dist.is_initialized():
         dist.destroy_process_group()
     return model

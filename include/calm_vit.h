@@ -457,6 +457,46 @@ int calm_optim_step(const calm_optim_tensor* tensors_dev, int32_t n_tensors, con
                     void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Exponential moving average of ALL parameters (additions to ABI v7), a launch of its own behind calm_optim_step — the
+ * weight EMA every ImageNet ViT recipe evaluates and checkpoints with (timm's ModelEmaV2 / torch's AveragedModel):
+ *   ema += w * (src - ema),  w = 1 - d,  d = decay (CALM_EMA_CONSTANT) | min(decay, (1 + n) / (10 + n)) (CALM_EMA_WARMUP)
+ * with n = count_dev[0], the number of updates applied so far; d is evaluated in fp32: nf = (float)n,
+ * d = min(decay, (1.0f + nf) / (10.0f + nf)) with a correctly rounded division, w = 1.0f - d.
+ *
+ * entries_dev: table in device memory.  Work items are chunks of calm_ema_chunk_elems() consecutive elements of one
+ * entry: chunk_entry_dev[k] = entry of chunk k, entry.chunk0 = its first chunk (as calm_cast_bf16 / calm_optim_step).
+ * Any 4-byte aligned src / ema; a chunk whose src + i0 and ema + i0 are both 16-byte aligned moves 16-byte vectors.
+ * src and ema of one entry, and the tensors of different entries, do not overlap.
+ *
+ * calm_ema_update — two launches.  The first (one thread) reads n and, when skip_dev (nullable device scalar, e.g.
+ *   calm_optim_step's stats_out + 1) is given and non-zero, writes weight_out = {0, 1} and leaves count_dev alone;
+ *   otherwise it writes weight_out = {w, 0} and count_dev[0] = n + 1.  The second (one workgroup per chunk) returns at
+ *   once when weight_out[1] != 0 — a skipped update stores nothing — and otherwise applies w.  weight_out[2] (device)
+ *   thereby reports the weight the call used.  No atomics, a fixed result per element: equal inputs give bit-identical
+ *   averages on all data-parallel ranks.
+ * calm_ema_swap — exchanges src and ema element for element (bits moved, no arithmetic): evaluation with the average
+ *   while every cached parameter address (optimizer plan, bf16 weight copies, captured graphs) stays valid.
+ * Neither allocates nor synchronises: both capture into a hipGraph.
+ * CALM_E_INVAL, before any launch: a null entries_dev / chunk_entry_dev (and count_dev / weight_out for the update),
+ * n_entries <= 0, n_chunks <= 0, decay outside [0, 1) or NaN, a schedule other than the two below.
+ * ------------------------------------------------------------------------------------- */
+typedef struct calm_ema_entry {      /* 32 bytes */
+    float* src;        /* live parameter */
+    float* ema;        /* its average */
+    int64_t numel;
+    int32_t chunk0;    /* index of this tensor's first chunk */
+    int32_t reserved;  /* 0 */
+} calm_ema_entry;
+#define CALM_EMA_CONSTANT 0
+#define CALM_EMA_WARMUP   1
+int32_t calm_ema_chunk_elems(void);          /* multiple of 4 */
+int calm_ema_update(const calm_ema_entry* entries_dev, int32_t n_entries, const int32_t* chunk_entry_dev,
+                    int32_t n_chunks, float decay, int32_t schedule, int32_t* count_dev,
+                    const float* skip_dev /* device scalar or NULL */, float* weight_out, void* stream);
+int calm_ema_swap(const calm_ema_entry* entries_dev, int32_t n_entries, const int32_t* chunk_entry_dev,
+                  int32_t n_chunks, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Device-side batch collate feeding the path: uint8 images [B,3,H,W] -> normalised fp32 batch with
  * per-sample horizontal flip (flip[b] != 0; NULL = none) and the batch-level CutMix / MixUp of
  * distributed_trainer_cls.py:58-61 (torchvision.transforms.v2 semantics: partner = the batch rolled by one):
