@@ -771,6 +771,20 @@ class HipBackend:
                                                _ptr(dk), _ptr(dv), _ptr(dM), B, Sq, Skv, H, hd, _stream()),
                    "calm_attention_bwd")
 
+    # the same backward split around the mask-MLP backward (ops.LatentMaskAttentionFn): front writes dS and dM, back
+    # takes dR and writes the complete dq, dk, dv — the two dR products ride on its contractions
+    def attn_bwd_fold_preferred(self, Sq, Skv, H, hd):
+        return bool(self.lib.calm_attention_bwd_fold_preferred(Sq, Skv, H, hd))
+
+    def attn_bwd_front(self, v, dout, P, dS, dM, B, Sq, Skv, H, hd):
+        _lib.check(self.lib.calm_attention_bwd_front(_ptr(v), _ptr(dout), _ptr(P), _ptr(dS), _ptr(dM), B, Sq, Skv, H, hd,
+                                                     _stream()), "calm_attention_bwd_front")
+
+    def attn_bwd_back(self, q, k, dout, P, dS, dR, dq, dk, dv, B, Sq, Skv, H, hd):
+        _lib.check(self.lib.calm_attention_bwd_back(_ptr(q), _ptr(k), _ptr(dout), _ptr(P), _ptr(dS), _ptr(dR), _ptr(dq),
+                                                    _ptr(dk), _ptr(dv), B, Sq, Skv, H, hd, _stream()),
+                   "calm_attention_bwd_back")
+
     def attn_fwd_lse(self, q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, lse, B, Sq, Skv, H, hd):
         _lib.check(self.lib.calm_attention_fwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(w1), _ptr(b1), _ptr(s1), _ptr(w2),
                                                    _ptr(b2), _ptr(s2), _ptr(out), _ptr(R), _ptr(hp), _ptr(hg),

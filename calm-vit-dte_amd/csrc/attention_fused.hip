@@ -141,13 +141,16 @@ struct AttGeo {
         const int hdp = 16 * DT, LDV = hdp + 4;                // 4*LDV % 32 == 16
         return {DT, hdp, LDV, SKV * LDV};
     }
-    // dynamic LDS bytes of the three kernels
+    // dynamic LDS bytes of the kernels
     static constexpr size_t fwd_bytes(int hd) {
         const int ph13 = V_OFF + at(hd).stripe;
         return sizeof(float) * (size_t)(ph13 > PH2 ? ph13 : PH2);
     }
     static constexpr size_t bwd_q_bytes(int hd) { return sizeof(float) * (size_t)(V_OFF + at(hd).stripe); }
     static constexpr size_t bwd_kv_bytes(int hd) { return sizeof(float) * (size_t)at(hd).stripe; }
+    // folded route: the front kernel stages no stripe, the dQ kernel nothing but the K_h stripe
+    static constexpr size_t bwd_front_bytes() { return sizeof(float) * (size_t)V_OFF; }
+    static constexpr size_t bwd_dq_bytes(int hd) { return sizeof(float) * (size_t)at(hd).stripe; }
 };
 
 // LEAN (calm_attention_infer): the forward of a model that will run no backward.  R, hp, hg, P and lse are absent — their
@@ -438,7 +441,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
 
 // =====================================================================================================
 // Backward of the attention core, two kernels with the same tiling/staging as the forward and NO cross-wave
-// reductions (the mask-MLP backward and the dR terms stay GEMMs):
+// reductions (the mask-MLP backward stays GEMMs; so do the dR terms, but on the folded route described below):
 //   Q side  (queries on the lanes, one wave = 16 queries, all keys on the accumulator rows)
 //       dP^T[j,i] = sum_d V_h[j,d] dO_h[i,d]          (same loop as QK^T: V in the K role, dO in the Q role)
 //       delta_i   = sum_j P[i,j] dP[i,j]               (in-lane + 2 shuffles)
@@ -448,6 +451,16 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnFwdP p) {
 //   KV side (keys on the lanes, one wave = 16 keys, all queries on the accumulator rows)
 //       dV^T[d,j] = sum_i dO_h[i,d] P[i,j]             (PV block: dO_h stripe, P tiles as B operand)
 //       dK^T[d,j] = scale sum_i Q_h[i,d] dS[i,j]       (PV block: Q_h stripe, dS tiles as B operand)
+// Folded route (calm_attention_bwd_front / _back, stored P): dR, the gradient of the raw logits R = Q_all K_all^T shared
+// by all heads, enters dQ and dK as dQ_all += dR K_all, dK_all += dR^T Q_all — per head the same contractions as above
+// with dR added to the operand:  dQ_h = (scale dS_h + dR) K_h,  dK_h = (scale dS_h + dR)^T Q_h.  dR comes out of the
+// caller's mask-MLP backward, which needs dM, so the backward is split around it into three launches:
+//   front   attn_bwd_q_kernel<.., DQ = false>   dS, dM                       (the Q side without its dQ block)
+//           -- caller: mask-MLP backward, dM -> dR --
+//   back    attn_bwd_kv_kernel<.., FOLD = true>  dV; dK^T = sum_i Q_h fmaf(scale, dS, dR)
+//           attn_bwd_dq_kernel                   dQ^T = sum_j K_h fmaf(scale, dS, dR)^T   (re-reads dS)
+// and the two per-image S x D x S GEMMs of the caller are gone.  No kernel's staging, barriers or loops differ from the
+// two-launch form.
 // =====================================================================================================
 struct AttnBwdP {
     const float* q; const float* k; const float* v; const float* dout;
@@ -459,14 +472,21 @@ struct AttnBwdP {
     float scale;
     const float* Mk;             // [B,Sq,Skv] mask  } row-LSE mode only (attn_bwd_q_kernel<.., true>): P is then
     const float* lse;            // [B,H,Sq]         } scratch that the Q side fills itself before it reads it
+    const float* dR;             // [B,Sq,Skv] gradient of the raw logits R — folded route only (back kernels)
 };
 
 // LSE = true: the forward saved no probabilities.  Each head starts by rebuilding its P rows from q, k, the mask and
 // the row log-sum-exp — S^T = K_h Q_h^T with the forward's staging and MFMA loop, P = exp(scale S + M - lse): no
 // maximum, no sum, no division — and writes them to p.P, where the unchanged body below and the K/V side read them.
 // Only accS is live in that prologue (accD does not exist yet), so the body's register budget is the stored-P one.
-template <int NJ, int NW, bool LSE>
+//
+// DQ = false: the front kernel of the folded route.  dR does not exist yet (it comes out of the mask-MLP backward, which
+// needs this kernel's dM), so dQ is left to attn_bwd_dq_kernel: the K_h stripe staging and the dQ MFMA block are compiled
+// out, q and k are never read and the launch has no stripe in LDS (AttGeo::bwd_front_bytes).  dS and dM go through the
+// same instructions in the same order as with DQ = true and are bit-identical to it.
+template <int NJ, int NW, bool LSE, bool DQ>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
+    static_assert(DQ || !LSE, "the row-LSE prologue reads q and k: it has no front-only form");
     constexpr int NTH = 64 * NW;
     constexpr int NV_K = (NJ + NW - 1) / NW;   // float4 per thread for a [16*NJ x 16] chunk
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -599,7 +619,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
 #pragma unroll 1
             for (int c = 0; c < nchq; ++c) {
                 const int cur = c & 1;
-                s_load(c);
+                if constexpr (DQ) s_load(c);
                 if (c + 1 < nchq) {
                     km_load<NTH>(rk, vh, D, SKV, 16 * (c + 1), hd);
                     km_load<NTH>(rq, doh, D, nq, 16 * (c + 1), hd);
@@ -613,7 +633,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
                             accD[t] = MFMA16(bufK(cur)[(4 * s + g) * LDJ + 16 * t + r16], bq, accD[t]);
                     }
                 }
-                s_store(c);
+                if constexpr (DQ) s_store(c);
                 if (c + 1 < nchq) {
                     km_store<NTH>(rk, bufK(cur ^ 1), LDJ, SKV);
                     km_store<NTH>(rq, bufQ(cur ^ 1), LDQ, nq);
@@ -666,7 +686,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
             }
         }
         // dQ^T[d,i] = scale * sum_j K_h[j,d] dS^T[j,i]
-        if (active) {
+        if (DQ && active) {
             float* qrow = p.dq + ((long)b * p.Sq + iq) * D + h * hd;
 #pragma unroll 1
             for (int d = 0; d < DT; d += 2) {
@@ -694,8 +714,46 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const AttnBwdP p) {
     }
 }
 
-// NI = query tiles (accumulator rows), one wave = 16 keys on the lanes
-template <int NI, int NW>
+// [rows x hd] stripe of one head (row stride D) -> bufV [rows][LDV], four 16-byte loads in flight per thread and trip: as
+// a rolled load -> store loop every trip waited out a full memory round trip (6-8 per stripe, two stripes per head)
+// (the geometry by reference, as the kernels' lambdas captured it: by value the key/value side compiles to one VGPR more)
+template <int NTH>
+__device__ __forceinline__ void stage_stripe(float* const& bufV, const float* src, const int& tid, const int& D,
+                                             const int& hd, const int& v_per_row, const int& v_total, const int& LDV) {
+    constexpr int SB = 4;
+#pragma unroll 1
+    for (int f0 = tid; f0 < v_total; f0 += SB * NTH) {
+        f32x4v val[SB];
+#pragma unroll
+        for (int u = 0; u < SB; ++u) {
+            const int f = f0 + u * NTH;
+            const int row = f / v_per_row, cq = f - row * v_per_row;
+            val[u] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+            if (f < v_total && 4 * cq < hd) val[u] = *reinterpret_cast<const f32x4v*>(src + (long)row * D + 4 * cq);
+        }
+#pragma unroll
+        for (int u = 0; u < SB; ++u) {
+            const int f = f0 + u * NTH;
+            const int row = f / v_per_row, cq = f - row * v_per_row;
+            if (f < v_total) *reinterpret_cast<f32x4v*>(bufV + row * LDV + 4 * cq) = val[u];
+        }
+    }
+}
+
+// NI = query tiles (accumulator rows), one wave = 16 keys on the lanes.
+//
+// FOLD = true (folded route, launched after the mask-MLP backward): dK_h = (scale dS_h + dR)^T Q_h — the dR^T Q product
+// of the caller rides on the contraction this kernel performs anyway.  The operand tile becomes fmaf(scale, dS, dR) and
+// the contraction is stored unscaled.  The dR tile (the dS addressing without the head term) is the same for every head
+// and is held in 4 NI registers across the head loop.  VGPRs / scratch bytes / waves per SIMD of the compiler's resource
+// report (hipcc -Rpass-analysis=kernel-resource-usage), NI = 2, 3, 5, 8, 11, 14:
+//   FOLD = false             70   82  105  141  168  214    scratch 28 at NI = 11    occupancy 5 5 4 3 3 2   (the parent's)
+//   FOLD, dR held            60   68   83  107  131  156    no scratch               occupancy 7 6 5 4 3 3
+//   FOLD, dR reloaded/head   52   56   66   92  116  144    no scratch               occupancy 8 7 7 5 4 3   (tried, not kept)
+// Held: it fits everywhere without scratch and at no fewer waves than the unfolded form, the workgroups per CU are then
+// set by the LDS stripe and the workgroup size (NI >= 8: held and reloaded both give 2, 1, 1), and it saves 4 NI L2 loads
+// per head whose latency nothing in this kernel's serial phases would cover.
+template <int NI, int NW, bool FOLD>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_kv_kernel(const AttnBwdP p) {
     constexpr int NTH = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -717,28 +775,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kv_kernel(const AttnBwdP p) 
     const float* qb = p.q + (long)b * p.Sq * D;
     const float* dob = p.dout + (long)b * p.Sq * D;
 
-    // [Sq x hd] stripe (row stride D) -> bufV, four 16-byte loads in flight per thread and trip: as a rolled
-    // load -> store loop every trip waited out a full memory round trip (6-8 per stripe, two stripes per head)
-    constexpr int SB = 4;
-    auto stage = [&](const float* src) {
-#pragma unroll 1
-        for (int f0 = tid; f0 < v_total; f0 += SB * NTH) {
-            f32x4v val[SB];
-#pragma unroll
-            for (int u = 0; u < SB; ++u) {
-                const int f = f0 + u * NTH;
-                const int row = f / v_per_row, cq = f - row * v_per_row;
-                val[u] = (f32x4v){0.f, 0.f, 0.f, 0.f};
-                if (f < v_total && 4 * cq < hd) val[u] = *reinterpret_cast<const f32x4v*>(src + (long)row * D + 4 * cq);
-            }
-#pragma unroll
-            for (int u = 0; u < SB; ++u) {
-                const int f = f0 + u * NTH;
-                const int row = f / v_per_row, cq = f - row * v_per_row;
-                if (f < v_total) *reinterpret_cast<f32x4v*>(bufV + row * LDV + 4 * cq) = val[u];
-            }
-        }
-    };
+    auto stage = [&](const float* src) { stage_stripe<NTH>(bufV, src, tid, D, hd, v_per_row, v_total, LDV); };
     auto contract = [&](const f32x4v (&X)[NI], float* out_row, float scale) {   // out^T[d,j] = sum_i stripe[i,d] X[i,j]
 #pragma unroll 1
         for (int d = 0; d < DT; d += 2) {
@@ -758,26 +795,131 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kv_kernel(const AttnBwdP p) 
         }
     };
 
-#pragma unroll 1
-    for (int h = 0; h < p.H; ++h) {
-        const long base = ((long)b * p.H + h) * p.Sq * p.Skv + (active ? jk : k0);
-        f32x4v X[NI];
-        // P tiles [i rows, key lanes]: 16 consecutive keys = one 64-byte segment per row
+    // FOLD: the P, dS and dR elements of a lane sit at the same 4 NI offsets from three bases that are uniform over the
+    // workgroup.  The offsets do not depend on the head, and left visible the compiler computes them all ahead of the head
+    // loop and keeps them live across it as 64-bit values — 8 NI registers, which is why the unfolded form sits at its
+    // register ceiling from NI = 11 on.  Here the row index is made opaque at the head of each load phase, so the offsets
+    // are rebuilt per load (two integer operations) and their registers are free again once the load has left.
+    const unsigned col = active ? jk : k0, skv = p.Skv;
+    auto rows = [&]() -> unsigned {
+        unsigned g4 = 4 * g;
+        asm volatile("" : "+v"(g4));
+        return g4;
+    };
+    auto at = [&](const float* __restrict__ base, int t, int r, unsigned g4) -> float {
+        return base[(16 * t + r + g4) * skv + col];
+    };
+    f32x4v dR[FOLD ? NI : 1];
+    if constexpr (FOLD) {
+        const float* __restrict__ dRb = p.dR + (long)b * p.Sq * p.Skv;
+        const unsigned g4 = rows();
 #pragma unroll
         for (int t = 0; t < NI; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) X[t][r] = p.P[base + (long)(16 * t + 4 * g + r) * p.Skv];
+            for (int r = 0; r < 4; ++r) dR[t][r] = at(dRb, t, r, g4);
+    }
+
+#pragma unroll 1
+    for (int h = 0; h < p.H; ++h) {
+        const long base = ((long)b * p.H + h) * p.Sq * p.Skv + (active ? jk : k0);
+        const float* __restrict__ Ph = p.P + ((long)b * p.H + h) * p.Sq * p.Skv;
+        const float* __restrict__ dSh = p.dS + ((long)b * p.H + h) * p.Sq * p.Skv;
+        f32x4v X[NI];
+        // P tiles [i rows, key lanes]: 16 consecutive keys = one 64-byte segment per row
+        unsigned g4 = FOLD ? rows() : 0;
+#pragma unroll
+        for (int t = 0; t < NI; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                X[t][r] = FOLD ? at(Ph, t, r, g4) : p.P[base + (long)(16 * t + 4 * g + r) * p.Skv];
         stage(dob + h * hd);
         __syncthreads();
         if (active) contract(X, p.dv + ((long)b * p.Skv + jk) * D + h * hd, 1.0f);
         __syncthreads();
+        if constexpr (FOLD) g4 = rows();
 #pragma unroll
         for (int t = 0; t < NI; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) X[t][r] = p.dS[base + (long)(16 * t + 4 * g + r) * p.Skv];
+            for (int r = 0; r < 4; ++r)
+                X[t][r] = FOLD ? at(dSh, t, r, g4) : p.dS[base + (long)(16 * t + 4 * g + r) * p.Skv];
         stage(qb + h * hd);
+        if constexpr (FOLD) {
+#pragma unroll
+            for (int t = 0; t < NI; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) X[t][r] = fmaf(p.scale, X[t][r], dR[t][r]);
+        }
         __syncthreads();
-        if (active) contract(X, p.dk + ((long)b * p.Skv + jk) * D + h * hd, p.scale);
+        if (active) contract(X, p.dk + ((long)b * p.Skv + jk) * D + h * hd, FOLD ? 1.0f : p.scale);
+        __syncthreads();
+    }
+}
+
+// dQ of the folded route, launched after the mask-MLP backward: dQ_h = (scale dS_h + dR) K_h — the dR K product of the
+// caller rides on the dQ block that used to close attn_bwd_q_kernel.  Query-tiled exactly like the Q side (one wave = 16
+// queries on the lanes, rows prow + 4g + 16t): the tile's dR rows are loaded once into NJ register quads, each head
+// requests its dS rows (all NJ quads in flight, ahead of the staging), stages the K_h stripe, forms
+// accD = fmaf(scale, dS, dR) and runs the Q side's dQ^T MFMA block; dq is stored without the scale.
+template <int NJ, int NW>
+__global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnBwdP p) {
+    constexpr int NTH = 64 * NW;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    typedef AttGeo<NJ, NW> G;
+    constexpr int SKV = G::SKV, TQ = G::TQ;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, g = lane >> 4;
+    const int b = blockIdx.y;
+    const int q0 = blockIdx.x * TQ;
+    const int nq = min(TQ, p.Sq - q0);
+    const bool active = 16 * wave < nq;
+    const int iq = q0 + 16 * wave + r16;
+    const int D = p.H * p.hd;
+    const int hd = p.hd;
+    const auto gh = G::at(hd);
+    const int DT = gh.DT, hdp = gh.hdp, LDV = gh.LDV;
+    float* bufV = smem;                                         // whole K_h stripe [Skv][LDV]
+    const int v_per_row = hdp >> 2, v_total = SKV * v_per_row;
+    const float* kb = p.k + (long)b * p.Skv * D;
+
+    const float* __restrict__ dRrow = p.dR + ((long)b * p.Sq + (active ? iq : q0)) * p.Skv + 4 * g;
+    f32x4v accR[NJ];
+#pragma unroll
+    for (int t = 0; t < NJ; ++t) accR[t] = *reinterpret_cast<const f32x4v*>(dRrow + 16 * t);
+
+#pragma unroll 1
+    for (int h = 0; h < p.H; ++h) {
+        const long prow = (((long)b * p.H + h) * p.Sq + (active ? iq : q0)) * p.Skv;
+        const float* __restrict__ dSrow = p.dS + prow + 4 * g;
+        f32x4v accD[NJ];
+#pragma unroll
+        for (int t = 0; t < NJ; ++t) accD[t] = *reinterpret_cast<const f32x4v*>(dSrow + 16 * t);
+        __builtin_amdgcn_sched_barrier(0);                      // the requests leave before the staging, not after it
+        stage_stripe<NTH>(bufV, kb + h * hd, tid, D, hd, v_per_row, v_total, LDV);
+#pragma unroll
+        for (int t = 0; t < NJ; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) accD[t][r] = fmaf(p.scale, accD[t][r], accR[t][r]);
+        __syncthreads();
+        // dQ^T[d,i] = sum_j K_h[j,d] (scale dS + dR)^T[j,i]
+        if (active) {
+            float* qrow = p.dq + ((long)b * p.Sq + iq) * D + h * hd;
+#pragma unroll 1
+            for (int d = 0; d < DT; d += 2) {
+                f32x4v accO = {0.f, 0.f, 0.f, 0.f}, accO2 = {0.f, 0.f, 0.f, 0.f};
+                const float* kcol = bufV + 16 * d + r16;
+                const int d2 = (d + 1 < DT) ? 16 : 0;
+#pragma unroll
+                for (int t = 0; t < NJ; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        accO = MFMA16(kcol[(16 * t + 4 * g + r) * LDV], accD[t][r], accO);
+                        accO2 = MFMA16(kcol[(16 * t + 4 * g + r) * LDV + d2], accD[t][r], accO2);
+                    }
+                if (16 * d + 4 * g < hd) *reinterpret_cast<f32x4v*>(qrow + 16 * d + 4 * g) = accO;
+                if (d + 1 < DT && 16 * (d + 1) + 4 * g < hd)
+                    *reinterpret_cast<f32x4v*>(qrow + 16 * (d + 1) + 4 * g) = accO2;
+            }
+        }
         __syncthreads();
     }
 }
@@ -799,9 +941,25 @@ int launch_bwd(const AttnBwdP& p, hipStream_t s) {
     constexpr int NJ = G::NJ, NW = G::NW;
     const int tiles = p.Sq / 16;
     dim3 grid((tiles + NW - 1) / NW, p.B);
-    const int e = launch(&attn_bwd_q_kernel<NJ, NW, LSE>, grid, 64 * NW, G::bwd_q_bytes(p.hd), s, p);
+    const int e = launch(&attn_bwd_q_kernel<NJ, NW, LSE, true>, grid, 64 * NW, G::bwd_q_bytes(p.hd), s, p);
     if (e) return e;
-    return launch(&attn_bwd_kv_kernel<NJ, NW>, grid, 64 * NW, G::bwd_kv_bytes(p.hd), s, p);
+    return launch(&attn_bwd_kv_kernel<NJ, NW, false>, grid, 64 * NW, G::bwd_kv_bytes(p.hd), s, p);
+}
+
+// the folded route: front (dS, dM) — the caller's mask-MLP backward turns dM into dR — back (dV, folded dK, folded dQ)
+template <class G>
+int launch_bwd_front(const AttnBwdP& p, hipStream_t s) {
+    constexpr int NJ = G::NJ, NW = G::NW;
+    dim3 grid((p.Sq / 16 + NW - 1) / NW, p.B);
+    return launch(&attn_bwd_q_kernel<NJ, NW, false, false>, grid, 64 * NW, G::bwd_front_bytes(), s, p);
+}
+template <class G>
+int launch_bwd_back(const AttnBwdP& p, hipStream_t s) {
+    constexpr int NJ = G::NJ, NW = G::NW;
+    dim3 grid((p.Sq / 16 + NW - 1) / NW, p.B);
+    const int e = launch(&attn_bwd_kv_kernel<NJ, NW, true>, grid, 64 * NW, G::bwd_kv_bytes(p.hd), s, p);
+    if (e) return e;
+    return launch(&attn_bwd_dq_kernel<NJ, NW>, grid, 64 * NW, G::bwd_dq_bytes(p.hd), s, p);
 }
 
 template <class G, bool LEAN>
@@ -917,6 +1075,51 @@ int calm_attention_bwd(const float* q, const float* k, const float* v, const flo
     if (B > 65535) return CALM_E_UNSUPP;
     AttnBwdP p{q, k, v, dout, P, dS, dq, dk, dv, dM, B, Sq, Skv, H, hd, 1.0f / sqrtf((float)hd), nullptr, nullptr};
     return attention_bwd_dispatch(p, false, as_stream(stream));
+}
+
+// The folded route (stored P): calm_attention_bwd split around the caller's mask-MLP backward, so that the two dR
+// products ride on the dQ / dK contractions.  front: dS and dM, bit-identical to calm_attention_bwd's.  back, once dR
+// [B,Sq,Skv] exists: dV, dK_h = (dS_h / sqrt(hd) + dR)^T Q_h, dQ_h = (dS_h / sqrt(hd) + dR) K_h — written, no atomics.
+int calm_attention_bwd_front(const float* v, const float* dout, const float* P, float* dS, float* dM, int32_t B,
+                             int32_t Sq, int32_t Skv, int32_t H, int32_t hd, void* stream) {
+    if (!v || !dout || !P || !dS || !dM || B <= 0) return CALM_E_INVAL;
+    if (!calm_attention_fwd_supported(Sq, Skv, H, hd)) return CALM_E_UNSUPP;
+    if (B > 65535) return CALM_E_UNSUPP;
+    AttnBwdP p{nullptr, nullptr, v, dout, P, dS, nullptr, nullptr, nullptr, dM, B, Sq, Skv, H, hd,
+               1.0f / sqrtf((float)hd), nullptr, nullptr, nullptr};
+    hipStream_t s = as_stream(stream);
+    return with_geo(Skv / 16, [&](auto g) -> int { return launch_bwd_front<decltype(g)>(p, s); });
+}
+
+int calm_attention_bwd_back(const float* q, const float* k, const float* dout, const float* P, const float* dS,
+                            const float* dR, float* dq, float* dk, float* dv, int32_t B, int32_t Sq, int32_t Skv,
+                            int32_t H, int32_t hd, void* stream) {
+    if (!q || !k || !dout || !P || !dS || !dR || !dq || !dk || !dv || B <= 0) return CALM_E_INVAL;
+    if (!calm_attention_fwd_supported(Sq, Skv, H, hd)) return CALM_E_UNSUPP;
+    if (B > 65535) return CALM_E_UNSUPP;
+    AttnBwdP p{q, k, nullptr, dout, P, const_cast<float*>(dS), dq, dk, dv, nullptr, B, Sq, Skv, H, hd,
+               1.0f / sqrtf((float)hd), nullptr, nullptr, dR};
+    hipStream_t s = as_stream(stream);
+    return with_geo(Skv / 16, [&](auto g) -> int { return launch_bwd_back<decltype(g)>(p, s); });
+}
+
+// Measured on MI355X (scripts/ab_attn_bwd.py, same process, B = 256; ms per attention block, core + the two dR products,
+// the mask-MLP backward between front and back left out as common to both):
+//                        today's route + dR GEMMs     front + back    ratio
+//   S=224 H=6  hd=112    1.467 (GEMM composition)     1.305           1.12x
+//   S=176 H=6  hd=88     0.882 (fused)                0.667           1.32x
+//   S=128 H=6  hd=64     0.343 (fused)                0.273           1.26x
+//   S=80  H=6  hd=40     0.168 (fused)                0.127           1.33x
+//   S=224 H=12 hd=56     1.935 (fused)                1.644           1.18x
+//   S=176 H=12 hd=44     1.127 (fused)                0.921           1.22x
+//   S=128 H=12 hd=32     0.414 (fused)                0.357           1.16x
+//   S=80  H=12 hd=20     0.229 (fused)                0.184           1.25x
+// The folded route wins at every measured stage, hd 112 included (there the fused pair + GEMMs takes 1.705), so it is
+// preferred wherever the kernels exist.  The key-side-only fold (today's Q side with dQ, folded KV kernel, dR K left a
+// GEMM) was not built: even credited with the whole dR^T Q GEMM and no cost at all it would take 1.46 / 0.77 / 0.30 /
+// 0.14 ms at the Small-224 stages — behind front + back everywhere.
+int calm_attention_bwd_fold_preferred(int32_t Sq, int32_t Skv, int32_t H, int32_t hd) {
+    return calm_attention_fwd_supported(Sq, Skv, H, hd) ? 1 : 0;
 }
 
 // Row-LSE backward: the caller's scratch holds the two [B,H,Sq,Skv] planes the two launches hand to each other — the

@@ -626,11 +626,13 @@ class RopeFn(Function):
         return d_content, d_xr, d_if, None, None
 
 
-def _attn_mask_bwd(be, defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2, w1o=None, w2o=None):
+def _attn_mask_bwd(be, defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2, w1o=None, w2o=None,
+                   fold=False):
     """What follows the attention core in every attention backward (stored-P, row-LSE, bf16): the mask-MLP backward
     from dM [B*Sq,Skv] and the two dR products, accumulated into dq / dk.  w1o / w2o are the operands of the two
     input-gradient GEMMs (the bf16 pipeline passes its bf16 weight copies); dR takes the dtype of q.
-    Returns dW1, db1, dW2, db2."""
+    Returns dW1, db1, dW2, db2 — and, with fold=True, dR [B,Sq,Skv] in place of the two products (dq / dk are then not
+    touched and may be None: the caller's back kernels fold dR into the per-head contractions)."""
     w1o, w2o = w1 if w1o is None else w1o, w2 if w2o is None else w2o
     B, Sq, D = q.shape
     Skv = k.shape[1]
@@ -648,6 +650,8 @@ def _attn_mask_bwd(be, defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u
     db1 = _colsum(be, dhp)
     dR = torch.empty(B, Sq, Skv, dtype=dt, device=dev)
     _lin_dgrad(be, dhp, w1o, s1, dR.view(B * Sq, Skv))
+    if fold:
+        return dW1, db1, dW2, db2, dR
     # dQ_all += dR K_all ; dK_all += dR^T Q_all
     be.gemm(dR, k, dq, Sq, D, Skv, (Skv, 1, Sq * Skv, 0), (1, D, Skv * D, 0), (D, Sq * D, 0), batch=(B, 1),
             accumulate=True)
@@ -713,6 +717,14 @@ class LatentMaskAttentionFn(Function):
         dP = torch.empty_like(P)
         dv, dq, dk = torch.empty_like(v), torch.empty_like(q), torch.empty_like(k)
         dM = torch.empty(B * Sq, Skv, dtype=dt, device=dev)
+        if hasattr(be, "attn_bwd_back") and be.attn_bwd_fold_preferred(Sq, Skv, H, hd):
+            # folded route: front (dS, dM) -> mask-MLP backward (dM -> dR) -> back (dV, and dQ / dK with the dR products
+            # folded into their per-head contractions); taken where it is measured faster than what follows
+            be.attn_bwd_front(v, dout, P, dP, dM, B, Sq, Skv, H, hd)
+            dW1, db1, dW2, db2, dR = _attn_mask_bwd(be, ctx.defer, dM, q, k, None, None, R, hp, hg, w1, w2, u1, v1, s1,
+                                                    u2, v2, s2, fold=True)
+            be.attn_bwd_back(q, k, dout, P, dP, dR, dq, dk, dv, B, Sq, Skv, H, hd)
+            return dq, dk, dv, dW1, db1, dW2, db2, None, None, None, None, None, None, None
         if be.attn_bwd_preferred(Sq, Skv, H, hd):
             # fused core: dP, softmax backward, head-sum of dS and the four per-head products in two launches
             # (taken where it is measured faster than the composition below: head dims <= 64)

@@ -266,6 +266,24 @@ int calm_attention_bwd(const float* q, const float* k, const float* v, const flo
                        float* dq, float* dk, float* dv, float* dM, int32_t B, int32_t Sq, int32_t Skv, int32_t H,
                        int32_t hd, void* stream);
 
+/* The same backward split around the caller's mask-MLP backward, so that the two dR products (the gradient of
+ * R = Q_all K_all^T, Vi_Tools:288-289: dQ_all += dR K_all, dK_all += dR^T Q_all) ride on the per-head contractions
+ * instead of being calm_gemm calls (additions to ABI v7 — no existing signature or struct changes, so the version
+ * number stays).  Same shapes, same argument checks and return codes as calm_attention_bwd.
+ *   calm_attention_bwd_front: the query side without dQ.  Writes dS and dM, bit-identical to calm_attention_bwd's;
+ *     reads neither q nor k.  The caller then runs the mask-MLP backward from dM, which yields dR [B,Sq,Skv].
+ *   calm_attention_bwd_back: dV_h = P^T dO_h; dK_h = (dS_h / sqrt(hd) + dR)^T Q_h; dQ_h = (dS_h / sqrt(hd) + dR) K_h.
+ *     dq, dk, dv are written (not accumulated) and are complete: nothing is left for the caller to add.  No atomics:
+ *     results repeat bit for bit.  dS is the tensor calm_attention_bwd_front wrote.
+ *   calm_attention_bwd_fold_preferred: supported AND front + back measured faster than the caller's present route
+ *     (calm_attention_bwd or the calm_gemm composition) followed by the two dR products. */
+int calm_attention_bwd_front(const float* v, const float* dout, const float* P, float* dS, float* dM, int32_t B,
+                             int32_t Sq, int32_t Skv, int32_t H, int32_t hd, void* stream);
+int calm_attention_bwd_back(const float* q, const float* k, const float* dout, const float* P, const float* dS,
+                            const float* dR, float* dq, float* dk, float* dv, int32_t B, int32_t Sq, int32_t Skv,
+                            int32_t H, int32_t hd, void* stream);
+int calm_attention_bwd_fold_preferred(int32_t Sq, int32_t Skv, int32_t H, int32_t hd);
+
 /* Row-LSE mode of the fp32 attention (Vi_Tools:288-299; additions to ABI v7 — no existing signature or struct
  * changes, so the version number stays): train without the saved probabilities.
  *   calm_attention_fwd_lse: calm_attention_fwd with P left out and lse [B,H,Sq] written instead,
