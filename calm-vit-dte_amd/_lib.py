@@ -54,6 +54,23 @@ RED_LAYERNORM_BWD, RED_ROPE_BWD, RED_LATENT_FWD, RED_COLSUM, RED_CNN_BWD = range
 RED_SOFT_CE, RED_HUBER = 5, 6                      # the loss entry points (csrc/loss.hip)
 
 
+class ReduceShape(C.Structure):
+    """struct calm_reduce_shape (48 bytes): the rows of partials a calm_part_* entry point wrote."""
+    _fields_ = [("G", _i32), ("n", _i32), ("stride", _i32), ("nseg", _i32), ("begin", _i32 * 7), ("reserved", _i32)]
+
+
+class ReduceEntry(C.Structure):
+    """struct calm_reduce_entry (104 bytes, one per reduction of calm_reduce_partials_batch)."""
+    _fields_ = [("partials", _p), ("G", _i32), ("n", _i32), ("stride", _i32), ("nseg", _i32), ("out", _p * 6),
+                ("begin", _i32 * 7), ("reserved", _i32)]
+
+
+class SnBwdEntry(C.Structure):
+    """struct calm_sn_bwd_entry (80 bytes, one per layer of calm_sn_weight_bwd_batch)."""
+    _fields_ = [("G", _p), ("w_orig", _p), ("u", _p), ("v", _p), ("sigma", _p), ("ls", _p), ("d_w_orig", _p), ("d_ls", _p),
+                ("rowdot", _p), ("rows", _i32), ("cols", _i32)]
+
+
 class OptimTensor(C.Structure):
     """struct calm_optim_tensor (64 bytes)."""
     _fields_ = [("param", _p), ("grad", _p), ("exp_avg", _p), ("exp_avg_sq", _p), ("sn_u", _p), ("sn_v", _p),
@@ -124,6 +141,15 @@ SIGNATURES = {
     "calm_gemm_set_option": (C.c_int, [_i32, _i32]),
     "calm_gemm_describe": (_i32, [C.POINTER(GemmArgs), C.POINTER(GemmPlan)]),
     "calm_reduce_scratch_floats": (_i64, [_i32, _i64, _i32]),
+    "calm_reduce_batch_max": (_i32, []),
+    "calm_reduce_partials_batch": (_i32, [C.POINTER(ReduceEntry), _i32, _p]),
+    "calm_part_layernorm_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p, C.POINTER(ReduceShape), _p]),
+    "calm_part_rope_bwd": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p,
+                                  C.POINTER(ReduceShape), _p]),
+    "calm_part_colsum": (_i32, [_p, _i64, _i32, _i32, _p, C.POINTER(ReduceShape), _p]),
+    "calm_part_cnn_residual_bwd": (_i32, [_p] * 12 + [_i32, _i32, _i32, _i32, _p, C.POINTER(ReduceShape), _p]),
+    "calm_sn_bwd_batch_max": (_i32, []),
+    "calm_sn_weight_bwd_batch": (_i32, [C.POINTER(SnBwdEntry), _i32, _p]),
     "calm_layernorm_fwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i32, _f32, _i32, _p]),
     "calm_layernorm_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p, _p]),
     "calm_cast_chunk_elems": (_i32, []),

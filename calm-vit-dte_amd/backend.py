@@ -340,6 +340,31 @@ class HipBackend:
             self._scratch_bufs[key] = buf
         return buf.data_ptr()
 
+    def _own_partials(self, op, rows, cols, device):
+        """Scratch of one DEFERRED reduction (the *_part methods): a buffer of the call's own, because its rows of partials
+        stay unread until reduce_partials_batch runs at the end of the backward — the shared buffer of _partials would be
+        overwritten by the next call."""
+        need = self._scratch_need.get((op, rows, cols))
+        if need is None:
+            need = self._scratch_need[(op, rows, cols)] = int(self.lib.calm_reduce_scratch_floats(op, rows, cols))
+        return torch.empty(need, dtype=torch.float32, device=device)
+
+    def reduce_partials_batch(self, items):
+        """items: [(partials, ReduceShape, [output tensors, one per segment])] as the *_part methods return them — every
+        reduction of the list in ceil(len / calm_reduce_batch_max()) launches, each bit-identical with the single form."""
+        ent = (_lib.ReduceEntry * len(items))()
+        for e, (part, shape, outs) in zip(ent, items):
+            if len(outs) != shape.nseg:
+                raise ValueError("reduce_partials_batch: one output per segment expected")
+            e.partials, e.G, e.n, e.stride, e.nseg = _ptr(part), shape.G, shape.n, shape.stride, shape.nseg
+            for k, o in enumerate(outs):
+                if o.numel() != shape.begin[k + 1] - shape.begin[k] or not o.is_contiguous():
+                    raise ValueError("reduce_partials_batch: output size does not match its segment")
+                e.out[k] = _ptr(o)
+            for k in range(shape.nseg + 1):
+                e.begin[k] = shape.begin[k]
+        _lib.check(self.lib.calm_reduce_partials_batch(ent, len(items), _stream()), "calm_reduce_partials_batch")
+
     # ---- GEMM -------------------------------------------------------------------------
     GEMM_OPT_PIPE, GEMM_OPT_PIPE32, GEMM_OPT_DETERMINISTIC = 0, 1, 2
 
@@ -680,6 +705,14 @@ class HipBackend:
                                                self._partials(_lib.RED_LAYERNORM_BWD, rows, D, x.device), _stream()),
                    "calm_layernorm_bwd")
 
+    def layernorm_bwd_part(self, dy, x, w, mean, rstd, dx, rows, D, dx_add=None):
+        """layernorm_bwd without the sum over workgroups: -> (partials, shape) for reduce_partials_batch."""
+        part, shape = self._own_partials(_lib.RED_LAYERNORM_BWD, rows, D, x.device), _lib.ReduceShape()
+        _lib.check(self.lib.calm_part_layernorm_bwd(_ptr(dy, bf16_ok=True), _ptr(x), _ptr(w), _ptr(mean), _ptr(rstd),
+                                                    _ptr(dx), _ptr(dx_add, True), rows, D, _st(dy), _ptr(part),
+                                                    C.byref(shape), _stream()), "calm_part_layernorm_bwd")
+        return part, shape
+
     # ---- bf16 weight copies --------------------------------------------------------------
     def cast_plan(self, pairs):
         """pairs: [(fp32 source tensor, bf16 destination tensor of the same numel)] -> plan for cast_run."""
@@ -739,6 +772,15 @@ class HipBackend:
                                           B, S, H, dc, dr, _st(d_out), _st(xr), _st(d_content), _st(d_xr),
                                           self._partials(_lib.RED_ROPE_BWD, B * S * H, dr, xr.device), _stream()),
                    "calm_rope_bwd")
+
+    def rope_bwd_part(self, d_out, xr, table, d_content, d_xr, B, S, H, dc, dr):
+        """rope_bwd without the sum over workgroups: -> (partials, shape) for reduce_partials_batch."""
+        part, shape = self._own_partials(_lib.RED_ROPE_BWD, B * S * H, dr, xr.device), _lib.ReduceShape()
+        _lib.check(self.lib.calm_part_rope_bwd(_ptr(d_out, bf16_ok=True), _ptr(xr, bf16_ok=True), _ptr(table),
+                                               _ptr(d_content, True, bf16_ok=True), _ptr(d_xr, bf16_ok=True),
+                                               B, S, H, dc, dr, _st(d_out), _st(xr), _st(d_content), _st(d_xr),
+                                               _ptr(part), C.byref(shape), _stream()), "calm_part_rope_bwd")
+        return part, shape
 
     # ---- softmax ----------------------------------------------------------------------
     def softmax_fwd(self, x, rows, cols):
@@ -870,6 +912,19 @@ class HipBackend:
                                                _ptr(dW), _ptr(d_ls, True), rows, cols, _ptr(scratch), _stream()),
                    "calm_sn_weight_bwd")
 
+    def sn_weight_bwd_batch(self, items):
+        """items: [(G, w, u, v, sigma, ls, dW, d_ls, rows, cols)], the arguments of sn_weight_bwd — all of them in two
+        launches per calm_sn_bwd_batch_max() layers, each layer bit-identical with the single form."""
+        rowdot = torch.empty(sum(it[8] for it in items), dtype=torch.float32, device=items[0][0].device)
+        ent = (_lib.SnBwdEntry * len(items))()
+        off = 0
+        for e, (G, w, u, v, sigma, ls, dW, d_ls, rows, cols) in zip(ent, items):
+            e.G, e.w_orig, e.u, e.v, e.sigma, e.ls = _ptr(G), _ptr(w), _ptr(u), _ptr(v), _ptr(sigma), _ptr(ls, True)
+            e.d_w_orig, e.d_ls, e.rowdot = _ptr(dW), _ptr(d_ls, True), rowdot.data_ptr() + 4 * off
+            e.rows, e.cols = rows, cols
+            off += rows
+        _lib.check(self.lib.calm_sn_weight_bwd_batch(ent, len(items), _stream()), "calm_sn_weight_bwd_batch")
+
     # ---- tokenisation / conv ----------------------------------------------------------
     def image_to_rows(self, img, rows, B, S):
         _lib.check(self.lib.calm_image_to_rows(_ptr(img), _ptr(rows), B, S, _stream()), "calm_image_to_rows")
@@ -902,6 +957,15 @@ class HipBackend:
                                                   B, S, hidden, int(residual),
                                                   self._partials(_lib.RED_CNN_BWD, B, S, dy.device), _stream()),
                    "calm_cnn_residual_bwd")
+
+    def cnn_bwd_part(self, dy, x, w0, s0, b0, w2, s2, b2, w4, s4, b4, dx, B, S, hidden, residual=True):
+        """cnn_bwd without the sum over workgroups: -> (partials, shape), six segments g0 | gb0 | g2 | gb2 | g4 | gb4."""
+        part, shape = self._own_partials(_lib.RED_CNN_BWD, B, S, dy.device), _lib.ReduceShape()
+        _lib.check(self.lib.calm_part_cnn_residual_bwd(_ptr(dy), _ptr(x), _ptr(w0), _ptr(s0), _ptr(b0), _ptr(w2),
+                                                       _ptr(s2), _ptr(b2), _ptr(w4), _ptr(s4), _ptr(b4), _ptr(dx),
+                                                       B, S, hidden, int(residual), _ptr(part), C.byref(shape),
+                                                       _stream()), "calm_part_cnn_residual_bwd")
+        return part, shape
 
     # ---- loss end of the step (csrc/loss.hip) -------------------------------------------
     def soft_ce_fwd(self, logits, targets, row_stats, loss, metrics, B, C):
@@ -954,6 +1018,13 @@ class HipBackend:
     def colsum(self, x, out, rows, cols):
         _lib.check(self.lib.calm_colsum(_ptr(x, bf16_ok=True), _ptr(out), rows, cols, _st(x),
                                         self._partials(_lib.RED_COLSUM, rows, cols, x.device), _stream()), "calm_colsum")
+
+    def colsum_part(self, x, rows, cols):
+        """colsum without the sum over workgroups: -> (partials, shape) for reduce_partials_batch."""
+        part, shape = self._own_partials(_lib.RED_COLSUM, rows, cols, x.device), _lib.ReduceShape()
+        _lib.check(self.lib.calm_part_colsum(_ptr(x, bf16_ok=True), rows, cols, _st(x), _ptr(part), C.byref(shape),
+                                             _stream()), "calm_part_colsum")
+        return part, shape
 
     def row_scale(self, x, s, out, rows, cols):
         _lib.check(self.lib.calm_row_scale(_ptr(x), _ptr(s), _ptr(out, bf16_ok=True), rows, cols, _st(out), _stream()),

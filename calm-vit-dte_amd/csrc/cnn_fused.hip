@@ -355,27 +355,56 @@ int calm_cnn_residual_fwd(const float* x, const float* w0, const float* s0, cons
     return calm_launch(cnn_fwd_kernel, grid, FW_NT, 0, stream, x, W, out, B, S, tps, n_tiles, residual ? 1.f : 0.f);
 }
 
+// The first launch of the CNN tail's backward: dx, and one row of CNN_PART_N partial weight gradients per workgroup
+static int cnn_bwd_launch(const float* dy, const float* x, const float* w0, const float* s0, const float* b0,
+                          const float* w2, const float* s2, const float* b2, const float* w4, const float* s4,
+                          const float* b4, float* dx, int32_t B, int32_t S, int32_t hidden, int32_t residual,
+                          float* partials, int* g_out, void* stream) {
+    if (!dy || !x || !w0 || !s0 || !b0 || !w2 || !s2 || !b2 || !w4 || !s4 || !b4 || !dx || !partials || B <= 0 || S <= 0)
+        return CALM_E_INVAL;
+    if (hidden != CH) return CALM_E_UNSUPP;
+    const int tps = (S + T - 1) / T;
+    const long n_tiles = (long)B * tps * tps;
+    const int grid = *g_out = (int)(n_tiles < CNN_BWD_MAX_GRID ? n_tiles : CNN_BWD_MAX_GRID);
+    CnnW W{w0, s0, b0, w2, s2, b2, w4, s4, b4};
+    return calm_launch(cnn_bwd_kernel, grid, BW_NT, 0, stream, dy, x, W, dx, partials, B, S, tps, n_tiles,
+                       residual ? 1.f : 0.f);
+}
+// columns of a partial row: g0 | gb0 | g2 | gb2 | g4 | gb4
+static void cnn_part_begin(int* begin) {
+    begin[0] = 0; begin[1] = 3 * CH; begin[2] = 4 * CH; begin[3] = 13 * CH; begin[4] = 14 * CH; begin[5] = 17 * CH;
+    begin[6] = CNN_PART_N;
+}
+
 int calm_cnn_residual_bwd(const float* dy, const float* x, const float* w0, const float* s0, const float* b0,
                           const float* w2, const float* s2, const float* b2, const float* w4, const float* s4,
                           const float* b4, float* dx, float* g0, float* gb0, float* g2, float* gb2, float* g4,
                           float* gb4, int32_t B, int32_t S, int32_t hidden, int32_t residual, float* partials,
                           void* stream) {
-    if (!dy || !x || !w0 || !s0 || !b0 || !w2 || !s2 || !b2 || !w4 || !s4 || !b4 || !dx || !g0 || !gb0 || !g2 ||
-        !gb2 || !g4 || !gb4 || !partials || B <= 0 || S <= 0)
-        return CALM_E_INVAL;
-    if (hidden != CH) return CALM_E_UNSUPP;
-    const int tps = (S + T - 1) / T;
-    const long n_tiles = (long)B * tps * tps;
-    const int grid = (int)(n_tiles < CNN_BWD_MAX_GRID ? n_tiles : CNN_BWD_MAX_GRID);
-    CnnW W{w0, s0, b0, w2, s2, b2, w4, s4, b4};
-    if (int e = calm_launch(cnn_bwd_kernel, grid, BW_NT, 0, stream, dy, x, W, dx, partials, B, S, tps, n_tiles,
-                            residual ? 1.f : 0.f))
+    if (!g0 || !gb0 || !g2 || !gb2 || !g4 || !gb4) return CALM_E_INVAL;
+    int grid = 0;
+    if (int e = cnn_bwd_launch(dy, x, w0, s0, b0, w2, s2, b2, w4, s4, b4, dx, B, S, hidden, residual, partials, &grid, stream))
         return e;
     CalmReduceDst d{};
     d.out[0] = g0; d.out[1] = gb0; d.out[2] = g2; d.out[3] = gb2; d.out[4] = g4; d.out[5] = gb4;
-    d.begin[0] = 0; d.begin[1] = 3 * CH; d.begin[2] = 4 * CH; d.begin[3] = 13 * CH; d.begin[4] = 14 * CH;
-    d.begin[5] = 17 * CH; d.begin[6] = CNN_PART_N; d.nseg = 6;
+    cnn_part_begin(d.begin);
+    d.nseg = 6;
     return calm_reduce_partials(partials, grid, CNN_PART_N, CNN_PART_STRIDE, d, stream);
+}
+
+int calm_part_cnn_residual_bwd(const float* dy, const float* x, const float* w0, const float* s0, const float* b0,
+                               const float* w2, const float* s2, const float* b2, const float* w4, const float* s4,
+                               const float* b4, float* dx, int32_t B, int32_t S, int32_t hidden, int32_t residual,
+                               float* partials, calm_reduce_shape* shape, void* stream) {
+    if (!shape) return CALM_E_INVAL;
+    int grid = 0;
+    if (int e = cnn_bwd_launch(dy, x, w0, s0, b0, w2, s2, b2, w4, s4, b4, dx, B, S, hidden, residual, partials, &grid, stream))
+        return e;
+    calm_reduce_shape s{};
+    s.G = grid; s.n = CNN_PART_N; s.stride = CNN_PART_STRIDE; s.nseg = 6;
+    cnn_part_begin(s.begin);
+    *shape = s;
+    return 0;
 }
 
 }  // extern "C"

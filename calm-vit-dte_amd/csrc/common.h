@@ -123,15 +123,16 @@ struct CalmReduceDst {
     int nseg;
 };
 #define CALM_RED_THREADS 1024
-static __global__ __launch_bounds__(CALM_RED_THREADS) void calm_reduce_partials_kernel(const float* __restrict__ part, int G,
-                                                                                      int n, int stride,
-                                                                                      const CalmReduceDst dst) {
+// One workgroup's share of a reduction: the 64 columns of column block `cb`.  `dst` is anything with out[] / begin[] / nseg
+// (CalmReduceDst, a calm_reduce_entry of the batched form): both kernels below run exactly these additions in this order.
+template <class Dst>
+__device__ __forceinline__ void calm_reduce_partials_block(const float* __restrict__ part, int G, int n, int stride,
+                                                           const Dst& dst, int cb, float (*red)[64]) {
     // 16 row lanes (waves) x 64 columns; a row lane owns g = rg, rg + 16, ... with FOUR running sums (g mod 64 picks the
     // sum), i.e. four loads in flight per thread: the first form of this kernel (4 row lanes x 2 sums, 256 threads) took
     // 19.5 us per call on average — G / 8 dependent L2 round trips — and, at 173 calls per step, 3.4 ms of the step
-    __shared__ float red[CALM_RED_THREADS / 64][64];
     const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + lane;
+    const int c = cb * 64 + lane;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     if (c < n) {
         const float* p = part + c;
@@ -157,6 +158,12 @@ static __global__ __launch_bounds__(CALM_RED_THREADS) void calm_reduce_partials_
         while (k + 1 < dst.nseg && c >= dst.begin[k + 1]) ++k;
         dst.out[k][c - dst.begin[k]] += (t[0] + t[1]) + (t[2] + t[3]);
     }
+}
+static __global__ __launch_bounds__(CALM_RED_THREADS) void calm_reduce_partials_kernel(const float* __restrict__ part, int G,
+                                                                                      int n, int stride,
+                                                                                      const CalmReduceDst dst) {
+    __shared__ float red[CALM_RED_THREADS / 64][64];
+    calm_reduce_partials_block(part, G, n, stride, dst, blockIdx.x, red);
 }
 // G rows of n partials, `stride` floats apart, into the outputs of dst / into one output of n floats (rows packed)
 static inline int calm_reduce_partials(const float* part, int G, int n, int stride, const CalmReduceDst& dst, void* stream) {

@@ -859,6 +859,31 @@ int colsum_grid(int64_t rows, int cols, bool vec, int* tx_out) {
     return (int)(g < 1 ? 1 : g > COLSUM_MAX_GRID ? COLSUM_MAX_GRID : g);
 }
 
+// ---- calm_reduce_partials_batch: the column blocks of many reductions as one grid ----------------------------------------
+// Entries and the prefix of their block counts travel by value in the kernel arguments; RED_BATCH_MAX keeps the struct
+// inside HIP's 4 KB of kernel arguments.  A workgroup finds its entry by walking the prefix (uniform, scalar loads) and
+// runs calm_reduce_partials_block, the body of the single-entry kernel.
+constexpr int RED_BATCH_MAX = 32;
+struct ReduceBatch {
+    calm_reduce_entry e[RED_BATCH_MAX];
+    int block0[RED_BATCH_MAX + 1];        // first workgroup of entry k (block0[count] = the grid)
+    int count;
+};
+static_assert(sizeof(ReduceBatch) <= 3584, "kernel arguments: 4 KB with the hidden ones");
+__global__ __launch_bounds__(CALM_RED_THREADS) void reduce_partials_batch_kernel(const ReduceBatch b) {
+    __shared__ float red[CALM_RED_THREADS / 64][64];
+    int k = 0;
+    while (k + 1 < b.count && (int)blockIdx.x >= b.block0[k + 1]) ++k;
+    const calm_reduce_entry& e = b.e[k];
+    calm_reduce_partials_block(e.partials, e.G, e.n, e.stride, e, (int)blockIdx.x - b.block0[k], red);
+}
+
+calm_reduce_shape reduce_shape_1(int G, int n) {
+    calm_reduce_shape s{};
+    s.G = G; s.n = n; s.stride = n; s.nseg = 1; s.begin[1] = n;
+    return s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -875,10 +900,11 @@ int calm_layernorm_fwd(const float* x, const float* w, void* y, float* mean, flo
     return calm_launch(kernel, grid_for(rows, NT / 64), NT, 0, stream, x, w, y, mean, rstd, rows, D, eps);
 }
 
-int calm_layernorm_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
-                       float* dx, float* dw, const float* dx_add, int64_t rows, int32_t D, int32_t dy_type,
-                       float* partials, void* stream) {
-    if (!dy || !x || !w || !mean || !rstd || !dx || !dw || !partials || rows <= 0 || D <= 0) return CALM_E_INVAL;
+// The first launch of the LayerNorm backward: dx, and one row of D partial dw sums per workgroup (*g_out of them)
+static int ln_bwd_launch(const void* dy, const float* x, const float* w, const float* mean, const float* rstd, float* dx,
+                         const float* dx_add, int64_t rows, int32_t D, int32_t dy_type, float* partials, int* g_out,
+                         void* stream) {
+    if (!dy || !x || !w || !mean || !rstd || !dx || !partials || rows <= 0 || D <= 0) return CALM_E_INVAL;
     if (!st_ok(dy_type)) return CALM_E_INVAL;
     if (D > 64 * LN_MAXC) return CALM_E_UNSUPP;
     const int nv = ln_vec_nv(D, x, dy, dx, w, dx_add);
@@ -886,9 +912,27 @@ int calm_layernorm_bwd(const void* dy, const float* x, const float* w, const flo
         constexpr bool G16 = decltype(g16)::value;
         return nv ? with_ln_nv(nv, [](auto n) { return &ln_bwd_vec_kernel<decltype(n)::value, G16>; }) : &ln_bwd_kernel<G16>;
     });
-    const int g = ln_bwd_grid(rows);
-    if (int e = calm_launch(kernel, g, NT, 0, stream, dy, x, w, mean, rstd, dx, partials, dx_add, rows, D)) return e;
+    *g_out = ln_bwd_grid(rows);
+    return calm_launch(kernel, *g_out, NT, 0, stream, dy, x, w, mean, rstd, dx, partials, dx_add, rows, D);
+}
+
+int calm_layernorm_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
+                       float* dx, float* dw, const float* dx_add, int64_t rows, int32_t D, int32_t dy_type,
+                       float* partials, void* stream) {
+    if (!dw) return CALM_E_INVAL;
+    int g = 0;
+    if (int e = ln_bwd_launch(dy, x, w, mean, rstd, dx, dx_add, rows, D, dy_type, partials, &g, stream)) return e;
     return calm_reduce_partials(partials, g, D, dw, stream);
+}
+
+int calm_part_layernorm_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
+                            float* dx, const float* dx_add, int64_t rows, int32_t D, int32_t dy_type, float* partials,
+                            calm_reduce_shape* shape, void* stream) {
+    if (!shape) return CALM_E_INVAL;
+    int g = 0;
+    if (int e = ln_bwd_launch(dy, x, w, mean, rstd, dx, dx_add, rows, D, dy_type, partials, &g, stream)) return e;
+    *shape = reduce_shape_1(g, D);
+    return 0;
 }
 
 int calm_rope_fwd(const void* content, const void* xr, const float* inv_freq, float* table, void* out, int32_t B,
@@ -910,11 +954,11 @@ int calm_rope_fwd(const void* content, const void* xr, const float* inv_freq, fl
                        p.nrows, S, H, dc, dr, content_type, xr_type, out_type);
 }
 
-int calm_rope_bwd(const void* d_out, const void* xr, const float* table, void* d_content, void* d_xr,
-                  float* d_inv_freq, int32_t B, int32_t S, int32_t H, int32_t dc, int32_t dr, int32_t dout_type,
-                  int32_t xr_type, int32_t dcontent_type, int32_t dxr_type, float* partials, void* stream) {
-    if (!d_out || !xr || !table || !d_xr || !d_inv_freq || !partials || B <= 0 || S <= 0 || H <= 0 || dc < 0 ||
-        dr <= 0 || (dr & 1))
+// The first launch of the RoPE backward: d_content / d_xr, and one row of dr/2 partial angle gradients per workgroup
+static int rope_bwd_launch(const void* d_out, const void* xr, const float* table, void* d_content, void* d_xr, int32_t B,
+                           int32_t S, int32_t H, int32_t dc, int32_t dr, int32_t dout_type, int32_t xr_type,
+                           int32_t dcontent_type, int32_t dxr_type, float* partials, int* g_out, void* stream) {
+    if (!d_out || !xr || !table || !d_xr || !partials || B <= 0 || S <= 0 || H <= 0 || dc < 0 || dr <= 0 || (dr & 1))
         return CALM_E_INVAL;
     if (dc > 0 && !d_content) return CALM_E_INVAL;
     if (!st_ok(dout_type) || !st_ok(xr_type) || !st_ok(dcontent_type) || !st_ok(dxr_type)) return CALM_E_INVAL;
@@ -922,13 +966,35 @@ int calm_rope_bwd(const void* d_out, const void* xr, const float* table, void* d
     // kernel serves every shape of the path: dr/2 <= 256 rotation pairs, tensors below 2^31 elements)
     const RopePlan p = rope_plan(B, S, H, dc, dr, dout_type, dcontent_type, xr_type, dxr_type);
     if (!p.fits) return CALM_E_UNSUPP;
-    if (int e = with_rope(p, [&](auto vw, auto tt) {
-            return calm_launch(rope_bwd_vec_kernel<decltype(vw)::value, decltype(tt)::value>, p.bwd_grid, NT, 0, stream,
-                               d_out, xr, table, d_content, d_xr, partials, (int)p.nrows, S, H, dc, dr, dout_type, xr_type,
-                               dcontent_type, dxr_type);
-        }))
+    *g_out = p.bwd_grid;
+    return with_rope(p, [&](auto vw, auto tt) {
+        return calm_launch(rope_bwd_vec_kernel<decltype(vw)::value, decltype(tt)::value>, p.bwd_grid, NT, 0, stream,
+                           d_out, xr, table, d_content, d_xr, partials, (int)p.nrows, S, H, dc, dr, dout_type, xr_type,
+                           dcontent_type, dxr_type);
+    });
+}
+
+int calm_rope_bwd(const void* d_out, const void* xr, const float* table, void* d_content, void* d_xr,
+                  float* d_inv_freq, int32_t B, int32_t S, int32_t H, int32_t dc, int32_t dr, int32_t dout_type,
+                  int32_t xr_type, int32_t dcontent_type, int32_t dxr_type, float* partials, void* stream) {
+    if (!d_inv_freq) return CALM_E_INVAL;
+    int g = 0;
+    if (int e = rope_bwd_launch(d_out, xr, table, d_content, d_xr, B, S, H, dc, dr, dout_type, xr_type, dcontent_type,
+                                dxr_type, partials, &g, stream))
         return e;
-    return calm_reduce_partials(partials, p.bwd_grid, dr / 2, d_inv_freq, stream);
+    return calm_reduce_partials(partials, g, dr / 2, d_inv_freq, stream);
+}
+
+int calm_part_rope_bwd(const void* d_out, const void* xr, const float* table, void* d_content, void* d_xr, int32_t B,
+                       int32_t S, int32_t H, int32_t dc, int32_t dr, int32_t dout_type, int32_t xr_type,
+                       int32_t dcontent_type, int32_t dxr_type, float* partials, calm_reduce_shape* shape, void* stream) {
+    if (!shape) return CALM_E_INVAL;
+    int g = 0;
+    if (int e = rope_bwd_launch(d_out, xr, table, d_content, d_xr, B, S, H, dc, dr, dout_type, xr_type, dcontent_type,
+                                dxr_type, partials, &g, stream))
+        return e;
+    *shape = reduce_shape_1(g, dr / 2);
+    return 0;
 }
 
 int calm_softmax_fwd(float* x, int64_t rows, int32_t cols, void* stream) {
@@ -992,21 +1058,66 @@ int calm_gelu_bwd(const float* dy, const float* z, float* dz, int64_t n, void* s
     return calm_launch(gelu_bwd_kernel, grid_for(n, NT), NT, 0, stream, dy, z, dz, n);
 }
 
-int calm_colsum(const void* x, float* out, int64_t rows, int32_t cols, int32_t x_type, float* partials, void* stream) {
-    if (!x || !out || !partials || rows <= 0 || cols <= 0) return CALM_E_INVAL;
+// The first launch of a column sum: one row of `cols` partial sums per workgroup
+static int colsum_launch(const void* x, int64_t rows, int32_t cols, int32_t x_type, float* partials, int* g_out, void* stream) {
+    if (!x || !partials || rows <= 0 || cols <= 0) return CALM_E_INVAL;
     if (!st_ok(x_type)) return CALM_E_INVAL;
     if (cols > COLSUM_MAXC) return CALM_E_UNSUPP;
     const bool vec = (cols & 3) == 0 && aligned16(x) && aligned16(partials) && rows >= 64;
     int tx = 0;
-    const int g = colsum_grid(rows, cols, vec, &tx);
-    const int e = !vec ? calm_launch(colsum_kernel, g, NT, 0, stream, x, partials, rows, cols, x_type)
-                       : with_int<32, 64, 128, 256>(tx, [&](auto t) {
-                             return with_bool(x_type == CALM_ST_BF16, [&](auto x16) {
-                                 return calm_launch(colsum_vec_kernel<decltype(t)::value, decltype(x16)::value>, g, CS_NT, 0,
-                                                    stream, x, partials, rows, cols);
-                             });
-                         });
+    const int g = *g_out = colsum_grid(rows, cols, vec, &tx);
+    return !vec ? calm_launch(colsum_kernel, g, NT, 0, stream, x, partials, rows, cols, x_type)
+                : with_int<32, 64, 128, 256>(tx, [&](auto t) {
+                      return with_bool(x_type == CALM_ST_BF16, [&](auto x16) {
+                          return calm_launch(colsum_vec_kernel<decltype(t)::value, decltype(x16)::value>, g, CS_NT, 0,
+                                             stream, x, partials, rows, cols);
+                      });
+                  });
+}
+
+int calm_colsum(const void* x, float* out, int64_t rows, int32_t cols, int32_t x_type, float* partials, void* stream) {
+    if (!out) return CALM_E_INVAL;
+    int g = 0;
+    const int e = colsum_launch(x, rows, cols, x_type, partials, &g, stream);
     return e ? e : calm_reduce_partials(partials, g, cols, out, stream);
+}
+
+int calm_part_colsum(const void* x, int64_t rows, int32_t cols, int32_t x_type, float* partials, calm_reduce_shape* shape,
+                     void* stream) {
+    if (!shape) return CALM_E_INVAL;
+    int g = 0;
+    if (int e = colsum_launch(x, rows, cols, x_type, partials, &g, stream)) return e;
+    *shape = reduce_shape_1(g, cols);
+    return 0;
+}
+
+// ---- many reductions in one launch ------------------------------------------------------------------------------------
+int32_t calm_reduce_batch_max(void) { return RED_BATCH_MAX; }
+
+int calm_reduce_partials_batch(const calm_reduce_entry* entries, int32_t n_entries, void* stream) {
+    if (!entries || n_entries <= 0) return CALM_E_INVAL;
+    for (int i = 0; i < n_entries; ++i) {
+        const calm_reduce_entry& e = entries[i];
+        if (!e.partials || e.G <= 0 || e.n <= 0 || e.stride < e.n || e.nseg < 1 || e.nseg > 6 || e.begin[0] != 0 ||
+            e.begin[e.nseg] != e.n)
+            return CALM_E_INVAL;
+        for (int k = 0; k < e.nseg; ++k)
+            if (!e.out[k] || e.begin[k + 1] <= e.begin[k]) return CALM_E_INVAL;
+    }
+    for (int i0 = 0; i0 < n_entries; i0 += RED_BATCH_MAX) {
+        ReduceBatch b{};
+        b.count = n_entries - i0 < RED_BATCH_MAX ? n_entries - i0 : RED_BATCH_MAX;
+        long grid = 0;
+        for (int k = 0; k < b.count; ++k) {
+            b.e[k] = entries[i0 + k];
+            b.block0[k] = (int)grid;
+            grid += (b.e[k].n + 63) / 64;
+        }
+        if (grid >= (1L << 31)) return CALM_E_UNSUPP;
+        b.block0[b.count] = (int)grid;
+        if (int e = calm_launch(reduce_partials_batch_kernel, (int)grid, CALM_RED_THREADS, 0, stream, b)) return e;
+    }
+    return 0;
 }
 
 /* floats of `partials` scratch an entry point with a cross-workgroup reduction needs (upper bound over its kernel

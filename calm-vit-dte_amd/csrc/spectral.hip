@@ -105,7 +105,29 @@ __global__ __launch_bounds__(NT) void sn_phase_c(const SnLayerDev* __restrict__ 
 }
 
 // ---- weight gradient through W_orig / sigma ------------------------------------------------
+// The single-layer kernels and the multi-layer ones (calm_sn_weight_bwd_batch) call the same three device functions, so a
+// layer's result does not depend on which form computed it.
 // pass 1: rowdot[r] = sum_k G[r,k] W[r,k] / sigma   (one wave per row)
+__device__ __forceinline__ void sn_rowdot_row(const float* __restrict__ G, const float* __restrict__ w, float inv,
+                                              float* __restrict__ rowdot, int r, int cols, int lane) {
+    float acc = 0.f;
+    for (int c = lane; c < cols; c += 64) acc += G[(long)r * cols + c] * w[(long)r * cols + c];
+    acc = wave_sum(acc);
+    if (lane == 0) rowdot[r] = acc * inv;
+}
+// dot = sum_r ls[r] rowdot[r] (every workgroup of the apply pass computes it for itself, in the same order)
+__device__ __forceinline__ float sn_apply_dot(const float* __restrict__ ls, const float* __restrict__ rowdot, int rows,
+                                              float* red) {
+    float d = 0.f;
+    for (int r = threadIdx.x; r < rows; r += NT) d += (ls ? ls[r] : 1.0f) * rowdot[r];
+    return block_sum_256(d, red);
+}
+// pass 2: dW[r,k] = (ls[r] G[r,k] - dot * u[r] v[k]) / sigma
+__device__ __forceinline__ float sn_apply_elem(const float* __restrict__ ls, float g, float dot, float ur, float vc, float inv,
+                                               int r) {
+    return ((ls ? ls[r] : 1.0f) * g - dot * ur * vc) * inv;
+}
+
 __global__ __launch_bounds__(NT) void sn_bwd_rowdot(const float* __restrict__ G, const float* __restrict__ w,
                                                     const float* __restrict__ sigma, float* __restrict__ rowdot,
                                                     int rows, int cols) {
@@ -113,32 +135,69 @@ __global__ __launch_bounds__(NT) void sn_bwd_rowdot(const float* __restrict__ G,
     const int wave = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * (NT / 64);
     const float inv = 1.0f / sigma[0];
-    for (int r = wave; r < rows; r += nwaves) {
-        float acc = 0.f;
-        for (int c = lane; c < cols; c += 64) acc += G[(long)r * cols + c] * w[(long)r * cols + c];
-        acc = wave_sum(acc);
-        if (lane == 0) rowdot[r] = acc * inv;
-    }
+    for (int r = wave; r < rows; r += nwaves) sn_rowdot_row(G, w, inv, rowdot, r, cols, lane);
 }
 
-// pass 2: dW[r,k] = (ls[r] G[r,k] - dot * u[r] v[k]) / sigma,  dot = sum_r ls[r] rowdot[r]
 __global__ __launch_bounds__(NT) void sn_bwd_apply(const float* __restrict__ G, const float* __restrict__ u,
                                                    const float* __restrict__ v, const float* __restrict__ sigma,
                                                    const float* __restrict__ ls, const float* __restrict__ rowdot,
                                                    float* __restrict__ dw, float* __restrict__ d_ls, int rows, int cols) {
     __shared__ float red[4];
-    float d = 0.f;
-    for (int r = threadIdx.x; r < rows; r += NT) d += (ls ? ls[r] : 1.0f) * rowdot[r];
-    const float dot = block_sum_256(d, red);
+    const float dot = sn_apply_dot(ls, rowdot, rows, red);
     const float inv = 1.0f / sigma[0];
     const long total = (long)rows * cols;
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
         const int r = (int)(i / cols);
         const int c = (int)(i - (long)r * cols);
-        dw[i] = ((ls ? ls[r] : 1.0f) * G[i] - dot * u[r] * v[c]) * inv;
+        dw[i] = sn_apply_elem(ls, G[i], dot, u[r], v[c], inv, r);
     }
     if (d_ls && blockIdx.x == 0)
         for (int r = threadIdx.x; r < rows; r += NT) d_ls[r] = rowdot[r];
+}
+
+// Multi-layer form.  The entries and the prefix of workgroup counts travel by value in the kernel arguments (no device
+// table: nothing to copy, safe under stream capture); SN_BATCH_MAX keeps them inside HIP's 4 KB of kernel arguments.
+constexpr int SN_BATCH_MAX = 32;
+constexpr int SN_ROWS_PER_BLOCK_A = NT / 64;       // row-dot pass: a wave per row
+constexpr int SN_APPLY_ELEMS = 4096;               // apply pass: a workgroup owns whole rows, about this many elements
+struct SnBwdBatch {
+    calm_sn_bwd_entry e[SN_BATCH_MAX];
+    int block0[SN_BATCH_MAX + 1];                  // first workgroup of entry k (block0[count] = the grid)
+    int count;
+};
+__device__ __forceinline__ int sn_batch_entry(const SnBwdBatch& b) {
+    int k = 0;
+    while (k + 1 < b.count && (int)blockIdx.x >= b.block0[k + 1]) ++k;
+    return k;
+}
+__host__ __device__ inline int sn_apply_rows_per_block(int cols) { return cols >= SN_APPLY_ELEMS ? 1 : SN_APPLY_ELEMS / cols; }
+
+__global__ __launch_bounds__(NT) void sn_bwd_rowdot_batch(const SnBwdBatch b) {
+    const int k = sn_batch_entry(b);
+    const calm_sn_bwd_entry& L = b.e[k];
+    const int r = ((int)blockIdx.x - b.block0[k]) * SN_ROWS_PER_BLOCK_A + (threadIdx.x >> 6);
+    if (r < L.rows) sn_rowdot_row(L.G, L.w_orig, 1.0f / L.sigma[0], L.rowdot, r, L.cols, threadIdx.x & 63);
+}
+
+__global__ __launch_bounds__(NT) void sn_bwd_apply_batch(const SnBwdBatch b) {
+    __shared__ float red[4];
+    const int k = sn_batch_entry(b);
+    const calm_sn_bwd_entry& L = b.e[k];
+    const float* __restrict__ ls = L.ls;
+    const float dot = sn_apply_dot(ls, L.rowdot, L.rows, red);
+    const float inv = 1.0f / L.sigma[0];
+    const int rpb = sn_apply_rows_per_block(L.cols);
+    const int r0 = ((int)blockIdx.x - b.block0[k]) * rpb;
+    const int r1 = min(r0 + rpb, L.rows);
+    const int cols = L.cols;
+    const long i1 = (long)r1 * cols;
+    for (long i = (long)r0 * cols + threadIdx.x; i < i1; i += NT) {
+        const int r = (int)(i / cols);
+        const int c = (int)(i - (long)r * cols);
+        L.d_w_orig[i] = sn_apply_elem(ls, L.G[i], dot, L.u[r], L.v[c], inv, r);
+    }
+    if (L.d_ls)
+        for (int r = r0 + threadIdx.x; r < r1; r += NT) L.d_ls[r] = L.rowdot[r];
 }
 
 // ---- per-step bf16 copies of all weights (bf16 pipeline) ------------------------------------------------------------
@@ -274,6 +333,37 @@ int calm_sn_weight_bwd(const float* G, const float* w_orig, const float* u, cons
     if (g2 > 1024) g2 = 1024;
     if (g2 < 1) g2 = 1;
     return calm_launch(sn_bwd_apply, g2, NT, 0, stream, G, u, v, sigma, ls, scratch, d_w_orig, d_ls, rows, cols);
+}
+
+int32_t calm_sn_bwd_batch_max(void) { return SN_BATCH_MAX; }
+
+int calm_sn_weight_bwd_batch(const calm_sn_bwd_entry* entries, int32_t n_entries, void* stream) {
+    if (!entries || n_entries <= 0) return CALM_E_INVAL;
+    for (int i = 0; i < n_entries; ++i) {
+        const calm_sn_bwd_entry& e = entries[i];
+        if (!e.G || !e.w_orig || !e.u || !e.v || !e.sigma || !e.d_w_orig || !e.rowdot || e.rows <= 0 || e.cols <= 0)
+            return CALM_E_INVAL;
+    }
+    for (int i0 = 0; i0 < n_entries; i0 += SN_BATCH_MAX) {
+        const int cnt = n_entries - i0 < SN_BATCH_MAX ? n_entries - i0 : SN_BATCH_MAX;
+        SnBwdBatch a{}, p{};
+        a.count = p.count = cnt;
+        long ga = 0, gp = 0;
+        for (int k = 0; k < cnt; ++k) {
+            a.e[k] = p.e[k] = entries[i0 + k];
+            a.block0[k] = (int)ga;
+            p.block0[k] = (int)gp;
+            ga += (a.e[k].rows + SN_ROWS_PER_BLOCK_A - 1) / SN_ROWS_PER_BLOCK_A;
+            const int rpb = sn_apply_rows_per_block(a.e[k].cols);
+            gp += (a.e[k].rows + rpb - 1) / rpb;
+        }
+        if (ga >= (1L << 31) || gp >= (1L << 31)) return CALM_E_UNSUPP;
+        a.block0[cnt] = (int)ga;
+        p.block0[cnt] = (int)gp;
+        if (int e = calm_launch(sn_bwd_rowdot_batch, (int)ga, NT, 0, stream, a)) return e;
+        if (int e = calm_launch(sn_bwd_apply_batch, (int)gp, NT, 0, stream, p)) return e;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -124,6 +124,155 @@ _zeros_big = _ZeroArena(1 << 24).take
 
 
 # ---------------------------------------------------------------------------------------
+# The gradient tail.  ~160 fixed-order reductions of a step (LayerNorm dw, RoPE d_inv_freq, bias column sums, the CNN tail's
+# weight gradients) and the spectral-norm corrections of the layer-scaled linears produce LEAF gradients: nothing reads
+# them before the backward ends.  While the queue is armed (`with grad_tail(params)` around backward(), the trainer's step
+# classes) a backward writes only its rows of partials — into a buffer of its own, kept by the queue — hands autograd the
+# zero-initialised output and enqueues the rest; one autograd-engine callback flushes the queue, as a handful of
+# multi-entry launches, before backward() returns.  Per entry the additions and their order are those of the immediate
+# path (the kernels share one device function): bit-identical gradients.
+# ---------------------------------------------------------------------------------------
+GRAD_TAIL = os.environ.get("CALM_GRAD_TAIL", "1") != "0"      # A/B switch
+
+
+def _leaf(p):
+    """`p` if it is a parameter-like leaf whose gradient autograd accumulates, else None."""
+    return p if p is not None and p.is_leaf and p.requires_grad else None
+
+
+# Set on a parameter by trainer.BucketedGradReducer: the id of ITS post-accumulate-grad hook (RemovableHandle.id), the one
+# hook that flushes the queue before it reads .grad.  Any other hook on a parameter would see the gradient unfinished.
+TAIL_HOOK_ATTR = "_calm_tail_flushing_hook"
+
+
+def _hooked(p):
+    """A hook reads (or replaces) the gradient of `p` during the backward, so it has to be finished in line.  This reads
+    torch's private per-tensor hook tables (`_backward_hooks`, `_post_accumulate_grad_hooks`, dicts keyed by handle id); a
+    torch without them counts as hooked — the in-line path is always right.  Hooks these tables do not show (C++ hooks on
+    the AccumulateGrad nodes, as DistributedDataParallel registers) are the reason the trainer's step classes do not arm
+    the tail at all for such a model (TrainStep._tail_enabled)."""
+    if not hasattr(p, "_backward_hooks") or not hasattr(p, "_post_accumulate_grad_hooks"):
+        return True
+    if p._backward_hooks:
+        return True
+    post = p._post_accumulate_grad_hooks
+    return bool(post) and set(post) != {getattr(p, TAIL_HOOK_ATTR, None)}
+
+
+class _GradTail:
+    def __init__(self):
+        self.lock = threading.RLock()       # (backward nodes run on the autograd engine's device thread)
+        self.armed = False
+        self.reduce, self.sn, self.pending = [], [], set()
+        self.callback_queued = False
+        self.flushes = 0                    # flushes that launched something
+
+    def takes(self, be, *params):
+        """Whether a backward may defer the gradients of `params` (all leaves that receive the tensors unchanged).  A
+        parameter that already has a deferred gradient in the queue (used twice in one graph) gets the queue flushed and
+        this gradient computed at once: AccumulateGrad may then add the two in either order.
+        This guards second uses that go through a DEFERRING operator only.  A deferred reduction is added to a zeroed
+        tensor, so a gradient that another node adds in place meanwhile survives; a deferred spectral-norm correction is
+        WRITTEN at the flush (dW / d_ls are torch.empty_like), so a spectral-normed, layer-scaled weight that also got a
+        gradient from an operator outside this file in the same graph would lose that part.  No weight of the model is
+        tied that way (each such weight feeds exactly one SNLinearFn / MlpFn)."""
+        if not self.armed or not hasattr(be, "reduce_partials_batch") or not hasattr(be, "sn_weight_bwd_batch"):
+            return False
+        if any(_leaf(p) is None or _hooked(p) for p in params):
+            return False
+        with self.lock:
+            again = any(id(p) in self.pending for p in params)
+        if again:
+            self.flush()
+            return False
+        return all(p.grad is None for p in params)
+
+    def _enqueue(self, queue, make_item, outs, params):
+        from torch.autograd import Variable
+        # the queue keeps ALIASES of the tensors handed to autograd: AccumulateGrad adopts a gradient only while it holds
+        # the sole reference to it, and copies it (unfinished) otherwise
+        outs = [o.detach() for o in outs]
+        with self.lock:
+            queue.append((make_item(outs), outs, params))
+            self.pending.update(id(p) for p in params)
+            if not self.callback_queued:
+                self.callback_queued = True
+                Variable._execution_engine.queue_callback(self._backward_end)
+
+    def add_reduce(self, part, shape, outs, params):
+        """A reduction pending: `outs` (zero-initialised, one per segment of `shape`) += the rows of `part`."""
+        self._enqueue(self.reduce, lambda o: (part, shape, o), outs, params)
+
+    def add_sn(self, G, w, u, v, sigma, ls, dW, d_ls, rows, cols):
+        self._enqueue(self.sn, lambda o: (G, w, u, v, sigma, ls, o[0], o[1], rows, cols), [dW, d_ls], (w, ls))
+
+    def _backward_end(self):
+        self.callback_queued = False
+        self.flush()
+
+    def flush(self):
+        """Run everything queued on the current stream (the end of a backward; BucketedGradReducer before it packs a
+        bucket; a second gradient for a parameter of the queue)."""
+        with self.lock:
+            red, sn = self.reduce, self.sn
+            self.reduce, self.sn, self.pending = [], [], set()
+        if not red and not sn:
+            return
+        be = get_backend()
+        if red:
+            be.reduce_partials_batch([item for item, _, _ in red])
+        if sn:
+            be.sn_weight_bwd_batch([item for item, _, _ in sn])
+        self.flushes += 1
+        for _, outs, params in red + sn:
+            for o, p in zip(outs, params):
+                # the queue wrote into the tensor it handed out; a .grad elsewhere is a copy autograd made before the flush
+                # (create_graph=True, a second reference to the gradient): that copy is unfinished.  (A parameter with a
+                # hook is never deferred, see _hooked.)
+                if p is not None and p.grad is not None and p.grad.data_ptr() != o.data_ptr():
+                    raise RuntimeError("a deferred gradient was copied by autograd before the end of the backward "
+                                       "(CALM_GRAD_TAIL=0 computes every gradient in line)")
+
+    def drop(self):
+        """The backward raised: the engine has discarded its callbacks with the graph task."""
+        with self.lock:
+            self.reduce, self.sn, self.pending = [], [], set()
+            self.callback_queued = False
+
+
+_tail = _GradTail()
+
+
+class grad_tail:
+    """`with grad_tail(params): loss.backward()` — arms the gradient tail for that backward when every parameter's .grad
+    is None at its start (AccumulateGrad would otherwise ADD a deferred, still unfinished tensor to the existing one).
+    Everything queued is flushed before backward() returns; nothing outlives the block."""
+
+    def __init__(self, params, enabled=True):
+        """enabled=False: a no-op (the caller knows of a reader of gradients that the queue cannot see)."""
+        self.params, self.enabled = params, enabled
+
+    def __enter__(self):
+        self.on = self.enabled and GRAD_TAIL and not _tail.armed and all(p.grad is None for p in self.params)
+        if self.on:
+            _tail.armed = True
+        return self.on
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.on:
+            _tail.armed = False
+            if exc_type is None:
+                _tail.flush()               # (empty unless the engine callback did not run)
+            else:
+                _tail.drop()
+        return False
+
+
+def flush_grad_tail():
+    _tail.flush()
+
+
+# ---------------------------------------------------------------------------------------
 # GEMM patterns (x2: [M,K], w: [N,K], dy2: [M,N]; all row-major contiguous)
 # ---------------------------------------------------------------------------------------
 def _lin_fwd(be, x2, w, sigma, out, bias=None, act=ACT_NONE, col_scale=None, residual=None, pre=None):
@@ -194,7 +343,10 @@ def _sn_wbwd(be, G, w, u, v, sigma, ls=None, defer=False):
     cols = w.numel() // rows
     dW = torch.empty_like(w)
     d_ls = torch.empty_like(ls) if ls is not None else None
-    be.sn_weight_bwd(G, w, u, v, sigma, ls, dW, d_ls, rows, cols)
+    if ls is not None and _tail.takes(be, w, ls):          # (without LayerScale the optimizer-side step defers it)
+        _tail.add_sn(G, w, u, v, sigma, ls, dW, d_ls, rows, cols)
+    else:
+        be.sn_weight_bwd(G, w, u, v, sigma, ls, dW, d_ls, rows, cols)
     return dW, d_ls
 
 
@@ -241,10 +393,23 @@ def _gop(be, g2):
     return g2
 
 
-def _colsum(be, x2):
+def _colsum(be, x2, param=None):
+    """param: the bias whose gradient this is, when the sum goes to autograd unchanged (the gradient tail may defer it)."""
     out = _zeros((x2.shape[1],), x2 if x2.dtype == torch.float32 else x2.new_empty(0, dtype=torch.float32))
-    be.colsum(x2, out, x2.shape[0], x2.shape[1])            # fp32 column sums of a fp32 or bf16 tensor
+    if param is not None and _tail.takes(be, param):
+        part, shape = be.colsum_part(x2, x2.shape[0], x2.shape[1])
+        _tail.add_reduce(part, shape, [out], (param,))
+    else:
+        be.colsum(x2, out, x2.shape[0], x2.shape[1])            # fp32 column sums of a fp32 or bf16 tensor
     return out
+
+
+def _ln_bwd(be, dy, x, w, mean, rstd, dx, dw, rows, D, dx_add=None):
+    if _tail.takes(be, w):
+        part, shape = be.layernorm_bwd_part(dy, x, w, mean, rstd, dx, rows, D, dx_add=dx_add)
+        _tail.add_reduce(part, shape, [dw], (w,))
+    else:
+        be.layernorm_bwd(dy, x, w, mean, rstd, dx, dw, rows, D, dx_add=dx_add)
 
 
 # ---------------------------------------------------------------------------------------
@@ -277,7 +442,7 @@ class LayerNormFn(Function):
         D = x.shape[-1]
         dx = torch.empty_like(x)
         dw = _zeros(w.shape, w)
-        be.layernorm_bwd(dy, x, w, mean, rstd, dx, dw, x.numel() // D, D)
+        _ln_bwd(be, dy, x, w, mean, rstd, dx, dw, x.numel() // D, D)
         return dx, dw, None, None
 
 
@@ -314,8 +479,8 @@ class LayerNormSkipFn(Function):
         D = x.shape[-1]
         dx = torch.empty_like(x)
         dw = _zeros(w.shape, w)
-        be.layernorm_bwd(dy, x, w, mean, rstd, dx, dw, x.numel() // D, D,
-                         dx_add=_c(dskip).reshape(x.shape) if dskip is not None else None)
+        _ln_bwd(be, dy, x, w, mean, rstd, dx, dw, x.numel() // D, D,
+                dx_add=_c(dskip).reshape(x.shape) if dskip is not None else None)
         return dx, dw, None
 
 
@@ -353,6 +518,7 @@ class SNLinearFn(Function):
         ctx.wgen = _wgen(w)
         ctx.defer = _deferred(w)
         ctx.has_bias = bias is not None
+        ctx.bias = _leaf(bias)
         ctx.has_res = residual is not None
         ctx.save_for_backward(x2, w, ls, u, v, sigma, pre)
         ctx.xshape = x.shape
@@ -389,7 +555,7 @@ class SNLinearFn(Function):
             else:
                 _lin_dgrad(be, dzg, wl, sigma, dx)
             dx = dx.view(ctx.xshape)
-        db = _colsum(be, dz) if ctx.has_bias else None
+        db = _colsum(be, dz, ctx.bias) if ctx.has_bias else None
         dres = dy if ctx.has_res else None
         return dx, dW, db, d_ls, dres, None, None, None, None, None, None
 
@@ -495,6 +661,7 @@ class MlpFn(Function):
         ctx.wops = (wop1, wop2)
         ctx.wgen = _wgen(w1, w2)
         ctx.has_b1, ctx.has_b2, ctx.has_res = b1 is not None, b2 is not None, residual is not None
+        ctx.biases = (_leaf(b1), _leaf(b2))
         ctx.defer = (_deferred(w1), _deferred(w2))
         ctx.xshape = x.shape
         ctx.save_for_backward(x2, hp, hg, w1, w2, ls, u1, v1, s1, u2, v2, s2, key if ctx.p > 0 else None)
@@ -514,7 +681,7 @@ class MlpFn(Function):
         G2 = _zeros_big(w2.shape, w2)
         _lin_wgrad(be, do2g, hg, G2)
         dW2, d_ls = _sn_wbwd(be, G2, w2, u2, v2, s2, ls, defer=ctx.defer[1])
-        db2 = _colsum(be, do2) if ctx.has_b2 else None
+        db2 = _colsum(be, do2, ctx.biases[1]) if ctx.has_b2 else None
         wop1, wop2 = ctx.wops
         if ls is not None:
             w2l = torch.empty_like(w2 if ctx.fp8 else wop2)
@@ -531,7 +698,7 @@ class MlpFn(Function):
         G1 = _zeros_big(w1.shape, w1)
         _lin_wgrad(be, dhp, x2, G1)
         dW1, _ = _sn_wbwd(be, G1, w1, u1, v1, s1, defer=ctx.defer[0])
-        db1 = _colsum(be, dhp) if ctx.has_b1 else None
+        db1 = _colsum(be, dhp, ctx.biases[0]) if ctx.has_b1 else None
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x2)
@@ -608,6 +775,7 @@ class RopeFn(Function):
         be.rope_fwd(content, xr, inv_freq, table, out, B, S, H, dc, dr)
         ctx.dims = (B, S, H, dc, dr)
         ctx.content_dtype = content.dtype if content is not None else None
+        ctx.inv_freq = _leaf(inv_freq)
         ctx.save_for_backward(xr, table)
         return out
 
@@ -622,12 +790,16 @@ class RopeFn(Function):
         d_xr = torch.empty_like(xr)                          # gradients take the storage type of their tensors
         d_content = torch.empty(B, S, H * dc, dtype=ctx.content_dtype, device=xr.device) if dc > 0 else None
         d_if = _zeros((dr // 2,), table)
-        be.rope_bwd(dout, xr, table, d_content, d_xr, d_if, B, S, H, dc, dr)
+        if ctx.inv_freq is not None and _tail.takes(be, ctx.inv_freq):
+            part, shape = be.rope_bwd_part(dout, xr, table, d_content, d_xr, B, S, H, dc, dr)
+            _tail.add_reduce(part, shape, [d_if], (ctx.inv_freq,))
+        else:
+            be.rope_bwd(dout, xr, table, d_content, d_xr, d_if, B, S, H, dc, dr)
         return d_content, d_xr, d_if, None, None
 
 
 def _attn_mask_bwd(be, defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2, w1o=None, w2o=None,
-                   fold=False):
+                   fold=False, biases=(None, None)):
     """What follows the attention core in every attention backward (stored-P, row-LSE, bf16): the mask-MLP backward
     from dM [B*Sq,Skv] and the two dR products, accumulated into dq / dk.  w1o / w2o are the operands of the two
     input-gradient GEMMs (the bf16 pipeline passes its bf16 weight copies); dR takes the dtype of q.
@@ -640,14 +812,14 @@ def _attn_mask_bwd(be, defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u
     G2 = _zeros_big(w2.shape, w2)
     _lin_wgrad(be, dM, hg, G2)
     dW2, _ = _sn_wbwd(be, G2, w2, u2, v2, s2, defer=defer[1])
-    db2 = _colsum(be, dM)
+    db2 = _colsum(be, dM, biases[1])
     dhp = torch.empty_like(hp)
     _lin_dgrad(be, dM, w2o, s2, dhp, act=ACT_GELU_BWD, aux=hp)
     R2 = R.view(B * Sq, Skv)
     G1 = _zeros_big(w1.shape, w1)
     _lin_wgrad(be, dhp, R2, G1)
     dW1, _ = _sn_wbwd(be, G1, w1, u1, v1, s1, defer=defer[0])
-    db1 = _colsum(be, dhp)
+    db1 = _colsum(be, dhp, biases[0])
     dR = torch.empty(B, Sq, Skv, dtype=dt, device=dev)
     _lin_dgrad(be, dhp, w1o, s1, dR.view(B * Sq, Skv))
     if fold:
@@ -697,6 +869,7 @@ class LatentMaskAttentionFn(Function):
                     batch=(B, H))
         ctx.H = H
         ctx.defer = (_deferred(w1), _deferred(w2))
+        ctx.biases = (_leaf(b1), _leaf(b2))
         ctx.save_for_backward(q, k, v, R, hp, hg, P, w1, w2, u1, v1, s1, u2, v2, s2)
         return out
 
@@ -722,7 +895,7 @@ class LatentMaskAttentionFn(Function):
             # folded into their per-head contractions); taken where it is measured faster than what follows
             be.attn_bwd_front(v, dout, P, dP, dM, B, Sq, Skv, H, hd)
             dW1, db1, dW2, db2, dR = _attn_mask_bwd(be, ctx.defer, dM, q, k, None, None, R, hp, hg, w1, w2, u1, v1, s1,
-                                                    u2, v2, s2, fold=True)
+                                                    u2, v2, s2, fold=True, biases=ctx.biases)
             be.attn_bwd_back(q, k, dout, P, dP, dR, dq, dk, dv, B, Sq, Skv, H, hd)
             return dq, dk, dv, dW1, db1, dW2, db2, None, None, None, None, None, None, None
         if be.attn_bwd_preferred(Sq, Skv, H, hd):
@@ -738,7 +911,8 @@ class LatentMaskAttentionFn(Function):
                     alpha=scale)
             be.gemm(dP, q, dk, Skv, hd, Sq, (1, Skv) + pb, (1, D, Sq * D, hd), (D, Skv * D, hd), batch=(B, H),
                     alpha=scale)
-        dW1, db1, dW2, db2 = _attn_mask_bwd(be, ctx.defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2)
+        dW1, db1, dW2, db2 = _attn_mask_bwd(be, ctx.defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2,
+                                            biases=ctx.biases)
         return dq, dk, dv, dW1, db1, dW2, db2, None, None, None, None, None, None, None
 
 
@@ -767,6 +941,7 @@ class LatentMaskAttentionLseFn(Function):
         be.attn_fwd_lse(q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, lse, B, Sq, Skv, H, hd)
         ctx.H = H
         ctx.defer = (_deferred(w1), _deferred(w2))
+        ctx.biases = (_leaf(b1), _leaf(b2))
         ctx.save_for_backward(q, k, v, R, hp, hg, Mk, lse, w1, w2, u1, v1, s1, u2, v2, s2)
         return out
 
@@ -788,7 +963,8 @@ class LatentMaskAttentionLseFn(Function):
         scratch = torch.empty(be.attn_bwd_lse_scratch_bytes(B, Sq, Skv, H, hd), dtype=torch.uint8, device=dev)
         be.attn_bwd_lse(q, k, v, dout, Mk, lse, scratch, dq, dk, dv, dM, B, Sq, Skv, H, hd)
         del scratch
-        dW1, db1, dW2, db2 = _attn_mask_bwd(be, ctx.defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2)
+        dW1, db1, dW2, db2 = _attn_mask_bwd(be, ctx.defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2,
+                                            biases=ctx.biases)
         return dq, dk, dv, dW1, db1, dW2, db2, None, None, None, None, None, None, None
 
 
@@ -814,6 +990,7 @@ class LatentMaskAttention16Fn(Function):
         be.attn16_fwd(q, k, v, w1o, b1, s1, w2o, b2, s2, out, R, hp, hg, Mk, MkT, lse, B, S, H, hd)
         ctx.H = H
         ctx.defer = (_deferred(w1), _deferred(w2))
+        ctx.biases = (_leaf(b1), _leaf(b2))
         ctx.wops = (w1o, w2o)
         ctx.wgen = _wgen(w1, w2)
         ctx.save_for_backward(q, k, v, out, R, hp, hg, Mk, MkT, lse, w1, w2, u1, v1, s1, u2, v2, s2)
@@ -840,7 +1017,7 @@ class LatentMaskAttention16Fn(Function):
         be.attn16_bwd(q, k, v, out, dout, Mk, MkT, lse, delta, dq, dk, dv, dM, B, S, H, hd)
         # mask MLP backward: typed GEMMs on the bf16 tensors, the dR products accumulated into the bf16 gradients
         dW1, db1, dW2, db2 = _attn_mask_bwd(be, ctx.defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u2, v2, s2,
-                                            w1o=w1o, w2o=w2o)
+                                            w1o=w1o, w2o=w2o, biases=ctx.biases)
         return dq, dk, dv, dW1, db1, dW2, db2, None, None, None, None, None, None, None
 
 
@@ -1194,8 +1371,13 @@ class CnnResidualFn(Function):
         dx = torch.empty_like(dy)
         gall = _zeros((Ch * 3 + Ch + Ch * 9 + Ch + 3 * Ch + 3,), dy)
         G0, db0, G2, db2, G4, db4 = torch.split(gall, [Ch * 3, Ch, Ch * 9, Ch, 3 * Ch, 3])
-        be.cnn_bwd(dy, x, w0, s0, b0, w2, s2, b2, w4, s4, b4, dx, G0, db0, G2, db2, G4, db4, B, S, Ch,
-                   residual=ctx.residual)
+        # the six sums go to autograd unchanged only when the optimizer-side step applies all three spectral-norm corrections
+        if all(ctx.defer) and _tail.takes(be, w0, b0, w2, b2, w4, b4):
+            part, shape = be.cnn_bwd_part(dy, x, w0, s0, b0, w2, s2, b2, w4, s4, b4, dx, B, S, Ch, residual=ctx.residual)
+            _tail.add_reduce(part, shape, [G0, db0, G2, db2, G4, db4], (w0, b0, w2, b2, w4, b4))
+        else:
+            be.cnn_bwd(dy, x, w0, s0, b0, w2, s2, b2, w4, s4, b4, dx, G0, db0, G2, db2, G4, db4, B, S, Ch,
+                       residual=ctx.residual)
         dW0, _ = _sn_wbwd(be, G0.view(Ch, 3), w0.view(Ch, 3), u0, v0, s0, defer=ctx.defer[0])
         dW2, _ = _sn_wbwd(be, G2.view(Ch, 9), w2.view(Ch, 9), u2, v2, s2, defer=ctx.defer[1])
         dW4, _ = _sn_wbwd(be, G4.view(3, Ch), w4.view(3, Ch), u4, v4, s4, defer=ctx.defer[2])

@@ -18,7 +18,8 @@ as set by torchrun):
         parameters in place for evaluation.
 
 The model also works under stock `torch.nn.parallel.DistributedDataParallel` (that is what the
-reference's train() does with it); the reducer here is the MI355X-tuned equivalent.
+reference's train() does with it); the reducer here is the MI355X-tuned equivalent.  Under DDP the step
+classes leave the gradient tail (ops.grad_tail) off: DDP reads gradients during the backward.
 """
 import contextlib
 import os
@@ -135,11 +136,13 @@ class BucketedGradReducer:
                 views.append(flat[off:off + p.numel()].view_as(p))
                 off += p.numel()
             self.buckets.append({"params": group, "flat": flat, "views": views, "pending": len(group)})
+        from . import ops
         self._where = {}
         for bi, b in enumerate(self.buckets):
             for p in b["params"]:
                 self._where[p] = bi
-                p.register_post_accumulate_grad_hook(self._hook)
+                handle = p.register_post_accumulate_grad_hook(self._hook)
+                setattr(p, ops.TAIL_HOOK_ATTR, handle.id)  # _launch flushes the gradient tail before it reads a .grad
 
     def _hook(self, p):
         b = self.buckets[self._where[p]]
@@ -148,6 +151,8 @@ class BucketedGradReducer:
             self._launch(b)
 
     def _launch(self, b):
+        from . import ops
+        ops.flush_grad_tail()           # gradients the backward deferred to its end are finished before they are packed
         grads = [p.grad for p in b["params"]]
         op = dist.ReduceOp.AVG if self.avg_in_collective else dist.ReduceOp.SUM
         if self.on_gpu:
@@ -252,12 +257,26 @@ class TrainStep:
             loss = soft_target_cross_entropy(y_hat.squeeze(), y_soft, self.metrics)      # cls:86
         return self._finish(loss, y_hat)
 
+    def _tail_enabled(self):
+        """The gradient tail hands autograd unfinished leaf gradients, so nothing but BucketedGradReducer (which flushes the
+        queue first) may read gradients during the backward.  DistributedDataParallel does — C++ hooks on the
+        AccumulateGrad nodes copy .grad into its buckets — and so would any other exchange this step does not know of:
+        not armed for a model that is, or contains, a DistributedDataParallel, nor in a world of more than one rank
+        without the reducer."""
+        if any(isinstance(mod, torch.nn.parallel.DistributedDataParallel) for mod in self.model.modules()):
+            return False
+        return not (self.reducer is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+
     def _finish(self, loss, y_hat):
         """backward, gradient exchange, unscale / clip / optimizer step, zero_grad (cls:87-96)."""
-        if self.scaler is not None:
-            self.scaler.scale(loss).backward()                             # cls:87
-        else:
-            loss.backward()
+        from . import ops
+        # the gradient tail (ops.grad_tail): leaf-gradient reductions of this backward run as a few multi-entry launches at
+        # its end; armed only while no parameter has a .grad that autograd would add an unfinished tensor to
+        with ops.grad_tail(self.params, enabled=self._tail_enabled()):
+            if self.scaler is not None:
+                self.scaler.scale(loss).backward()                             # cls:87
+            else:
+                loss.backward()
         if self.reducer is not None:
             self.reducer.finish()
         if isinstance(self.opt, FusedClipAdamW):                           # cls:88-96 in three launches

@@ -190,6 +190,50 @@ enum { CALM_RED_LAYERNORM_BWD = 0, CALM_RED_ROPE_BWD = 1, CALM_RED_LATENT_FWD = 
 int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols);
 
 /* ---------------------------------------------------------------------------------------
+ * Deferred reductions (additions to ABI v7 — no existing signature or struct changes, so the version number stays).
+ * The second launch of the entry points above is pure latency (a few microseconds for at most a megabyte or two), and
+ * its outputs are leaf gradients that nothing reads before the backward ends.  A caller may therefore run the FIRST
+ * launch alone — calm_part_layernorm_bwd, calm_part_rope_bwd, calm_part_colsum, calm_part_cnn_residual_bwd: the
+ * siblings of calm_layernorm_bwd / calm_rope_bwd / calm_colsum / calm_cnn_residual_bwd without the output of the sum
+ * — keep each call's `partials` alive (one buffer per call, sized by calm_reduce_scratch_floats as before), and combine
+ * many of them later with calm_reduce_partials_batch.  Each sibling reports the rows of partials it wrote through
+ * calm_reduce_shape; the batch runs, per entry, exactly the additions of the single form in the same order (one shared
+ * device function), so the results are bit-identical.
+ *
+ * calm_reduce_entry: G rows of n partials, `stride` floats apart; columns [begin[k], begin[k+1]) are ADDED to out[k]
+ * (nseg <= 6 outputs side by side, begin[0] = 0, begin[nseg] = n).  The entries travel by value in the kernel arguments
+ * (no device table, no host-to-device copy: safe under stream capture), calm_reduce_batch_max() per launch; a longer
+ * list is split into several launches.  `entries` is host memory and is not read after the call returns.
+ * ------------------------------------------------------------------------------------- */
+typedef struct calm_reduce_shape {
+    int32_t G, n, stride, nseg;
+    int32_t begin[7];
+    int32_t reserved;
+} calm_reduce_shape;
+typedef struct calm_reduce_entry {
+    const float* partials;
+    int32_t G, n, stride, nseg;
+    float* out[6];
+    int32_t begin[7];
+    int32_t reserved;
+} calm_reduce_entry;
+int32_t calm_reduce_batch_max(void);
+int calm_reduce_partials_batch(const calm_reduce_entry* entries, int32_t n_entries, void* stream);
+int calm_part_layernorm_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
+                            float* dx, const float* dx_add, int64_t rows, int32_t D, int32_t dy_type, float* partials,
+                            calm_reduce_shape* shape, void* stream);
+int calm_part_rope_bwd(const void* d_out, const void* xr, const float* table, void* d_content, void* d_xr, int32_t B,
+                       int32_t S, int32_t H, int32_t dc, int32_t dr, int32_t dout_type, int32_t xr_type,
+                       int32_t dcontent_type, int32_t dxr_type, float* partials, calm_reduce_shape* shape, void* stream);
+int calm_part_colsum(const void* x, int64_t rows, int32_t cols, int32_t x_type /* CALM_ST_* */, float* partials,
+                     calm_reduce_shape* shape, void* stream);
+/* (shape->begin: the six segments g0 | gb0 | g2 | gb2 | g4 | gb4 of a partial row) */
+int calm_part_cnn_residual_bwd(const float* dy, const float* x, const float* w0, const float* s0, const float* b0,
+                               const float* w2, const float* s2, const float* b2, const float* w4, const float* s4,
+                               const float* b4, float* dx, int32_t B, int32_t S, int32_t hidden, int32_t residual,
+                               float* partials, calm_reduce_shape* shape, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * LayerNorm(D, eps, bias=False) over the last axis (Vi_Tools:131-132,197,494; fwd 211-215,311,523).
  * x,y: [rows, D] contiguous.  mean,rstd: [rows] saved for backward.
  * bwd: dx = rstd*(w*dy - mean_D(w*dy) - xhat*mean_D(w*dy*xhat)) [+ dx_add]; dw[D] += sum_rows dy*xhat
@@ -429,6 +473,18 @@ int calm_cast_f32_one(const void* src, float* dst, int64_t n, void* stream);
 int calm_sn_weight_bwd(const float* G, const float* w_orig, const float* u, const float* v,
                        const float* sigma, const float* ls, float* d_w_orig, float* d_ls,
                        int32_t rows, int32_t cols, float* scratch, void* stream);
+/* The same correction for many layers in two launches per calm_sn_bwd_batch_max() layers (an addition to ABI v7): the
+ * row-dot pass over work items (layer, row) and the apply pass over (layer, row chunk), entries by value in the kernel
+ * arguments as for calm_reduce_partials_batch.  Per layer the arithmetic and the summation order are those of
+ * calm_sn_weight_bwd (shared device functions): bit-identical results, with and without ls.  rowdot: >= rows floats of
+ * scratch per entry, alive until the launches have run on `stream`.  `entries` is host memory. */
+typedef struct calm_sn_bwd_entry {
+    const float *G, *w_orig, *u, *v, *sigma, *ls;   /* ls nullable */
+    float *d_w_orig, *d_ls, *rowdot;                /* d_ls nullable */
+    int32_t rows, cols;
+} calm_sn_bwd_entry;
+int32_t calm_sn_bwd_batch_max(void);
+int calm_sn_weight_bwd_batch(const calm_sn_bwd_entry* entries, int32_t n_entries, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Optimizer-side step over ALL parameters in three launches (distributed_trainer_cls.py:88-96,158):
