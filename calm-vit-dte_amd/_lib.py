@@ -96,6 +96,11 @@ class EmaEntry(C.Structure):
     _fields_ = [("src", _p), ("ema", _p), ("numel", _i64), ("chunk0", _i32), ("reserved", _i32)]
 
 
+class SnapshotEntry(C.Structure):
+    """struct calm_snapshot_entry (32 bytes)."""
+    _fields_ = [("tensor", _p), ("offset", _i64), ("nbytes", _i64), ("chunk0", _i32), ("reserved", _i32)]
+
+
 class SnLayer(C.Structure):
     """struct calm_sn_layer."""
     _fields_ = [("w", _p), ("u", _p), ("v", _p), ("sigma", _p), ("rows", _i32), ("cols", _i32)]
@@ -189,6 +194,9 @@ SIGNATURES = {
     "calm_ema_chunk_elems": (_i32, []),
     "calm_ema_update": (_i32, [_p, _i32, _p, _i32, _f32, _i32, _p, _p, _p, _p]),
     "calm_ema_swap": (_i32, [_p, _i32, _p, _i32, _p]),
+    "calm_snapshot_chunk_bytes": (_i32, []),
+    "calm_snapshot_pack": (_i32, [_p, _i32, _p, _i32, _p, _i64, _p]),
+    "calm_snapshot_unpack": (_i32, [_p, _i32, _p, _i32, _p, _i64, _p]),
     "calm_collate_mix": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_collate_crop_mix": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_augment_collate": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),

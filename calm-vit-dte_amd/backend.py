@@ -301,6 +301,97 @@ class EmaPlan:
         self.ema_ptrs = ent["ema"].copy()
 
 
+SNAPSHOT_ALIGN = 16
+
+
+def snapshot_layout(specs):
+    """The packed layout of a training snapshot, a pure host function (GPU and CPU models alike, and the reader of a
+    file): specs = [(name, dtype, shape)] in the order they are packed -> (offsets, sizes, packed_bytes).  Every offset is
+    the running end rounded up to SNAPSHOT_ALIGN = 16 bytes, the order is the given one, a tensor without elements takes
+    no room (size 0 at the running offset).  Sizes are whole 4-byte words — calm_snapshot_pack moves words — and anything
+    else is refused by name."""
+    offsets, sizes, end = [], [], 0
+    for name, dtype, shape in specs:
+        numel = 1
+        for d in shape:
+            if int(d) < 0:
+                raise ValueError(f"snapshot layout: {name} has a negative extent {tuple(shape)}")
+            numel *= int(d)
+        nbytes = numel * torch.empty((), dtype=dtype).element_size()
+        if nbytes % 4:
+            raise ValueError(f"snapshot layout: {name} ({dtype}, {tuple(shape)}) is {nbytes} bytes, not whole 4-byte words")
+        off = -(-end // SNAPSHOT_ALIGN) * SNAPSHOT_ALIGN
+        offsets.append(off)
+        sizes.append(nbytes)
+        if nbytes:
+            end = off + nbytes
+    return offsets, sizes, -(-end // SNAPSHOT_ALIGN) * SNAPSHOT_ALIGN
+
+
+def snapshot_chunks(sizes, chunk_bytes):
+    """The chunk table of calm_snapshot_pack / _unpack over entries of `sizes` bytes (all > 0): (chunk0 per entry, the
+    entry of every chunk).  Host only."""
+    chunk0, chunk_entry = [], []
+    for i, nb in enumerate(sizes):
+        if nb <= 0:
+            raise ValueError("snapshot chunk table: entries have at least one word")
+        chunk0.append(len(chunk_entry))
+        chunk_entry += [i] * ((nb + chunk_bytes - 1) // chunk_bytes)
+    return chunk0, chunk_entry
+
+
+class SnapshotPlan:
+    """Device tables of calm_snapshot_entry records for calm_snapshot_pack / _unpack over a fixed list of live tensors, and
+    the packed device buffer they gather into (zeroed once: the padding between entries is never written again, so equal
+    states give equal buffers).  `offsets` / `sizes` are per given tensor (snapshot_layout over them; a tensor without
+    elements has size 0 and no entry), `ptrs` the addresses the table holds.  What the host can check is checked here:
+    device, contiguity, 4-byte alignment, whole words, tensors that overlap one another."""
+
+    def __init__(self, be, tensors, names=None):
+        tensors = list(tensors)
+        names = list(names) if names is not None else [f"tensor {i}" for i in range(len(tensors))]
+        if len(names) != len(tensors):
+            raise ValueError("snapshot plan: one name per tensor")
+        for n, t in zip(names, tensors):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise TypeError(f"snapshot plan: {n} is not a CUDA tensor")
+            if not t.is_contiguous():
+                raise TypeError(f"snapshot plan: {n} is not contiguous")
+            if t.data_ptr() % 4 and t.numel():
+                raise ValueError(f"snapshot plan: {n} is not 4-byte aligned")
+        self.offsets, self.sizes, self.packed_bytes = snapshot_layout([(n, t.dtype, tuple(t.shape))
+                                                                       for n, t in zip(names, tensors)])
+        live = [(t, off, nb) for t, off, nb in zip(tensors, self.offsets, self.sizes) if nb > 0]
+        if not live:
+            raise ValueError("snapshot plan needs at least one tensor with elements")
+        devices = {t.device for t, _, _ in live}
+        if len(devices) != 1:
+            raise ValueError(f"snapshot plan: tensors on one device expected, got {sorted(map(str, devices))}")
+        for (_, off, nb) in live:                                  # (what snapshot_layout guarantees, kept as a check)
+            if off % SNAPSHOT_ALIGN or nb % 4 or off + nb > self.packed_bytes:
+                raise ValueError("snapshot plan: an entry leaves the packed buffer")
+        spans = sorted((t.data_ptr(), t.data_ptr() + nb) for t, _, nb in live)
+        if any(b[0] < a[1] for a, b in zip(spans, spans[1:])):        # two entries scattering into one word is a race
+            raise ValueError("snapshot plan expects tensors that do not overlap in memory")
+        self.chunk_bytes = int(be.lib.calm_snapshot_chunk_bytes())
+        chunk0, chunk_entry = snapshot_chunks([nb for _, _, nb in live], self.chunk_bytes)
+        ent = np.zeros(len(live), dtype=np.dtype(_lib.SnapshotEntry))
+        for i, (t, off, nb) in enumerate(live):
+            e = ent[i]
+            e["tensor"], e["offset"], e["nbytes"], e["chunk0"] = t.data_ptr(), off, nb, chunk0[i]
+        dev = live[0][0].device
+        self.n = len(live)
+        self.n_chunks = len(chunk_entry)
+        self.entries = ent
+        self.table_dev = torch.from_numpy(ent.view(np.uint8).reshape(-1).copy()).to(dev)
+        self.chunk_dev = torch.tensor(chunk_entry, dtype=torch.int32, device=dev)
+        self.packed = torch.zeros(self.packed_bytes, dtype=torch.uint8, device=dev)
+        if self.packed.data_ptr() % SNAPSHOT_ALIGN:
+            raise RuntimeError("snapshot plan: the packed buffer is not 16-byte aligned")
+        self.ptrs = ent["tensor"].copy()
+        self.tensors = [t for t, _, _ in live]                        # keeps the addresses in the table alive
+
+
 class SnPlan:
     """Device-resident plan for the batched spectral-norm power iteration."""
 
@@ -692,6 +783,21 @@ class HipBackend:
         """Exchange every parameter with its average, in place."""
         _lib.check(self.lib.calm_ema_swap(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
                                           _stream()), "calm_ema_swap")
+
+    # ---- training snapshots --------------------------------------------------------------
+    def snapshot_plan(self, tensors, names=None):
+        """tensors: the live CUDA tensors of a training state, in pack order -> SnapshotPlan (tables + packed buffer)."""
+        return SnapshotPlan(self, tensors, names)
+
+    def snapshot_pack(self, plan):
+        """Gather every tensor of the plan into plan.packed: one launch on the current stream."""
+        _lib.check(self.lib.calm_snapshot_pack(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
+                                               plan.packed.data_ptr(), plan.packed_bytes, _stream()), "calm_snapshot_pack")
+
+    def snapshot_unpack(self, plan):
+        """Scatter plan.packed back into the tensors of the plan, in place: one launch on the current stream."""
+        _lib.check(self.lib.calm_snapshot_unpack(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
+                                                 plan.packed.data_ptr(), plan.packed_bytes, _stream()), "calm_snapshot_unpack")
 
     # ---- LayerNorm --------------------------------------------------------------------
     def layernorm_fwd(self, x, w, y, mean, rstd, rows, D, eps):

@@ -1310,6 +1310,438 @@ class ModelEMA:
         return sd
 
 
+class _TailSampler(torch.utils.data.Sampler):
+    """The indices of `sampler` without its first `skip` ones: the rest of an epoch whose first batches a run that is
+    being resumed has already trained on.  The indices are dropped here — nothing is loaded and thrown away."""
+
+    def __init__(self, sampler, skip):
+        self.sampler, self.skip = sampler, max(int(skip), 0)
+
+    def __iter__(self):
+        return iter(list(self.sampler)[self.skip:])
+
+    def __len__(self):
+        return max(len(self.sampler) - self.skip, 0)
+
+
+def resume_tail(sampler, skip_batches, batch_size):
+    """Sampler over what is left of the current epoch of `sampler` (set_epoch already called) behind its first
+    `skip_batches` batches of `batch_size` samples."""
+    return _TailSampler(sampler, int(skip_batches) * int(batch_size))
+
+
+def _b64(t):
+    import base64
+    return base64.b64encode(t.cpu().numpy().tobytes()).decode("ascii")
+
+
+def _unb64(text):
+    import base64
+    import numpy as np
+    return torch.from_numpy(np.frombuffer(base64.b64decode(text), dtype=np.uint8).copy())
+
+
+class TrainState:
+    """The whole state of a training run as ONE file, written without stalling the training thread, and resumed from
+    exactly: parameters and buffers, the optimizer's moments and step count, the weight EMA and its update count, the
+    step metrics, the GradScaler's scale and the growth count of the fused step, the scheduler, the learning rate, the
+    torch CPU / CUDA RNG states, the numpy generators of the device collate / augmentation and the position in the run.
+    The tensor set is the one GraphedTrainStep(restore_after_warmup=True) puts back, which
+    tests/test_determinism_gpu.py shows to be sufficient bit for bit.
+
+        st = TrainState(model, optimizer, scaler, scheduler, ema, step, metrics, generators={"collate": dcoll.rng})
+        st.save_async(path, {"epoch": e, "batch": b, "step": n})    # one kernel launch on the training stream
+        st.poll()                                                   # once per step: hands a finished copy to the writer
+        st.wait()                                                   # the file is in place (or the writer's error raises)
+        progress = st.load(path)                                    # in place: every plan and captured graph stays valid
+        st.close()
+
+    On a GPU the tensors are gathered into one device buffer by calm_snapshot_pack (one launch on the current stream); a
+    side stream that waits for it copies the buffer into one pinned host buffer; poll() sees that copy's event complete
+    and starts a plain Python thread that computes the CRC32, writes `path + ".tmp"`, fsyncs and renames — that thread
+    makes no torch or HIP call, every GPU API call stays on the calling thread.  load() reads the payload into the pinned
+    buffer, copies it to the device once and scatters it with calm_snapshot_unpack.  A CPU model packs with plain tensor
+    copies into the same layout (backend.snapshot_layout), so a file written on either kind of device loads on the other.
+
+    Entries are named, so a file is checked against the live objects before a byte is scattered: `model.<state_dict key>`,
+    `optim.exp_avg.<i>` / `optim.exp_avg_sq.<i>` / `optim.step` (FusedClipAdamW; loaded strictly in place), `ema.shadow.<name>`
+    / `ema.count`, `metrics`, `step.clean_steps`, `scaler.scale`.  For a torch optimizer the tensors of
+    `state_dict()["state"]` that live on the model's device are packed in order as `optim.state.<i>.<key>`, every other
+    value goes into the header, and the load goes through `optimizer.load_state_dict`.
+
+    File: 8 bytes magic, uint64 little-endian header length, the JSON header, zero padding to a multiple of 4 096 bytes,
+    the payload.  The header holds the format version, the entry list (name, dtype, shape, offset, nbytes), packed_bytes,
+    the payload's CRC32 and the host state — JSON throughout, no pickle.  With `sidecar_rank=r` the per-rank host state (RNG
+    states, generators) is written to and read from the small JSON file `<path>.rank<r>.json` instead: in a world of
+    more than one rank every rank keeps its own, and only rank 0 writes the payload (`payload=False` elsewhere)."""
+
+    MAGIC = b"CALMSNAP"
+    VERSION = 1
+    PAGE = 4096
+    _PER_RANK = ("rng", "generators", "rank")
+
+    def __init__(self, model, optimizer, scaler=None, scheduler=None, ema=None, step=None, metrics=None, generators=None,
+                 payload=True, sidecar_rank=None):
+        self.model, self.opt, self.scheduler, self.ema, self.metrics = model, optimizer, scheduler, ema, metrics
+        self.scaler = scaler if scaler is not None and scaler.is_enabled() else None
+        self.generators = dict(generators) if isinstance(generators, dict) else \
+            {str(i): g for i, g in enumerate(generators or [])}
+        self.payload, self.sidecar_rank = bool(payload), sidecar_rank
+        self._optim_desc = None
+        self.fused = isinstance(optimizer, FusedClipAdamW)
+        self.device = next(model.parameters()).device
+        self.on_gpu = self.device.type == "cuda"
+        if self.scaler is not None and self.on_gpu:
+            self.scaler.scale(torch.ones((), dtype=torch.float32, device=self.device))   # creates the scale tensor
+        self._ema_count = torch.zeros(1, dtype=torch.int32) if ema is not None and ema._plan is None else None
+        self._plan = self._plan_key = None
+        self._host = self._host_np = None
+        self._side = torch.cuda.Stream(device=self.device) if self.on_gpu else None
+        self._copied = None                       # event behind the device-to-host copy of the save in flight
+        self._job = None                          # (path, header fields) of a save whose copy has not been handed over
+        self._thread = None
+        self._error = None
+        self.step = None
+        self.bind_step(step)
+
+    # ---- the tensor set ---------------------------------------------------------------------------------------
+    def bind_step(self, step):
+        """The TrainStep whose GradScaler growth count (fused optimizer: `_clean_steps`) belongs to the state; a
+        GraphedTrainStep stands for its captured inner step.  Rebinding waits for a save in flight."""
+        self.wait()
+        step = getattr(step, "inner", step)
+        if step is not None and self.fused and self.scaler is not None and not hasattr(step, "_clean_steps"):
+            step._clean_steps = torch.zeros((), dtype=torch.int32, device=self.device)     # as TrainStep._finish makes them
+            step._one = torch.ones((), dtype=torch.float32, device=self.device)
+        self.step = step
+        self._plan_key = None
+
+    def _fixed_entries(self):
+        """[(name, tensor)] of everything that is loaded in place, in file order except for a torch optimizer's state."""
+        head = [("model." + k, v) for k, v in self.model.state_dict().items()]
+        optim, tail = [], []
+        if self.fused:
+            optim += [(f"optim.exp_avg.{i}", t) for i, t in enumerate(self.opt.exp_avg)]
+            optim += [(f"optim.exp_avg_sq.{i}", t) for i, t in enumerate(self.opt.exp_avg_sq)]
+            optim.append(("optim.step", self.opt._plan.step_dev))
+        if self.ema is not None:
+            tail += [("ema.shadow." + n, s) for n, s in zip(self.ema.names, self.ema.shadows)]
+            tail.append(("ema.count", self.ema._plan.count_dev if self.ema._plan is not None else self._ema_count))
+        if self.metrics is not None:
+            tail.append(("metrics", self.metrics.buf))
+        if self.step is not None and hasattr(self.step, "_clean_steps") and self.fused and self.scaler is not None:
+            tail.append(("step.clean_steps", self.step._clean_steps))
+        if self.scaler is not None and self.on_gpu:
+            tail.append(("scaler.scale", self.scaler._scale))
+        return head, optim, tail
+
+    def _torch_optim_state(self):
+        """A torch optimizer's state_dict() split into packed tensors and a JSON description."""
+        sd = self.opt.state_dict()
+        entries, desc = [], {}
+        for idx, st in sd["state"].items():
+            d = desc[str(idx)] = {}
+            for key, v in st.items():
+                if isinstance(v, torch.Tensor) and v.device == self.device:
+                    name = f"optim.state.{idx}.{key}"
+                    entries.append((name, v))
+                    d[key] = {"entry": name}
+                elif isinstance(v, torch.Tensor):
+                    d[key] = {"tensor": v.cpu().reshape(-1).tolist(), "dtype": str(v.dtype).replace("torch.", ""),
+                              "shape": list(v.shape)}
+                else:
+                    d[key] = {"value": v}
+        return entries, {"state": desc, "param_groups": sd["param_groups"]}
+
+    def _check_ready(self, what):
+        if self.ema is not None and self.ema.is_swapped:
+            raise RuntimeError(f"TrainState.{what}: the weight averages are swapped into the model; swap() back first")
+
+    @staticmethod
+    def _spec(entries):
+        return [(n, t.dtype, tuple(t.shape)) for n, t in entries]
+
+    def _bind(self, entries):
+        """The plan (GPU) and the host buffer for this entry list; rebuilt only when the list changes."""
+        from . import backend
+        key = tuple((n, t.data_ptr(), t.dtype, tuple(t.shape)) for n, t in entries)
+        if key == self._plan_key:
+            return
+        offsets, sizes, total = backend.snapshot_layout(self._spec(entries))
+        if self.on_gpu:
+            self._plan = backend.get_backend().snapshot_plan([t for _, t in entries], [n for n, _ in entries])
+            assert self._plan.offsets == offsets and self._plan.packed_bytes == total
+        self._layout = (offsets, sizes, total)
+        if self._host is None or self._host.numel() != total:
+            self._host = torch.zeros(max(total, 1), dtype=torch.uint8)
+            if self.on_gpu:
+                self._host = self._host.pin_memory()
+            self._host_np = self._host.numpy()[:total]
+        self._plan_key = key
+        self._entries = entries
+        self._entry_list = [{"name": n, "dtype": str(t.dtype).replace("torch.", ""), "shape": list(t.shape),
+                             "offset": off, "nbytes": nb} for (n, t), off, nb in zip(entries, offsets, sizes)]
+
+    def _current_entries(self):
+        if self.fused and self._plan_key is not None:
+            return self._entries                  # a fixed set of tensors (the optimizer and the EMA refuse moved ones)
+        head, optim, tail = self._fixed_entries()
+        self._optim_desc = None
+        if not self.fused:
+            optim, self._optim_desc = self._torch_optim_state()
+        return head + optim + tail
+
+    # ---- host state -------------------------------------------------------------------------------------------
+    def host_state(self, progress):
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        rank = dist.get_rank() if world > 1 else 0
+        h = {"progress": {k: int(progress[k]) for k in ("epoch", "batch", "step")}, "world": world, "rank": rank,
+             "lr": self.opt.param_groups[0]["lr"],
+             "scheduler": None if self.scheduler is None else self.scheduler.state_dict(),
+             "rng": {"torch_cpu": _b64(torch.get_rng_state()),
+                     "cuda": _b64(torch.cuda.get_rng_state(self.device)) if self.on_gpu else None},
+             "generators": {n: g.bit_generator.state for n, g in self.generators.items()}}
+        if not self.fused and self.payload:
+            h["optimizer"] = self._optim_desc
+            if self.scaler is not None:            # torch's own GradScaler policy: its growth count (reading it synchronises)
+                h["scaler"] = {"growth_tracker": int(self.scaler.state_dict()["_growth_tracker"])}
+        return h
+
+    def _set_rng(self, h):
+        torch.set_rng_state(_unb64(h["rng"]["torch_cpu"]))
+        if self.on_gpu and h["rng"].get("cuda") is not None:
+            torch.cuda.set_rng_state(_unb64(h["rng"]["cuda"]), self.device)
+
+    def reapply_rng(self):
+        """Set the torch RNG states of the last load() again: a DataLoader iterator draws its base seed from the CPU
+        generator when it is made, and a run resumed inside an epoch makes that iterator after the state was loaded —
+        the uninterrupted run made it before the state was saved."""
+        if self._loaded_host is not None:
+            self._set_rng(self._loaded_host)
+
+    # ---- save ------------------------------------------------------------------------------------------------
+    def save_async(self, path, progress):
+        """Snapshot the state as it is now on the current stream; returns once the pack is enqueued."""
+        import json
+        self.wait()
+        self._check_ready("save_async")
+        if not self.payload:                      # a rank that only keeps its own host state
+            side = self.host_state(progress)
+            self._write_atomic(self.sidecar(path), json.dumps({k: side[k] for k in self._PER_RANK + ("progress", "world")}).encode())
+            return
+        entries = self._current_entries()
+        self._bind(entries)
+        offsets, sizes, total = self._layout
+        if self._ema_count is not None:
+            self._ema_count.fill_(self.ema._count)
+        host = self.host_state(progress)
+        header = {"version": self.VERSION, "packed_bytes": total, "entries": self._entry_list}
+        if self.sidecar_rank is not None:
+            side = {k: host.pop(k) for k in self._PER_RANK}
+            side["progress"], side["world"] = host["progress"], host["world"]
+            self._write_atomic(self.sidecar(path), json.dumps(side).encode())
+        header["host"] = host
+        json.dumps(host)                          # what cannot be written raises here, on the caller's thread
+        if self.on_gpu:
+            from .backend import get_backend
+            get_backend().snapshot_pack(self._plan)
+            packed = torch.cuda.Event()
+            packed.record()
+            with torch.cuda.stream(self._side):
+                self._side.wait_event(packed)
+                self._host[:total].copy_(self._plan.packed, non_blocking=True)
+                self._copied = torch.cuda.Event()
+                self._copied.record(self._side)
+            self._job = (path, header)
+        else:
+            with torch.no_grad():
+                for (n, t), off, nb in zip(entries, offsets, sizes):
+                    if nb:
+                        self._host[off:off + nb] = t.detach().contiguous().reshape(-1).view(torch.uint8)
+            self._job = (path, header)
+            self.poll()
+
+    def sidecar(self, path):
+        return f"{path}.rank{int(self.sidecar_rank)}.json"
+
+    def poll(self):
+        """Hand a finished device-to-host copy to the writer thread (never blocks)."""
+        if self._job is None or (self._copied is not None and not self._copied.query()):
+            return
+        import threading
+        (path, header), self._job, self._copied = self._job, None, None
+        self._thread = threading.Thread(target=self._write, args=(path, header, self._host_np), daemon=True)
+        self._thread.start()
+
+    def _write(self, path, header, payload):
+        """Writer thread: plain Python, no torch or HIP call."""
+        try:
+            import json
+            import struct
+            import zlib
+            header["crc32"] = zlib.crc32(payload) & 0xFFFFFFFF
+            text = json.dumps(header).encode()
+            pad = -(16 + len(text)) % self.PAGE
+            self._write_atomic(path, self.MAGIC + struct.pack("<Q", len(text)) + text + b"\0" * pad, payload)
+        except BaseException as e:              # re-raised by wait()
+            self._error = e
+
+    @staticmethod
+    def _write_atomic(path, *parts):
+        d = os.path.dirname(os.path.abspath(path))
+        os.makedirs(d, exist_ok=True)
+        tmp = path + ".tmp"
+        with open(tmp, "wb") as f:
+            for part in parts:
+                f.write(part)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+
+    def wait(self):
+        """Block until the save in flight is in place; re-raise what its writer raised."""
+        if getattr(self, "_job", None) is not None:
+            if self._copied is not None:
+                self._copied.synchronize()
+            self.poll()
+        if getattr(self, "_thread", None) is not None:
+            self._thread.join()
+            self._thread = None
+        if getattr(self, "_error", None) is not None:
+            e, self._error = self._error, None
+            raise e
+
+    def close(self):
+        self.wait()
+
+    # ---- load ------------------------------------------------------------------------------------------------
+    @classmethod
+    def read_header(cls, path):
+        """(header dict, payload offset) of a snapshot file; refuses a wrong magic or version and a short file."""
+        import json
+        import struct
+        size = os.path.getsize(path)
+        with open(path, "rb") as f:
+            head = f.read(16)
+            if len(head) < 16 or head[:8] != cls.MAGIC:
+                raise ValueError(f"{path}: not a training snapshot (magic {head[:8]!r}, expected {cls.MAGIC!r})")
+            n = struct.unpack("<Q", head[8:])[0]
+            if 16 + n > size:
+                raise ValueError(f"{path}: short file: the header is {n} bytes, the file holds {size}")
+            header = json.loads(f.read(n).decode())
+        if header.get("version") != cls.VERSION:
+            raise ValueError(f"{path}: snapshot format version {header.get('version')!r}, this build reads {cls.VERSION}")
+        start = -(-(16 + n) // cls.PAGE) * cls.PAGE
+        if start + int(header["packed_bytes"]) > size:
+            raise ValueError(f"{path}: short file: {size} bytes, header and payload need {start + int(header['packed_bytes'])}")
+        return header, start
+
+    def load(self, path):
+        """Put the state of the file back, in place; returns its progress.  Refuses, naming the first difference, a wrong
+        magic or version, a short file, a CRC mismatch, an entry whose name, dtype or shape differs from the live set and
+        another world size."""
+        import json
+        import zlib
+        from . import backend
+        self.wait()
+        self._check_ready("load")
+        header, start = self.read_header(path)
+        host = dict(header["host"])
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        if int(host["world"]) != world:
+            raise ValueError(f"{path}: written by a world of {host['world']} ranks, this one has {world}")
+        if self.sidecar_rank is not None:
+            with open(self.sidecar(path)) as f:
+                side = json.load(f)
+            if side["progress"] != host["progress"] or int(side["world"]) != world:
+                raise ValueError(f"{self.sidecar(path)}: written at {side['progress']} in a world of {side['world']}, "
+                                 f"{path} at {host['progress']} in a world of {host['world']}")
+            host.update({k: side[k] for k in self._PER_RANK})
+        if set(host["generators"]) != set(self.generators):
+            raise ValueError(f"{path}: generators {sorted(host['generators'])} in the file, {sorted(self.generators)} given")
+        # the entries: everything but a torch optimizer's state must be the live set, name by name
+        head, optim, tail = self._fixed_entries()
+        live = head + optim + tail
+        entries, k = [], 0
+        dt = lambda e: getattr(torch, e["dtype"])  # noqa: E731
+        for i, e in enumerate(header["entries"]):
+            if not self.fused and e["name"].startswith("optim.state."):
+                entries.append((e["name"], torch.zeros(e["shape"], dtype=dt(e), device=self.device)))
+                continue
+            if k >= len(live):
+                raise ValueError(f"{path}: entry {i} ({e['name']}) has no counterpart in the live state")
+            n, t = live[k]
+            if e["name"] != n:
+                raise ValueError(f"{path}: entry {i} is {e['name']} in the file and {n} in the live state")
+            if dt(e) != t.dtype or tuple(e["shape"]) != tuple(t.shape):
+                raise ValueError(f"{path}: entry {n} is {e['dtype']} {tuple(e['shape'])} in the file and "
+                                 f"{str(t.dtype).replace('torch.', '')} {tuple(t.shape)} in the live state")
+            entries.append((n, t))
+            k += 1
+        if k < len(live):
+            raise ValueError(f"{path}: the live state has {live[k][0]}, the file does not")
+        offsets, sizes, total = backend.snapshot_layout(self._spec(entries))
+        if total != int(header["packed_bytes"]) or offsets != [e["offset"] for e in header["entries"]] \
+                or sizes != [e["nbytes"] for e in header["entries"]]:
+            raise ValueError(f"{path}: the offsets in the header are not the layout of its entries")
+        self._plan_key = None
+        self._bind(entries)
+        with open(path, "rb") as f:
+            f.seek(start)
+            got = f.readinto(memoryview(self._host_np)) if total else 0
+        if got != total:
+            raise ValueError(f"{path}: short file: {got} of {total} payload bytes")
+        crc = zlib.crc32(self._host_np) & 0xFFFFFFFF
+        if crc != int(header["crc32"]):
+            raise ValueError(f"{path}: payload CRC32 {crc:#010x}, the header says {int(header['crc32']):#010x}")
+        with torch.no_grad():
+            if self.on_gpu:
+                self._plan.packed.copy_(self._host[:total], non_blocking=True)
+                backend.get_backend().snapshot_unpack(self._plan)
+                torch.cuda.current_stream().synchronize()          # the pinned buffer and fresh tensors are free again
+            else:
+                for (n, t), off, nb in zip(entries, offsets, sizes):
+                    if nb:
+                        t.copy_(self._host[off:off + nb].view(t.dtype).reshape(t.shape))
+        # host state
+        if self._ema_count is not None:
+            self.ema._count = int(self._ema_count[0])
+        if not self.fused:
+            by_name = dict(entries)
+            state = {}
+            for idx, d in host["optimizer"]["state"].items():
+                st = state[int(idx)] = {}
+                for key, v in d.items():
+                    if "entry" in v:
+                        st[key] = by_name[v["entry"]]
+                    elif "tensor" in v:
+                        st[key] = torch.tensor(v["tensor"], dtype=getattr(torch, v["dtype"])).reshape(v["shape"])
+                    else:
+                        st[key] = v["value"]
+            groups = host["optimizer"]["param_groups"]
+            for g in groups:
+                if "betas" in g:
+                    g["betas"] = tuple(g["betas"])
+            self.opt.load_state_dict({"state": state, "param_groups": groups})
+            if self.scaler is not None and "scaler" in host:
+                sd = self.scaler.state_dict()
+                sd["_growth_tracker"] = int(host["scaler"]["growth_tracker"])
+                self.scaler.load_state_dict(sd)
+            self._plan_key = None                 # the tensors made above are now the optimizer's (or copies of them)
+        self.opt.param_groups[0]["lr"] = host["lr"]
+        if self.scheduler is not None:
+            if host["scheduler"] is None:
+                raise ValueError(f"{path}: written without a scheduler, this run has one")
+            self.scheduler.load_state_dict(host["scheduler"])
+        for n, g in self.generators.items():
+            g.bit_generator.state = host["generators"][n]
+        self._loaded_host = host
+        self._set_rng(host)
+        return dict(host["progress"])
+
+    _loaded_host = None
+
+
 class GraphedTrainStep:
     """The same step captured once into a hipGraph and replayed: every kernel of the library only enqueues on the
     current stream (no allocation, no host sync), so forward + loss + backward + gradient exchange + unscale / clip /
@@ -1459,7 +1891,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           checkpoint_path=None, num_classes=1000, num_workers=0, collate_fn="mix", log_every=100, max_steps=None,
           destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
           device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None,
-          ema=None):
+          ema=None, snapshot_path=None, snapshot_every=None, resume=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -1526,7 +1958,20 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     parameters — every rank then holds the same average without any communication — and updated behind every optimizer
     step (not behind one skipped for inf/NaN gradients).  With checkpoint_path, rank 0 also writes
     `ema.model_state_dict()` beside it as `<stem>_ema<ext>` once per epoch.  The live model is what is returned; the
-    ModelEMA is `model._calm_ema` afterwards (on the CPU with the model)."""
+    ModelEMA is `model._calm_ema` afterwards (on the CPU with the model).
+
+    snapshot_path / snapshot_every / resume (training snapshots, `TrainState`): with snapshot_path, rank 0 writes the
+    whole state of the run — model, optimizer, EMA, scaler, scheduler, RNG states, collate / augmentation generators,
+    position — to that one file right behind every snapshot_every-th step, at every epoch end and behind the last step
+    of a run that max_steps cuts short; the training thread pays one kernel launch per snapshot, the copy and the write
+    run beside the following steps.  In a world of more than one rank every rank also writes its own host state (its RNG
+    states and generators differ) to `<snapshot_path>.rank<r>.json`; no collective is added.  The per-epoch
+    checkpoint_path files are written as before.  resume=path: every rank loads that file (and its sidecar) in place
+    before the first step, the loop continues at the saved epoch and batch — the indices of the batches already trained
+    on are dropped from the sampler, nothing is loaded and thrown away — and max_steps counts from the restored step.
+    The resumed trajectory equals the uninterrupted one bit for bit where the augmentation generators live in the main
+    process (device_collate=True, or num_workers=0); the `SoftMixCollate` generators inside persistent DataLoader
+    workers are not captured, and a resumed run then draws a fresh stream from them."""
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
     if device_metrics and not (use_gpu and _backend.get_loss_kernels()):
@@ -1553,6 +1998,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             raise ValueError("random_resized_crop excludes device_resize and crop: it is the crop and the resize")
     if graph and not (use_gpu and (optimizer == "fused" or isinstance(optimizer, FusedClipAdamW))):
         raise ValueError('graph=True needs use_gpu=True and optimizer="fused" (FusedClipAdamW)')
+    if snapshot_every is not None and (snapshot_path is None or int(snapshot_every) < 1):
+        raise ValueError("snapshot_every counts steps (>= 1) between the snapshots written to snapshot_path")
     if ema is not None:
         ema_kw = dict(ema) if isinstance(ema, dict) else {"decay": float(ema)}
         if not set(ema_kw) <= {"decay", "warmup"} or not 0.0 <= float(ema_kw.get("decay", 0.9999)) < 1.0:
@@ -1603,12 +2050,41 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     model.train()
     n_steps = 0
     gstep = None
+    st = None
+    start_epoch = start_batch = 0
+    if snapshot_path is not None or resume is not None:
+        gens = {}
+        if dcoll is not None:
+            gens["collate"] = dcoll.rng
+            if daug is not None:
+                gens["augment"] = daug.rng
+            if random_resized_crop is not None:
+                gens["resized_crop"] = random_resized_crop.rng
+        elif isinstance(collate_fn, SoftMixCollate) and num_workers == 0:
+            gens["mix"] = collate_fn.rng
+        st = TrainState(model, optimizer, scaler=scaler if use_gpu else None, scheduler=scheduler, ema=ema_obj, step=step,
+                        metrics=metrics, generators=gens, payload=rank == 0 and local_rank == 0,
+                        sidecar_rank=rank if world > 1 else None)
     try:
-        for epoch in range(epochs):
+        if resume is not None:
+            progress = st.load(resume)
+            start_epoch, start_batch, n_steps = progress["epoch"], progress["batch"], progress["step"]
+        for epoch in range(start_epoch, epochs):
             sampler.set_epoch(epoch)
             model.train()
             epoch_loss = 0.0
-            for i, batch in enumerate(loader):
+            skip = start_batch if epoch == start_epoch else 0
+            epoch_loader = loader
+            if skip:                                # the rest of the epoch the saved run was in: indices dropped, not data
+                epoch_loader = DataLoader(dataset, batch_size=batch_size, sampler=resume_tail(sampler, skip, batch_size),
+                                          collate_fn=collate_fn, num_workers=num_workers, pin_memory=use_gpu,
+                                          drop_last=bool(graph))
+            batches = iter(epoch_loader)
+            if skip:
+                st.reapply_rng()                    # (the iterator drew its base seed; the saved run had drawn it before)
+            n_batches = skip + len(epoch_loader)
+            i = skip - 1
+            for i, batch in enumerate(batches, start=skip):
                 decisions, window = None, crop
                 if resize_window:
                     packed, meta, y = batch
@@ -1632,18 +2108,28 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                     gstep = GraphedTrainStep(model, optimizer, x, y, max_norm=1.0, scaler=scaler,
                                              autocast_dtype=torch.bfloat16, reducer=reducer, restore_after_warmup=True,
                                              metrics=metrics, ema=ema_obj)
+                    if st is not None:              # the captured step keeps its own growth count: the current one moves in
+                        if hasattr(step, "_clean_steps") and hasattr(gstep.inner, "_clean_steps"):
+                            gstep.inner._clean_steps.copy_(step._clean_steps)
+                        st.bind_step(gstep)
                 if gstep is not None and x.shape == gstep.x.shape and y.shape == gstep.y.shape:
                     loss, y_hat = gstep(x, y)
                 else:
                     loss, y_hat = step(x, y)
+                n_steps += 1
+                done = max_steps is not None and n_steps >= max_steps
+                if st is not None:                  # right behind the step, before anything else touches state
+                    if snapshot_path is not None and ((snapshot_every and n_steps % int(snapshot_every) == 0)
+                                                      or (done and i + 1 < n_batches)):
+                        st.save_async(snapshot_path, {"epoch": epoch, "batch": i + 1, "step": n_steps})
+                    st.poll()
                 if metrics is None:
                     epoch_loss += loss.item()                                                              # cls:97
                 if rank == 0 and local_rank == 0 and i % log_every == 0:
                     correct = (y_hat.reshape(y.shape[0], -1).argmax(1) == y.argmax(1)).sum().item()
                     print(f"Epoch: {epoch + 1}, Batch: {i + 1}, Device: [{rank}, {local_rank}], Loss: {float(loss)}, "
                           f"Accuracy: {100.0 * correct / y.size(0):.4f}%")
-                n_steps += 1
-                if max_steps is not None and n_steps >= max_steps:
+                if done:
                     break
             if metrics is not None:
                 loss_sum, agree, rows, _ = metrics.read()          # the epoch's one device-to-host copy
@@ -1659,9 +2145,13 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                     torch.save(ema_obj.model_state_dict(), stem + "_ema" + ext)
             if scheduler is not None:
                 scheduler.step()                                                                           # cls:108-109
+            if st is not None and snapshot_path is not None and i + 1 >= n_batches:     # the epoch ran to its end
+                st.save_async(snapshot_path, {"epoch": epoch + 1, "batch": 0, "step": n_steps})
             if max_steps is not None and n_steps >= max_steps:
                 break
     finally:
+        if st is not None:                 # the last snapshot is in place before the graph and the process group go
+            st.close()
         if gstep is not None:              # the captured graph holds RCCL kernels: released before the process group
             gstep = None
             import gc

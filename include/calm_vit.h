@@ -571,6 +571,36 @@ int calm_ema_swap(const calm_ema_entry* entries_dev, int32_t n_entries, const in
                   int32_t n_chunks, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Training snapshots (additions to ABI v7): every state tensor of a run gathered into one contiguous device buffer in
+ * one launch, and scattered back in place in one launch — what trainer.TrainState saves and resumes from.
+ *   calm_snapshot_pack    packed[entry.offset + b] = entry.tensor[b]   for every entry, 0 <= b < entry.nbytes
+ *   calm_snapshot_unpack  entry.tensor[b] = packed[entry.offset + b]
+ * Bits are moved through integer registers (no arithmetic: NaN payloads and integer counters survive).  Work items are
+ * chunks of calm_snapshot_chunk_bytes() consecutive bytes of one entry: chunk_entry_dev[k] = entry of chunk k,
+ * entry.chunk0 = its first chunk (as calm_ema_swap).  One workgroup per chunk, every word moved by one thread: no atomics,
+ * no workspace, nothing allocates or synchronises (both capture into a hipGraph).  `packed` is 16-byte aligned
+ * (CALM_E_LAYOUT otherwise) and offsets are multiples of 16, so the packed side of every chunk is 16-byte aligned; a chunk
+ * whose tensor side is too moves 16-byte vectors with a word tail, any other 4-byte aligned tensor moves single words.
+ * The bytes of `packed` between two entries are never written by pack and never read by unpack.  The entries do not
+ * overlap, in memory or in the buffer, and offset + nbytes <= packed_bytes: the host that builds the table checks it (a
+ * record that leaves the buffer moves nothing).
+ * CALM_E_INVAL, before any launch: a null entries_dev / chunk_entry_dev / packed, n_entries <= 0, n_chunks <= 0,
+ * packed_bytes <= 0.
+ * ------------------------------------------------------------------------------------- */
+typedef struct calm_snapshot_entry {   /* 32 bytes */
+    void*   tensor;      /* live tensor, 4-byte aligned, contiguous           */
+    int64_t offset;      /* byte offset in the packed buffer, multiple of 16 */
+    int64_t nbytes;      /* multiple of 4, > 0                               */
+    int32_t chunk0;      /* index of this entry's first chunk                */
+    int32_t reserved;    /* 0 */
+} calm_snapshot_entry;
+int32_t calm_snapshot_chunk_bytes(void);   /* multiple of 16 */
+int calm_snapshot_pack(const calm_snapshot_entry* entries_dev, int32_t n_entries, const int32_t* chunk_entry_dev,
+                       int32_t n_chunks, void* packed, int64_t packed_bytes, void* stream);
+int calm_snapshot_unpack(const calm_snapshot_entry* entries_dev, int32_t n_entries, const int32_t* chunk_entry_dev,
+                         int32_t n_chunks, const void* packed, int64_t packed_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Device-side batch collate feeding the path: uint8 images [B,3,H,W] -> normalised fp32 batch with
  * per-sample horizontal flip (flip[b] != 0; NULL = none) and the batch-level CutMix / MixUp of
  * distributed_trainer_cls.py:58-61 (torchvision.transforms.v2 semantics: partner = the batch rolled by one):
