@@ -190,7 +190,37 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-class OptimPlan:
+def chunk_table(lengths, chunk):
+    """The host half of the chunk walk of csrc/chunk_table.h: entries of `lengths` units each are cut into chunks of
+    `chunk` units -> (chunk0 per entry, the entry of every chunk).  An entry of length 0 has no chunk.  Host only."""
+    chunk0, chunk_entry = [], []
+    for i, n in enumerate(lengths):
+        chunk0.append(len(chunk_entry))
+        chunk_entry += [i] * ((n + chunk - 1) // chunk)
+    return chunk0, chunk_entry
+
+
+def _disjoint(spans):
+    """No two of the [begin, end) address ranges share a byte (an exchange of, or a scatter into, ranges that do is a race)."""
+    spans = sorted(spans)
+    return not any(b[0] < a[1] for a, b in zip(spans, spans[1:]))
+
+
+class ChunkPlan:
+    """What every chunk-table launch is given: `n` records in `table_dev` (device bytes) and the record of each of the
+    `n_chunks` chunks in `chunk_dev` (int32)."""
+
+    def _tables(self, rec, lengths, chunk, dev):
+        """rec: numpy array of the records (its chunk0 field is filled in here), `lengths[i]` units in record i."""
+        chunk0, chunk_entry = chunk_table(lengths, chunk)
+        rec["chunk0"] = chunk0
+        self.n = len(rec)
+        self.n_chunks = len(chunk_entry)
+        self.table_dev = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(dev)
+        self.chunk_dev = torch.tensor(chunk_entry, dtype=torch.int32, device=dev)
+
+
+class OptimPlan(ChunkPlan):
     """Device table of calm_optim_tensor records for calm_optim_step; only the gradient pointers change per step.
 
     The pointers travel through a RING of pinned staging buffers, each guarded by an event recorded behind its
@@ -201,10 +231,7 @@ class OptimPlan:
     RING = 4
 
     def __init__(self, be, records):
-        chunk = int(be.lib.calm_optim_chunk_elems())
-        self.n = len(records)
-        rec = np.zeros(self.n, dtype=np.dtype(_lib.OptimTensor))
-        chunk_tensor = []
+        rec = np.zeros(len(records), dtype=np.dtype(_lib.OptimTensor))
         for i, r in enumerate(records):
             p = r["param"]
             if not p.is_contiguous():
@@ -219,18 +246,15 @@ class OptimPlan:
                 if rows * cols != p.numel() or p.numel() >= 2 ** 31:      # the kernels index (row, col) in 32 bits
                     raise ValueError("spectral-norm layer too large for the optimizer-side step")
                 e["sn_u"], e["sn_v"], e["sn_sigma"], e["rows"], e["cols"] = _ptr(u), _ptr(v), _ptr(sigma), rows, cols
-            e["chunk0"] = len(chunk_tensor)
-            chunk_tensor += [i] * ((p.numel() + chunk - 1) // chunk)
         dev = records[0]["param"].device
+        # (table_dev as uploaded here has no gradient pointers: upload() rewrites it in front of every step)
+        self._tables(rec, [r["param"].numel() for r in records], int(be.lib.calm_optim_chunk_elems()), dev)
         self.rec = rec
-        self.n_chunks = len(chunk_tensor)
-        self.chunk_dev = torch.tensor(chunk_tensor, dtype=torch.int32, device=dev)
         self.hosts = [torch.empty(rec.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
         self.graph_host = torch.empty(rec.nbytes, dtype=torch.uint8).pin_memory()   # the table a captured step copies from
         self.events = [None] * self.RING
         self.slot = 0
         self.uploaded = None                    # gradient pointers of the table now (being) copied to table_dev
-        self.table_dev = torch.empty(rec.nbytes, dtype=torch.uint8, device=dev)
         self.scratch = torch.empty(6 * self.n + 4 + 3 * self.n_chunks, dtype=torch.float32, device=dev)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)      # advanced by the device, not on skipped steps
         self.param_ptrs = rec["param"].copy()
@@ -261,7 +285,7 @@ class OptimPlan:
         self.uploaded = grad_ptrs.copy()
 
 
-class EmaPlan:
+class EmaPlan(ChunkPlan):
     """Device tables of calm_ema_entry records for calm_ema_update / calm_ema_swap, fixed at construction: the entry
     table, the chunk table, the update counter `count_dev` (int32[1], advanced by the device, not on skipped updates) and
     `weight_out` (float32[2]: the weight 1 - d of the last update, and whether it was skipped).  `src_ptrs` / `ema_ptrs`
@@ -269,7 +293,6 @@ class EmaPlan:
     no elements have no entry."""
 
     def __init__(self, be, pairs):
-        chunk = int(be.lib.calm_ema_chunk_elems())
         for src, ema in pairs:
             if not (src.is_contiguous() and ema.is_contiguous()):
                 raise TypeError("weight EMA expects contiguous parameters and averages")
@@ -280,21 +303,13 @@ class EmaPlan:
         if not pairs:
             raise ValueError("weight EMA needs at least one tensor with elements")
         ent = np.zeros(len(pairs), dtype=np.dtype(_lib.EmaEntry))
-        chunk_entry, spans = [], []
         for i, (src, ema) in enumerate(pairs):
             e = ent[i]
             e["src"], e["ema"], e["numel"] = src.data_ptr(), ema.data_ptr(), src.numel()
-            e["chunk0"] = len(chunk_entry)
-            chunk_entry += [i] * ((src.numel() + chunk - 1) // chunk)
-            spans += [(src.data_ptr(), src.data_ptr() + 4 * src.numel()), (ema.data_ptr(), ema.data_ptr() + 4 * src.numel())]
-        spans.sort()
-        if any(b[0] < a[1] for a, b in zip(spans, spans[1:])):        # an exchange of overlapping ranges is a race
+        if not _disjoint((t.data_ptr(), t.data_ptr() + 4 * t.numel()) for pr in pairs for t in pr):
             raise ValueError("weight EMA expects parameters and averages that do not overlap in memory")
         dev = pairs[0][0].device
-        self.n = len(pairs)
-        self.n_chunks = len(chunk_entry)
-        self.table_dev = torch.from_numpy(ent.view(np.uint8).reshape(-1).copy()).to(dev)
-        self.chunk_dev = torch.tensor(chunk_entry, dtype=torch.int32, device=dev)
+        self._tables(ent, [src.numel() for src, _ in pairs], int(be.lib.calm_ema_chunk_elems()), dev)
         self.count_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.weight_out = torch.zeros(2, dtype=torch.float32, device=dev)
         self.src_ptrs = ent["src"].copy()
@@ -331,16 +346,12 @@ def snapshot_layout(specs):
 def snapshot_chunks(sizes, chunk_bytes):
     """The chunk table of calm_snapshot_pack / _unpack over entries of `sizes` bytes (all > 0): (chunk0 per entry, the
     entry of every chunk).  Host only."""
-    chunk0, chunk_entry = [], []
-    for i, nb in enumerate(sizes):
-        if nb <= 0:
-            raise ValueError("snapshot chunk table: entries have at least one word")
-        chunk0.append(len(chunk_entry))
-        chunk_entry += [i] * ((nb + chunk_bytes - 1) // chunk_bytes)
-    return chunk0, chunk_entry
+    if any(nb <= 0 for nb in sizes):
+        raise ValueError("snapshot chunk table: entries have at least one word")
+    return chunk_table(sizes, chunk_bytes)
 
 
-class SnapshotPlan:
+class SnapshotPlan(ChunkPlan):
     """Device tables of calm_snapshot_entry records for calm_snapshot_pack / _unpack over a fixed list of live tensors, and
     the packed device buffer they gather into (zeroed once: the padding between entries is never written again, so equal
     states give equal buffers).  `offsets` / `sizes` are per given tensor (snapshot_layout over them; a tensor without
@@ -370,26 +381,33 @@ class SnapshotPlan:
         for (_, off, nb) in live:                                  # (what snapshot_layout guarantees, kept as a check)
             if off % SNAPSHOT_ALIGN or nb % 4 or off + nb > self.packed_bytes:
                 raise ValueError("snapshot plan: an entry leaves the packed buffer")
-        spans = sorted((t.data_ptr(), t.data_ptr() + nb) for t, _, nb in live)
-        if any(b[0] < a[1] for a, b in zip(spans, spans[1:])):        # two entries scattering into one word is a race
+        if not _disjoint((t.data_ptr(), t.data_ptr() + nb) for t, _, nb in live):
             raise ValueError("snapshot plan expects tensors that do not overlap in memory")
         self.chunk_bytes = int(be.lib.calm_snapshot_chunk_bytes())
-        chunk0, chunk_entry = snapshot_chunks([nb for _, _, nb in live], self.chunk_bytes)
         ent = np.zeros(len(live), dtype=np.dtype(_lib.SnapshotEntry))
         for i, (t, off, nb) in enumerate(live):
             e = ent[i]
-            e["tensor"], e["offset"], e["nbytes"], e["chunk0"] = t.data_ptr(), off, nb, chunk0[i]
+            e["tensor"], e["offset"], e["nbytes"] = t.data_ptr(), off, nb
         dev = live[0][0].device
-        self.n = len(live)
-        self.n_chunks = len(chunk_entry)
+        self._tables(ent, [nb for _, _, nb in live], self.chunk_bytes, dev)          # (live entries: every nb > 0)
         self.entries = ent
-        self.table_dev = torch.from_numpy(ent.view(np.uint8).reshape(-1).copy()).to(dev)
-        self.chunk_dev = torch.tensor(chunk_entry, dtype=torch.int32, device=dev)
         self.packed = torch.zeros(self.packed_bytes, dtype=torch.uint8, device=dev)
         if self.packed.data_ptr() % SNAPSHOT_ALIGN:
             raise RuntimeError("snapshot plan: the packed buffer is not 16-byte aligned")
         self.ptrs = ent["tensor"].copy()
         self.tensors = [t for t, _, _ in live]                        # keeps the addresses in the table alive
+
+
+class CastPlan(ChunkPlan):
+    """Device tables of calm_cast_entry records for calm_cast_bf16 over fixed (fp32 source, bf16 destination) pairs."""
+
+    def __init__(self, be, pairs):
+        ent = np.zeros(len(pairs), dtype=np.dtype(_lib.CastEntry))
+        for i, (src, dst) in enumerate(pairs):
+            if dst.dtype != torch.bfloat16 or dst.numel() != src.numel() or not (src.is_contiguous() and dst.is_contiguous()):
+                raise TypeError("cast_plan: contiguous fp32 source / bf16 destination of equal size expected")
+            ent[i]["src"], ent[i]["dst"], ent[i]["numel"] = _ptr(src), _ptr(dst, bf16_ok=True), src.numel()
+        self._tables(ent, [src.numel() for src, _ in pairs], int(be.lib.calm_cast_chunk_elems()), pairs[0][0].device)
 
 
 class SnPlan:
@@ -822,21 +840,7 @@ class HipBackend:
     # ---- bf16 weight copies --------------------------------------------------------------
     def cast_plan(self, pairs):
         """pairs: [(fp32 source tensor, bf16 destination tensor of the same numel)] -> plan for cast_run."""
-        chunk = int(self.lib.calm_cast_chunk_elems())
-        ent = np.zeros(len(pairs), dtype=np.dtype(_lib.CastEntry))
-        chunk_entry = []
-        for i, (src, dst) in enumerate(pairs):
-            if dst.dtype != torch.bfloat16 or dst.numel() != src.numel() or not (src.is_contiguous() and dst.is_contiguous()):
-                raise TypeError("cast_plan: contiguous fp32 source / bf16 destination of equal size expected")
-            ent[i]["src"], ent[i]["dst"], ent[i]["numel"] = _ptr(src), _ptr(dst, bf16_ok=True), src.numel()
-            ent[i]["chunk0"] = len(chunk_entry)
-            chunk_entry += [i] * ((src.numel() + chunk - 1) // chunk)
-        dev = pairs[0][0].device
-        plan = SnPlan(None, torch.from_numpy(ent.view(np.uint8).reshape(-1).copy()).to(dev),
-                      torch.tensor(chunk_entry, dtype=torch.int32, device=dev),
-                      tuple(t.data_ptr() for pr in pairs for t in pr))
-        plan.n_chunks = len(chunk_entry)
-        return plan
+        return CastPlan(self, pairs)
 
     # ---- fp8 (BASELINE config #5) ------------------------------------------------------
     def quantize_fp8(self, x, q_dtype):
@@ -862,7 +866,7 @@ class HipBackend:
                    "calm_cast_bf16_one")
 
     def cast_run(self, plan):
-        _lib.check(self.lib.calm_cast_bf16(plan.blob_dev.data_ptr(), plan.scratch.data_ptr(), plan.n_chunks, _stream()),
+        _lib.check(self.lib.calm_cast_bf16(plan.table_dev.data_ptr(), plan.chunk_dev.data_ptr(), plan.n_chunks, _stream()),
                    "calm_cast_bf16")
 
     # ---- RoPE -------------------------------------------------------------------------

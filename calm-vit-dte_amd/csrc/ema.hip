@@ -5,29 +5,16 @@
 //                        d = decay | min(decay, (1 + n) / (10 + n)), weight_out = {1 - d, 0}, count = n + 1
 //   pass 2  ema_update   per chunk: nothing if weight_out[1] != 0, otherwise ema += w * (src - ema)
 //   swap    ema_swap     per chunk: src <-> ema, bits moved through integer registers (NaN payloads survive)
-// Work item = chunk of CHUNK consecutive elements of one entry (table built by the host, as for calm_cast_bf16 and
-// calm_optim_step).  A chunk whose src + i0 and ema + i0 are both 16-byte aligned moves 16-byte vectors with a scalar tail;
+// Work item = chunk of CHUNK consecutive elements of one entry (the walk of chunk_table.h).  A chunk whose src + i0 and ema + i0 are both 16-byte aligned moves 16-byte vectors with a scalar tail;
 // any other 4-byte aligned pair moves single words.  Every element belongs to one thread of one workgroup: no workgroup
 // reads a word another one of the same launch writes, no atomics, and the result per element does not depend on the grid.
-#include "common.h"
+#include "chunk_table.h"
 
 namespace {
 
 constexpr int NT = 256;
-constexpr int CHUNK = 16384;                 // elements per work item (64 per thread)
+constexpr int CHUNK = CHUNK_ELEMS;           // elements per work item (64 per thread)
 constexpr int U = 4;                         // 16-byte vectors a thread has in flight per tensor
-static_assert(CHUNK % 4 == 0, "the vector path starts every chunk on a multiple of 4 elements");
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// A pointer read out of the table is a generic one to the compiler (flat_load / flat_store); these say it is device memory
-// (global_load / global_store: one wait counter, no aperture check).
-#define EMA_GLOBAL __attribute__((address_space(1)))
-typedef EMA_GLOBAL float gf32;
-typedef EMA_GLOBAL f32x4 gf32x4;
-typedef EMA_GLOBAL uint32_t gu32;
-typedef EMA_GLOBAL u32x4 gu32x4;
-
-__device__ __forceinline__ bool dev_aligned16(const EMA_GLOBAL void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 __global__ void ema_weight(float decay, int schedule, int* __restrict__ count, const float* __restrict__ skip,
                            float* __restrict__ weight_out) {
@@ -48,39 +35,28 @@ __global__ void ema_weight(float decay, int schedule, int* __restrict__ count, c
 }
 
 // src and ema are not __restrict__ for the compiler (they come out of a table), so the loads of U vectors are issued
-// by hand ahead of the first store: U x 2 x 16 bytes in flight per thread
+// ahead of the first store (loads_ahead_of_stores): U x 2 x 16 bytes in flight per thread
 __global__ __launch_bounds__(NT) void ema_update(const calm_ema_entry* __restrict__ E, const int* __restrict__ chunk_entry,
                                                  const float* __restrict__ weight) {
     if (weight[1] != 0.f) return;             // skipped step (inf/NaN gradients): the average keeps every bit
     const float w = weight[0];
     const calm_ema_entry e = E[chunk_entry[blockIdx.x]];
-    const long i0 = (long)(blockIdx.x - e.chunk0) * CHUNK;
-    const long i1 = min(i0 + (long)CHUNK, (long)e.numel);
+    const auto [i0, i1] = chunk_span(blockIdx.x, CHUNK, e.chunk0, e.numel);
     const gf32* src = (const gf32*)e.src;
     gf32* ema = (gf32*)e.ema;
     if (dev_aligned16(src + i0) && dev_aligned16(ema + i0)) {
         const long v1 = i0 + ((i1 - i0) & ~3L);
-        for (long b = i0 + 4 * threadIdx.x; b < v1; b += 4 * NT * U) {
-            f32x4 x[U], a[U];
+        struct Pair { f32x4 x, a; };
+        const auto load = [&](long i) __attribute__((always_inline)) {
+            return Pair{*(const gf32x4*)(src + i), *(const gf32x4*)(ema + i)};
+        };
+        const auto store = [&](long i, const Pair& v) __attribute__((always_inline)) {
+            f32x4 r;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long i = b + (long)u * 4 * NT;
-                if (i < v1) {
-                    x[u] = *(const gf32x4*)(src + i);
-                    a[u] = *(const gf32x4*)(ema + i);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long i = b + (long)u * 4 * NT;
-                if (i < v1) {
-                    f32x4 r;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) r[k] = fmaf(w, x[u][k] - a[u][k], a[u][k]);
-                    *(gf32x4*)(ema + i) = r;
-                }
-            }
-        }
+            for (int k = 0; k < 4; ++k) r[k] = fmaf(w, v.x[k] - v.a[k], v.a[k]);
+            *(gf32x4*)(ema + i) = r;
+        };
+        loads_ahead_of_stores<U, 4, NT>(i0, v1, load, store);
         for (long i = v1 + threadIdx.x; i < i1; i += NT) ema[i] = fmaf(w, src[i] - ema[i], ema[i]);
     } else {
         for (long i = i0 + threadIdx.x; i < i1; i += NT) ema[i] = fmaf(w, src[i] - ema[i], ema[i]);
@@ -89,31 +65,20 @@ __global__ __launch_bounds__(NT) void ema_update(const calm_ema_entry* __restric
 
 __global__ __launch_bounds__(NT) void ema_swap(const calm_ema_entry* __restrict__ E, const int* __restrict__ chunk_entry) {
     const calm_ema_entry e = E[chunk_entry[blockIdx.x]];
-    const long i0 = (long)(blockIdx.x - e.chunk0) * CHUNK;
-    const long i1 = min(i0 + (long)CHUNK, (long)e.numel);
+    const auto [i0, i1] = chunk_span(blockIdx.x, CHUNK, e.chunk0, e.numel);
     gu32* s = (gu32*)e.src;
     gu32* a = (gu32*)e.ema;
     if (dev_aligned16(s + i0) && dev_aligned16(a + i0)) {
         const long v1 = i0 + ((i1 - i0) & ~3L);
-        for (long b = i0 + 4 * threadIdx.x; b < v1; b += 4 * NT * U) {
-            u32x4 x[U], y[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long i = b + (long)u * 4 * NT;
-                if (i < v1) {
-                    x[u] = *(const gu32x4*)(s + i);
-                    y[u] = *(const gu32x4*)(a + i);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long i = b + (long)u * 4 * NT;
-                if (i < v1) {
-                    *(gu32x4*)(s + i) = y[u];
-                    *(gu32x4*)(a + i) = x[u];
-                }
-            }
-        }
+        struct Pair { u32x4 x, y; };
+        const auto load = [&](long i) __attribute__((always_inline)) {
+            return Pair{*(const gu32x4*)(s + i), *(const gu32x4*)(a + i)};
+        };
+        const auto store = [&](long i, const Pair& v) __attribute__((always_inline)) {
+            *(gu32x4*)(s + i) = v.y;
+            *(gu32x4*)(a + i) = v.x;
+        };
+        loads_ahead_of_stores<U, 4, NT>(i0, v1, load, store);
         for (long i = v1 + threadIdx.x; i < i1; i += NT) { const uint32_t x = s[i]; s[i] = a[i]; a[i] = x; }
     } else {
         for (long i = i0 + threadIdx.x; i < i1; i += NT) { const uint32_t x = s[i]; s[i] = a[i]; a[i] = x; }

@@ -15,12 +15,12 @@
 //                           p *= 1 - lr*wd; m = b1 m + (1-b1) g'; v = b2 v + (1-b2) g'^2;
 //                           p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps);   skipped entirely if found_inf
 // Work item = chunk of CHUNK consecutive elements of one tensor (table built by the host).
-#include "common.h"
+#include "chunk_table.h"
 
 namespace {
 
 constexpr int NT = 256;
-constexpr int CHUNK = 16384;                 // elements per work item (64 per thread)
+constexpr int CHUNK = CHUNK_ELEMS;           // elements per work item (64 per thread)
 constexpr int ST = 6;                        // per-tensor scratch: sum g^2, <G,W>, u^T G v, |u|^2, |v|^2, c
 constexpr int CP = 3;                        // per-chunk partials: sum g^2, <G,W>, u^T G v
 
@@ -35,8 +35,7 @@ __global__ __launch_bounds__(NT) void optim_stats(const calm_optim_tensor* __res
     __shared__ float red[4];
     const int t = chunk_tensor[blockIdx.x];
     const calm_optim_tensor e = T[t];
-    const long i0 = (long)(blockIdx.x - e.chunk0) * CHUNK;
-    const long i1 = min(i0 + (long)CHUNK, (long)e.numel);
+    const auto [i0, i1] = chunk_span(blockIdx.x, CHUNK, e.chunk0, e.numel);
     float s2 = 0.f, gw = 0.f, guv = 0.f;
     bool bad = false;
     if (e.sn_sigma) {
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(NT) void optim_finalize(const calm_optim_tensor* __
     float acc = 0.f;
     for (int t = threadIdx.x; t < n; t += NT) {
         const calm_optim_tensor e = T[t];
-        const int nch = (int)((e.numel + CHUNK - 1) / CHUNK);
+        const int nch = chunk_count(CHUNK, e.numel);
         float n2 = 0.f, gw = 0.f, guv = 0.f;
         for (int k = 0; k < nch; ++k) {                             // fixed order: chunk 0, 1, 2, ...
             const float* cp = chunk_part + (long)CP * (e.chunk0 + k);
@@ -121,8 +120,7 @@ __global__ __launch_bounds__(NT) void optim_update(const calm_optim_tensor* __re
     if (lr_dev) hp.lr = lr_dev[0];            // a captured step follows the LR schedule through this device scalar
     const int t = chunk_tensor[blockIdx.x];
     const calm_optim_tensor e = T[t];
-    const long i0 = (long)(blockIdx.x - e.chunk0) * CHUNK;
-    const long i1 = min(i0 + (long)CHUNK, (long)e.numel);
+    const auto [i0, i1] = chunk_span(blockIdx.x, CHUNK, e.chunk0, e.numel);
     const float mul = G->clip;
     const float decay = 1.0f - hp.lr * hp.weight_decay;
     const float bc1 = 1.0f - powf(hp.beta1, (float)hp.step), bc2 = 1.0f - powf(hp.beta2, (float)hp.step);

@@ -4,29 +4,21 @@
 // stream pays one launch and a side stream moves the one buffer.
 //   pack    per chunk: packed[offset + b] = tensor[b]
 //   unpack  per chunk: tensor[b] = packed[offset + b]
-// Work item = chunk of CHUNK_BYTES consecutive bytes of one entry (table built by the host, as for calm_ema_swap).  Bits
+// Work item = chunk of CHUNK_BYTES consecutive bytes of one entry (the walk of chunk_table.h, counted in words).  Bits
 // move through integer registers, no arithmetic: NaN payloads and the int32 counters survive.  The packed side of a chunk
 // is always 16-byte aligned (offsets and CHUNK_BYTES are multiples of 16, the buffer's base is checked); a chunk whose
 // tensor side is 16-byte aligned as well moves 16-byte vectors, U in flight per thread, with a scalar tail; any other
 // 4-byte aligned tensor moves single words.  Every word belongs to one thread of one workgroup: no atomics, no workspace;
 // the bytes between two entries of the packed buffer are neither written by pack nor read by unpack.
-#include "common.h"
+#include "chunk_table.h"
 
 namespace {
 
 constexpr int NT = 256;
-constexpr int CHUNK_BYTES = 65536;           // per work item (64 words per thread)
-constexpr int CHUNK_WORDS = CHUNK_BYTES / 4;
+constexpr int CHUNK_WORDS = CHUNK_ELEMS;     // per work item (64 words per thread)
+constexpr int CHUNK_BYTES = 4 * CHUNK_WORDS;
 constexpr int U = 4;                         // 16-byte vectors a thread has in flight
 static_assert(CHUNK_BYTES % 16 == 0, "a chunk starts on a 16-byte boundary of the packed buffer");
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// pointers read out of the table are generic to the compiler; these say device memory (global_load / global_store)
-#define SNAP_GLOBAL __attribute__((address_space(1)))
-typedef SNAP_GLOBAL uint32_t gu32;
-typedef SNAP_GLOBAL u32x4 gu32x4;
-
-__device__ __forceinline__ bool dev_aligned16(const SNAP_GLOBAL void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // PACK: src = tensor, dst = packed; otherwise the other way round.  The loads of U vectors are issued ahead of the first
 // store (src and dst come out of a table: the compiler cannot know that they do not alias).
@@ -37,8 +29,7 @@ __global__ __launch_bounds__(NT) void snapshot_move(const calm_snapshot_entry* _
     // a record the host would have refused moves nothing (the table is checked where it is built; this keeps a bad one
     // inside the buffer)
     if (e.offset < 0 || e.nbytes <= 0 || e.offset > packed_bytes || e.nbytes > packed_bytes - e.offset) return;
-    const long w0 = (long)((int)blockIdx.x - e.chunk0) * CHUNK_WORDS;
-    const long w1 = min(w0 + (long)CHUNK_WORDS, (long)(e.nbytes >> 2));
+    const auto [w0, w1] = chunk_span((int)blockIdx.x, CHUNK_WORDS, e.chunk0, e.nbytes >> 2);
     if (w0 < 0) return;
     gu32* t = (gu32*)e.tensor;
     gu32* p = (gu32*)(packed + e.offset);
@@ -46,34 +37,14 @@ __global__ __launch_bounds__(NT) void snapshot_move(const calm_snapshot_entry* _
     gu32* dst = PACK ? p : t;
     if (dev_aligned16(t + w0)) {
         const long v1 = w0 + ((w1 - w0) & ~3L);
-        for (long b = w0 + 4 * threadIdx.x; b < v1; b += 4 * NT * U) {
-            u32x4 x[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long i = b + (long)u * 4 * NT;
-                if (i < v1) x[u] = *(const gu32x4*)(src + i);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long i = b + (long)u * 4 * NT;
-                if (i < v1) *(gu32x4*)(dst + i) = x[u];
-            }
-        }
+        loads_ahead_of_stores<U, 4, NT>(
+            w0, v1, [&](long i) __attribute__((always_inline)) { return *(const gu32x4*)(src + i); },
+            [&](long i, const u32x4& x) __attribute__((always_inline)) { *(gu32x4*)(dst + i) = x; });
         for (long i = v1 + threadIdx.x; i < w1; i += NT) dst[i] = src[i];
     } else {
-        for (long b = w0 + threadIdx.x; b < w1; b += (long)NT * U) {
-            uint32_t x[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long i = b + (long)u * NT;
-                if (i < w1) x[u] = src[i];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long i = b + (long)u * NT;
-                if (i < w1) dst[i] = x[u];
-            }
-        }
+        loads_ahead_of_stores<U, 1, NT>(
+            w0, w1, [&](long i) __attribute__((always_inline)) { return src[i]; },
+            [&](long i, uint32_t x) __attribute__((always_inline)) { dst[i] = x; });
     }
 }
 

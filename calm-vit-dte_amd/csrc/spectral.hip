@@ -11,7 +11,7 @@
 //   B: v      = t / max(|t|, eps);  s[r] = W[r,:] . v       (every block renormalises t itself)
 //   C: u      = s / max(|s|, eps);  sigma = u . s           (one block per layer)
 // eval: phase B uses the stored v, phase C the stored u (sigma = u . W v, no update).
-#include "common.h"
+#include "chunk_table.h"
 
 namespace {
 
@@ -201,13 +201,14 @@ __global__ __launch_bounds__(NT) void sn_bwd_apply_batch(const SnBwdBatch b) {
 }
 
 // ---- per-step bf16 copies of all weights (bf16 pipeline) ------------------------------------------------------------
-constexpr int CAST_CHUNK = 16384;            // elements per work item (64 per thread)
+// The walk of chunk_table.h.  This kernel and the optimizer's keep generic (flat_*) pointers and one vector per trip:
+// global loads or loads_ahead_of_stores would change their speed, which is a change of its own.
+constexpr int CAST_CHUNK = CHUNK_ELEMS;      // elements per work item (64 per thread)
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(NT) void cast_bf16_kernel(const calm_cast_entry* __restrict__ E, const int* __restrict__ chunk_entry) {
     const calm_cast_entry e = E[chunk_entry[blockIdx.x]];
-    const long i0 = (long)(blockIdx.x - e.chunk0) * CAST_CHUNK;
-    const long i1 = min(i0 + (long)CAST_CHUNK, (long)e.numel);
+    const auto [i0, i1] = chunk_span(blockIdx.x, CAST_CHUNK, e.chunk0, e.numel);
     __bf16* dst = reinterpret_cast<__bf16*>(e.dst);
     if (((reinterpret_cast<uintptr_t>(e.src) & 15) | (reinterpret_cast<uintptr_t>(e.dst) & 7)) == 0) {
         const long v1 = i0 + ((i1 - i0) & ~3L);

@@ -987,6 +987,13 @@ def _clear_deferred(refs, attr, token):
             delattr(p, attr)
 
 
+def _stale_ptrs(tensors, ptrs):
+    """A plan caches raw addresses: has any of `tensors` left the address recorded for it in `ptrs` (uint64 array)?"""
+    import numpy as np
+    now = np.fromiter((t.data_ptr() for t in tensors), dtype=np.uint64, count=len(tensors))
+    return not np.array_equal(now, ptrs)
+
+
 class FusedClipAdamW(torch.optim.Optimizer):
     """unscale + inf/NaN check + clip_grad_norm_(max_norm) + AdamW + zero_grad of distributed_trainer_cls.py:88-96 as
     THREE kernel launches over all parameters (calm_optim_step), with the spectral-norm weight-gradient correction
@@ -1072,9 +1079,7 @@ class FusedClipAdamW(torch.optim.Optimizer):
     def _check_plan(self):
         """The plan caches raw addresses: refuse to update orphaned storage after the model was moved / re-materialised
         (model.to(...), .float(), a replaced buffer) once the optimizer exists."""
-        import numpy as np
-        now = np.fromiter((p.data_ptr() for p in self.params), dtype=np.uint64, count=len(self.params))
-        ok = np.array_equal(now, self._plan.param_ptrs)
+        ok = not _stale_ptrs(self.params, self._plan.param_ptrs)
         for m, pu, pv, ps in self._sn_tensors:
             ok = ok and m.weight_u.data_ptr() == pu and m.weight_v.data_ptr() == pv and m._sigma.data_ptr() == ps
         if not ok:
@@ -1208,9 +1213,7 @@ class ModelEMA:
 
     def _check(self):
         """The plan caches raw addresses (as FusedClipAdamW._check_plan): refuse to read orphaned storage."""
-        import numpy as np
-        now = np.fromiter((p.data_ptr() for p in self.params), dtype=np.uint64, count=len(self.params))
-        if not np.array_equal(now, self._ptrs):
+        if _stale_ptrs(self.params, self._ptrs):
             raise RuntimeError("ModelEMA: parameters were moved or replaced after the average was built (model.to / .float "
                                "/ load with assign=True); build it after the model is on its final device, or rebind()")
 
