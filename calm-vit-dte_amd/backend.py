@@ -785,6 +785,17 @@ class HipBackend:
                                             _ptr(plan.scratch), C.byref(h), _ptr(grad_scale, True), _ptr(stats_out),
                                             plan.step_dev.data_ptr(), _ptr(lr_dev, True), _stream()), "calm_optim_step")
 
+    def grad_accum(self, plan, grads, acc_ptrs_dev, first):
+        """calm_grad_accum over the table of `plan` (the optimizer's deferred plan, this micro-batch's gradient pointers
+        uploaded as for optim_step): acc = (first ? 0 : acc) + corrected gradient.  acc_ptrs_dev: int64 device tensor of
+        plan.n accumulator addresses.  Uses the first plan.n_chunks floats of plan.scratch."""
+        if acc_ptrs_dev.numel() != plan.n or acc_ptrs_dev.dtype != torch.int64 or not acc_ptrs_dev.is_cuda:
+            raise ValueError("grad_accum expects one int64 accumulator address per tensor of the plan, on the device")
+        plan.upload(np.asarray([_ptr(g) for g in grads], dtype=np.uint64))
+        _lib.check(self.lib.calm_grad_accum(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
+                                            acc_ptrs_dev.data_ptr(), _ptr(plan.scratch), int(bool(first)), _stream()),
+                   "calm_grad_accum")
+
     # ---- weight EMA ---------------------------------------------------------------------
     def ema_plan(self, pairs):
         """pairs: [(fp32 parameter, its fp32 average of the same shape)] -> plan for ema_update / ema_swap."""

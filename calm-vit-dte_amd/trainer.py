@@ -13,6 +13,9 @@ as set by torchrun):
         all-reduced (mean) on a SIDE HIP stream while the rest of backward keeps running.
   * `TrainStep`                        <- one iteration of the step loop               (cls:79-96):
         forward, CE with soft targets, backward, unscale / clip_grad_norm_(1.0), AdamW, zero_grad.
+  * `AccumTrainStep` / `FusedClipAdamWindow` / `HeldGradReducer`   (no counterpart: the reference has no accumulation)
+        gradient accumulation over k micro-batches per optimizer step: calm_grad_accum behind every micro-backward, one
+        gradient exchange and one optimizer-side step per window.
   * `ModelEMA`                         (no counterpart: the reference keeps no weight average)
         exponential moving average of the parameters, one kernel pass behind the optimizer step; exchanged into the
         parameters in place for evaluation.
@@ -201,6 +204,56 @@ class BucketedGradReducer:
             b["pending"] = len(b["params"])
 
 
+class HeldGradReducer(BucketedGradReducer):
+    """BucketedGradReducer for gradient accumulation: while `hold` is set the per-parameter hooks do nothing, and the
+    exchange runs once per window at its boundary.  With FusedClipAdamWindow the window's sums are accumulated IN the
+    bucket views (`views_of`) and `reduce_held()` all-reduces the flat buckets as they stand; with a torch optimizer the
+    boundary is the ordinary `finish()` — the hooks were held, every bucket still has `pending > 0`, so it packs the
+    summed `.grad`s and launches.  One collective per bucket per window either way.  Stock DistributedDataParallel knows
+    nothing of a window and all-reduces every micro-batch."""
+
+    def __init__(self, model, bucket_mb=64, process_group=None, tail_mb=8, force=False, hold=True):
+        super().__init__(model, bucket_mb=bucket_mb, process_group=process_group, tail_mb=tail_mb, force=force)
+        self.hold = hold
+
+    def _hook(self, p):
+        if not self.hold:
+            super()._hook(p)
+
+    def views_of(self, params):
+        """The bucket view of every one of `params`."""
+        where = {p: v for b in self.buckets for p, v in zip(b["params"], b["views"])}
+        return [where[p] for p in params]
+
+    @torch.no_grad()
+    def reduce_held(self):
+        """All-reduce every flat bucket as it stands — no pack copy — on the side stream, with the AVG (RCCL) or
+        SUM-then-scale (gloo) choice and the synchronous form of `_launch`, and point every `p.grad` at its view as
+        `finish()` does.  The collectives start behind the window's last accumulate: overlapping them with the last
+        micro-backward is out of scope."""
+        if not self.enabled:
+            return
+        op = dist.ReduceOp.AVG if self.avg_in_collective else dist.ReduceOp.SUM
+        inv = 1.0 / self.world
+        if self.on_gpu:
+            self.side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(self.side):
+                for b in self.buckets:
+                    dist.all_reduce(b["flat"], op=op, group=self.pg, async_op=False)
+                    if not self.avg_in_collective:
+                        b["flat"].mul_(inv)
+            torch.cuda.current_stream().wait_stream(self.side)
+        else:
+            works = [dist.all_reduce(b["flat"], op=op, group=self.pg, async_op=True) for b in self.buckets]
+            for work, b in zip(works, self.buckets):
+                work.wait()
+                if not self.avg_in_collective:
+                    b["flat"].mul_(inv)
+        for b in self.buckets:
+            for p, v in zip(b["params"], b["views"]):
+                p.grad = v
+
+
 def soft_target_cross_entropy(logits, soft_targets, metrics=None):
     """torch.nn.CrossEntropyLoss() with class-probability targets (cls:63,86; CutMix/MixUp labels).
 
@@ -362,6 +415,131 @@ class RegTrainStep(TrainStep):
             from .ops import HuberTokensFn
             return HuberTokensFn.apply(tokens, x, 1.0)
         return torch.nn.functional.huber_loss(img, x)
+
+
+class AccumTrainStep(TrainStep):
+    """TrainStep with gradient accumulation over `accumulate` = k micro-batches.
+
+    Every call runs forward, loss and backward of one micro-batch (the gradient tail armed as in TrainStep); the k-th
+    call of a window also runs the gradient exchange and TrainStep's unscale / clip / optimizer step / EMA / scale update,
+    ONCE, on the mean of the window's k gradients.  `boundary` tells whether the last call stepped; `flush()` steps an
+    incomplete window of m < k micro-batches with divisor m.  With FusedClipAdamWindow every micro-batch goes through
+    `accumulate()` (the deferred spectral-norm correction with that micro-batch's u, v, sigma, fp32 sums, `.grad`
+    released); with a torch optimizer autograd adds into `.grad` and the sum is scaled by 1/m behind `unscale_`, in front
+    of `clip_grad_norm_`: the two paths mean the same thing.  A window equals the torch loop "k x (forward, backward),
+    then unscale / clip / step" with spectral norm iterating at every forward — not one k-times-larger batch.  The
+    GradScaler's scale is read once per window and cannot change inside one; an inf/NaN in any micro-batch skips the
+    whole window (EMA and step count untouched, scale backed off) and the next window's first micro-batch overwrites its
+    sums.  reducer: a HeldGradReducer; with FusedClipAdamWindow its bucket views become the accumulators.
+
+    The optimizer-side sequence of `_optimizer_step` repeats TrainStep._finish's, which is left as it is."""
+
+    def __init__(self, model, optimizer, reducer=None, accumulate=2, **kw):
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError(f"accumulate counts micro-batches per optimizer step (>= 1), got {accumulate!r}")
+        if isinstance(optimizer, FusedClipAdamW) and not isinstance(optimizer, FusedClipAdamWindow):
+            raise TypeError("AccumTrainStep needs FusedClipAdamWindow (FusedClipAdamW corrects the spectral-norm gradients "
+                            "once per step, with the last forward's u, v, sigma)")
+        if reducer is not None and reducer.enabled and not isinstance(reducer, HeldGradReducer):
+            raise TypeError("AccumTrainStep needs a HeldGradReducer (BucketedGradReducer all-reduces every backward)")
+        super().__init__(model, optimizer, reducer, **kw)
+        self.accumulate = int(accumulate)
+        self.window = 0                               # micro-batches in the open window
+        self.boundary = True                          # whether the last call stepped the optimizer
+        self.fused = isinstance(optimizer, FusedClipAdamWindow)
+        if reducer is not None and reducer.enabled:
+            reducer.hold = True
+            if self.fused:
+                optimizer.bind_accumulators(reducer.views_of(optimizer.params))      # the sums ARE the buckets
+
+    def _finish(self, loss, y_hat):
+        from . import ops
+        with ops.grad_tail(self.params, enabled=self._tail_enabled()):
+            if self.scaler is not None:
+                self.scaler.scale(loss).backward()
+            else:
+                loss.backward()
+        self._device = loss.device
+        if self.fused:
+            self.opt.accumulate()
+        self.window += 1
+        self.boundary = self.window >= self.accumulate
+        if self.boundary:
+            self._close_window()
+        return loss.detach(), y_hat.detach()
+
+    def flush(self):
+        """Step an incomplete window (the m < accumulate micro-batches an epoch ends with), dividing by m.  False, and
+        nothing done, when no window is open."""
+        if self.window == 0:
+            return False
+        self._close_window()
+        self.boundary = True
+        return True
+
+    def _close_window(self):
+        m = self.window
+        if self.reducer is not None and self.reducer.enabled:
+            if self.fused:
+                self.reducer.reduce_held()
+            else:
+                self.reducer.finish()
+        self._optimizer_step(self._device, m)
+        self.window = 0
+
+    def _optimizer_step(self, device, m):
+        """TrainStep._finish's sequence behind the backward, on the gradients of m micro-batches (their mean)."""
+        if self.fused:
+            self.opt.max_norm = self.max_norm
+            if self.scaler is not None and self.scaler.is_enabled():
+                sc = self.scaler
+                if not hasattr(self, "_clean_steps"):
+                    self._clean_steps = torch.zeros((), dtype=torch.int32, device=device)
+                    self._one = torch.ones((), dtype=torch.float32, device=device)
+                scale = sc.scale(self._one)                      # the scale of the whole window, no host sync
+                stats = self.opt.step(grad_scale=scale)          # divides by scale * m
+                if self.ema is not None:
+                    self.ema.update(skip=stats[1:2])
+                bad = stats[1] > 0
+                self._clean_steps.copy_(torch.where(bad, torch.zeros_like(self._clean_steps), self._clean_steps + 1))
+                grow = self._clean_steps >= sc.get_growth_interval()
+                new_scale = torch.where(bad, scale * sc.get_backoff_factor(),
+                                        torch.where(grow, scale * sc.get_growth_factor(), scale))
+                self._clean_steps.copy_(torch.where(grow, torch.zeros_like(self._clean_steps), self._clean_steps))
+                sc.update(new_scale.detach())
+            else:
+                stats = self.opt.step()
+                if self.ema is not None:
+                    self.ema.update(skip=stats[1:2])
+            return
+        if self.scaler is not None:
+            self.scaler.unscale_(self.opt)
+        if m > 1:                                                # the mean of the window, in front of the clip
+            torch._foreach_mul_([p.grad for p in self.params if p.grad is not None], 1.0 / m)
+        torch.nn.utils.clip_grad_norm_(self.params, max_norm=self.max_norm, error_if_nonfinite=False)
+        skip = None
+        if self.scaler is not None:
+            watch = self.ema is not None and self.scaler.is_enabled()
+            if watch:
+                if not hasattr(self, "_ema_one"):
+                    self._ema_one = torch.ones(1, dtype=torch.float32, device=device)
+                old_scale = self.scaler.scale(self._ema_one)
+            self.scaler.step(self.opt)
+            self.scaler.update()
+            if watch:
+                skip = (self.scaler.scale(self._ema_one) < old_scale).to(torch.float32)
+        else:
+            self.opt.step()
+        if self.ema is not None:
+            self.ema.update(skip=skip)
+        self.opt.zero_grad()
+
+
+class AccumRegTrainStep(AccumTrainStep, RegTrainStep):
+    """RegTrainStep (the generative trainer's forward and loss) with AccumTrainStep's window."""
+
+    def __init__(self, model, optimizer, reducer=None, accumulate=2, kl_weight=0.1, **kw):
+        super().__init__(model, optimizer, reducer, accumulate=accumulate, kl_weight=kl_weight, **kw)
 
 
 class DeviceCollate:
@@ -1133,6 +1311,142 @@ class FusedClipAdamW(torch.optim.Optimizer):
             dst.copy_(src)
 
 
+def grad_accum_torch(records, grads, accs, first):
+    """calm_grad_accum in torch, for a backend without `grad_accum` (CPU parameters): acc = (first ? 0 : acc) + g', with
+    g' = (G - <G, W_orig>/sigma u v^T) * (1/sigma) for a record with `sn`, g' = G otherwise.  With first, `accs` are
+    written without being read."""
+    for r, g, a in zip(records, grads, accs):
+        if r["sn"] is not None:
+            u, v, sigma, rows, cols = r["sn"]
+            G = g.reshape(rows, cols)
+            c = (G * r["param"].reshape(rows, cols)).sum() / sigma
+            g = (G - (c * u)[:, None] * v[None, :]) * (1.0 / sigma)
+        if first:
+            a.copy_(g.reshape(a.shape))
+        else:
+            a.add_(g.reshape(a.shape))
+
+
+class FusedClipAdamWindow(FusedClipAdamW):
+    """FusedClipAdamW with a gradient-accumulation window.
+
+    `accumulate()` takes the current `.grad`s into the window: calm_grad_accum walks the optimizer's own (deferred) table
+    with this micro-batch's gradient pointers, applies the spectral-norm correction with the u, v, sigma of the forward
+    that produced them — the power iteration advances them in place at every training forward, so raw gradients summed
+    over several forwards could not be corrected once at the end — and adds the finished gradients to fp32 accumulators
+    (`first = 1` at the start of a window: written without being read, they may hold NaN from a skipped window).  Every
+    `.grad` is then released: the next backward finds the gradient tail armable and autograd adopts fresh buffers.
+    `step()` with `window > 0` runs calm_optim_step over a second, "plain" plan — the same parameters, moments and device
+    step counter, no correction, gradients = the accumulators, whose addresses are fixed, so its table is uploaded once
+    — with `grad_scale * window` (or `window`) as the divisor: the mean over the micro-batches costs no pass.  `step()`
+    with `window == 0` is FusedClipAdamW.step()."""
+
+    def __init__(self, model, *args, **kw):
+        super().__init__(model, *args, **kw)
+        sn = {id(p): m for p, (m, _, _, _) in zip(self._deferred, self._sn_tensors)}
+        self._records = []
+        for p, ea, eas in zip(self.params, self.exp_avg, self.exp_avg_sq):
+            m = sn.get(id(p))
+            info = None if m is None else (m.weight_u, m.weight_v, m._sigma, m.rows, m.cols)
+            self._records.append({"param": p.data, "exp_avg": ea, "exp_avg_sq": eas, "sn": info})
+        self.window = 0                         # micro-batches accumulated since the last step
+        self._acc = self._acc_plan = self._acc_ptrs = self._acc_ptrs_dev = None
+        self._window_divisors = {}
+
+    def bind_accumulators(self, accs=None):
+        """Build the window: the fp32 accumulators (`accs`: tensors shaped like the parameters to accumulate in, e.g. the
+        HeldGradReducer's bucket views; None: allocated here) and the plain plan that steps from them.  Refused inside
+        an open window."""
+        import numpy as np
+        if self.window > 0:
+            raise RuntimeError("FusedClipAdamWindow.bind_accumulators: a window is open; step() or zero_grad() first")
+        if accs is None:
+            accs = [torch.zeros_like(p, dtype=torch.float32) for p in self.params]
+        accs = list(accs)
+        if len(accs) != len(self.params) or any(a.shape != p.shape or a.dtype != torch.float32 or a.device != p.device
+                                                or not a.is_contiguous() for a, p in zip(accs, self.params)):
+            raise ValueError("FusedClipAdamWindow.bind_accumulators: one contiguous fp32 tensor per parameter, of its shape "
+                             "and on its device")
+        plan = self.be.optim_plan([dict(r, sn=None) for r in self._records])
+        plan.step_dev = self._plan.step_dev     # one counter: snapshots and step_count see every step
+        self._acc, self._acc_plan = accs, plan
+        self._acc_ptrs = np.asarray([a.data_ptr() for a in accs], dtype=np.uint64)
+        self._acc_ptrs_dev = torch.from_numpy(self._acc_ptrs.view(np.int64).copy()).to(self.params[0].device)
+
+    def _check_plan(self):
+        super()._check_plan()
+        if self._acc is not None and _stale_ptrs(self._acc, self._acc_ptrs):
+            raise RuntimeError("FusedClipAdamWindow: an accumulator was moved or replaced after the window was built")
+
+    def _check_owner(self):
+        self._check_plan()
+        for p in self._deferred:
+            if getattr(p, self._defer_attr, None) != self._token:
+                raise RuntimeError("FusedClipAdamW: another optimizer took over (or cleared) the deferred spectral-norm "
+                                   "correction of this model; only the newest optimizer of a model may step")
+
+    @torch.no_grad()
+    def accumulate(self):
+        """Take the current `.grad`s into the window (a parameter without one contributes zeros) and release them."""
+        if self._acc is None:
+            self.bind_accumulators()
+        self._check_owner()
+        grads = []
+        for p in self.params:
+            g = p.grad
+            if g is None:
+                g = torch.zeros_like(p)
+            elif not g.is_contiguous():
+                g = g.contiguous()
+            grads.append(g)
+        first = self.window == 0                # the old sums (NaN after a skipped window) are overwritten, not read
+        if hasattr(self.be, "grad_accum"):
+            self.be.grad_accum(self._plan, grads, self._acc_ptrs_dev, first)
+        else:
+            grad_accum_torch(self._records, grads, self._acc, first)
+        for p in self.params:
+            p.grad = None
+        self.window += 1
+
+    def _window_divisor(self, grad_scale):
+        """grad_scale * window (or window alone) as the device scalar calm_optim_step divides by."""
+        if grad_scale is not None:
+            return grad_scale * float(self.window)
+        d = self._window_divisors.get(self.window)
+        if d is None:
+            d = self._window_divisors[self.window] = torch.full((1,), float(self.window), dtype=torch.float32,
+                                                                device=self.params[0].device)
+        return d
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale=None):
+        """With `window > 0`: one optimizer-side step on the mean of the window's accumulated gradients, then
+        `window = 0`.  With `window == 0`: FusedClipAdamW.step()."""
+        if self.window == 0:
+            return super().step(closure=closure, grad_scale=grad_scale)
+        if closure is not None:
+            raise NotImplementedError("FusedClipAdamW.step takes no closure")
+        self._check_owner()
+        for p, a in zip(self.params, self._acc):
+            if p.grad is not None and p.grad.data_ptr() != a.data_ptr():
+                raise RuntimeError("FusedClipAdamWindow.step: a window is open and a parameter has a gradient outside it; "
+                                   "accumulate() takes gradients into the window")
+        hp = (float(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.max_norm or 0.0, 0)
+        if self.lr_on_device and not torch.cuda.is_current_stream_capturing():
+            self.sync_lr_to_device()
+        self.be.optim_step(self._acc_plan, self._acc, hp, self._window_divisor(grad_scale), self.stats,
+                           lr_dev=self._lr_dev if self.lr_on_device else None)
+        self.window = 0
+        for p in self.params:
+            p.grad = None
+        return self.stats
+
+    def zero_grad(self, set_to_none=True):
+        """Release every `.grad` and discard an open window."""
+        super().zero_grad(set_to_none)
+        self.window = 0
+
+
 def ema_weight(decay, schedule, n):
     """The weight w = 1 - d of weight-EMA update number n + 1 as calm_ema_update's first launch evaluates it, in fp32:
     d = decay (EMA_CONSTANT) or min(decay, (1 + n) / (10 + n)) (EMA_WARMUP).  numpy's float32 division is correctly
@@ -1528,6 +1842,9 @@ class TrainState:
         import json
         self.wait()
         self._check_ready("save_async")
+        if getattr(self.opt, "window", 0) > 0 or getattr(self.step, "window", 0) > 0:
+            raise RuntimeError("TrainState.save_async: a gradient-accumulation window is open; snapshots are taken behind "
+                               "an optimizer step (AccumTrainStep.boundary / flush())")
         if not self.payload:                      # a rank that only keeps its own host state
             side = self.host_state(progress)
             self._write_atomic(self.sidecar(path), json.dumps({k: side[k] for k in self._PER_RANK + ("progress", "world")}).encode())
@@ -1894,7 +2211,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           checkpoint_path=None, num_classes=1000, num_workers=0, collate_fn="mix", log_every=100, max_steps=None,
           destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
           device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None,
-          ema=None, snapshot_path=None, snapshot_every=None, resume=None):
+          ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -1974,7 +2291,17 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     on are dropped from the sampler, nothing is loaded and thrown away — and max_steps counts from the restored step.
     The resumed trajectory equals the uninterrupted one bit for bit where the augmentation generators live in the main
     process (device_collate=True, or num_workers=0); the `SoftMixCollate` generators inside persistent DataLoader
-    workers are not captured, and a resumed run then draws a fresh stream from them."""
+    workers are not captured, and a resumed run then draws a fresh stream from them.
+
+    accumulate=k > 1 (gradient accumulation: `AccumTrainStep`, `"fused"` builds a `FusedClipAdamWindow`, the reducer is a
+    `HeldGradReducer`; excludes graph=True): every batch of the loader is a micro-batch and every k-th one steps the
+    optimizer on the mean of the window's gradients — the effective batch is k * batch_size per rank with the memory of
+    one.  max_steps and snapshot_every count OPTIMIZER steps, log_every keeps counting batches.  The incomplete window
+    an epoch ends with is stepped (divisor: its own length) before the checkpoint and scheduler.step(), so windows start
+    at batch indices that are multiples of k in every epoch.  Snapshots are written only right behind an optimizer step,
+    and resume= continues at such a boundary.  The gradients are exchanged once per window.  A window equals the torch
+    loop "k x (forward, backward), then unscale / clip / step" with spectral norm iterating at every forward; it does
+    not equal one k-times-larger batch."""
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
     if device_metrics and not (use_gpu and _backend.get_loss_kernels()):
@@ -2001,6 +2328,13 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             raise ValueError("random_resized_crop excludes device_resize and crop: it is the crop and the resize")
     if graph and not (use_gpu and (optimizer == "fused" or isinstance(optimizer, FusedClipAdamW))):
         raise ValueError('graph=True needs use_gpu=True and optimizer="fused" (FusedClipAdamW)')
+    if int(accumulate) != accumulate or accumulate < 1:
+        raise ValueError(f"train: accumulate counts micro-batches per optimizer step (>= 1), got {accumulate!r}")
+    accumulate = int(accumulate)
+    if accumulate > 1 and graph:
+        raise ValueError("train: accumulate > 1 excludes graph=True (capturing an accumulation window is not supported)")
+    if accumulate > 1 and isinstance(optimizer, FusedClipAdamW) and not isinstance(optimizer, FusedClipAdamWindow):
+        raise ValueError('train: accumulate > 1 needs optimizer="fused" or a FusedClipAdamWindow, not a FusedClipAdamW')
     if snapshot_every is not None and (snapshot_path is None or int(snapshot_every) < 1):
         raise ValueError("snapshot_every counts steps (>= 1) between the snapshots written to snapshot_path")
     if ema is not None:
@@ -2020,14 +2354,14 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             torch.cuda.empty_cache()
     model = initializer.to(device)
     if optimizer == "fused":
-        optimizer = FusedClipAdamW(model)
+        optimizer = FusedClipAdamWindow(model) if accumulate > 1 else FusedClipAdamW(model)
     if scheduler is None or scheduler is True:
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=epochs, eta_min=1e-6)      # cls:52
     elif scheduler is False:
         scheduler = None
     sync_module_states(model)
     ema_obj = ModelEMA(model, **ema_kw) if ema is not None else None
-    reducer = BucketedGradReducer(model) if world > 1 else None
+    reducer = (HeldGradReducer(model) if accumulate > 1 else BucketedGradReducer(model)) if world > 1 else None
     if world > 1:
         sampler = DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=True, seed=2006)       # cls:56
     else:
@@ -2048,8 +2382,12 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                         pin_memory=use_gpu, persistent_workers=num_workers > 0, drop_last=bool(graph))
     scaler = torch.amp.GradScaler("cuda", enabled=use_gpu)                                                 # cls:64
     metrics = StepMetrics(device) if device_metrics else None
-    step = TrainStep(model, optimizer, reducer, max_norm=1.0, scaler=scaler if use_gpu else None,
-                     autocast_dtype=torch.bfloat16 if use_gpu else None, metrics=metrics, ema=ema_obj)
+    step_kw = dict(max_norm=1.0, scaler=scaler if use_gpu else None, autocast_dtype=torch.bfloat16 if use_gpu else None,
+                   metrics=metrics, ema=ema_obj)
+    if accumulate > 1:
+        step = AccumTrainStep(model, optimizer, reducer, accumulate=accumulate, **step_kw)
+    else:
+        step = TrainStep(model, optimizer, reducer, **step_kw)
     model.train()
     n_steps = 0
     gstep = None
@@ -2119,11 +2457,12 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                     loss, y_hat = gstep(x, y)
                 else:
                     loss, y_hat = step(x, y)
-                n_steps += 1
-                done = max_steps is not None and n_steps >= max_steps
+                stepped = accumulate == 1 or step.boundary          # accumulate > 1: a window's last micro-batch steps
+                n_steps += int(stepped)
+                done = stepped and max_steps is not None and n_steps >= max_steps
                 if st is not None:                  # right behind the step, before anything else touches state
-                    if snapshot_path is not None and ((snapshot_every and n_steps % int(snapshot_every) == 0)
-                                                      or (done and i + 1 < n_batches)):
+                    if stepped and snapshot_path is not None and ((snapshot_every and n_steps % int(snapshot_every) == 0)
+                                                                  or (done and i + 1 < n_batches)):
                         st.save_async(snapshot_path, {"epoch": epoch, "batch": i + 1, "step": n_steps})
                     st.poll()
                 if metrics is None:
@@ -2134,6 +2473,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                           f"Accuracy: {100.0 * correct / y.size(0):.4f}%")
                 if done:
                     break
+            if accumulate > 1 and step.flush():     # the epoch's last, incomplete window: stepped before the checkpoint
+                n_steps += 1
             if metrics is not None:
                 loss_sum, agree, rows, _ = metrics.read()          # the epoch's one device-to-host copy
                 metrics.reset()

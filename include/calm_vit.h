@@ -531,6 +531,28 @@ int calm_optim_step(const calm_optim_tensor* tensors_dev, int32_t n_tensors, con
                     void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Gradient accumulation over micro-batches (addition to ABI v7), between a backward and calm_optim_step:
+ *   acc[t][i] = first ? g'[i] : acc[t][i] + g'[i]
+ * for every tensor t of calm_optim_step's table (tensors_dev / chunk_tensor_dev exactly as handed to it, gradient
+ * pointers of THIS micro-batch), with g' = grad for a plain tensor and, for one with sn_sigma != NULL,
+ *   g' = (G - <G, W_orig/sigma> u v^T) / sigma
+ * evaluated with the u, v, sigma the table points at NOW: the deferred spectral-norm correction is applied per
+ * micro-batch, because the power iteration advances u, v, sigma at every training forward.  The accumulators then hold
+ * finished gradients; the window's optimizer step runs calm_optim_step over a table with sn_* = NULL and grad = acc, and
+ * passes grad_scale * (number of micro-batches) as its grad_scale to average.
+ * acc_dev: device array of n_tensors accumulator pointers (fp32, 4-byte aligned, numel elements each, overlapping
+ * nothing else of the call).  scratch: n_chunks floats.  first = 1: the accumulators are written without being read
+ * (they may hold anything, NaN included).  No unscale, no clip, no inf/NaN flag: a non-finite gradient stays non-finite
+ * in the accumulator, where calm_optim_step's own check finds it.
+ * Two launches, no atomics, <G, W_orig> summed per chunk and then in chunk order: a fixed result per element, bit-identical
+ * on all data-parallel ranks given equal inputs.  Does not allocate or synchronise.
+ * CALM_E_INVAL, before any launch: a null tensors_dev / chunk_tensor_dev / acc_dev / scratch, n_tensors <= 0,
+ * n_chunks <= 0, first other than 0 or 1.
+ * ------------------------------------------------------------------------------------- */
+int calm_grad_accum(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev,
+                    int32_t n_chunks, float* const* acc_dev, float* scratch, int32_t first, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Exponential moving average of ALL parameters (additions to ABI v7), a launch of its own behind calm_optim_step — the
  * weight EMA every ImageNet ViT recipe evaluates and checkpoints with (timm's ModelEmaV2 / torch's AveragedModel):
  *   ema += w * (src - ema),  w = 1 - d,  d = decay (CALM_EMA_CONSTANT) | min(decay, (1 + n) / (10 + n)) (CALM_EMA_WARMUP)
