@@ -153,10 +153,13 @@ class BucketedGradReducer:
         if b["pending"] == 0:
             self._launch(b)
 
-    def _launch(self, b):
-        from . import ops
-        ops.flush_grad_tail()           # gradients the backward deferred to its end are finished before they are packed
-        grads = [p.grad for p in b["params"]]
+    def _launch(self, b, pack=True):
+        """Launch the all-reduce of bucket `b`; pack=True first copies the `.grad`s into its views, pack=False reduces the
+        flat bucket as it stands."""
+        if pack:
+            from . import ops
+            ops.flush_grad_tail()       # gradients the backward deferred to its end are finished before they are packed
+            grads = [p.grad for p in b["params"]]
         op = dist.ReduceOp.AVG if self.avg_in_collective else dist.ReduceOp.SUM
         if self.on_gpu:
             # the side stream starts after everything enqueued so far: the gradients exist, and the previous step's
@@ -169,13 +172,15 @@ class BucketedGradReducer:
             # finish() and ended in a segfault inside capture_end, gpurun_out/rccl.log)
             self.side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self.side):
-                torch._foreach_copy_(b["views"], grads)
+                if pack:
+                    torch._foreach_copy_(b["views"], grads)
                 dist.all_reduce(b["flat"], op=op, group=self.pg, async_op=False)
                 if not self.avg_in_collective:
                     b["flat"].mul_(1.0 / self.world)
             work = None
         else:
-            torch._foreach_copy_(b["views"], grads)
+            if pack:
+                torch._foreach_copy_(b["views"], grads)
             work = dist.all_reduce(b["flat"], op=op, group=self.pg, async_op=True)
         self._works.append((work, b))
 
@@ -189,6 +194,11 @@ class BucketedGradReducer:
                     if p.grad is None:
                         p.grad = torch.zeros_like(p)
                 self._launch(b)
+        self._join()
+
+    def _join(self):
+        """Behind the launches: every `p.grad` points at its slice of the reduced bucket and the compute stream waits for
+        the collectives."""
         inv = 1.0 / self.world
         for work, b in self._works:
             if work is not None:                    # CPU (gloo) path: asynchronous collectives, waited for here
@@ -200,7 +210,7 @@ class BucketedGradReducer:
         if self.on_gpu:
             torch.cuda.current_stream().wait_stream(self.side)
         self._works.clear()
-        for b in self.buckets:
+        for b in self.buckets:                      # (under `hold` the hooks never counted down: this changes nothing)
             b["pending"] = len(b["params"])
 
 
@@ -227,31 +237,14 @@ class HeldGradReducer(BucketedGradReducer):
 
     @torch.no_grad()
     def reduce_held(self):
-        """All-reduce every flat bucket as it stands — no pack copy — on the side stream, with the AVG (RCCL) or
-        SUM-then-scale (gloo) choice and the synchronous form of `_launch`, and point every `p.grad` at its view as
-        `finish()` does.  The collectives start behind the window's last accumulate: overlapping them with the last
-        micro-backward is out of scope."""
+        """All-reduce every flat bucket as it stands — no pack copy — and point every `p.grad` at its view, as `finish()`
+        does.  The collectives start behind the window's last accumulate: overlapping them with the last micro-backward
+        is out of scope."""
         if not self.enabled:
             return
-        op = dist.ReduceOp.AVG if self.avg_in_collective else dist.ReduceOp.SUM
-        inv = 1.0 / self.world
-        if self.on_gpu:
-            self.side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self.side):
-                for b in self.buckets:
-                    dist.all_reduce(b["flat"], op=op, group=self.pg, async_op=False)
-                    if not self.avg_in_collective:
-                        b["flat"].mul_(inv)
-            torch.cuda.current_stream().wait_stream(self.side)
-        else:
-            works = [dist.all_reduce(b["flat"], op=op, group=self.pg, async_op=True) for b in self.buckets]
-            for work, b in zip(works, self.buckets):
-                work.wait()
-                if not self.avg_in_collective:
-                    b["flat"].mul_(inv)
         for b in self.buckets:
-            for p, v in zip(b["params"], b["views"]):
-                p.grad = v
+            self._launch(b, pack=False)
+        self._join()
 
 
 def soft_target_cross_entropy(logits, soft_targets, metrics=None):
@@ -302,6 +295,17 @@ class TrainStep:
         self.scaler = scaler
         self.autocast_dtype = autocast_dtype          # torch.bfloat16: the reference's `with autocast(...)` (cls:84)
         self.params = [p for p in model.parameters() if p.requires_grad]
+        # the device constants of the optimizer-side sequence, made once for the configurations that read them (None
+        # otherwise): the GradScaler growth count of the fused step with the scalar its scale is read through, and the
+        # (1,) scalar through which the torch path watches the scale for a skipped step
+        self._clean_steps = self._one = self._ema_one = None
+        if scaler is not None and scaler.is_enabled():
+            dev = self.params[0].device
+            if isinstance(optimizer, FusedClipAdamW):
+                self._clean_steps = torch.zeros((), dtype=torch.int32, device=dev)
+                self._one = torch.ones((), dtype=torch.float32, device=dev)
+            elif ema is not None:
+                self._ema_one = torch.ones(1, dtype=torch.float32, device=dev)
 
     def __call__(self, x, y_soft):
         with torch.autocast(device_type="cuda", dtype=self.autocast_dtype or torch.bfloat16,
@@ -322,6 +326,12 @@ class TrainStep:
 
     def _finish(self, loss, y_hat):
         """backward, gradient exchange, unscale / clip / optimizer step, zero_grad (cls:87-96)."""
+        self._backward(loss)
+        self._exchange()
+        self._optimizer_step()
+        return loss.detach(), y_hat.detach()
+
+    def _backward(self, loss):
         from . import ops
         # the gradient tail (ops.grad_tail): leaf-gradient reductions of this backward run as a few multi-entry launches at
         # its end; armed only while no parameter has a .grad that autograd would add an unfinished tensor to
@@ -330,19 +340,22 @@ class TrainStep:
                 self.scaler.scale(loss).backward()                             # cls:87
             else:
                 loss.backward()
+
+    def _exchange(self):
         if self.reducer is not None:
             self.reducer.finish()
+
+    def _optimizer_step(self, m=1):
+        """unscale / inf check / clip / optimizer step / EMA / scale update / zero_grad on the gradients of m micro-batches
+        (their mean; m > 1 only from AccumTrainStep, where the fused optimizer's open window carries the divisor)."""
         if isinstance(self.opt, FusedClipAdamW):                           # cls:88-96 in three launches
             self.opt.max_norm = self.max_norm
-            if self.scaler is not None and self.scaler.is_enabled():
+            if self._clean_steps is not None:
                 # GradScaler semantics on device, no host sync: unscale + inf check + skip-on-inf happen inside
                 # calm_optim_step; the scale then backs off (x backoff) on inf/NaN or grows (x growth) after
                 # growth_interval clean steps, exactly as scaler.step() / scaler.update() would do it
                 sc = self.scaler
-                if not hasattr(self, "_clean_steps"):
-                    self._clean_steps = torch.zeros((), dtype=torch.int32, device=loss.device)
-                    self._one = torch.ones((), dtype=torch.float32, device=loss.device)
-                scale = sc.scale(self._one)                      # the current scale as a device tensor, no host sync
+                scale = sc.scale(self._one)     # the current scale as a device tensor, no host sync; read once per window
                 stats = self.opt.step(grad_scale=scale)
                 if self.ema is not None:
                     self.ema.update(skip=stats[1:2])             # found_inf of this step, read on the device
@@ -360,18 +373,18 @@ class TrainStep:
                 stats = self.opt.step()
                 if self.ema is not None:
                     self.ema.update(skip=stats[1:2])
-            return loss.detach(), y_hat.detach()
+            return
         if self.scaler is not None:
             self.scaler.unscale_(self.opt)                                 # cls:88
+        if m > 1:                                                          # the mean of the window, in front of the clip
+            torch._foreach_mul_([p.grad for p in self.params if p.grad is not None], 1.0 / m)
         torch.nn.utils.clip_grad_norm_(self.params, max_norm=self.max_norm, error_if_nonfinite=False)   # cls:92
         skip = None
         if self.scaler is not None:
-            watch = self.ema is not None and self.scaler.is_enabled()
+            watch = self._ema_one is not None
             if watch:
                 # scaler.step() skips optimizer.step() on inf/NaN and scaler.update() then backs the scale off: the step
                 # was skipped exactly when the scale shrank.  Public API only, device arithmetic, no host sync.
-                if not hasattr(self, "_ema_one"):
-                    self._ema_one = torch.ones(1, dtype=torch.float32, device=loss.device)
                 old_scale = self.scaler.scale(self._ema_one)
             self.scaler.step(self.opt)                                     # cls:93-94
             self.scaler.update()
@@ -382,7 +395,6 @@ class TrainStep:
         if self.ema is not None:
             self.ema.update(skip=skip)
         self.opt.zero_grad()                                               # cls:96
-        return loss.detach(), y_hat.detach()
 
 
 class RegTrainStep(TrainStep):
@@ -430,9 +442,7 @@ class AccumTrainStep(TrainStep):
     then unscale / clip / step" with spectral norm iterating at every forward — not one k-times-larger batch.  The
     GradScaler's scale is read once per window and cannot change inside one; an inf/NaN in any micro-batch skips the
     whole window (EMA and step count untouched, scale backed off) and the next window's first micro-batch overwrites its
-    sums.  reducer: a HeldGradReducer; with FusedClipAdamWindow its bucket views become the accumulators.
-
-    The optimizer-side sequence of `_optimizer_step` repeats TrainStep._finish's, which is left as it is."""
+    sums.  reducer: a HeldGradReducer; with FusedClipAdamWindow its bucket views become the accumulators."""
 
     def __init__(self, model, optimizer, reducer=None, accumulate=2, **kw):
         if int(accumulate) != accumulate or accumulate < 1:
@@ -453,13 +463,7 @@ class AccumTrainStep(TrainStep):
                 optimizer.bind_accumulators(reducer.views_of(optimizer.params))      # the sums ARE the buckets
 
     def _finish(self, loss, y_hat):
-        from . import ops
-        with ops.grad_tail(self.params, enabled=self._tail_enabled()):
-            if self.scaler is not None:
-                self.scaler.scale(loss).backward()
-            else:
-                loss.backward()
-        self._device = loss.device
+        self._backward(loss)
         if self.fused:
             self.opt.accumulate()
         self.window += 1
@@ -484,55 +488,8 @@ class AccumTrainStep(TrainStep):
                 self.reducer.reduce_held()
             else:
                 self.reducer.finish()
-        self._optimizer_step(self._device, m)
+        self._optimizer_step(m)
         self.window = 0
-
-    def _optimizer_step(self, device, m):
-        """TrainStep._finish's sequence behind the backward, on the gradients of m micro-batches (their mean)."""
-        if self.fused:
-            self.opt.max_norm = self.max_norm
-            if self.scaler is not None and self.scaler.is_enabled():
-                sc = self.scaler
-                if not hasattr(self, "_clean_steps"):
-                    self._clean_steps = torch.zeros((), dtype=torch.int32, device=device)
-                    self._one = torch.ones((), dtype=torch.float32, device=device)
-                scale = sc.scale(self._one)                      # the scale of the whole window, no host sync
-                stats = self.opt.step(grad_scale=scale)          # divides by scale * m
-                if self.ema is not None:
-                    self.ema.update(skip=stats[1:2])
-                bad = stats[1] > 0
-                self._clean_steps.copy_(torch.where(bad, torch.zeros_like(self._clean_steps), self._clean_steps + 1))
-                grow = self._clean_steps >= sc.get_growth_interval()
-                new_scale = torch.where(bad, scale * sc.get_backoff_factor(),
-                                        torch.where(grow, scale * sc.get_growth_factor(), scale))
-                self._clean_steps.copy_(torch.where(grow, torch.zeros_like(self._clean_steps), self._clean_steps))
-                sc.update(new_scale.detach())
-            else:
-                stats = self.opt.step()
-                if self.ema is not None:
-                    self.ema.update(skip=stats[1:2])
-            return
-        if self.scaler is not None:
-            self.scaler.unscale_(self.opt)
-        if m > 1:                                                # the mean of the window, in front of the clip
-            torch._foreach_mul_([p.grad for p in self.params if p.grad is not None], 1.0 / m)
-        torch.nn.utils.clip_grad_norm_(self.params, max_norm=self.max_norm, error_if_nonfinite=False)
-        skip = None
-        if self.scaler is not None:
-            watch = self.ema is not None and self.scaler.is_enabled()
-            if watch:
-                if not hasattr(self, "_ema_one"):
-                    self._ema_one = torch.ones(1, dtype=torch.float32, device=device)
-                old_scale = self.scaler.scale(self._ema_one)
-            self.scaler.step(self.opt)
-            self.scaler.update()
-            if watch:
-                skip = (self.scaler.scale(self._ema_one) < old_scale).to(torch.float32)
-        else:
-            self.opt.step()
-        if self.ema is not None:
-            self.ema.update(skip=skip)
-        self.opt.zero_grad()
 
 
 class AccumRegTrainStep(AccumTrainStep, RegTrainStep):
@@ -1201,7 +1158,7 @@ class FusedClipAdamW(torch.optim.Optimizer):
             for m in model.modules():
                 if isinstance(m, SpectralWeight) and not getattr(m, "layer_scaled", False):
                     sn[id(m.weight_orig)] = m
-        records, self._deferred, self._sn_tensors = [], [], []
+        self._records, self._deferred, self._sn_tensors = [], [], []
         for p, ea, eas in zip(self.params, self.exp_avg, self.exp_avg_sq):
             m = sn.get(id(p))
             info = None
@@ -1209,8 +1166,8 @@ class FusedClipAdamW(torch.optim.Optimizer):
                 info = (m.weight_u, m.weight_v, m._sigma, m.rows, m.cols)
                 self._deferred.append(p)
                 self._sn_tensors.append((m, m.weight_u.data_ptr(), m.weight_v.data_ptr(), m._sigma.data_ptr()))
-            records.append({"param": p.data, "exp_avg": ea, "exp_avg_sq": eas, "sn": info})
-        self._plan = self.be.optim_plan(records)
+            self._records.append({"param": p.data, "exp_avg": ea, "exp_avg_sq": eas, "sn": info})
+        self._plan = self.be.optim_plan(self._records)
         # the deferral is a mark on the PARAMETER OBJECT (ops reads it in forward), not a set of raw addresses: it
         # survives a re-materialised buffer and cannot be inherited by an unrelated tensor at a recycled address
         # The mark carries its owner: a second optimizer built over the same model takes the marks over, and the first
@@ -1265,32 +1222,45 @@ class FusedClipAdamW(torch.optim.Optimizer):
                                "optimizer was built (model.to / .float / load with assign=True); build the optimizer "
                                "after the model is on its final device")
 
+    def _check_owner(self):
+        self._check_plan()
+        for p in self._deferred:
+            if getattr(p, self._defer_attr, None) != self._token:
+                raise RuntimeError("FusedClipAdamW: another optimizer took over (or cleared) the deferred spectral-norm "
+                                   "correction of this model; only the newest optimizer of a model may step")
+
+    def _contiguous_grads(self, keep):
+        """The `.grad` of every parameter, contiguous, zeros where there is none; keep: a gradient made here becomes the
+        parameter's `.grad`."""
+        grads = []
+        for p in self.params:
+            g = p.grad
+            if g is None or not g.is_contiguous():
+                g = torch.zeros_like(p) if g is None else g.contiguous()
+                if keep:
+                    p.grad = g
+            grads.append(g)
+        return grads
+
+    def _launch(self, plan, grads, divisor):
+        """calm_optim_step over `plan` with `grads` divided by `divisor` (a device scalar, or None); every `.grad` is
+        released afterwards.  Returns the stats tensor."""
+        hp = (float(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.max_norm or 0.0, 0)
+        if self.lr_on_device and not torch.cuda.is_current_stream_capturing():
+            self.sync_lr_to_device()
+        self.be.optim_step(plan, grads, hp, divisor, self.stats, lr_dev=self._lr_dev if self.lr_on_device else None)
+        for p in self.params:
+            p.grad = None
+        return self.stats
+
     @torch.no_grad()
     def step(self, closure=None, grad_scale=None):
         """One optimizer-side step on the current `.grad`s; grads are released (set to None) afterwards.
         grad_scale: device scalar the loss was multiplied by (GradScaler), or None.  Returns the stats tensor."""
         if closure is not None:
             raise NotImplementedError("FusedClipAdamW.step takes no closure")
-        self._check_plan()
-        for p in self._deferred:
-            if getattr(p, self._defer_attr, None) != self._token:
-                raise RuntimeError("FusedClipAdamW: another optimizer took over (or cleared) the deferred spectral-norm "
-                                   "correction of this model; only the newest optimizer of a model may step")
-        grads = []
-        for p in self.params:
-            g = p.grad
-            if g is None:
-                g = p.grad = torch.zeros_like(p)
-            elif not g.is_contiguous():
-                g = p.grad = g.contiguous()
-            grads.append(g)
-        hp = (float(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.max_norm or 0.0, 0)
-        if self.lr_on_device and not torch.cuda.is_current_stream_capturing():
-            self.sync_lr_to_device()
-        self.be.optim_step(self._plan, grads, hp, grad_scale, self.stats, lr_dev=self._lr_dev if self.lr_on_device else None)
-        for p in self.params:
-            p.grad = None
-        return self.stats
+        self._check_owner()
+        return self._launch(self._plan, self._contiguous_grads(keep=True), grad_scale)
 
     def zero_grad(self, set_to_none=True):
         for p in self.params:
@@ -1343,12 +1313,6 @@ class FusedClipAdamWindow(FusedClipAdamW):
 
     def __init__(self, model, *args, **kw):
         super().__init__(model, *args, **kw)
-        sn = {id(p): m for p, (m, _, _, _) in zip(self._deferred, self._sn_tensors)}
-        self._records = []
-        for p, ea, eas in zip(self.params, self.exp_avg, self.exp_avg_sq):
-            m = sn.get(id(p))
-            info = None if m is None else (m.weight_u, m.weight_v, m._sigma, m.rows, m.cols)
-            self._records.append({"param": p.data, "exp_avg": ea, "exp_avg_sq": eas, "sn": info})
         self.window = 0                         # micro-batches accumulated since the last step
         self._acc = self._acc_plan = self._acc_ptrs = self._acc_ptrs_dev = None
         self._window_divisors = {}
@@ -1378,27 +1342,13 @@ class FusedClipAdamWindow(FusedClipAdamW):
         if self._acc is not None and _stale_ptrs(self._acc, self._acc_ptrs):
             raise RuntimeError("FusedClipAdamWindow: an accumulator was moved or replaced after the window was built")
 
-    def _check_owner(self):
-        self._check_plan()
-        for p in self._deferred:
-            if getattr(p, self._defer_attr, None) != self._token:
-                raise RuntimeError("FusedClipAdamW: another optimizer took over (or cleared) the deferred spectral-norm "
-                                   "correction of this model; only the newest optimizer of a model may step")
-
     @torch.no_grad()
     def accumulate(self):
         """Take the current `.grad`s into the window (a parameter without one contributes zeros) and release them."""
         if self._acc is None:
             self.bind_accumulators()
         self._check_owner()
-        grads = []
-        for p in self.params:
-            g = p.grad
-            if g is None:
-                g = torch.zeros_like(p)
-            elif not g.is_contiguous():
-                g = g.contiguous()
-            grads.append(g)
+        grads = self._contiguous_grads(keep=False)
         first = self.window == 0                # the old sums (NaN after a skipped window) are overwritten, not read
         if hasattr(self.be, "grad_accum"):
             self.be.grad_accum(self._plan, grads, self._acc_ptrs_dev, first)
@@ -1422,24 +1372,16 @@ class FusedClipAdamWindow(FusedClipAdamW):
     def step(self, closure=None, grad_scale=None):
         """With `window > 0`: one optimizer-side step on the mean of the window's accumulated gradients, then
         `window = 0`.  With `window == 0`: FusedClipAdamW.step()."""
-        if self.window == 0:
-            return super().step(closure=closure, grad_scale=grad_scale)
-        if closure is not None:
-            raise NotImplementedError("FusedClipAdamW.step takes no closure")
+        if self.window == 0 or closure is not None:
+            return super().step(closure=closure, grad_scale=grad_scale)      # (which refuses a closure)
         self._check_owner()
         for p, a in zip(self.params, self._acc):
             if p.grad is not None and p.grad.data_ptr() != a.data_ptr():
                 raise RuntimeError("FusedClipAdamWindow.step: a window is open and a parameter has a gradient outside it; "
                                    "accumulate() takes gradients into the window")
-        hp = (float(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.max_norm or 0.0, 0)
-        if self.lr_on_device and not torch.cuda.is_current_stream_capturing():
-            self.sync_lr_to_device()
-        self.be.optim_step(self._acc_plan, self._acc, hp, self._window_divisor(grad_scale), self.stats,
-                           lr_dev=self._lr_dev if self.lr_on_device else None)
+        stats = self._launch(self._acc_plan, self._acc, self._window_divisor(grad_scale))
         self.window = 0
-        for p in self.params:
-            p.grad = None
-        return self.stats
+        return stats
 
     def zero_grad(self, set_to_none=True):
         """Release every `.grad` and discard an open window."""
@@ -1727,9 +1669,10 @@ class TrainState:
         GraphedTrainStep stands for its captured inner step.  Rebinding waits for a save in flight."""
         self.wait()
         step = getattr(step, "inner", step)
-        if step is not None and self.fused and self.scaler is not None and not hasattr(step, "_clean_steps"):
-            step._clean_steps = torch.zeros((), dtype=torch.int32, device=self.device)     # as TrainStep._finish makes them
-            step._one = torch.ones((), dtype=torch.float32, device=self.device)
+        if step is not None and self.fused and self.scaler is not None and step._clean_steps is None:
+            raise ValueError(f"TrainState.bind_step: {type(step).__name__} keeps no GradScaler growth count (it was built "
+                             "without this state's scaler or without its fused optimizer), so the state would lack "
+                             "step.clean_steps; give the step and the state the same optimizer and scaler")
         self.step = step
         self._plan_key = None
 
@@ -1746,7 +1689,7 @@ class TrainState:
             tail.append(("ema.count", self.ema._plan.count_dev if self.ema._plan is not None else self._ema_count))
         if self.metrics is not None:
             tail.append(("metrics", self.metrics.buf))
-        if self.step is not None and hasattr(self.step, "_clean_steps") and self.fused and self.scaler is not None:
+        if self.step is not None and self.step._clean_steps is not None and self.fused and self.scaler is not None:
             tail.append(("step.clean_steps", self.step._clean_steps))
         if self.scaler is not None and self.on_gpu:
             tail.append(("scaler.scale", self.scaler._scale))
@@ -2067,7 +2010,7 @@ class GraphedTrainStep:
     current stream (no allocation, no host sync), so forward + loss + backward + gradient exchange + unscale / clip /
     AdamW is one graph launch — with the library's fused optimizer-side step (FusedClipAdamW: its step counter, plan
     and learning rate live on the device) or a capturable torch optimizer, with or without the reference trainer's
-    autocast(bfloat16) + GradScaler (the scale update is device arithmetic, see TrainStep._finish).  Removes the ~3000
+    autocast(bfloat16) + GradScaler (the scale update is device arithmetic: TrainStep._optimizer_step).  Removes the ~3000
     host-side launches per step: the host's share of a step drops from tens of milliseconds to one graph launch, which
     is what keeps 8 ranks on one host from becoming host-bound.  N > 1: pass the BucketedGradReducer — its bucket
     copies and RCCL all-reduces are captured with the step (round 4; the collectives are issued in the
@@ -2126,8 +2069,8 @@ class GraphedTrainStep:
             torch.cuda.set_rng_state(snap[1], example_x.device)
             if snap[2] is not None:
                 scaler.update(new_scale=float(snap[2]))                # fill_ on the scale tensor the graph reads
-                if hasattr(self.inner, "_clean_steps"):
-                    self.inner._clean_steps.zero_()                    # (TrainStep._finish keeps the growth count itself)
+                if self.inner._clean_steps is not None:
+                    self.inner._clean_steps.zero_()                    # (the fused step keeps the growth count itself)
             torch.cuda.synchronize()
 
     def __call__(self, x, y_soft):
@@ -2450,7 +2393,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                                              autocast_dtype=torch.bfloat16, reducer=reducer, restore_after_warmup=True,
                                              metrics=metrics, ema=ema_obj)
                     if st is not None:              # the captured step keeps its own growth count: the current one moves in
-                        if hasattr(step, "_clean_steps") and hasattr(gstep.inner, "_clean_steps"):
+                        if step._clean_steps is not None:       # (then the captured step, built alike, has one too)
                             gstep.inner._clean_steps.copy_(step._clean_steps)
                         st.bind_step(gstep)
                 if gstep is not None and x.shape == gstep.x.shape and y.shape == gstep.y.shape:

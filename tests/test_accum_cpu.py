@@ -219,6 +219,37 @@ def test_unfused_window_equals_the_hand_written_torch_loop_bit_for_bit():
         assert ema.num_updates == 2                                 # one update per optimizer step
 
 
+@pytest.mark.parametrize("config", ["plain", "ema", "ema_scaler"])
+def test_a_window_of_one_is_the_single_batch_step_bit_for_bit(config):
+    """AccumTrainStep(accumulate=1) against TrainStep, torch AdamW: parameters, optimizer state and EMA shadows after every
+    step.  The window class runs TrainStep's own optimizer-side sequence (m = 1: no 1/m pass), not a copy of it."""
+    assert "_optimizer_step" not in vars(trainer.AccumTrainStep)
+    with calm.backend.use_backend(EmulatedBackend()):
+        runs = []
+        for cls, kw in ((trainer.TrainStep, {}), (trainer.AccumTrainStep, {"accumulate": 1})):
+            torch.manual_seed(9)
+            m = build_model("tiny32_cls", None).train()
+            opt = trainer.make_optimizer(m)
+            ema = trainer.ModelEMA(m, 0.9) if config != "plain" else None
+            scaler = torch.amp.GradScaler("cpu", init_scale=4.0, growth_interval=2) if config == "ema_scaler" else None
+            runs.append((m, opt, ema, cls(m, opt, ema=ema, scaler=scaler, **kw)))
+        (m_a, opt_a, ema_a, step_a), (m_b, opt_b, ema_b, step_b) = runs
+        assert (step_b._ema_one is not None) == (config == "ema_scaler") and step_b._clean_steps is None
+        for k in range(3):
+            loss_a, _ = step_a(*_batch(k))
+            loss_b, _ = step_b(*_batch(k))
+            assert step_b.boundary and step_b.window == 0 and torch.equal(loss_a, loss_b)
+            sd_a, sd_b = m_a.state_dict(), m_b.state_dict()
+            assert all(torch.equal(sd_a[n], sd_b[n]) for n in sd_a), k
+            st_a, st_b = opt_a.state_dict()["state"], opt_b.state_dict()["state"]
+            assert len(st_a) == len(st_b) > 0
+            for i in st_a:
+                assert all(torch.equal(torch.as_tensor(st_a[i][n]), torch.as_tensor(st_b[i][n])) for n in st_a[i]), (k, i)
+            if ema_a is not None:
+                assert ema_a.num_updates == ema_b.num_updates == k + 1
+                assert all(torch.equal(a, b) for a, b in zip(ema_a.shadows, ema_b.shadows)), k
+
+
 def test_generative_step_steps_only_at_the_boundary():
     """AccumRegTrainStep: RegTrainStep's forward and loss, AccumTrainStep's window."""
     with calm.backend.use_backend(EmulatedBackend()):

@@ -249,6 +249,38 @@ def test_save_and_load_are_refused_while_the_ema_is_swapped_in(tmp_path):
             opt.close()
 
 
+def test_a_step_without_the_growth_count_is_refused_where_the_state_needs_it(tmp_path):
+    """Fused optimizer and an enabled scaler: `step.clean_steps` belongs to the file.  TrainStep makes the counter when it is
+    built with that scaler; a step built without it is refused by name, not given one behind its back."""
+    with calm.backend.use_backend(EmulatedBackend()):
+        torch.manual_seed(4)
+        m = build_model("tiny32_cls", None).train()
+        opt = trainer.FusedClipAdamW(m)
+        try:
+            scaler = torch.amp.GradScaler("cpu")
+            assert scaler.is_enabled()
+            bare = trainer.RegTrainStep(m, opt)
+            assert bare._clean_steps is None and bare._one is None
+            with pytest.raises(ValueError, match="RegTrainStep keeps no GradScaler growth count"):
+                trainer.TrainState(m, opt, scaler=scaler, step=bare)
+            assert bare._clean_steps is None                        # no repair
+            step = trainer.TrainStep(m, opt, scaler=scaler)
+            assert step._clean_steps.dtype == torch.int32 and step._clean_steps.shape == () and step._one.shape == ()
+            st = trainer.TrainState(m, opt, scaler=scaler, step=step)
+            with pytest.raises(ValueError, match="RegTrainStep keeps no GradScaler growth count"):
+                st.bind_step(bare)
+            assert st.step is step                                  # the refused step was not bound
+            path = str(tmp_path / "s.snap")
+            st.save_async(path, {"epoch": 0, "batch": 0, "step": 0})
+            st.wait()
+            assert "step.clean_steps" in [e["name"] for e in trainer.TrainState.read_header(path)[0]["entries"]]
+            st.close()
+            st = trainer.TrainState(m, opt, step=bare)              # no scaler: nothing to keep, nothing to refuse
+            st.close()
+        finally:
+            opt.close()
+
+
 def test_generator_and_rng_states_round_trip_through_json():
     g = np.random.default_rng(2006)
     g.beta(0.8, 0.8, 5)
