@@ -100,7 +100,8 @@ _loss_kernels = os.environ.get("CALM_LOSS_KERNELS", "0") not in ("", "0")       
 
 def set_loss_kernels(on):
     """True: trainer.soft_target_cross_entropy / RegTrainStep / evaluate run calm_soft_ce_* / calm_huber_tokens_* /
-    calm_top1_count where their conditions hold (fp32 CUDA tensors; see trainer.py).  False (default): stock torch,
+    calm_top1_count, and EvalMetrics runs calm_eval_metrics, where their conditions hold (fp32 CUDA tensors, for
+    calm_eval_metrics bf16 as well; see trainer.py).  False (default): stock torch,
     bit for bit what the step computed before the kernels existed."""
     global _loss_kernels
     _loss_kernels = bool(on)
@@ -114,6 +115,12 @@ def loss_kernels_take(t):
     """Whether the loss kernels serve tensor `t` now: the switch is on and `t` is an fp32 tensor the installed backend
     can address (HipBackend: CUDA tensors only)."""
     return _loss_kernels and t.dtype == torch.float32 and (t.is_cuda or not isinstance(get_backend(), HipBackend))
+
+
+def eval_kernels_take(t):
+    """Whether calm_eval_metrics serves logits `t` now (trainer.EvalMetrics): as loss_kernels_take, and bf16 as well."""
+    return (_loss_kernels and t.dtype in (torch.float32, torch.bfloat16)
+            and (t.is_cuda or not isinstance(get_backend(), HipBackend)))
 
 
 def effective_precision():
@@ -1115,6 +1122,31 @@ class HipBackend:
             raise TypeError("top1_count expects contiguous int64 CUDA labels")
         _lib.check(self.lib.calm_top1_count(_ptr(logits), logits.stride(0), labels.data_ptr(), _ptr(metrics), B, C,
                                             _stream()), "calm_top1_count")
+
+    def eval_metrics(self, logits, labels, ks, counts, loss_sum, confusion, B, C, partials=None):
+        """calm_eval_metrics: logits [B,C] fp32 or bf16 with unit column stride (any row stride), labels [B] int64; the
+        batch's tallies are ADDED to counts (int64 [7 + 2C]: rows, skipped, nonfinite, hits@ks[0..3], support[C],
+        hits1[C]), loss_sum (float64 [1]) and confusion (int64 [C,C] or None).  ks: 1 to 4 integers >= 1.  partials: the
+        caller's own record scratch (fp32, >= 4 * B elements) — the shared reduction scratch when None."""
+        if not labels.is_cuda or labels.dtype != torch.int64 or not labels.is_contiguous():
+            raise TypeError("eval_metrics expects contiguous int64 CUDA labels")
+        for name, t, dt in (("counts", counts, torch.int64), ("loss_sum", loss_sum, torch.float64),
+                            ("confusion", confusion, torch.int64)):
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+                raise TypeError(f"eval_metrics expects a contiguous {dt} CUDA tensor for {name}")
+        if counts.numel() < _lib.EVAL_COUNTS_HEAD + 2 * C or (confusion is not None and confusion.numel() < C * C):
+            raise ValueError("eval_metrics: counts holds 7 + 2 C values, confusion C * C")
+        if partials is None:
+            part = self._partials(_lib.RED_EVAL, B, C, logits.device)
+        else:
+            if partials.numel() < 4 * B:
+                raise ValueError("eval_metrics: partials holds one 16-byte record per row")
+            part = _ptr(partials)
+        karr = (_lib.C.c_int32 * len(ks))(*[int(k) for k in ks])
+        _lib.check(self.lib.calm_eval_metrics(_ptr(logits, bf16_ok=True), logits.stride(0), _st(logits), labels.data_ptr(),
+                                              karr, len(ks), counts.data_ptr(), loss_sum.data_ptr(),
+                                              None if confusion is None else confusion.data_ptr(), B, C, part, _stream()),
+                   "calm_eval_metrics")
 
     # ---- dropout (csrc/dropout.hip) -----------------------------------------------------
     def dropout(self, x, residual, y, n, p, key, e0=0):

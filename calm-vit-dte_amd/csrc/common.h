@@ -192,3 +192,4 @@ constexpr int CNN_BWD_MAX_GRID = 256;
 constexpr int CNN_PART_STRIDE = 560;           // floats between the CNN tail's partial rows (cnn_fused.hip: CNN_PART_N of them used)
 constexpr int SOFT_CE_PART_ROWS = 2;           // soft-target CE: one workgroup per sample; B row losses, then B agreement flags
 constexpr int HUBER_MAX_GRID = 2048;           // one block sum per workgroup
+constexpr int EVAL_REC_FLOATS = 4;             // calm_eval_metrics: one 16-byte record per row (no cross-workgroup sum in launch 1)

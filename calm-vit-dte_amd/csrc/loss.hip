@@ -206,6 +206,221 @@ static __global__ __launch_bounds__(TOP1_NT) void top1_count_kernel(const float*
     }
 }
 
+// ---- validation metrics: top-k, cross-entropy, per-class counts --------------------------------------------------------
+// Launch 1, eval_rows_kernel: one wave per row, four rows per workgroup, ceil(B / 4) workgroups (top1_count_kernel above
+// sends everything through one CU).  Pass 1: row maximum with its lowest index and the NaN flag; pass 2 (the row comes
+// back from the cache): sum exp(z - max) and the number of classes that BEAT the label — z_c > z_l, or z_c == z_l and
+// c < l — so the label is in the top k exactly when beaten < k.  One 16-byte record per row, written by lane 0.
+// Launch 2, eval_fold_kernel: one workgroup folds the records into the caller's accumulators; every counter has one
+// owning thread and the loss is added in a fixed order.
+#define EVAL_SKIPPED 1       // record flags: the label is outside [0, C)
+#define EVAL_NONFINITE 2     //               the row holds a NaN
+#define EVAL_FOLD_NT 1024    // threads of the fold = rows per staged chunk = stride between the classes a thread owns
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+struct EvalKs { int k[4]; int nk; };
+
+__device__ __forceinline__ float bf16_bits_to_float(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
+// the logits of one row in storage type T (float, or the bits of a bf16): element c, or group q of VEC elements
+template <bool BF16> struct EvalRow;
+template <> struct EvalRow<false> {
+    static constexpr int VEC = 4;
+    const float* z;
+    __device__ __forceinline__ float at(int c) const { return z[c]; }
+    __device__ __forceinline__ void group(int q, float* v) const {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(z + 4 * q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = t[k];
+    }
+};
+template <> struct EvalRow<true> {
+    static constexpr int VEC = 8;
+    const unsigned short* z;
+    __device__ __forceinline__ float at(int c) const { return bf16_bits_to_float(z[c]); }
+    __device__ __forceinline__ void group(int q, float* v) const {
+        const u16x8 t = *reinterpret_cast<const u16x8*>(z + 8 * q);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = bf16_bits_to_float(t[k]);
+    }
+};
+
+// cv: number of leading VEC-element groups of a row that may be read as 16-byte vectors (0: scalar path for the whole row)
+template <bool BF16>
+static __global__ __launch_bounds__(LOSS_NT) void eval_rows_kernel(const void* __restrict__ logits, long ld,
+                                                                   const long long* __restrict__ labels,
+                                                                   float* __restrict__ partials, int B, int C, int cv) {
+    using Row = EvalRow<BF16>;
+    constexpr int VEC = Row::VEC;
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (LOSS_NT / 64) + (threadIdx.x >> 6);
+    if (b >= B) return;                                              // (whole waves leave; nothing below is block-wide)
+    const long long lab = labels[b];
+    i32x4 rec = {0, 0, 0, EVAL_SKIPPED};
+    if (lab >= 0 && lab < C) {
+        const int l = (int)lab;
+        Row row{reinterpret_cast<decltype(Row::z)>(logits) + (long)b * ld};
+        const float zl = row.at(l);
+        float zm = -INFINITY;
+        int zi = 0x7fffffff;
+        bool bad = false;
+        float v[VEC];
+        for (int q = lane; q < cv; q += 64) {
+            row.group(q, v);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                bad |= v[k] != v[k];
+                if (v[k] > zm) { zm = v[k]; zi = VEC * q + k; }
+            }
+        }
+        for (int c = VEC * cv + lane; c < C; c += 64) {
+            const float zc = row.at(c);
+            bad |= zc != zc;
+            if (zc > zm) { zm = zc; zi = c; }
+        }
+        if (zm == -INFINITY && zi == 0x7fffffff && lane < C) zi = lane;     // (as top1_count_kernel: an all -inf row -> 0)
+        wave_argmax(zm, zi);
+        const bool any_bad = __any(bad);
+
+        float se = 0.f;
+        int beaten = 0;
+        for (int q = lane; q < cv; q += 64) {
+            row.group(q, v);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                se += __expf(v[k] - zm);
+                beaten += (v[k] > zl) | ((v[k] == zl) & (VEC * q + k < l));
+            }
+        }
+        for (int c = VEC * cv + lane; c < C; c += 64) {
+            const float zc = row.at(c);
+            se += __expf(zc - zm);
+            beaten += (zc > zl) | ((zc == zl) & (c < l));
+        }
+        se = wave_sum(se);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) beaten += __shfl_xor(beaten, o, 64);
+        const float nll = (zm - zl) + logf(se);
+        rec = i32x4{__float_as_int(nll), beaten, zi, any_bad ? EVAL_NONFINITE : 0};
+    }
+    if (lane == 0) *reinterpret_cast<i32x4*>(partials + 4 * (long)b) = rec;
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Rows are staged EVAL_FOLD_NT at a time: thread t reads record and label of row r0 + t, keeps the scalar tallies and its
+// share of the loss (rows t, t + 1024, ... in increasing order; a fixed tree over the 1024 running sums at the end), and
+// leaves (label, or -1 when the row is not counted), (label where the prediction equals it, or -1) and (pred, or -1 when
+// the row is not finite) in LDS.  Thread t then owns classes t, t + 1024, ...: it scans the staged rows once per owned
+// class and adds what it found to that class's support, top-1 hits and confusion row with plain read-modify-writes — no
+// other thread touches those addresses.
+static __global__ __launch_bounds__(EVAL_FOLD_NT) void eval_fold_kernel(const float* __restrict__ partials,
+                                                                        const long long* __restrict__ labels,
+                                                                        long long* __restrict__ counts,
+                                                                        double* __restrict__ loss_sum,
+                                                                        long long* __restrict__ confusion, int B, int C,
+                                                                        const EvalKs ks) {
+    __shared__ i32x4 key_v[EVAL_FOLD_NT / 4];                        // (read back sixteen rows at a time)
+    __shared__ i32x4 hit_v[EVAL_FOLD_NT / 4];
+    __shared__ int pred_s[EVAL_FOLD_NT];
+    int* key_s = reinterpret_cast<int*>(key_v);
+    int* hit_s = reinterpret_cast<int*>(hit_v);
+    __shared__ float redf[EVAL_FOLD_NT / 64];
+    __shared__ int redi[7][EVAL_FOLD_NT / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    float s = 0.f;
+    int tally[7] = {0, 0, 0, 0, 0, 0, 0};                            // rows, skipped, nonfinite, hits@ks[0..3]
+    for (int r0 = 0; r0 < B; r0 += EVAL_FOLD_NT) {
+        const int n = B - r0 < EVAL_FOLD_NT ? B - r0 : EVAL_FOLD_NT;
+        int key = -1, pred = -1;
+        if (t < n) {
+            const i32x4 rec = *reinterpret_cast<const i32x4*>(partials + 4 * (long)(r0 + t));
+            if (rec[3] & EVAL_SKIPPED) {
+                tally[1] += 1;
+            } else {
+                tally[0] += 1;
+                key = (int)labels[r0 + t];
+                if (rec[3] & EVAL_NONFINITE) {
+                    tally[2] += 1;
+                } else {
+                    pred = rec[2];
+                    s += __int_as_float(rec[0]);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) tally[3 + i] += (i < ks.nk) & (rec[1] < ks.k[i]);
+                }
+            }
+        }
+        key_s[t] = key;
+        hit_s[t] = pred == key ? key : -1;                           // (the label where the row is a top-1 hit)
+        pred_s[t] = pred;
+        __syncthreads();
+        // Every thread reads the same addresses (LDS broadcasts), sixteen rows per turn, and the counting does not branch.
+        // This loop is the launch: ONE CU runs C x n compares twice (label, hit), ~100 instructions per wave and turn —
+        // 14 us of a 17 us call at B = 256, C = 1000 (rocprofv3; the row kernel takes 4.6).  A wave holds 64 classes, so
+        // SOME lane matches in most groups of sixteen rows: a row-by-row walk of every group with a match (two dependent
+        // LDS reads and a branch per row) took 21 us.  Only the confusion matrix needs the rows one by one, and it reads
+        // LDS again only for a row that matches.
+        const int n16 = (n + 15) & ~15;                               // (keys behind row n are -1)
+        for (int c = t; c < C; c += EVAL_FOLD_NT) {
+            int sup = 0, h1 = 0;
+            for (int r = 0; r < n16; r += 16) {
+                i32x4 k[4];
+                int m = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    k[j] = key_v[(r >> 2) + j];
+                    const i32x4 h = hit_v[(r >> 2) + j];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        m += k[j][e] == c;
+                        h1 += h[e] == c;
+                    }
+                }
+                sup += m;
+                if (confusion && m) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            if (k[j][e] != c) continue;
+                            const int p = pred_s[r + 4 * j + e];
+                            if ((unsigned)p < (unsigned)C) confusion[(long)c * C + p] += 1;      // (-1: not finite)
+                        }
+                    }
+                }
+            }
+            if (sup) counts[7 + c] += sup;
+            if (h1) counts[7 + (long)C + c] += h1;
+        }
+        __syncthreads();
+    }
+    s = wave_sum(s);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) tally[i] = wave_sum_int(tally[i]);
+    if (lane == 0) {
+        redf[w] = s;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) redi[i][w] = tally[i];
+    }
+    __syncthreads();
+    if (t == 0) {
+        float total = 0.f;
+#pragma unroll
+        for (int k = 0; k < EVAL_FOLD_NT / 64; ++k) total += redf[k];
+        loss_sum[0] += (double)total;
+    }
+    if (t >= 64 && t < 64 + 3 + ks.nk) {                             // (one owner per scalar counter, off thread 0's wave)
+        const int i = t - 64;
+        long long total = 0;
+#pragma unroll
+        for (int k = 0; k < EVAL_FOLD_NT / 64; ++k) total += redi[i][k];
+        counts[i] += total;
+    }
+}
+
 // ---- token-layout Huber ------------------------------------------------------------------------------------------------
 // A token row (b,i) is 3S contiguous floats, tokens[b,i,3j+c], against the three S-float rows x[b,c,i,:].  A workgroup
 // takes R consecutive token rows per turn: the 3R image rows are staged into LDS with 16-byte loads ([r][c][j], the
@@ -317,6 +532,34 @@ int calm_top1_count(const float* logits, int64_t ld, const int64_t* labels, floa
     const int c4 = aligned16(logits) && (ld & 3) == 0 ? C >> 2 : 0;
     return calm_launch(top1_count_kernel, 1, TOP1_NT, 0, stream, logits, ld, reinterpret_cast<const long long*>(labels),
                        metrics, B, C, c4);
+}
+
+int calm_eval_metrics(const void* logits, int64_t ld, int32_t logits_type, const int64_t* labels, const int32_t* ks,
+                      int32_t nk, int64_t* counts, double* loss_sum, int64_t* confusion, int32_t B, int32_t C,
+                      float* partials, void* stream) {
+    if (!logits || !labels || !ks || !counts || !loss_sum || !partials || B <= 0 || C <= 0 || ld < C) return CALM_E_INVAL;
+    if (nk < 1 || nk > 4) return CALM_E_INVAL;
+    if (logits_type != CALM_ST_F32 && logits_type != CALM_ST_BF16) return CALM_E_INVAL;
+    EvalKs k{};
+    k.nk = nk;
+    for (int i = 0; i < nk; ++i) {
+        if (ks[i] < 1) return CALM_E_INVAL;
+        k.k[i] = ks[i];
+    }
+    if (C > 65536) return CALM_E_UNSUPP;                         // a fold thread owns C / 1024 classes, a scan of the chunk each
+    if (!aligned16(partials)) return CALM_E_LAYOUT;              // (the records are 16-byte stores)
+    const bool bf16 = logits_type == CALM_ST_BF16;
+    const int vec = bf16 ? 8 : 4;
+    const int cv = aligned16(logits) && (ld % vec) == 0 ? C / vec : 0;
+    const int grid = (B + LOSS_NT / 64 - 1) / (LOSS_NT / 64);
+    const long long* lab = reinterpret_cast<const long long*>(labels);
+    if (int e = with_bool(bf16, [&](auto b16) {
+            return calm_launch(eval_rows_kernel<decltype(b16)::value>, grid, LOSS_NT, 0, stream, logits, ld, lab, partials, B,
+                               C, cv);
+        }))
+        return e;
+    return calm_launch(eval_fold_kernel, 1, EVAL_FOLD_NT, 0, stream, partials, lab, reinterpret_cast<long long*>(counts),
+                       loss_sum, reinterpret_cast<long long*>(confusion), B, C, k);
 }
 
 int calm_huber_tokens_fwd(const float* tokens, const float* x, float delta, float* loss, int32_t B, int32_t S,

@@ -1137,6 +1137,7 @@ int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols) {
         case CALM_RED_CNN_BWD: return (int64_t)CNN_BWD_MAX_GRID * CNN_PART_STRIDE;
         case CALM_RED_SOFT_CE: return SOFT_CE_PART_ROWS * rows;
         case CALM_RED_HUBER: return HUBER_MAX_GRID;
+        case CALM_RED_EVAL: return EVAL_REC_FLOATS * rows;
         default: return 0;
     }
 }

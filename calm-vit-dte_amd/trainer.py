@@ -19,6 +19,10 @@ as set by torchrun):
   * `ModelEMA`                         (no counterpart: the reference keeps no weight average)
         exponential moving average of the parameters, one kernel pass behind the optimizer step; exchanged into the
         parameters in place for evaluation.
+  * `EvalMetrics` / `validation_shard` / `evaluate(report=True)`   (the reference has the top-1 loop of CALM_ViT_V2.py:228-239 only)
+        top-k, cross-entropy, per-class accuracy and confusion matrix of held-out data, tallied on the device
+        (calm_eval_metrics) and summed over the ranks; `train(val_dataset=...)` runs it per epoch and keeps the best
+        checkpoint.
 
 The model also works under stock `torch.nn.parallel.DistributedDataParallel` (that is what the
 reference's train() does with it); the reducer here is the MI355X-tuned equivalent.  Under DDP the step
@@ -278,6 +282,107 @@ class StepMetrics:
 
     def reset(self):
         self.buf.zero_()                    # in place: a captured step keeps adding at this address
+
+
+def eval_metrics_torch(logits, labels, ks, counts, loss_sum, confusion):
+    """What calm_eval_metrics adds to its accumulators (include/calm_vit.h), in torch on the tensors' device: class c BEATS
+    label l when z_c > z_l, or z_c == z_l and c < l, and the label is in the top k exactly when fewer than k classes beat
+    it; a row whose label is outside [0, C) is skipped (counted in `skipped` alone); a row holding a NaN is counted in
+    rows, nonfinite and its class's support, is never a hit and adds to neither the loss nor the confusion matrix.  The
+    integers equal the kernel's; the loss is the same fp32 formula summed in torch's order."""
+    z = logits.float()
+    B, C = z.shape
+    labels = labels.to(z.device, torch.int64)
+    valid = (labels >= 0) & (labels < C)
+    l = labels.clamp(0, C - 1)
+    zl = z.gather(1, l[:, None])
+    cls = torch.arange(C, device=z.device)[None, :]
+    beaten = ((z > zl) | ((z == zl) & (cls < l[:, None]))).sum(dim=1)
+    nan = torch.isnan(z).any(dim=1)
+    finite = valid & ~nan
+    zf = torch.where(finite[:, None], z, torch.zeros_like(z))      # (argmax / max of a NaN row are not used)
+    m, pred = zf.max(dim=1)                                         # first maximal value: the lowest index wins
+    nll = (m - zl[:, 0]) + torch.log(torch.exp(zf - m[:, None]).sum(dim=1))
+    head = [valid.sum(), (~valid).sum(), (valid & nan).sum()] + [(finite & (beaten < int(k))).sum() for k in ks]
+    counts[:len(head)] += torch.stack(head).to(counts.dtype)
+    counts[7:7 + C] += torch.bincount(l[valid], minlength=C)
+    counts[7 + C:7 + 2 * C] += torch.bincount(l[finite & (pred == l)], minlength=C)
+    loss_sum += torch.where(finite, nll, torch.zeros_like(nll)).sum().double()
+    if confusion is not None:
+        confusion.view(-1).add_(torch.bincount(l[finite] * C + pred[finite], minlength=C * C))
+
+
+class EvalMetrics:
+    """Validation tallies on the device: rows, top-k hits, the cross-entropy sum, per-class support and top-1 hits and,
+    with confusion=True, the [label, prediction] confusion matrix — `counts` (int64 [7 + 2C]: rows, skipped, nonfinite,
+    hits@topk[0..3], support[C], hits1[C]), `loss_sum` (float64 [1]) and `confusion` (int64 [C,C] or None), the
+    accumulators of calm_eval_metrics (include/calm_vit.h).
+
+    update(logits, labels) adds one batch.  With the loss kernels switched on (backend.set_loss_kernels) and fp32 or bf16
+    CUDA logits it is ONE library call — two launches, no host synchronisation, and after the first call at the largest
+    batch size no allocation, so it can be captured into a graph; otherwise `eval_metrics_torch`, the same definitions in
+    torch, with the same integers.  all_reduce() sums the accumulators over a process group, read() is one device-to-host
+    copy, reset() zeroes in place."""
+
+    def __init__(self, num_classes, topk=(1, 5), confusion=False, device="cpu"):
+        topk = tuple(topk)
+        if not 1 <= len(topk) <= 4 or any(int(k) != k or k < 1 for k in topk) or len(set(topk)) != len(topk):
+            raise ValueError(f"EvalMetrics: topk takes one to four distinct integers >= 1, got {topk!r}")
+        if int(num_classes) != num_classes or not 1 <= num_classes <= 65536:
+            raise ValueError(f"EvalMetrics: num_classes within 1 .. 65536 expected, got {num_classes!r}")
+        self.num_classes, self.topk = int(num_classes), tuple(int(k) for k in topk)
+        C = self.num_classes
+        self.counts = torch.zeros(7 + 2 * C, dtype=torch.int64, device=device)
+        self.loss_sum = torch.zeros(1, dtype=torch.float64, device=device)
+        self.confusion = torch.zeros(C, C, dtype=torch.int64, device=device) if confusion else None
+        self._records = None                 # the kernel's per-row records: grown to the largest batch seen
+
+    def tensors(self):
+        return [t for t in (self.counts, self.loss_sum, self.confusion) if t is not None]
+
+    def update(self, logits, labels):
+        from . import backend
+        if logits.dim() != 2 or logits.shape[1] != self.num_classes or labels.shape != logits.shape[:1]:
+            raise ValueError(f"EvalMetrics.update: logits [B, {self.num_classes}] and labels [B] expected, got "
+                             f"{tuple(logits.shape)} and {tuple(labels.shape)}")
+        if backend.eval_kernels_take(logits):
+            B, C = logits.shape
+            logits = logits if logits.stride(1) == 1 else logits.contiguous()
+            labels = labels.to(logits.device, torch.int64).contiguous()
+            if self._records is None or self._records.numel() < 4 * B:
+                self._records = torch.empty(4 * B, dtype=torch.float32, device=logits.device)
+            backend.get_backend().eval_metrics(logits, labels, self.topk, self.counts, self.loss_sum, self.confusion, B, C,
+                                               self._records)
+        else:
+            eval_metrics_torch(logits, labels, self.topk, self.counts, self.loss_sum, self.confusion)
+
+    def all_reduce(self, group=None):
+        for t in self.tensors():
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+
+    def reset(self):
+        for t in self.tensors():
+            t.zero_()                       # in place: a captured update keeps adding at these addresses
+
+    def read(self):
+        """The report as a plain dict, from ONE device-to-host copy: n (rows counted), skipped, nonfinite, loss (mean over
+        the finite rows), top<k> for every k (hits / n), per_class_accuracy (float64 [C]; NaN where a class has no
+        support), mean_per_class_accuracy (over the classes that have support) and confusion (int64 [C,C]) if kept."""
+        C = self.num_classes
+        flat = torch.cat([self.counts, self.loss_sum.view(torch.int64)]
+                         + ([self.confusion.reshape(-1)] if self.confusion is not None else [])).to("cpu")
+        n, skipped, nonfinite = (int(v) for v in flat[:3])
+        rep = {"n": n, "skipped": skipped, "nonfinite": nonfinite,
+               "loss": float(flat[7 + 2 * C:8 + 2 * C].view(torch.float64)) / max(n - nonfinite, 1)}
+        for i, k in enumerate(self.topk):
+            rep[f"top{k}"] = int(flat[3 + i]) / max(n, 1)
+        support, hits1 = flat[7:7 + C].double(), flat[7 + C:7 + 2 * C].double()
+        acc = torch.where(support > 0, hits1 / support.clamp(min=1), torch.full_like(support, float("nan")))
+        rep["per_class_accuracy"] = acc
+        rep["mean_per_class_accuracy"] = float(acc[support > 0].mean()) if bool((support > 0).any()) else 0.0
+        if self.confusion is not None:
+            rep["confusion"] = flat[8 + 2 * C:].reshape(C, C).clone()
+        return rep
 
 
 class TrainStep:
@@ -1012,7 +1117,8 @@ class Predictor:
         self.graph = self.x = self.out = None
 
 
-def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, transform=None, transform_out="tokens", ema=None):
+def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, transform=None, transform_out="tokens", ema=None,
+             report=False, topk=(1, 5), confusion=False, process_group=None):
     """Top-1 accuracy over (x, labels) batches in eval mode (CALM_ViT_V2.py:228-239).  With the loss kernels switched on
     the hits are counted on the device (calm_top1_count into a StepMetrics) and read once after the last batch instead of
     once per batch.  lean / graph: the forward goes through a Predictor (lean kernels; graph=True captures it at the first
@@ -1025,13 +1131,21 @@ def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, trans
     model whose first layer is not this ViT's first Block, which alone takes row tokens — the kernel has both outputs and
     the caller has to be able to choose).
     ema: a ModelEMA of `model`.  The whole loop runs inside `ema.applied()`: the averages are exchanged into the parameters
-    in place (every cached address and captured graph stays valid) and exchanged back when the loop ends or raises."""
+    in place (every cached address and captured graph stays valid) and exchanged back when the loop ends or raises.
+    report=True: instead of the top-1 float the call returns the dict of `EvalMetrics.read()` — n, skipped, nonfinite,
+    loss (mean cross-entropy), top<k> for every k of `topk`, per_class_accuracy, mean_per_class_accuracy and, with
+    confusion=True, the confusion matrix — over integer labels [B].  Every batch is one `EvalMetrics.update` (one library
+    call without a host synchronisation where the loss kernels serve the logits), and the tallies are summed over
+    `process_group`, or over the default group when torch.distributed is initialised, before the one read: every rank
+    evaluates its own `validation_shard` and every rank returns the report of the whole set.  At least one batch is
+    needed (the class count comes from the logits).  report=False (the default) is the loop as it was."""
     if ema is not None:
         if ema.model is not model:
             raise ValueError("evaluate: ema= must be the ModelEMA of the model being evaluated")
         with ema.applied():
             return evaluate(model, batches, lean=lean, graph=graph, autocast_dtype=autocast_dtype, transform=transform,
-                            transform_out=transform_out)
+                            transform_out=transform_out, report=report, topk=topk, confusion=confusion,
+                            process_group=process_group)
     from . import backend
     if transform is not None:
         if not isinstance(transform, DeviceResizedCrop):
@@ -1053,6 +1167,7 @@ def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, trans
     correct = total = 0
     metrics = None
     predictor = None
+    tallies = None
     with torch.no_grad():
         for x, labels in batches:
             if lean or graph:
@@ -1062,6 +1177,11 @@ def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, trans
             else:
                 y_hat, _ = model(x)
             logits = y_hat.reshape(x.shape[0], -1)
+            if report:
+                if tallies is None:
+                    tallies = EvalMetrics(logits.shape[1], topk=topk, confusion=confusion, device=logits.device)
+                tallies.update(logits, labels.to(logits.device))
+                continue
             if backend.get_loss_kernels() and labels.dim() == 1 and backend.loss_kernels_take(logits):
                 if metrics is None:
                     metrics = StepMetrics(logits.device)
@@ -1077,7 +1197,22 @@ def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, trans
     if predictor is not None:
         predictor.close()
     model.train(was_training)
+    if report:
+        if tallies is None:
+            raise ValueError("evaluate: report=True needs at least one batch")
+        if process_group is not None or (dist.is_available() and dist.is_initialized()):
+            tallies.all_reduce(process_group)
+        return tallies.read()
     return correct / max(total, 1)
+
+
+def validation_shard(dataset, rank, world):
+    """The samples rank, rank + world, ... of `dataset`, WITHOUT padding: DistributedSampler fills the shards up with
+    repeated samples, which a validation pass would count twice.  The shards of all ranks cover every index exactly once,
+    so the `n` of an all-reduced report equals len(dataset)."""
+    if not 0 <= rank < world:
+        raise ValueError(f"validation_shard: rank {rank} is outside a world of {world}")
+    return torch.utils.data.Subset(dataset, range(rank, len(dataset), world))
 
 
 def save_samples(imgs, out_dir, prefix="sample_"):
@@ -2150,11 +2285,83 @@ class SoftMixCollate:
         return self.mix(x, labels, mode, lam, box)
 
 
+def _val_best_so_far(val_log):
+    """{"top1": best live top-1, "ema_top1": best averaged top-1} from the lines of an existing validation log."""
+    import json
+    best = {}
+    if os.path.exists(val_log):
+        with open(val_log) as f:
+            for line in f:
+                if not line.strip():
+                    continue
+                rec = json.loads(line)
+                for key, rep in (("top1", rec), ("ema_top1", rec.get("ema"))):
+                    if rep is not None and "top1" in rep and rep["top1"] > best.get(key, -1.0):
+                        best[key] = rep["top1"]
+    return best
+
+
+def _validate_epoch(model, ema, val_dataset, rank, world, device, batch_size, transform, topk, epoch, n_steps,
+                    checkpoint_path, val_log, best, verbose):
+    """One validation pass of train(): every rank evaluates its shard (live weights, then the averaged ones), the reports
+    are all-reduced inside evaluate; the caller's rank 0 passes checkpoint_path / val_log / verbose and does the writing.
+    The RNG states and the training flag are as before when it returns."""
+    import json
+    from torch.utils.data import DataLoader
+    use_gpu = device.type == "cuda"
+    cpu_rng = torch.get_rng_state()
+    dev_rng = torch.cuda.get_rng_state(device) if use_gpu else None
+    was_training = model.training
+    shard = validation_shard(val_dataset, rank, world)
+    collate = RaggedU8Collate() if transform is not None else None
+
+    def batches():
+        for batch in DataLoader(shard, batch_size=int(batch_size), shuffle=False, collate_fn=collate, num_workers=0):
+            if transform is not None:
+                yield batch                                   # (packed, meta, labels): evaluate moves and transforms it
+            else:
+                x, labels = batch
+                yield x.to(device, non_blocking=True), labels.to(device, non_blocking=True)
+    try:
+        kw = dict(lean=True, autocast_dtype=torch.bfloat16 if use_gpu else None, transform=transform, report=True, topk=topk)
+        rep = evaluate(model, batches(), **kw)
+        rep_ema = evaluate(model, batches(), ema=ema, **kw) if ema is not None else None
+    finally:
+        torch.set_rng_state(cpu_rng)
+        if dev_rng is not None:
+            torch.cuda.set_rng_state(dev_rng, device)
+        model.train(was_training)
+    scalars = lambda r: {k: v for k, v in r.items() if not isinstance(v, torch.Tensor)}
+    line = {"epoch": epoch + 1, "step": n_steps, **scalars(rep)}
+    if rep_ema is not None:
+        line["ema"] = scalars(rep_ema)
+    if verbose:
+        for tag, r in (("", rep), (" (EMA)", rep_ema)):
+            if r is not None:
+                tops = ", ".join(f"top-{k}: {100.0 * r[f'top{k}']:.4f}%" for k in topk)
+                print(f"Epoch: {epoch + 1}, Validation{tag}: {tops}, Loss: {r['loss']}, "
+                      f"Mean per-class accuracy: {100.0 * r['mean_per_class_accuracy']:.4f}%, Samples: {r['n']}")
+    if val_log is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(val_log)), exist_ok=True)
+        with open(val_log, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    if checkpoint_path:
+        stem, ext = os.path.splitext(checkpoint_path)
+        if rep["top1"] > best.get("top1", -1.0):
+            best["top1"] = rep["top1"]
+            torch.save(model.state_dict(), stem + "_best" + ext)
+        if rep_ema is not None and rep_ema["top1"] > best.get("ema_top1", -1.0):
+            best["ema_top1"] = rep_ema["top1"]
+            torch.save(ema.model_state_dict(), stem + "_ema_best" + ext)
+    return line
+
+
 def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, epochs=15, batch_size=128,
           checkpoint_path=None, num_classes=1000, num_workers=0, collate_fn="mix", log_every=100, max_steps=None,
           destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
           device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None,
-          ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1):
+          ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
+          val_batch_size=None, val_transform=None, val_topk=(1, 5)):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -2244,7 +2451,20 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     at batch indices that are multiples of k in every epoch.  Snapshots are written only right behind an optimizer step,
     and resume= continues at such a boundary.  The gradients are exchanged once per window.  A window equals the torch
     loop "k x (forward, backward), then unscale / clip / step" with spectral norm iterating at every forward; it does
-    not equal one k-times-larger batch."""
+    not equal one k-times-larger batch.
+
+    val_dataset (validation; yields (x, integer label), or (uint8 [h, w, 3], label) with val_transform): behind every
+    val_every-th epoch's checkpoint and in front of scheduler.step() every rank evaluates its `validation_shard` in
+    batches of val_batch_size (default: batch_size) through a lean `Predictor` — `evaluate(report=True, lean=True,
+    topk=val_topk, transform=val_transform)`, under autocast(bf16) on a GPU as the training forward — and the tallies are
+    summed over the ranks.  Rank 0 prints one line (top-k, loss, mean per-class accuracy) and appends one JSON line
+    {"epoch", "step", report without the per-class arrays} to `<checkpoint stem>_val.jsonl`; when top-1 strictly
+    improves on the best so far it also writes `<stem>_best<ext>`.  With ema, the pass is repeated on the averaged weights
+    (`ema.applied()`), logged under "ema", and `<stem>_ema_best<ext>` is kept the same way.  resume= takes the best
+    values so far from the existing `_val.jsonl` and appends to it; a run without resume= starts the log anew.  Validation does not move the run: the CPU and device RNG states are
+    saved around it and put back and the model is left in training mode, so the returned parameters equal those of the
+    same run without val_dataset bit for bit.  val_topk must contain 1; checkpoint_path may be None (nothing is written,
+    rank 0 still prints)."""
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
     if device_metrics and not (use_gpu and _backend.get_loss_kernels()):
@@ -2284,7 +2504,19 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         ema_kw = dict(ema) if isinstance(ema, dict) else {"decay": float(ema)}
         if not set(ema_kw) <= {"decay", "warmup"} or not 0.0 <= float(ema_kw.get("decay", 0.9999)) < 1.0:
             raise ValueError(f'train: ema takes a decay in [0, 1) or a dict with "decay" / "warmup", got {ema!r}')
+    if int(val_every) != val_every or val_every < 1:
+        raise ValueError(f"train: val_every counts epochs between validation passes (>= 1), got {val_every!r}")
+    if val_transform is not None and not use_gpu:
+        raise ValueError("train: val_transform needs use_gpu=True (the validation transform is a HIP kernel)")
+    if val_dataset is not None:
+        if val_batch_size is not None and (int(val_batch_size) != val_batch_size or val_batch_size < 1):
+            raise ValueError(f"train: val_batch_size counts samples (>= 1), got {val_batch_size!r}")
+        if 1 not in tuple(val_topk):
+            raise ValueError(f"train: val_topk must contain 1 (the best checkpoint follows top-1), got {val_topk!r}")
+        EvalMetrics(num_classes, topk=val_topk)             # (refuses a malformed val_topk here, not after the first epoch)
     rank, local_rank, world = init_distributed(use_gpu)
+    if val_dataset is not None and len(val_dataset) < world:
+        raise ValueError(f"train: val_dataset holds {len(val_dataset)} samples, fewer than the {world} ranks")
     device = torch.device(f"cuda:{local_rank}" if use_gpu else "cpu")
     if use_gpu:
         torch.cuda.set_device(device)
@@ -2349,6 +2581,12 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         st = TrainState(model, optimizer, scaler=scaler if use_gpu else None, scheduler=scheduler, ema=ema_obj, step=step,
                         metrics=metrics, generators=gens, payload=rank == 0 and local_rank == 0,
                         sidecar_rank=rank if world > 1 else None)
+    val_log = val_best = None
+    if val_dataset is not None:
+        val_log = os.path.splitext(checkpoint_path)[0] + "_val.jsonl" if checkpoint_path else None
+        val_best = _val_best_so_far(val_log) if resume is not None and val_log else {}
+        if resume is None and val_log and rank == 0 and local_rank == 0 and os.path.exists(val_log):
+            os.remove(val_log)                              # a new run starts its own log; a resumed one appends
     try:
         if resume is not None:
             progress = st.load(resume)
@@ -2430,6 +2668,11 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                 if ema_obj is not None:
                     stem, ext = os.path.splitext(checkpoint_path)
                     torch.save(ema_obj.model_state_dict(), stem + "_ema" + ext)
+            if val_dataset is not None and (epoch + 1) % int(val_every) == 0:
+                _validate_epoch(model, ema_obj, val_dataset, rank, world, device, val_batch_size or batch_size, val_transform,
+                                val_topk, epoch, n_steps, checkpoint_path if rank == 0 and local_rank == 0 else None,
+                                val_log if rank == 0 and local_rank == 0 else None, val_best,
+                                verbose=rank == 0 and local_rank == 0)
             if scheduler is not None:
                 scheduler.step()                                                                           # cls:108-109
             if st is not None and snapshot_path is not None and i + 1 >= n_batches:     # the epoch ran to its end

@@ -184,9 +184,10 @@ int calm_gemm_describe(const calm_gemm_args* args, calm_gemm_plan* plan);
  *   CALM_RED_CNN_BWD          B                    S
  *   CALM_RED_SOFT_CE          B                    C            (the loss entry points, additions to ABI v7)
  *   CALM_RED_HUBER            B*S                  3S
+ *   CALM_RED_EVAL             B                    C            (calm_eval_metrics: one 16-byte record per row)
  * ------------------------------------------------------------------------------------- */
 enum { CALM_RED_LAYERNORM_BWD = 0, CALM_RED_ROPE_BWD = 1, CALM_RED_LATENT_FWD = 2, CALM_RED_COLSUM = 3, CALM_RED_CNN_BWD = 4,
-       CALM_RED_SOFT_CE = 5, CALM_RED_HUBER = 6 };
+       CALM_RED_SOFT_CE = 5, CALM_RED_HUBER = 6, CALM_RED_EVAL = 7 };
 int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols);
 
 /* ---------------------------------------------------------------------------------------
@@ -888,6 +889,36 @@ int calm_huber_tokens_bwd(const float* tokens, const float* x, float delta, cons
                           int32_t B, int32_t S, void* stream);
 /* metrics[1] += #{b : argmax_c z[b,:] == labels[b]},  metrics[2] += B        (CALM_ViT_V2.py:228-239) */
 int calm_top1_count(const float* logits, int64_t ld, const int64_t* labels, float* metrics, int32_t B, int32_t C, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Validation metrics (an addition to ABI v7 — no existing signature or struct changes, so the version number stays):
+ * top-k hits, the cross-entropy sum, per-class support / top-1 hits and (optionally) the confusion matrix of one batch of
+ * logits against integer labels, ADDED to caller-owned device accumulators by two launches.  No atomics: every counter
+ * has one owning thread, the loss is added in a fixed order, results repeat bit for bit.
+ *
+ * logits [B,C], row stride ld elements, logits_type CALM_ST_F32 or CALM_ST_BF16 (rows are read as 16-byte vectors where
+ * the base is 16-byte aligned and ld is a multiple of the 4 / 8 elements of one, element by element otherwise); labels [B] int64.
+ *   row kernel (one wave per row, four rows per workgroup): writes one 16-byte record per row into `partials`
+ *   (calm_reduce_scratch_floats(CALM_RED_EVAL, B, C) = 4 * B floats, 16-byte aligned):
+ *       { float nll = (max - z_l) + log(sum exp(z - max));  int32 beaten;  int32 pred;  int32 flags }
+ *     beaten = #{c : z_c > z_l, or z_c == z_l and c < l}: the label l is in the top k exactly when beaten < k (for k = 1
+ *     the tie rule of calm_top1_count: the lowest index wins);  pred = argmax, lowest index among equals;
+ *     flags bit 0: the label is outside [0, C) — the row is SKIPPED: counted in `skipped` and in nothing else;
+ *     flags bit 1: the row holds a NaN — the row is NON-FINITE: counted in `rows`, `nonfinite` and its class's support,
+ *     never a hit, and it adds to neither the loss sum nor the confusion matrix.
+ *   fold kernel (one workgroup): loss_sum[0] (double) += the fp32 sum, in a fixed order, of the nll of the counted finite
+ *     rows;  counts (int64, 7 + 2 C values) += this batch's
+ *       [0] rows   [1] skipped   [2] nonfinite   [3 + i] hits@ks[i], i < nk ([3 + nk .. 6] are left alone)
+ *       [7 .. 7 + C) support[c] = #{counted rows with label c}     [7 + C .. 7 + 2 C) hits1[c] = #{of those, pred == c}
+ *     confusion (nullable, int64 [C,C]): confusion[label * C + pred] += 1 for every counted finite row.
+ * ks: HOST array of nk values, 1 <= nk <= 4, every k >= 1 (a k above C counts every finite counted row).
+ * CALM_E_INVAL: a null logits / labels / ks / counts / loss_sum / partials, B <= 0, C <= 0, ld < C, nk outside 1 .. 4,
+ * a k < 1, a storage type other than the two above;  CALM_E_UNSUPP: C > 65536;  CALM_E_LAYOUT: partials not 16-byte
+ * aligned.  All of them before any launch.
+ * ------------------------------------------------------------------------------------- */
+int calm_eval_metrics(const void* logits, int64_t ld, int32_t logits_type, const int64_t* labels, const int32_t* ks,
+                      int32_t nk, int64_t* counts, double* loss_sum, int64_t* confusion /* nullable */, int32_t B, int32_t C,
+                      float* partials, void* stream);
 
 #ifdef __cplusplus
 }
