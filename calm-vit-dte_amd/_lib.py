@@ -53,6 +53,8 @@ class GemmPlan(C.Structure):
 RED_LAYERNORM_BWD, RED_ROPE_BWD, RED_LATENT_FWD, RED_COLSUM, RED_CNN_BWD = range(5)     # CALM_RED_*
 RED_SOFT_CE, RED_HUBER = 5, 6                      # the loss entry points (csrc/loss.hip)
 RED_EVAL = 7                                       # calm_eval_metrics: one 16-byte record per row
+RED_RECON = 8                                      # calm_recon_metrics: one 32-byte record per workgroup
+RECON_ROWS, RECON_NCHW = 0, 1                      # calm_recon_metrics' target_layout (CALM_RECON_*)
 EVAL_COUNTS_HEAD = 7                               # counts: rows, skipped, nonfinite, hits@k[0..3], then support[C], hits1[C]
 
 
@@ -227,6 +229,9 @@ SIGNATURES = {
     "calm_huber_tokens_bwd": (_i32, [_p, _p, _f32, _p, _p, _i32, _i32, _p]),
     "calm_top1_count": (_i32, [_p, _i64, _p, _p, _i32, _i32, _p]),
     "calm_eval_metrics": (_i32, [_p, _i64, _i32, _p, C.POINTER(_i32), _i32, _p, _p, _p, _i32, _i32, _p, _p]),
+    "calm_recon_huber_rows_fwd": (_i32, [_p, _p, _f32, _p, _i64, _p, _p]),
+    "calm_recon_huber_rows_bwd": (_i32, [_p, _p, _f32, _p, _p, _i64, _p]),
+    "calm_recon_metrics": (_i32, [_p, _i32, _p, _i32, C.POINTER(_f32), C.POINTER(_f32), _f32, _i32, _p, _i32, _i32, _p, _p]),
     "calm_dropout": (_i32, [_p, _p, _p, _i64, _i64, _f32, _p, _i32, _i32, _i32, _p]),
 }
 

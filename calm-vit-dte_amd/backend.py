@@ -123,6 +123,12 @@ def eval_kernels_take(t):
             and (t.is_cuda or not isinstance(get_backend(), HipBackend)))
 
 
+def recon_kernels_take(tokens, target):
+    """Whether calm_recon_metrics serves this pair now (trainer.ReconMetrics): the switch is on, the generated tokens are
+    fp32 or bf16, the target is fp32, and the installed backend can address both."""
+    return eval_kernels_take(tokens) and target.dtype == torch.float32 and target.device == tokens.device
+
+
 def effective_precision():
     """The pipe a GEMM issued now runs on.  Inside `torch.autocast("cuda", dtype=torch.bfloat16)` — how the reference
     trainer calls the model (distributed_trainer_cls.py:84-85) — Linear/matmul operands are rounded to bf16 with fp32
@@ -1147,6 +1153,45 @@ class HipBackend:
                                               karr, len(ks), counts.data_ptr(), loss_sum.data_ptr(),
                                               None if confusion is None else confusion.data_ptr(), B, C, part, _stream()),
                    "calm_eval_metrics")
+
+    # ---- the generative job on row tokens (csrc/recon.hip) -------------------------------
+    def huber_rows_fwd(self, tokens, target, delta, loss, n):
+        """nn.HuberLoss(delta) between two contiguous fp32 tensors of one flat layout, n elements; loss 0-dim."""
+        _lib.check(self.lib.calm_recon_huber_rows_fwd(_ptr(tokens), _ptr(target), float(delta), _ptr(loss), n,
+                                                      self._partials(_lib.RED_HUBER, n, 1, tokens.device), _stream()),
+                   "calm_recon_huber_rows_fwd")
+
+    def huber_rows_bwd(self, tokens, target, delta, dloss, dtokens, n):
+        _lib.check(self.lib.calm_recon_huber_rows_bwd(_ptr(tokens), _ptr(target), float(delta), _ptr(dloss), _ptr(dtokens),
+                                                      n, _stream()), "calm_recon_huber_rows_bwd")
+
+    def recon_metrics(self, tokens, target, layout, mean, std, delta, want_ssim, sums, B, S, partials=None):
+        """calm_recon_metrics: generated tokens [B,S,3S] fp32 or bf16 against the fp32 target, rows [B,S,3S]
+        (layout = RECON_ROWS) or image [B,3,S,S] (RECON_NCHW), both contiguous; the batch's tallies are ADDED to sums
+        (float64 [8]: images, non-finite images, Huber / abs / square sums, elements, PSNR sum, SSIM sum).  partials: the
+        caller's own record scratch (fp32) — the shared reduction scratch when None."""
+        if not sums.is_cuda or sums.dtype != torch.float64 or sums.numel() < 8 or not sums.is_contiguous():
+            raise TypeError("recon_metrics expects a contiguous float64 CUDA tensor of 8 values for sums")
+        if not (tokens.is_contiguous() and target.is_contiguous()) or tokens.numel() != 3 * B * S * S \
+                or target.numel() != tokens.numel():
+            raise ValueError("recon_metrics: contiguous tokens [B,S,3S] and a target of as many elements expected")
+        if partials is None:
+            part = self._partials(_lib.RED_RECON, B, S, tokens.device)
+        else:
+            if partials.numel() < self.recon_scratch_floats(B, S):
+                raise ValueError("recon_metrics: partials is smaller than calm_reduce_scratch_floats(CALM_RED_RECON, B, S)")
+            part = _ptr(partials)
+        m3, s3 = (_lib.C.c_float * 3)(*[float(v) for v in mean]), (_lib.C.c_float * 3)(*[float(v) for v in std])
+        _lib.check(self.lib.calm_recon_metrics(_ptr(tokens, bf16_ok=True), _st(tokens), _ptr(target), int(layout), m3, s3,
+                                               float(delta), int(bool(want_ssim)), sums.data_ptr(), B, S, part, _stream()),
+                   "calm_recon_metrics")
+
+    def recon_scratch_floats(self, B, S):
+        """Floats of record scratch one recon_metrics call at (B, S) writes (calm_reduce_scratch_floats, cached)."""
+        need = self._scratch_need.get((_lib.RED_RECON, B, S))
+        if need is None:
+            need = self._scratch_need[(_lib.RED_RECON, B, S)] = int(self.lib.calm_reduce_scratch_floats(_lib.RED_RECON, B, S))
+        return need
 
     # ---- dropout (csrc/dropout.hip) -----------------------------------------------------
     def dropout(self, x, residual, y, n, p, key, e0=0):

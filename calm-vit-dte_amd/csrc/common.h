@@ -193,3 +193,14 @@ constexpr int CNN_PART_STRIDE = 560;           // floats between the CNN tail's 
 constexpr int SOFT_CE_PART_ROWS = 2;           // soft-target CE: one workgroup per sample; B row losses, then B agreement flags
 constexpr int HUBER_MAX_GRID = 2048;           // one block sum per workgroup
 constexpr int EVAL_REC_FLOATS = 4;             // calm_eval_metrics: one 16-byte record per row (no cross-workgroup sum in launch 1)
+// calm_recon_metrics (recon.hip): a workgroup owns RECON band rows x RECON_STRIP_OUT output columns of one image and writes
+// one record of RECON_REC_FLOATS floats; the band is 32 output rows at Base sizes (42 rows read for 32: the halo costs
+// 1.31 x the tensor), shorter for small images so that more than one workgroup shares an image.
+constexpr int RECON_REC_FLOATS = 8;
+constexpr int RECON_WIN = 11;                  // the SSIM window
+constexpr int RECON_STRIP_PX = 256;            // pixels of one row a workgroup reads: 768 elements, three per thread
+constexpr int RECON_STRIP_OUT = RECON_STRIP_PX - (RECON_WIN - 1);
+__host__ __device__ static inline int recon_valid(int S) { return S > RECON_WIN - 1 ? S - (RECON_WIN - 1) : 1; }
+static inline int recon_band_rows(int S) { const int v = recon_valid(S); return v >= 128 ? 32 : v >= 48 ? 16 : 4; }
+static inline int recon_bands(int S) { return (recon_valid(S) + recon_band_rows(S) - 1) / recon_band_rows(S); }
+static inline int recon_strips(int S) { return (recon_valid(S) + RECON_STRIP_OUT - 1) / RECON_STRIP_OUT; }

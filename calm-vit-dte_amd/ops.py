@@ -1185,6 +1185,34 @@ class HuberTokensFn(Function):
         return dtokens, None, None
 
 
+class HuberRowsFn(Function):
+    """nn.HuberLoss(delta) between the generative model's tokens and a target of the SAME layout — the row-token batch of
+    the device collate, which is the channels-last image (Vi_Tools:389-391): calm_recon_huber_rows_fwd / _bwd."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, tokens, target, delta=1.0):
+        be = get_backend()
+        tokens, target = _c(tokens), _c(target)
+        if tokens.shape != target.shape:
+            raise ValueError("HuberRowsFn expects tokens and a target of one shape")
+        loss = torch.empty((), dtype=torch.float32, device=tokens.device)
+        be.huber_rows_fwd(tokens, target, delta, loss, tokens.numel())
+        ctx.save_for_backward(tokens, target)
+        ctx.delta = float(delta)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    @_amp_bwd
+    def backward(ctx, g):
+        be = get_backend()
+        tokens, target = ctx.saved_tensors
+        dtokens = torch.empty_like(tokens)
+        be.huber_rows_bwd(tokens, target, ctx.delta, _dloss(g), dtokens, tokens.numel())
+        return dtokens, None, None
+
+
 class AddFn(Function):
     """Residual / U-net skip adds (Vi_Tools:309,315,403,513-522) and the latent running sum (43-44)."""
 

@@ -23,6 +23,10 @@ as set by torchrun):
         top-k, cross-entropy, per-class accuracy and confusion matrix of held-out data, tallied on the device
         (calm_eval_metrics) and summed over the ranks; `train(val_dataset=...)` runs it per epoch and keeps the best
         checkpoint.
+  * `RegTrainStep` / `ReconMetrics` / `evaluate(recon=True)` / `train(task="reg")`   <- distributed_trainer_reg.py:25-112
+        the generative job: Huber + kl_weight * kl on the image or on the device collate's row tokens, and Huber / MAE /
+        MSE / PSNR / SSIM of held-out data tallied on the device (calm_recon_metrics); the best checkpoint follows the
+        lowest validation Huber.
 
 The model also works under stock `torch.nn.parallel.DistributedDataParallel` (that is what the
 reference's train() does with it); the reducer here is the MI355X-tuned equivalent.  Under DDP the step
@@ -385,6 +389,107 @@ class EvalMetrics:
         return rep
 
 
+RECON_WINDOW, RECON_SIGMA, RECON_C1, RECON_C2 = 11, 1.5, 0.01 ** 2, 0.03 ** 2      # SSIM (Wang et al. 2004)
+
+
+def recon_metrics_torch(tokens, target, mean, std, delta, ssim, sums):
+    """What calm_recon_metrics adds to `sums` (float64 [8], include/calm_vit.h), as a plain fp32 torch composition on the
+    tensors' device: tokens [B,S,3S] are the channels-last generated image; target is rows [B,S,3S] or the image
+    [B,3,S,S].  An image holding a non-finite generated value adds to [0] and [1] only.  Huber / abs / square sums in
+    normalised space; pixel space is clamp(v * std_c + mean_c, 0, 1); PSNR_b = 10 log10(1 / max(mse_b, 1e-10)); SSIM_b is
+    the mean over the (S - 10)^2 valid positions and the channels of the 11 x 11 Gaussian (sigma 1.5) window form with
+    population moments (conv2d per channel).  ssim=False leaves [7] alone."""
+    g = tokens.float()
+    B, S = g.shape[0], g.shape[1]
+    gi = g.reshape(B, S, S, 3).permute(0, 3, 1, 2)
+    t = target.to(g.device).float()
+    ti = t if t.dim() == 4 else t.reshape(B, S, S, 3).permute(0, 3, 1, 2)
+    finite = torch.isfinite(gi).reshape(B, -1).all(dim=1)
+    d = gi - ti
+    ad = d.abs()
+    hub = torch.where(ad <= delta, 0.5 * d * d, delta * (ad - 0.5 * delta))
+    m = torch.tensor(mean, dtype=torch.float32, device=g.device).view(1, 3, 1, 1)
+    sd = torch.tensor(std, dtype=torch.float32, device=g.device).view(1, 3, 1, 1)
+    px, py = (gi * sd + m).clamp(0.0, 1.0), (ti * sd + m).clamp(0.0, 1.0)
+    mse = ((px - py) ** 2).reshape(B, -1).mean(dim=1)
+    psnr = 10.0 * torch.log10(1.0 / mse.clamp(min=1e-10))
+    zero = torch.zeros(B, dtype=torch.float32, device=g.device)
+    kept = lambda v: torch.where(finite, v, zero).sum().double()        # noqa: E731
+    vals = [torch.tensor(float(B), dtype=torch.float64, device=g.device), (~finite).sum().double(),
+            kept(hub.reshape(B, -1).sum(dim=1)), kept(ad.reshape(B, -1).sum(dim=1)), kept((d * d).reshape(B, -1).sum(dim=1)),
+            finite.sum().double() * (3 * S * S), kept(psnr)]
+    if ssim:
+        k = torch.arange(RECON_WINDOW, dtype=torch.float32, device=g.device) - (RECON_WINDOW - 1) / 2
+        w1 = torch.exp(-k * k / (2.0 * RECON_SIGMA ** 2))
+        w1 = w1 / w1.sum()
+        win = (w1[:, None] * w1[None, :]).expand(3, 1, RECON_WINDOW, RECON_WINDOW).contiguous()
+        filt = lambda v: torch.nn.functional.conv2d(v, win, groups=3)       # noqa: E731
+        ux, uy = filt(px), filt(py)
+        sxx, syy, sxy = filt(px * px) - ux * ux, filt(py * py) - uy * uy, filt(px * py) - ux * uy
+        smap = ((2 * ux * uy + RECON_C1) * (2 * sxy + RECON_C2)) / ((ux * ux + uy * uy + RECON_C1) * (sxx + syy + RECON_C2))
+        vals.append(kept(smap.reshape(B, -1).mean(dim=1)))
+    sums[:len(vals)] += torch.stack(vals)
+
+
+class ReconMetrics:
+    """Reconstruction tallies of a generative model on the device, the counterpart of EvalMetrics: `sums` (float64 [8]) is
+    the accumulator of calm_recon_metrics (include/calm_vit.h) — images, non-finite images, Huber / abs / square sums in
+    normalised space, elements, and the per-image PSNR and SSIM sums in pixel space (clamp(v * std_c + mean_c, 0, 1)).
+
+    update(tokens, target) adds one batch: tokens [B,S,3S] as the model returns them (fp32 or bf16), target the fp32 input,
+    rows [B,S,3S] or image [B,3,S,S].  With the loss kernels switched on and tensors the backend serves it is ONE library
+    call — two launches, no host synchronisation, no allocation after the first call at the largest batch, so it can be
+    captured into a graph; otherwise `recon_metrics_torch`, the same definitions in fp32 torch.  all_reduce() sums over a
+    process group, read() is one device-to-host copy, reset() zeroes in place.  ssim=False skips the windowed pass (and
+    serves images with S < 11)."""
+
+    def __init__(self, mean, std, delta=1.0, ssim=True, device="cpu"):
+        mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        if len(mean) != 3 or len(std) != 3 or not float(delta) > 0.0:
+            raise ValueError("ReconMetrics: mean and std hold three values each and delta is positive")
+        self.mean, self.std, self.delta, self.ssim = mean, std, float(delta), bool(ssim)
+        self.sums = torch.zeros(8, dtype=torch.float64, device=device)
+        self._records = None                 # the kernel's per-workgroup records: grown to the largest batch seen
+
+    def tensors(self):
+        return [self.sums]
+
+    def update(self, tokens, target):
+        from . import backend, _lib
+        if tokens.dim() != 3 or tokens.shape[2] != 3 * tokens.shape[1]:
+            raise ValueError(f"ReconMetrics.update: tokens [B,S,3S] expected, got {tuple(tokens.shape)}")
+        B, S = tokens.shape[0], tokens.shape[1]
+        if tuple(target.shape) not in ((B, S, 3 * S), (B, 3, S, S)):
+            raise ValueError(f"ReconMetrics.update: a target [B,S,3S] or [B,3,S,S] of the tokens' batch expected, got "
+                             f"{tuple(target.shape)}")
+        if self.ssim and S < RECON_WINDOW:
+            raise ValueError(f"ReconMetrics.update: SSIM needs S >= {RECON_WINDOW}, got {S} (build with ssim=False)")
+        if backend.recon_kernels_take(tokens, target) and S <= 4096:
+            be = backend.get_backend()
+            need = be.recon_scratch_floats(B, S)
+            if self._records is None or self._records.numel() < need:
+                self._records = torch.empty(need, dtype=torch.float32, device=tokens.device)
+            be.recon_metrics(tokens.contiguous(), target.contiguous(), _lib.RECON_NCHW if target.dim() == 4 else
+                             _lib.RECON_ROWS, self.mean, self.std, self.delta, self.ssim, self.sums, B, S, self._records)
+        else:
+            recon_metrics_torch(tokens, target, self.mean, self.std, self.delta, self.ssim, self.sums)
+
+    def all_reduce(self, group=None):
+        dist.all_reduce(self.sums, op=dist.ReduceOp.SUM, group=group)
+
+    def reset(self):
+        self.sums.zero_()                   # in place: a captured update keeps adding at this address
+
+    def read(self):
+        """{n, nonfinite, huber, mae, mse, psnr, ssim} from ONE device-to-host copy: huber / mae / mse are means over the
+        elements of the finite images, psnr / ssim means over the finite images; ssim is None when built with ssim=False."""
+        v = self.sums.to("cpu").tolist()
+        n, bad = int(v[0]), int(v[1])
+        elems, imgs = max(v[5], 1.0), max(n - bad, 1)
+        return {"n": n, "nonfinite": bad, "huber": v[2] / elems, "mae": v[3] / elems, "mse": v[4] / elems,
+                "psnr": v[6] / imgs, "ssim": v[7] / imgs if self.ssim else None}
+
+
 class TrainStep:
     """One iteration of distributed_trainer_cls.py:79-96 (per rank)."""
 
@@ -513,7 +618,9 @@ class RegTrainStep(TrainStep):
         self.kl_weight = kl_weight
 
     def __call__(self, x, _y=None):
-        S = x.shape[-1]
+        """x: the image [B,3,S,S], or the row tokens [B,S,3S] of the device collate — the channels-last image
+        (Vi_Tools:389-391), which is then the Huber target in the layout of the model's output."""
+        S = x.shape[1] if x.dim() == 3 else x.shape[-1]
         with torch.autocast(device_type="cuda", dtype=self.autocast_dtype or torch.bfloat16,
                             enabled=self.autocast_dtype is not None and x.is_cuda):        # reg:76
             y_hat, kl = self.model(x)                                      # reg:77
@@ -524,8 +631,16 @@ class RegTrainStep(TrainStep):
     @staticmethod
     def _huber(tokens, img, x):
         """nn.HuberLoss() (reg:59, delta = 1): on the token layout through calm_huber_tokens_* when the loss kernels are
-        switched on and serve the shape (S % 4 == 0, fp32), stock torch on the permuted view otherwise."""
+        switched on and serve the shape (S % 4 == 0, fp32), stock torch on the permuted view otherwise.  A 3-d x is the
+        row-token batch: calm_recon_huber_rows_* (ops.HuberRowsFn) when the loss kernels take the tensors, stock torch on
+        the two token tensors otherwise."""
         from . import backend
+        if x.dim() == 3:
+            y_hat = tokens.reshape(x.shape)
+            if backend.get_loss_kernels() and x.dtype == torch.float32 and backend.loss_kernels_take(tokens):
+                from .ops import HuberRowsFn
+                return HuberRowsFn.apply(y_hat, x, 1.0)
+            return torch.nn.functional.huber_loss(y_hat, x)
         if (backend.get_loss_kernels() and tokens.dim() == 3 and x.dim() == 4 and x.dtype == torch.float32
                 and x.shape[-1] % 4 == 0 and x.shape[-1] <= 4096 and tokens.shape[0] == x.shape[0]
                 and backend.loss_kernels_take(tokens)):
@@ -1118,7 +1233,7 @@ class Predictor:
 
 
 def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, transform=None, transform_out="tokens", ema=None,
-             report=False, topk=(1, 5), confusion=False, process_group=None):
+             report=False, topk=(1, 5), confusion=False, process_group=None, recon=False):
     """Top-1 accuracy over (x, labels) batches in eval mode (CALM_ViT_V2.py:228-239).  With the loss kernels switched on
     the hits are counted on the device (calm_top1_count into a StepMetrics) and read once after the last batch instead of
     once per batch.  lean / graph: the forward goes through a Predictor (lean kernels; graph=True captures it at the first
@@ -1138,14 +1253,20 @@ def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, trans
     call without a host synchronisation where the loss kernels serve the logits), and the tallies are summed over
     `process_group`, or over the default group when torch.distributed is initialised, before the one read: every rank
     evaluates its own `validation_shard` and every rank returns the report of the whole set.  At least one batch is
-    needed (the class count comes from the logits).  report=False (the default) is the loop as it was."""
+    needed (the class count comes from the logits).  report=False (the default) is the loop as it was.
+    recon=True (a `generate=True` model; excludes report=True): `batches` yield x or (x, _), x the image [B,3,S,S] or the row
+    tokens [B,S,3S]; the model's tokens are measured against x by a `ReconMetrics` (DeviceCollate's mean / std, delta 1,
+    SSIM where S >= 11) — one library call per batch where the loss kernels serve the tensors — with the same lean /
+    graph / ema / transform / process_group handling, and the call returns `ReconMetrics.read()` of the whole set."""
+    if recon and report:
+        raise ValueError("evaluate: recon=True and report=True exclude each other (one model is not both kinds)")
     if ema is not None:
         if ema.model is not model:
             raise ValueError("evaluate: ema= must be the ModelEMA of the model being evaluated")
         with ema.applied():
             return evaluate(model, batches, lean=lean, graph=graph, autocast_dtype=autocast_dtype, transform=transform,
                             transform_out=transform_out, report=report, topk=topk, confusion=confusion,
-                            process_group=process_group)
+                            process_group=process_group, recon=recon)
     from . import backend
     if transform is not None:
         if not isinstance(transform, DeviceResizedCrop):
@@ -1169,13 +1290,20 @@ def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, trans
     predictor = None
     tallies = None
     with torch.no_grad():
-        for x, labels in batches:
+        for batch in batches:
+            x, labels = batch if isinstance(batch, (tuple, list)) else (batch, None)
             if lean or graph:
                 if predictor is None:
                     predictor = Predictor(model, example_x=x if graph else None, autocast_dtype=autocast_dtype, graph=graph)
                 y_hat, _ = predictor(x)
             else:
                 y_hat, _ = model(x)
+            if recon:
+                S = x.shape[1] if x.dim() == 3 else x.shape[-1]
+                if tallies is None:
+                    tallies = ReconMetrics(DeviceCollate.MEAN, DeviceCollate.STD, ssim=S >= RECON_WINDOW, device=y_hat.device)
+                tallies.update(y_hat.reshape(x.shape[0], S, 3 * S), x)
+                continue
             logits = y_hat.reshape(x.shape[0], -1)
             if report:
                 if tallies is None:
@@ -1197,9 +1325,9 @@ def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, trans
     if predictor is not None:
         predictor.close()
     model.train(was_training)
-    if report:
+    if report or recon:
         if tallies is None:
-            raise ValueError("evaluate: report=True needs at least one batch")
+            raise ValueError(f"evaluate: {'report' if report else 'recon'}=True needs at least one batch")
         if process_group is not None or (dist.is_available() and dist.is_initialized()):
             tallies.all_reduce(process_group)
         return tallies.read()
@@ -2285,10 +2413,19 @@ class SoftMixCollate:
         return self.mix(x, labels, mode, lam, box)
 
 
-def _val_best_so_far(val_log):
-    """{"top1": best live top-1, "ema_top1": best averaged top-1} from the lines of an existing validation log."""
+def _val_best_so_far(val_log, key="top1", lower=False):
+    """{"top1": best live top-1, "ema_top1": best averaged top-1} from the lines of an existing validation log; with
+    key="huber", lower=True the lowest validation Huber of a generative run under "huber" / "ema_huber"."""
     import json
     best = {}
+    if lower:
+        if os.path.exists(val_log):
+            with open(val_log) as f:
+                for rec in (json.loads(line) for line in f if line.strip()):
+                    for name, r in ((key, rec), ("ema_" + key, rec.get("ema"))):
+                        if r is not None and key in r and r[key] < best.get(name, float("inf")):
+                            best[name] = r[key]
+        return best
     if os.path.exists(val_log):
         with open(val_log) as f:
             for line in f:
@@ -2302,10 +2439,11 @@ def _val_best_so_far(val_log):
 
 
 def _validate_epoch(model, ema, val_dataset, rank, world, device, batch_size, transform, topk, epoch, n_steps,
-                    checkpoint_path, val_log, best, verbose):
+                    checkpoint_path, val_log, best, verbose, recon=False, transform_out="tokens"):
     """One validation pass of train(): every rank evaluates its shard (live weights, then the averaged ones), the reports
     are all-reduced inside evaluate; the caller's rank 0 passes checkpoint_path / val_log / verbose and does the writing.
-    The RNG states and the training flag are as before when it returns."""
+    The RNG states and the training flag are as before when it returns.  recon=True: the generative job — the samples'
+    labels are ignored, the report is ReconMetrics.read() and the best checkpoint follows the strictly lower Huber."""
     import json
     from torch.utils.data import DataLoader
     use_gpu = device.type == "cuda"
@@ -2320,10 +2458,12 @@ def _validate_epoch(model, ema, val_dataset, rank, world, device, batch_size, tr
             if transform is not None:
                 yield batch                                   # (packed, meta, labels): evaluate moves and transforms it
             else:
-                x, labels = batch
-                yield x.to(device, non_blocking=True), labels.to(device, non_blocking=True)
+                x, labels = batch if isinstance(batch, (tuple, list)) else (batch, None)
+                yield x.to(device, non_blocking=True), None if labels is None or recon else labels.to(device, non_blocking=True)
     try:
-        kw = dict(lean=True, autocast_dtype=torch.bfloat16 if use_gpu else None, transform=transform, report=True, topk=topk)
+        kw = dict(lean=True, autocast_dtype=torch.bfloat16 if use_gpu else None, transform=transform,
+                  transform_out=transform_out)
+        kw.update(dict(recon=True) if recon else dict(report=True, topk=topk))
         rep = evaluate(model, batches(), **kw)
         rep_ema = evaluate(model, batches(), ema=ema, **kw) if ema is not None else None
     finally:
@@ -2337,7 +2477,10 @@ def _validate_epoch(model, ema, val_dataset, rank, world, device, batch_size, tr
         line["ema"] = scalars(rep_ema)
     if verbose:
         for tag, r in (("", rep), (" (EMA)", rep_ema)):
-            if r is not None:
+            if r is not None and recon:
+                print(f"Epoch: {epoch + 1}, Validation{tag}: Huber: {r['huber']}, MAE: {r['mae']}, MSE: {r['mse']}, "
+                      f"PSNR: {r['psnr']:.4f} dB, SSIM: {r['ssim']}, Samples: {r['n']}, Non-finite: {r['nonfinite']}")
+            elif r is not None:
                 tops = ", ".join(f"top-{k}: {100.0 * r[f'top{k}']:.4f}%" for k in topk)
                 print(f"Epoch: {epoch + 1}, Validation{tag}: {tops}, Loss: {r['loss']}, "
                       f"Mean per-class accuracy: {100.0 * r['mean_per_class_accuracy']:.4f}%, Samples: {r['n']}")
@@ -2347,6 +2490,14 @@ def _validate_epoch(model, ema, val_dataset, rank, world, device, batch_size, tr
             f.write(json.dumps(line) + "\n")
     if checkpoint_path:
         stem, ext = os.path.splitext(checkpoint_path)
+        if recon:
+            if rep["huber"] < best.get("huber", float("inf")):
+                best["huber"] = rep["huber"]
+                torch.save(model.state_dict(), stem + "_best" + ext)
+            if rep_ema is not None and rep_ema["huber"] < best.get("ema_huber", float("inf")):
+                best["ema_huber"] = rep_ema["huber"]
+                torch.save(ema.model_state_dict(), stem + "_ema_best" + ext)
+            return line
         if rep["top1"] > best.get("top1", -1.0):
             best["top1"] = rep["top1"]
             torch.save(model.state_dict(), stem + "_best" + ext)
@@ -2361,7 +2512,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
           device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None,
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
-          val_batch_size=None, val_transform=None, val_topk=(1, 5)):
+          val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -2464,9 +2615,32 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     values so far from the existing `_val.jsonl` and appends to it; a run without resume= starts the log anew.  Validation does not move the run: the CPU and device RNG states are
     saved around it and put back and the model is left in training mode, so the returned parameters equal those of the
     same run without val_dataset bit for bit.  val_topk must contain 1; checkpoint_path may be None (nothing is written,
-    rank 0 still prints)."""
+    rank 0 still prints).
+
+    task="reg": the reference's SECOND job, the generative trainer (distributed_trainer_reg.py:25-112), for a
+    `generate=True` model: `RegTrainStep` (`AccumRegTrainStep` with accumulate > 1) — HuberLoss(generated image, input) +
+    kl_weight * kl (reg:59,78-87) — the default collate without CutMix / MixUp (reg:58; labels, if the dataset yields any,
+    are ignored), a log line with the loss alone (reg:100), the checkpoint per epoch (reg:102) and, with samples_dir, rank
+    0's `save_samples` of the last batch's generated images behind it (reg:103).  device_collate and everything that
+    needs it work as for "cls": the collate is called with decisions that mix nothing — the draws are made as before, so
+    the generators advance as they do under "cls", and MixUp with lam = 1 is the identity on a uint8 batch — the soft labels
+    are dropped and the row tokens are both the model's input and the Huber target.  ema, snapshots, resume and accumulate
+    work as for "cls".  val_dataset runs `evaluate(recon=True, lean=True)` per rank shard, logs the `ReconMetrics`
+    scalars and keeps `<stem>_best<ext>` / `<stem>_ema_best<ext>` by strictly LOWER validation Huber (val_topk is not
+    used).  graph=True and device_metrics=True are refused (the captured step and the device metrics are the
+    classification job's)."""
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
+    if task not in ("cls", "reg"):
+        raise ValueError(f'train: task is "cls" or "reg", got {task!r}')
+    reg = task == "reg"
+    if reg and graph:
+        raise ValueError('train: task="reg" excludes graph=True (GraphedTrainStep captures the classification step)')
+    if reg and device_metrics:
+        raise ValueError('train: task="reg" excludes device_metrics=True (StepMetrics belongs to the classification loss)')
+    generates = getattr(initializer, "generate", None)
+    if generates is not None and bool(generates) != reg:
+        raise ValueError(f'train: task="{task}" needs a model built with generate={reg}, got generate={bool(generates)}')
     if device_metrics and not (use_gpu and _backend.get_loss_kernels()):
         raise ValueError("device_metrics=True needs use_gpu=True and the loss kernels switched on "
                          "(backend.set_loss_kernels(True) or CALM_LOSS_KERNELS=1)")
@@ -2511,9 +2685,10 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     if val_dataset is not None:
         if val_batch_size is not None and (int(val_batch_size) != val_batch_size or val_batch_size < 1):
             raise ValueError(f"train: val_batch_size counts samples (>= 1), got {val_batch_size!r}")
-        if 1 not in tuple(val_topk):
+        if not reg and 1 not in tuple(val_topk):
             raise ValueError(f"train: val_topk must contain 1 (the best checkpoint follows top-1), got {val_topk!r}")
-        EvalMetrics(num_classes, topk=val_topk)             # (refuses a malformed val_topk here, not after the first epoch)
+        if not reg:
+            EvalMetrics(num_classes, topk=val_topk)         # (refuses a malformed val_topk here, not after the first epoch)
     rank, local_rank, world = init_distributed(use_gpu)
     if val_dataset is not None and len(val_dataset) < world:
         raise ValueError(f"train: val_dataset holds {len(val_dataset)} samples, fewer than the {world} ranks")
@@ -2543,6 +2718,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         sampler = DistributedSampler(dataset, num_replicas=1, rank=0, shuffle=True, seed=2006)
     sampler.set_epoch(0)
     dcoll = None
+    no_mix = (lambda d: (1, 1.0, None, d[3])) if reg else (lambda d: d)     # MixUp with lam = 1: nothing is mixed
     if device_collate:
         if not use_gpu:
             raise ValueError("device_collate=True needs use_gpu=True (the collate is a HIP kernel)")
@@ -2552,14 +2728,20 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         if device_resize is not None or random_resized_crop is not None:
             collate_fn = RaggedU8Collate()                  # images of any size: one packed buffer and its table
     elif collate_fn == "mix":
-        collate_fn = SoftMixCollate(num_classes=num_classes, seed=2006 + rank)
+        collate_fn = None if reg else SoftMixCollate(num_classes=num_classes, seed=2006 + rank)      # reg:58
     loader = DataLoader(dataset, batch_size=batch_size, sampler=sampler, collate_fn=collate_fn, num_workers=num_workers,
                         pin_memory=use_gpu, persistent_workers=num_workers > 0, drop_last=bool(graph))
     scaler = torch.amp.GradScaler("cuda", enabled=use_gpu)                                                 # cls:64
     metrics = StepMetrics(device) if device_metrics else None
     step_kw = dict(max_norm=1.0, scaler=scaler if use_gpu else None, autocast_dtype=torch.bfloat16 if use_gpu else None,
                    metrics=metrics, ema=ema_obj)
-    if accumulate > 1:
+    if reg:
+        del step_kw["metrics"]
+        if accumulate > 1:
+            step = AccumRegTrainStep(model, optimizer, reducer, accumulate=accumulate, kl_weight=kl_weight, **step_kw)
+        else:
+            step = RegTrainStep(model, optimizer, reducer, kl_weight=kl_weight, **step_kw)
+    elif accumulate > 1:
         step = AccumTrainStep(model, optimizer, reducer, accumulate=accumulate, **step_kw)
     else:
         step = TrainStep(model, optimizer, reducer, **step_kw)
@@ -2584,7 +2766,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     val_log = val_best = None
     if val_dataset is not None:
         val_log = os.path.splitext(checkpoint_path)[0] + "_val.jsonl" if checkpoint_path else None
-        val_best = _val_best_so_far(val_log) if resume is not None and val_log else {}
+        val_best = (_val_best_so_far(val_log, *(("huber", True) if reg else ()))
+                    if resume is not None and val_log else {})
         if resume is None and val_log and rank == 0 and local_rank == 0 and os.path.exists(val_log):
             os.remove(val_log)                              # a new run starts its own log; a resumed one appends
     try:
@@ -2610,7 +2793,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                 decisions, window = None, crop
                 if resize_window:
                     packed, meta, y = batch
-                    decisions = dcoll.draw(len(meta), *dwin.size)          # the order of DeviceCollate.__call__: decisions,
+                    decisions = no_mix(dcoll.draw(len(meta), *dwin.size))  # the order of DeviceCollate.__call__: decisions,
                     corners = dcoll.draw_corners(len(meta), *dres.size, *dwin.size)    # then corners
                     x = dwin(packed.to(device, non_blocking=True), meta, corners=corners)   # only the crop window, uint8
                     window = None                                          # the batch is at the crop size already
@@ -2621,11 +2804,19 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                     packed, meta, y = batch
                     x = dres(packed.to(device, non_blocking=True), meta)   # packed originals -> [B,3,oh,ow] uint8
                 else:
-                    x, y = batch
+                    x, y = batch if isinstance(batch, (tuple, list)) else (batch, None)
                     x = x.to(device, non_blocking=True)
-                y = y.to(device, non_blocking=True)
-                if dcoll is not None:                                      # uint8 batch -> row tokens + soft labels
-                    x, y = dcoll(x, y.long(), decisions=decisions, crop=window, tokens=True, augment=daug)
+                if reg:                                                    # the labels are ignored (reg:74-77)
+                    y = None
+                    if dcoll is not None:                                  # uint8 batch -> row tokens; the draws as for "cls"
+                        if decisions is None:
+                            decisions = no_mix(dcoll.draw(x.shape[0], *(window if window is not None else x.shape[-2:])))
+                        x, _ = dcoll(x, torch.zeros(x.shape[0], dtype=torch.int64, device=device), decisions=decisions,
+                                     crop=window, tokens=True, augment=daug)
+                else:
+                    y = y.to(device, non_blocking=True)
+                    if dcoll is not None:                                  # uint8 batch -> row tokens + soft labels
+                        x, y = dcoll(x, y.long(), decisions=decisions, crop=window, tokens=True, augment=daug)
                 if graph and gstep is None:
                     gstep = GraphedTrainStep(model, optimizer, x, y, max_norm=1.0, scaler=scaler,
                                              autocast_dtype=torch.bfloat16, reducer=reducer, restore_after_warmup=True,
@@ -2634,7 +2825,9 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                         if step._clean_steps is not None:       # (then the captured step, built alike, has one too)
                             gstep.inner._clean_steps.copy_(step._clean_steps)
                         st.bind_step(gstep)
-                if gstep is not None and x.shape == gstep.x.shape and y.shape == gstep.y.shape:
+                if reg:
+                    loss, y_hat = step(x)
+                elif gstep is not None and x.shape == gstep.x.shape and y.shape == gstep.y.shape:
                     loss, y_hat = gstep(x, y)
                 else:
                     loss, y_hat = step(x, y)
@@ -2648,7 +2841,10 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                     st.poll()
                 if metrics is None:
                     epoch_loss += loss.item()                                                              # cls:97
-                if rank == 0 and local_rank == 0 and i % log_every == 0:
+                if reg:
+                    if rank == 0 and local_rank == 0 and i % log_every == 0:                               # reg:100
+                        print(f"Epoch: {epoch + 1}, Batch: {i + 1}, Device: [{rank}, {local_rank}], Loss: {float(loss)}")
+                elif rank == 0 and local_rank == 0 and i % log_every == 0:
                     correct = (y_hat.reshape(y.shape[0], -1).argmax(1) == y.argmax(1)).sum().item()
                     print(f"Epoch: {epoch + 1}, Batch: {i + 1}, Device: [{rank}, {local_rank}], Loss: {float(loss)}, "
                           f"Accuracy: {100.0 * correct / y.size(0):.4f}%")
@@ -2668,11 +2864,14 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                 if ema_obj is not None:
                     stem, ext = os.path.splitext(checkpoint_path)
                     torch.save(ema_obj.model_state_dict(), stem + "_ema" + ext)
+            if reg and samples_dir and rank == 0 and local_rank == 0 and i >= 0:
+                save_samples(y_hat, samples_dir)                                                           # reg:103
             if val_dataset is not None and (epoch + 1) % int(val_every) == 0:
                 _validate_epoch(model, ema_obj, val_dataset, rank, world, device, val_batch_size or batch_size, val_transform,
                                 val_topk, epoch, n_steps, checkpoint_path if rank == 0 and local_rank == 0 else None,
                                 val_log if rank == 0 and local_rank == 0 else None, val_best,
-                                verbose=rank == 0 and local_rank == 0)
+                                verbose=rank == 0 and local_rank == 0, recon=reg,
+                                transform_out="tokens" if dcoll is not None or not reg else "image")
             if scheduler is not None:
                 scheduler.step()                                                                           # cls:108-109
             if st is not None and snapshot_path is not None and i + 1 >= n_batches:     # the epoch ran to its end

@@ -185,9 +185,10 @@ int calm_gemm_describe(const calm_gemm_args* args, calm_gemm_plan* plan);
  *   CALM_RED_SOFT_CE          B                    C            (the loss entry points, additions to ABI v7)
  *   CALM_RED_HUBER            B*S                  3S
  *   CALM_RED_EVAL             B                    C            (calm_eval_metrics: one 16-byte record per row)
+ *   CALM_RED_RECON            B                    S            (calm_recon_metrics: one 32-byte record per workgroup)
  * ------------------------------------------------------------------------------------- */
 enum { CALM_RED_LAYERNORM_BWD = 0, CALM_RED_ROPE_BWD = 1, CALM_RED_LATENT_FWD = 2, CALM_RED_COLSUM = 3, CALM_RED_CNN_BWD = 4,
-       CALM_RED_SOFT_CE = 5, CALM_RED_HUBER = 6, CALM_RED_EVAL = 7 };
+       CALM_RED_SOFT_CE = 5, CALM_RED_HUBER = 6, CALM_RED_EVAL = 7, CALM_RED_RECON = 8 };
 int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols);
 
 /* ---------------------------------------------------------------------------------------
@@ -919,6 +920,48 @@ int calm_top1_count(const float* logits, int64_t ld, const int64_t* labels, floa
 int calm_eval_metrics(const void* logits, int64_t ld, int32_t logits_type, const int64_t* labels, const int32_t* ks,
                       int32_t nk, int64_t* counts, double* loss_sum, int64_t* confusion /* nullable */, int32_t B, int32_t C,
                       float* partials, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The generative job on row tokens (additions to ABI v7 — no existing signature or struct changes, so the version number
+ * stays; csrc/recon.hip).  With the device collate the batch reaches the model as row tokens [B,S,3S], which ARE the
+ * channels-last image: the Huber target has the layout of the model's output, and validation wants reconstruction
+ * measures instead of class counts.  No atomics; cross-workgroup sums go through `partials` and are added in a fixed
+ * order: results repeat bit for bit.
+ *
+ * calm_recon_huber_rows_fwd / _bwd: nn.HuberLoss(delta), mean over n elements, between two fp32 tensors of the same flat
+ *   layout.  0 < n < 2^31 (CALM_E_INVAL / CALM_E_UNSUPP).  Both tensors (and dtokens) are accessed as 16-byte vectors when
+ *   every base is 16-byte aligned, element by element otherwise; the last n % 4 elements always go one by one.  partials:
+ *   calm_reduce_scratch_floats(CALM_RED_HUBER, ...) floats.  dloss is a DEVICE scalar (it carries GradScaler's scale).
+ *
+ * calm_recon_metrics: the reconstruction tallies of one batch, ADDED to the caller's device accumulator `double sums[8]`:
+ *     [0] images counted
+ *     [1] images holding a non-finite generated value; such an image adds to [0] and [1] and to nothing else
+ *     [2] sum of Huber_delta(d) over elements, normalised space, d = generated - target
+ *     [3] sum of |d|            [4] sum of d^2            [5] elements counted (3 S S per finite image)
+ *     [6] sum over images of PSNR_b = 10 log10(1 / max(mse_b, 1e-10)), mse_b over the 3 S S pixel-space values of image b
+ *     [7] sum over images of SSIM_b (left alone when want_ssim is 0)
+ *   tokens [B,S,3S] (tokens[b,i,3j+c]), tokens_type CALM_ST_F32 or CALM_ST_BF16; target fp32, target_layout
+ *   CALM_RECON_ROWS ([B,S,3S]) or CALM_RECON_NCHW ([B,3,S,S]).  Pixel space: p = clamp(v * std[c] + mean[c], 0, 1) on both
+ *   tensors; mean / std are HOST arrays of three floats, read before the call returns.  SSIM (Wang et al. 2004) per channel
+ *   in pixel space: 11 x 11 Gaussian window, sigma 1.5, weights normalised to sum 1, "valid" positions only ((S - 10)^2 per
+ *   channel), C1 = 0.01^2, C2 = 0.03^2, population moments; SSIM_b is the mean over positions and channels.
+ *   Launch 1: a workgroup owns a band of output rows of one image (and a strip of 246 output columns when S > 256); it
+ *   writes one 32-byte record {huber, abs, sq, pixel sq, ssim, non-finite flag, 0, 0} into `partials`
+ *   (calm_reduce_scratch_floats(CALM_RED_RECON, B, S) floats, 16-byte aligned).  Launch 2: one workgroup adds an image's
+ *   records in double in record order and then the per-image values to `sums` in image order.
+ *   CALM_E_INVAL: a null tokens / target / mean / std / sums / partials, B <= 0, S <= 0, an unknown storage type or
+ *   layout;  CALM_E_UNSUPP: S < 11 with want_ssim, S > 4096, 2^31 workgroups or more;  CALM_E_LAYOUT: partials not
+ *   16-byte aligned, tokens / target not aligned to their element.  All of them before any launch.
+ * ------------------------------------------------------------------------------------- */
+enum { CALM_RECON_ROWS = 0, CALM_RECON_NCHW = 1 };
+int calm_recon_huber_rows_fwd(const float* tokens, const float* target, float delta, float* loss /* scalar, overwritten */,
+                              int64_t n, float* partials, void* stream);
+/* dtokens[e] = dloss / n * clamp(tokens[e] - target[e], -delta, delta) */
+int calm_recon_huber_rows_bwd(const float* tokens, const float* target, float delta, const float* dloss, float* dtokens,
+                              int64_t n, void* stream);
+int calm_recon_metrics(const void* tokens, int32_t tokens_type, const float* target, int32_t target_layout,
+                       const float* mean /* host [3] */, const float* std /* host [3] */, float delta, int32_t want_ssim,
+                       double* sums /* device [8] */, int32_t B, int32_t S, float* partials, void* stream);
 
 #ifdef __cplusplus
 }
