@@ -54,6 +54,9 @@ RED_LAYERNORM_BWD, RED_ROPE_BWD, RED_LATENT_FWD, RED_COLSUM, RED_CNN_BWD = range
 RED_SOFT_CE, RED_HUBER = 5, 6                      # the loss entry points (csrc/loss.hip)
 RED_EVAL = 7                                       # calm_eval_metrics: one 16-byte record per row
 RED_RECON = 8                                      # calm_recon_metrics: one 32-byte record per workgroup
+RED_DISTILL = 9                                    # calm_distill_fwd: five sums per row
+DISTILL_SOFT, DISTILL_HARD = 0, 1                  # calm_distill_*'s mode (CALM_DISTILL_*)
+DISTILL_ROW_STATS = 8                              # CALM_DISTILL_ROW_STATS: floats per row of calm_distill_*'s row_stats
 RECON_ROWS, RECON_NCHW = 0, 1                      # calm_recon_metrics' target_layout (CALM_RECON_*)
 EVAL_COUNTS_HEAD = 7                               # counts: rows, skipped, nonfinite, hits@k[0..3], then support[C], hits1[C]
 
@@ -232,6 +235,8 @@ SIGNATURES = {
     "calm_recon_huber_rows_fwd": (_i32, [_p, _p, _f32, _p, _i64, _p, _p]),
     "calm_recon_huber_rows_bwd": (_i32, [_p, _p, _f32, _p, _p, _i64, _p]),
     "calm_recon_metrics": (_i32, [_p, _i32, _p, _i32, C.POINTER(_f32), C.POINTER(_f32), _f32, _i32, _p, _i32, _i32, _p, _p]),
+    "calm_distill_fwd": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i64, _f32, _f32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p]),
+    "calm_distill_bwd": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i64, _f32, _f32, _i32, _p, _p, _p, _i32, _i32, _p]),
     "calm_dropout": (_i32, [_p, _p, _p, _i64, _i64, _f32, _p, _i32, _i32, _i32, _p]),
 }
 

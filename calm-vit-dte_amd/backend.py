@@ -1114,6 +1114,46 @@ class HipBackend:
                                              _ptr(row_stats), _ptr(dloss), _ptr(dlogits), B, C, _stream()),
                    "calm_soft_ce_bwd")
 
+    # knowledge distillation: logits / targets fp32 and teacher fp32 or bf16, all [B,C] with unit column stride (any row
+    # stride); row_stats [B, DISTILL_ROW_STATS]; mode "soft" | "hard"; metrics / dmetrics [4] or None
+    _DISTILL_MODES = {"soft": _lib.DISTILL_SOFT, "hard": _lib.DISTILL_HARD}
+
+    def _distill_inputs(self, what, logits, teacher, targets, row_stats, mode, B, C):
+        if mode not in self._DISTILL_MODES:
+            raise ValueError(f'{what}: mode is "soft" or "hard", got {mode!r}')
+        for name, t in (("logits", logits), ("teacher", teacher), ("targets", targets)):
+            if t.dim() != 2 or tuple(t.shape) != (B, C) or t.stride(1) != 1:
+                raise ValueError(f"{what}: {name} is [B,C] with unit column stride")
+        if row_stats.numel() < B * _lib.DISTILL_ROW_STATS or not row_stats.is_contiguous():
+            raise ValueError(f"{what}: row_stats is contiguous [B, {_lib.DISTILL_ROW_STATS}]")
+        return (_ptr(logits), logits.stride(0), _ptr(teacher, bf16_ok=True), teacher.stride(0), _st(teacher), _ptr(targets),
+                targets.stride(0))
+
+    def distill_fwd(self, logits, teacher, targets, temperature, alpha, mode, row_stats, loss, metrics, dmetrics, B, C):
+        head = self._distill_inputs("distill_fwd", logits, teacher, targets, row_stats, mode, B, C)
+        for name, t in (("metrics", metrics), ("dmetrics", dmetrics)):
+            if t is not None and (t.numel() < 4 or not t.is_contiguous()):
+                raise ValueError(f"distill_fwd: {name} holds four contiguous floats")
+        _lib.check(self.lib.calm_distill_fwd(*head, float(temperature), float(alpha), self._DISTILL_MODES[mode],
+                                             _ptr(row_stats), _ptr(loss), _ptr(metrics, True), _ptr(dmetrics, True), B, C,
+                                             self._partials(_lib.RED_DISTILL, B, C, logits.device), _stream()),
+                   "calm_distill_fwd")
+
+    def distill_bwd(self, logits, teacher, targets, temperature, alpha, mode, row_stats, dloss, dlogits, B, C):
+        head = self._distill_inputs("distill_bwd", logits, teacher, targets, row_stats, mode, B, C)
+        if tuple(dlogits.shape) != (B, C) or not dlogits.is_contiguous():
+            raise ValueError("distill_bwd: dlogits is contiguous [B,C]")
+        _lib.check(self.lib.calm_distill_bwd(*head, float(temperature), float(alpha), self._DISTILL_MODES[mode],
+                                             _ptr(row_stats), _ptr(dloss), _ptr(dlogits), B, C, _stream()),
+                   "calm_distill_bwd")
+
+    def distill_scratch_floats(self, B, C):
+        """Floats of `partials` one distill_fwd call at (B, C) writes (calm_reduce_scratch_floats, cached)."""
+        need = self._scratch_need.get((_lib.RED_DISTILL, B, C))
+        if need is None:
+            need = self._scratch_need[(_lib.RED_DISTILL, B, C)] = int(self.lib.calm_reduce_scratch_floats(_lib.RED_DISTILL, B, C))
+        return need
+
     def huber_tokens_fwd(self, tokens, x, delta, loss, B, S):
         _lib.check(self.lib.calm_huber_tokens_fwd(_ptr(tokens), _ptr(x), float(delta), _ptr(loss), B, S,
                                                   self._partials(_lib.RED_HUBER, B * S, 3 * S, tokens.device), _stream()),

@@ -421,6 +421,280 @@ static __global__ __launch_bounds__(EVAL_FOLD_NT) void eval_fold_kernel(const fl
     }
 }
 
+// ---- knowledge distillation: cross-entropy + KL / hard-label term ------------------------------------------------------
+// One workgroup per row; thread t owns the 8-element groups t, t + 256, ... of the row in all three inputs.  Up to
+// DISTILL_CACHED_C classes that is ONE group per thread, loaded once and kept in registers (24 values) through the three
+// passes of the forward, so every input is read from memory once; longer rows are read again per pass (12 bytes per class
+// and row: they come back from the cache).  Each pass ends in one block-wide combine through its own LDS slots (one
+// barrier per pass).  The launches are bound by latency, not bandwidth: 3 MB at B = 256, C = 1000.
+//   pass 1: max / argmax of z, t and y (ties to the lowest index), sum y, NaN flags
+//   pass 2: sum exp(z - zm), sum exp((z - zm) / T), sum exp((t - tm) / T), sum y (zm - z)
+//   pass 3 (soft): sum q (log q - log pT) with log q = (t - tm) / T - lsq, log pT = (z - zm) / T - lsT, q = exp(log q)
+#define DISTILL_CACHED_C (8 * LOSS_NT)
+struct DistillArgs {
+    const float* logits;
+    const void* teacher;
+    const float* targets;
+    long ld, tld, td;
+    float inv_t, alpha, w, gw;   // 1 / T;  alpha;  the distillation term's weight in the loss: alpha T^2 (soft) or alpha
+                                 // (hard); in the gradient: alpha T or alpha
+    int mode, B, C;
+    int zvec, tvec, yvec;        // whether the rows of each input may be read as 16-byte vectors
+};
+
+// n <= 8 elements from c0 on of an fp32 row / a teacher row in its storage type (elements behind n are 0 and not used)
+__device__ __forceinline__ void distill_load8(const float* row, int c0, int n, bool vec, float* v) {
+    if (vec && n == 8) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(row + c0);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(row + c0 + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { v[k] = a[k]; v[4 + k] = b[k]; }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = k < n ? row[c0 + k] : 0.f;
+    }
+}
+template <bool BF16>
+__device__ __forceinline__ void distill_load8_teacher(const void* row, int c0, int n, bool vec, float* v) {
+    if constexpr (BF16) {
+        const unsigned short* r = reinterpret_cast<const unsigned short*>(row);
+        if (vec && n == 8) {
+            const u16x8 a = *reinterpret_cast<const u16x8*>(r + c0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = bf16_bits_to_float(a[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = k < n ? bf16_bits_to_float(r[c0 + k]) : 0.f;
+        }
+    } else {
+        distill_load8(reinterpret_cast<const float*>(row), c0, n, vec, v);
+    }
+}
+
+// body(c0, n, z, t, y) for every group this thread owns, in increasing c0
+template <bool CACHED, bool BF16, class Body>
+__device__ __forceinline__ void distill_groups(const DistillArgs& a, const float* z, const void* t, const float* y,
+                                               const float* zc, const float* tc, const float* yc, int nc, Body&& body) {
+    if constexpr (CACHED) {
+        if (nc > 0) body(8 * (int)threadIdx.x, nc, zc, tc, yc);
+    } else {
+        const int groups = (a.C + 7) >> 3;
+        for (int q = threadIdx.x; q < groups; q += LOSS_NT) {
+            const int c0 = 8 * q, n = a.C - c0 < 8 ? a.C - c0 : 8;
+            float z8[8], t8[8], y8[8];
+            distill_load8(z, c0, n, a.zvec, z8);
+            distill_load8_teacher<BF16>(t, c0, n, a.tvec, t8);
+            distill_load8(y, c0, n, a.yvec, y8);
+            body(c0, n, z8, t8, y8);
+        }
+    }
+}
+
+template <bool CACHED, bool BF16>
+static __global__ __launch_bounds__(LOSS_NT) void distill_fwd_kernel(const DistillArgs a, float* __restrict__ row_stats,
+                                                                     float* __restrict__ partials) {
+    __shared__ float red1[4][8], red2[4][4], red3[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int B = a.B, C = a.C;
+    const float* z = a.logits + (long)b * a.ld;
+    const float* y = a.targets + (long)b * a.td;
+    const void* t = BF16 ? static_cast<const void*>(reinterpret_cast<const unsigned short*>(a.teacher) + (long)b * a.tld)
+                         : static_cast<const void*>(reinterpret_cast<const float*>(a.teacher) + (long)b * a.tld);
+    float zc[8], tc[8], yc[8];
+    int nc = 0;
+    if (CACHED && 8 * tid < C) {
+        nc = C - 8 * tid < 8 ? C - 8 * tid : 8;
+        distill_load8(z, 8 * tid, nc, a.zvec, zc);
+        distill_load8_teacher<BF16>(t, 8 * tid, nc, a.tvec, tc);
+        distill_load8(y, 8 * tid, nc, a.yvec, yc);
+    }
+
+    // pass 1
+    float zm = -INFINITY, tm = -INFINITY, ym = -INFINITY, ysum = 0.f;
+    int zi = 0x7fffffff, ti = 0x7fffffff, yi = 0x7fffffff;
+    bool bad_z = false, bad_t = false, bad_y = false;
+    distill_groups<CACHED, BF16>(a, z, t, y, zc, tc, yc, nc, [&](int c0, int n, const float* zv, const float* tv, const float* yv) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (k < n) {
+                bad_z |= zv[k] != zv[k];
+                bad_t |= tv[k] != tv[k];
+                bad_y |= yv[k] != yv[k];
+                if (zv[k] > zm) { zm = zv[k]; zi = c0 + k; }
+                if (tv[k] > tm) { tm = tv[k]; ti = c0 + k; }
+                if (yv[k] > ym) { ym = yv[k]; yi = c0 + k; }
+                ysum += yv[k];
+            }
+        }
+    });
+    // a thread that saw only -inf (or nothing) still holds index INT_MAX: the merge prefers any real index at equal value
+    if (8 * tid < C) {
+        if (zm == -INFINITY && zi == 0x7fffffff) zi = 8 * tid;
+        if (tm == -INFINITY && ti == 0x7fffffff) ti = 8 * tid;
+        if (ym == -INFINITY && yi == 0x7fffffff) yi = 8 * tid;
+    }
+    wave_argmax(zm, zi);
+    wave_argmax(tm, ti);
+    wave_argmax(ym, yi);
+    ysum = wave_sum(ysum);
+    const int bad = (__any(bad_z) ? 1 : 0) | (__any(bad_t) ? 2 : 0) | (__any(bad_y) ? 4 : 0);
+    if (lane == 0) {
+        red1[w][0] = zm; red1[w][1] = __int_as_float(zi);
+        red1[w][2] = tm; red1[w][3] = __int_as_float(ti);
+        red1[w][4] = ym; red1[w][5] = __int_as_float(yi);
+        red1[w][6] = ysum; red1[w][7] = __int_as_float(bad);
+    }
+    __syncthreads();
+    zm = red1[0][0]; zi = __float_as_int(red1[0][1]);
+    tm = red1[0][2]; ti = __float_as_int(red1[0][3]);
+    ym = red1[0][4]; yi = __float_as_int(red1[0][5]);
+    int any_bad = __float_as_int(red1[0][7]);
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+        argmax_merge(zm, zi, red1[k][0], __float_as_int(red1[k][1]));
+        argmax_merge(tm, ti, red1[k][2], __float_as_int(red1[k][3]));
+        argmax_merge(ym, yi, red1[k][4], __float_as_int(red1[k][5]));
+        any_bad |= __float_as_int(red1[k][7]);
+    }
+    ysum = (red1[0][6] + red1[1][6]) + (red1[2][6] + red1[3][6]);
+
+    // pass 2
+    const float inv_t = a.inv_t;
+    float se1 = 0.f, set = 0.f, seq = 0.f, yd = 0.f;
+    distill_groups<CACHED, BF16>(a, z, t, y, zc, tc, yc, nc, [&](int, int n, const float* zv, const float* tv, const float* yv) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (k < n) {
+                const float dz = zv[k] - zm;
+                se1 += __expf(dz);
+                set += __expf(dz * inv_t);
+                seq += __expf((tv[k] - tm) * inv_t);
+                yd = fmaf(yv[k], -dz, yd);
+            }
+        }
+    });
+    se1 = wave_sum(se1);
+    set = wave_sum(set);
+    seq = wave_sum(seq);
+    yd = wave_sum(yd);
+    if (lane == 0) { red2[w][0] = se1; red2[w][1] = set; red2[w][2] = seq; red2[w][3] = yd; }
+    __syncthreads();
+    const float ls1 = logf((red2[0][0] + red2[1][0]) + (red2[2][0] + red2[3][0]));
+    const float lst = logf((red2[0][1] + red2[1][1]) + (red2[2][1] + red2[3][1]));
+    const float lsq = logf((red2[0][2] + red2[1][2]) + (red2[2][2] + red2[3][2]));
+    yd = (red2[0][3] + red2[1][3]) + (red2[2][3] + red2[3][3]);
+
+    // pass 3
+    float d;
+    if (a.mode == CALM_DISTILL_SOFT) {
+        float acc = 0.f;
+        distill_groups<CACHED, BF16>(a, z, t, y, zc, tc, yc, nc, [&](int, int n, const float* zv, const float* tv, const float*) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (k < n) {
+                    const float lq = (tv[k] - tm) * inv_t - lsq;
+                    const float lp = (zv[k] - zm) * inv_t - lst;
+                    const float q = __expf(lq);
+                    acc += q == 0.f ? 0.f : q * (lq - lp);           // (a NaN is not 0: it goes on)
+                }
+            }
+        });
+        acc = wave_sum(acc);
+        if (lane == 0) red3[w] = acc;
+        __syncthreads();
+        d = (red3[0] + red3[1]) + (red3[2] + red3[3]);
+    } else {
+        d = (zm - z[ti < C ? ti : 0]) + ls1;                         // -log p1_k (every thread reads the one address)
+        if (any_bad & 2) d = NAN;                                    // the argmax skipped a NaN: hand it on
+    }
+    if (tid == 0) {
+        const float ce = fmaf(ls1, ysum, yd);
+        float* rs = row_stats + (long)b * CALM_DISTILL_ROW_STATS;
+        rs[0] = zm; rs[1] = ls1; rs[2] = lst; rs[3] = tm; rs[4] = lsq; rs[5] = (float)ti; rs[6] = ysum;
+        rs[7] = (a.mode == CALM_DISTILL_HARD && (any_bad & 2)) ? NAN : 0.f;      // (the backward adds it: NaN loss, NaN gradient)
+        partials[b] = (1.f - a.alpha) * ce + a.w * d;
+        partials[B + b] = ce;
+        partials[2 * B + b] = d;
+        partials[3 * B + b] = (!(any_bad & 5) && zi == yi) ? 1.f : 0.f;
+        partials[4 * B + b] = (!(any_bad & 3) && zi == ti) ? 1.f : 0.f;
+    }
+}
+
+// ONE workgroup adds the five per-row values in a fixed order (thread t takes rows t, t + 256, ... in increasing index,
+// then a fixed tree over the 256 running sums), overwrites the loss and updates the two metric buffers
+static __global__ __launch_bounds__(LOSS_NT) void distill_final_kernel(const float* __restrict__ part, int B,
+                                                                       float* __restrict__ loss, float* __restrict__ metrics,
+                                                                       float* __restrict__ dmetrics) {
+    __shared__ float red[8];
+    float s[DISTILL_PART_ROWS];
+#pragma unroll
+    for (int k = 0; k < DISTILL_PART_ROWS; ++k) {
+        float v = 0.f;
+        for (int g = threadIdx.x; g < B; g += LOSS_NT) v += part[(long)k * B + g];
+        s[k] = block_sum_256(v, red);
+    }
+    if (threadIdx.x == 0) {
+        loss[0] = s[0] / (float)B;
+        if (metrics) {
+            metrics[0] += s[0];
+            metrics[1] += s[3];
+            metrics[2] += (float)B;
+            metrics[3] += 1.f;
+        }
+        if (dmetrics) {
+            dmetrics[0] += s[1];
+            dmetrics[1] += s[2];
+            dmetrics[2] += s[4];
+            dmetrics[3] += (float)B;
+        }
+    }
+}
+
+// One workgroup per row, every input read once, nothing summed: all the row quantities are in row_stats.
+template <bool BF16>
+static __global__ __launch_bounds__(LOSS_NT) void distill_bwd_kernel(const DistillArgs a, const float* __restrict__ row_stats,
+                                                                     const float* __restrict__ dloss,
+                                                                     float* __restrict__ dlogits, int dvec) {
+    const int b = blockIdx.x, C = a.C;
+    const float* z = a.logits + (long)b * a.ld;
+    const float* y = a.targets + (long)b * a.td;
+    const void* t = BF16 ? static_cast<const void*>(reinterpret_cast<const unsigned short*>(a.teacher) + (long)b * a.tld)
+                         : static_cast<const void*>(reinterpret_cast<const float*>(a.teacher) + (long)b * a.tld);
+    float* dz = dlogits + (long)b * C;
+    const float* rs = row_stats + (long)b * CALM_DISTILL_ROW_STATS;
+    const float zm = rs[0], ls1 = rs[1], lst = rs[2], tm = rs[3], lsq = rs[4], ysum = rs[6], poison = rs[7];
+    const int kt = (int)rs[5];
+    const float g = dloss[0] / (float)a.B;
+    const float inv_t = a.inv_t, ce_w = 1.f - a.alpha;
+    const bool soft = a.mode == CALM_DISTILL_SOFT;
+    const float kd_w = a.gw;
+    const int groups = (C + 7) >> 3;
+    for (int q = threadIdx.x; q < groups; q += LOSS_NT) {
+        const int c0 = 8 * q, n = C - c0 < 8 ? C - c0 : 8;
+        float zv[8], tv[8] = {}, yv[8], o[8];
+        distill_load8(z, c0, n, a.zvec, zv);
+        distill_load8(y, c0, n, a.yvec, yv);
+        if (soft) distill_load8_teacher<BF16>(t, c0, n, a.tvec, tv);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float dzk = zv[k] - zm;
+            const float p1 = __expf(dzk - ls1);
+            float kd;
+            if (soft) kd = __expf(dzk * inv_t - lst) - __expf((tv[k] - tm) * inv_t - lsq);
+            else kd = (p1 - (c0 + k == kt ? 1.f : 0.f)) + poison;
+            o[k] = g * fmaf(ce_w, fmaf(p1, ysum, -yv[k]), kd_w * kd);
+        }
+        if (dvec && n == 8) {
+            *reinterpret_cast<f32x4*>(dz + c0) = f32x4{o[0], o[1], o[2], o[3]};
+            *reinterpret_cast<f32x4*>(dz + c0 + 4) = f32x4{o[4], o[5], o[6], o[7]};
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (k < n) dz[c0 + k] = o[k];
+        }
+    }
+}
+
 // ---- token-layout Huber ------------------------------------------------------------------------------------------------
 // A token row (b,i) is 3S contiguous floats, tokens[b,i,3j+c], against the three S-float rows x[b,c,i,:].  A workgroup
 // takes R consecutive token rows per turn: the 3R image rows are staged into LDS with 16-byte loads ([r][c][j], the
@@ -584,6 +858,60 @@ int calm_huber_tokens_bwd(const float* tokens, const float* x, float delta, cons
     if (!aligned16(tokens) || !aligned16(x) || !aligned16(dtokens)) return CALM_E_LAYOUT;
     return calm_launch(huber_tokens_kernel<true>, huber_grid(g), LOSS_NT, huber_lds_bytes(g), stream, tokens, x, delta, dloss,
                        dtokens, g);
+}
+
+// the checks both directions share (all before any launch) and the kernels' view of the arguments
+static int distill_args(const float* logits, int64_t ld, const void* teacher, int64_t tld, int32_t teacher_type,
+                        const float* targets, int64_t td, float temperature, float alpha, int32_t mode, int32_t B, int32_t C,
+                        DistillArgs* a) {
+    if (!logits || !teacher || !targets || B <= 0 || C <= 0 || ld < C || tld < C || td < C) return CALM_E_INVAL;
+    if (!(temperature > 0.f) || !isfinite(temperature) || !(alpha >= 0.f && alpha <= 1.f)) return CALM_E_INVAL;
+    if (mode != CALM_DISTILL_SOFT && mode != CALM_DISTILL_HARD) return CALM_E_INVAL;
+    if (teacher_type != CALM_ST_F32 && teacher_type != CALM_ST_BF16) return CALM_E_INVAL;
+    if (C > 65536) return CALM_E_UNSUPP;                         // (the teacher argmax travels as a float in row_stats)
+    const bool soft = mode == CALM_DISTILL_SOFT;
+    a->logits = logits; a->teacher = teacher; a->targets = targets;
+    a->ld = (long)ld; a->tld = (long)tld; a->td = (long)td;
+    a->inv_t = 1.0f / temperature;
+    a->alpha = alpha;
+    a->w = soft ? alpha * temperature * temperature : alpha;
+    a->gw = soft ? alpha * temperature : alpha;
+    a->mode = mode; a->B = B; a->C = C;
+    a->zvec = aligned16(logits) && (ld & 3) == 0;
+    a->yvec = aligned16(targets) && (td & 3) == 0;
+    a->tvec = aligned16(teacher) && (tld % (teacher_type == CALM_ST_BF16 ? 8 : 4)) == 0;
+    return 0;
+}
+
+int calm_distill_fwd(const float* logits, int64_t ld, const void* teacher, int64_t tld, int32_t teacher_type,
+                     const float* targets, int64_t td, float temperature, float alpha, int32_t mode, float* row_stats,
+                     float* loss, float* metrics, float* dmetrics, int32_t B, int32_t C, float* partials, void* stream) {
+    if (!row_stats || !loss || !partials) return CALM_E_INVAL;
+    DistillArgs a;
+    if (int e = distill_args(logits, ld, teacher, tld, teacher_type, targets, td, temperature, alpha, mode, B, C, &a)) return e;
+    if (!aligned16(partials)) return CALM_E_LAYOUT;
+    // one workgroup per sample: DISTILL_PART_ROWS * B floats of partials
+    const bool bf16 = teacher_type == CALM_ST_BF16, cached = C <= DISTILL_CACHED_C;
+    if (int e = with_bool(bf16, [&](auto b16) {
+            return with_bool(cached, [&](auto c) {
+                return calm_launch(distill_fwd_kernel<decltype(c)::value, decltype(b16)::value>, B, LOSS_NT, 0, stream, a,
+                                   row_stats, partials);
+            });
+        }))
+        return e;
+    return calm_launch(distill_final_kernel, 1, LOSS_NT, 0, stream, partials, B, loss, metrics, dmetrics);
+}
+
+int calm_distill_bwd(const float* logits, int64_t ld, const void* teacher, int64_t tld, int32_t teacher_type,
+                     const float* targets, int64_t td, float temperature, float alpha, int32_t mode, const float* row_stats,
+                     const float* dloss, float* dlogits, int32_t B, int32_t C, void* stream) {
+    if (!row_stats || !dloss || !dlogits) return CALM_E_INVAL;
+    DistillArgs a;
+    if (int e = distill_args(logits, ld, teacher, tld, teacher_type, targets, td, temperature, alpha, mode, B, C, &a)) return e;
+    const int dvec = aligned16(dlogits) && (C & 3) == 0;
+    return with_bool(teacher_type == CALM_ST_BF16, [&](auto b16) {
+        return calm_launch(distill_bwd_kernel<decltype(b16)::value>, B, LOSS_NT, 0, stream, a, row_stats, dloss, dlogits, dvec);
+    });
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
+from . import _lib
 from .backend import (ACT_GELU, ACT_GELU_BWD, ACT_NONE, act_dtype, bf16_pipeline, effective_precision, fp8_linears,
                       get_attention_storage, get_backend)
 from .spectral_norm import W16_ATTR, W16_GEN_ATTR
@@ -1153,6 +1154,41 @@ class SoftTargetCrossEntropyFn(Function):
         dlogits = torch.empty(B, C, dtype=torch.float32, device=logits.device)
         be.soft_ce_bwd(logits, targets, row_stats, _dloss(g), dlogits, B, C)
         return dlogits, None, None
+
+
+class DistillLossFn(Function):
+    """Knowledge distillation against a frozen teacher's logits (calm_distill_fwd / _bwd, include/calm_vit.h):
+    (1 - alpha) * CrossEntropy(logits, targets) + alpha * T^2 * KL(softmax(teacher / T) || softmax(logits / T)) in "soft"
+    mode, (1 - alpha) * CrossEntropy(logits, targets) + alpha * CrossEntropy(logits, argmax teacher) in "hard" mode, mean
+    over the batch.  logits, targets [B,C] fp32, teacher [B,C] fp32 or bf16 -> 0-dim fp32 loss; the gradient goes to the
+    logits alone.  metrics: the device float[4] of SoftTargetCrossEntropyFn; dmetrics: the device float[4] of
+    trainer.DistillMetrics (sum of CE, sum of D, teacher agreement, rows), or None."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, logits, teacher, targets, temperature=1.0, alpha=0.5, mode="soft", metrics=None, dmetrics=None):
+        be = get_backend()
+        logits, teacher, targets = _rows_unit_stride(logits), _rows_unit_stride(teacher.detach()), _rows_unit_stride(targets)
+        B, C = logits.shape
+        if targets.shape != logits.shape or teacher.shape != logits.shape:
+            raise ValueError("the distillation loss expects teacher logits and targets of the logits' shape")
+        row_stats = torch.empty(B, _lib.DISTILL_ROW_STATS, dtype=torch.float32, device=logits.device)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        be.distill_fwd(logits, teacher, targets, temperature, alpha, mode, row_stats, loss, metrics, dmetrics, B, C)
+        ctx.save_for_backward(logits, teacher, targets, row_stats)
+        ctx.hyper = (float(temperature), float(alpha), mode)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    @_amp_bwd
+    def backward(ctx, g):
+        be = get_backend()
+        logits, teacher, targets, row_stats = ctx.saved_tensors
+        B, C = logits.shape
+        dlogits = torch.empty(B, C, dtype=torch.float32, device=logits.device)
+        be.distill_bwd(logits, teacher, targets, *ctx.hyper, row_stats, _dloss(g), dlogits, B, C)
+        return (dlogits,) + (None,) * 7
 
 
 class HuberTokensFn(Function):

@@ -33,6 +33,7 @@ reference's train() does with it); the reducer here is the MI355X-tuned equivale
 classes leave the gradient tail (ops.grad_tail) off: DDP reads gradients during the backward.
 """
 import contextlib
+import math
 import os
 import weakref
 
@@ -288,6 +289,59 @@ class StepMetrics:
         self.buf.zero_()                    # in place: a captured step keeps adding at this address
 
 
+def distill_loss_torch(logits, teacher_logits, soft_targets, alpha=0.5, temperature=1.0, mode="soft"):
+    """The distillation loss in stock torch: Hinton-style soft distillation — (1 - alpha) * CE(z, y) + alpha * T^2 *
+    KL(softmax(t / T) || softmax(z / T)), batch mean — or, in "hard" mode, DeiT-style hard distillation — (1 - alpha) *
+    CE(z, y) + alpha * CE(z, argmax t).  No gradient reaches the teacher logits."""
+    F = torch.nn.functional
+    z, y, t, a, T = logits, soft_targets, teacher_logits.detach().to(logits.dtype), alpha, temperature
+    if z.dim() == 1:                                    # (squeeze() at batch 1)
+        z, y, t = z[None], y[None], t[None]
+    if mode == "hard":
+        return (1 - a) * F.cross_entropy(z, y) + a * F.cross_entropy(z, t.argmax(1))
+    if mode != "soft":
+        raise ValueError(f'distillation mode is "soft" or "hard", got {mode!r}')
+    return (1 - a) * F.cross_entropy(z, y) + a * T ** 2 * F.kl_div(F.log_softmax(z / T, 1), F.softmax(t / T, 1),
+                                                                   reduction="batchmean")
+
+
+def distillation_loss(logits, teacher_logits, soft_targets, alpha=0.5, temperature=1.0, mode="soft", metrics=None,
+                      distill_metrics=None):
+    """The loss of a student trained against a frozen teacher's logits on the CutMix / MixUp labels `soft_targets`.
+
+    Under the conditions of soft_target_cross_entropy — the loss kernels switched on, 2-D fp32 logits the installed backend
+    can address, fp32 targets of their shape — and with a backend that has distill_fwd, the two terms are one kernel pass
+    per direction (calm_distill_fwd / _bwd, ops.DistillLossFn; the teacher logits fp32 or bf16); `metrics` (a StepMetrics)
+    and `distill_metrics` (a DistillMetrics) then accumulate on the device.  Everything else is distill_loss_torch."""
+    from . import backend
+    if (backend.get_loss_kernels() and logits.dim() == 2 and soft_targets.dtype == torch.float32
+            and soft_targets.shape == logits.shape and teacher_logits.shape == logits.shape
+            and teacher_logits.dtype in (torch.float32, torch.bfloat16) and teacher_logits.device == logits.device
+            and backend.loss_kernels_take(logits) and hasattr(backend.get_backend(), "distill_fwd")):
+        from .ops import DistillLossFn
+        return DistillLossFn.apply(logits, teacher_logits, soft_targets, float(temperature), float(alpha), mode,
+                                   None if metrics is None else metrics.buf,
+                                   None if distill_metrics is None else distill_metrics.buf)
+    return distill_loss_torch(logits, teacher_logits, soft_targets, alpha, temperature, mode)
+
+
+class DistillMetrics:
+    """The device float[4] that calm_distill_fwd adds to (include/calm_vit.h): sum of the rows' cross-entropy, sum of the
+    rows' distillation term (unweighted), rows whose argmax equals the teacher's, rows.  Read once per epoch."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(4, dtype=torch.float32, device=device)
+
+    def read(self):
+        """(ce_sum, d_sum, agree, rows) as Python numbers: ONE device-to-host copy.  The counts are fp32 on the device,
+        exact below 2^24."""
+        ce_sum, d_sum, agree, rows = self.buf.to("cpu").tolist()
+        return float(ce_sum), float(d_sum), int(agree), int(rows)
+
+    def reset(self):
+        self.buf.zero_()
+
+
 def eval_metrics_torch(logits, labels, ks, counts, loss_sum, confusion):
     """What calm_eval_metrics adds to its accumulators (include/calm_vit.h), in torch on the tensors' device: class c BEATS
     label l when z_c > z_l, or z_c == z_l and c < l, and the label is in the top k exactly when fewer than k classes beat
@@ -521,8 +575,11 @@ class TrainStep:
         with torch.autocast(device_type="cuda", dtype=self.autocast_dtype or torch.bfloat16,
                             enabled=self.autocast_dtype is not None and x.is_cuda):        # cls:84
             y_hat, _ = self.model(x)                                       # cls:85
-            loss = soft_target_cross_entropy(y_hat.squeeze(), y_soft, self.metrics)      # cls:86
+            loss = self._loss(y_hat, y_soft)                               # cls:86
         return self._finish(loss, y_hat)
+
+    def _loss(self, y_hat, y_soft):
+        return soft_target_cross_entropy(y_hat.squeeze(), y_soft, self.metrics)
 
     def _tail_enabled(self):
         """The gradient tail hands autograd unfinished leaf gradients, so nothing but BucketedGradReducer (which flushes the
@@ -672,7 +729,7 @@ class AccumTrainStep(TrainStep):
                             "once per step, with the last forward's u, v, sigma)")
         if reducer is not None and reducer.enabled and not isinstance(reducer, HeldGradReducer):
             raise TypeError("AccumTrainStep needs a HeldGradReducer (BucketedGradReducer all-reduces every backward)")
-        super().__init__(model, optimizer, reducer, **kw)
+        super().__init__(model, optimizer, reducer=reducer, **kw)    # (by keyword: DistillTrainStep's third is the teacher)
         self.accumulate = int(accumulate)
         self.window = 0                               # micro-batches in the open window
         self.boundary = True                          # whether the last call stepped the optimizer
@@ -717,6 +774,62 @@ class AccumRegTrainStep(AccumTrainStep, RegTrainStep):
 
     def __init__(self, model, optimizer, reducer=None, accumulate=2, kl_weight=0.1, **kw):
         super().__init__(model, optimizer, reducer, accumulate=accumulate, kl_weight=kl_weight, **kw)
+
+
+class DistillTrainStep(TrainStep):
+    """TrainStep against a frozen teacher: the teacher's logits of the same batch first — a lean eval forward under
+    torch.no_grad() through a `Predictor`, which stores nothing for a backward and draws no noise, so no RNG stream moves —
+    then TrainStep's forward with `distillation_loss` in place of the cross-entropy, then the same backward / exchange /
+    optimizer sequence.
+
+    teacher: an nn.Module (wrapped in Predictor(teacher, autocast_dtype=...)) or a ready Predictor.  Its parameters get
+    requires_grad_(False); it belongs to no optimizer, reducer, EMA, checkpoint or snapshot.  teacher_graph=True: the
+    teacher forward is captured into a hipGraph at the shape of the first batch this step sees and replayed for every
+    batch of that shape; other shapes run eagerly (Predictor's rule).  distill_metrics: a DistillMetrics the loss kernel
+    accumulates into (only with the loss kernels switched on).  The teacher runs on the step's stream, in front of the
+    student forward."""
+
+    def __init__(self, model, optimizer, teacher, reducer=None, alpha=0.5, temperature=1.0, mode="soft", teacher_graph=False,
+                 distill_metrics=None, **kw):
+        super().__init__(model, optimizer, reducer, **kw)
+        if mode not in ("soft", "hard"):
+            raise ValueError(f'DistillTrainStep: mode is "soft" or "hard", got {mode!r}')
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"DistillTrainStep: alpha lies in [0, 1], got {alpha!r}")
+        if not (float(temperature) > 0.0 and math.isfinite(float(temperature))):
+            raise ValueError(f"DistillTrainStep: temperature is a positive finite number, got {temperature!r}")
+        self.alpha, self.temperature, self.mode = float(alpha), float(temperature), mode
+        self.distill_metrics = distill_metrics
+        self.teacher = teacher if isinstance(teacher, Predictor) else Predictor(teacher, autocast_dtype=self.autocast_dtype)
+        self.teacher_graph = bool(teacher_graph) and self.teacher.graph is None
+        for p in self.teacher.model.parameters():
+            p.requires_grad_(False)
+        self._teacher_logits = None
+
+    def _teacher_forward(self, x):
+        if self.teacher_graph and x.is_cuda:                # the first batch: capture the teacher forward at its shape
+            self.teacher = Predictor(self.teacher.model, example_x=x, autocast_dtype=self.teacher.autocast_dtype, graph=True)
+            self.teacher_graph = False
+        out = self.teacher(x)
+        return (out[0] if isinstance(out, (tuple, list)) else out).detach()
+
+    def __call__(self, x, y_soft):
+        self._teacher_logits = self._teacher_forward(x)
+        try:
+            return super().__call__(x, y_soft)
+        finally:
+            self._teacher_logits = None
+
+    def _loss(self, y_hat, y_soft):
+        return distillation_loss(y_hat.squeeze(), self._teacher_logits.squeeze(), y_soft, self.alpha, self.temperature,
+                                 self.mode, self.metrics, self.distill_metrics)
+
+
+class AccumDistillTrainStep(AccumTrainStep, DistillTrainStep):
+    """DistillTrainStep (the teacher forward and the distillation loss) with AccumTrainStep's window."""
+
+    def __init__(self, model, optimizer, teacher, reducer=None, accumulate=2, **kw):
+        super().__init__(model, optimizer, reducer, accumulate=accumulate, teacher=teacher, **kw)
 
 
 class DeviceCollate:
@@ -2512,7 +2625,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
           device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None,
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
-          val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None):
+          val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
+          teacher=None, distill=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -2628,7 +2742,21 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     work as for "cls".  val_dataset runs `evaluate(recon=True, lean=True)` per rank shard, logs the `ReconMetrics`
     scalars and keeps `<stem>_best<ext>` / `<stem>_ema_best<ext>` by strictly LOWER validation Huber (val_topk is not
     used).  graph=True and device_metrics=True are refused (the captured step and the device metrics are the
-    classification job's)."""
+    classification job's).
+
+    teacher (knowledge distillation; an nn.Module or a `Predictor`, a classifier over the same classes): the step is a
+    `DistillTrainStep` (`AccumDistillTrainStep` with accumulate > 1) — the frozen teacher's logits of every batch, image or
+    row tokens alike, then `distillation_loss`.  distill: a dict with any of "alpha" (0.5), "temperature" (1.0), "mode"
+    ("soft": (1 - alpha) CE + alpha T^2 KL, or "hard": (1 - alpha) CE + alpha CE against the teacher's argmax) and "graph"
+    (False; True captures the teacher forward into a hipGraph at the first batch's shape).  The teacher is moved to the
+    device and put in eval mode for the run, its parameters and buffers are broadcast from rank 0, and it is handed back
+    on the device and in the mode it came in; it is never part of the optimizer, the gradient exchange, the EMA, a
+    checkpoint or a snapshot, so resume= needs the same teacher handed in again and then continues bit for bit.  With the
+    loss kernels switched on, rank 0 prints one extra line per epoch from a single read of a `DistillMetrics`: mean
+    cross-entropy, mean distillation term, agreement with the teacher (of the batches since the epoch began or the run was
+    resumed).  The log_every line is unchanged; its loss is the total.  accumulate, ema, device_collate and its
+    companions, val_dataset and snapshots work as before.  task="reg", graph=True (the captured step builds its own
+    TrainStep), a `generate=True` teacher and distill without teacher are refused."""
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
     if task not in ("cls", "reg"):
@@ -2641,6 +2769,30 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     generates = getattr(initializer, "generate", None)
     if generates is not None and bool(generates) != reg:
         raise ValueError(f'train: task="{task}" needs a model built with generate={reg}, got generate={bool(generates)}')
+    distill_kw = {}
+    if distill is not None:
+        if teacher is None:
+            raise ValueError("train: distill= sets the loss against a teacher; it needs teacher=")
+        distill_kw = dict(distill)
+        if not set(distill_kw) <= {"alpha", "temperature", "mode", "graph"}:
+            raise ValueError(f'train: distill takes the keys "alpha", "temperature", "mode", "graph", got {sorted(distill_kw)}')
+    teacher_mod = None
+    if teacher is not None:
+        teacher_mod = teacher.model if isinstance(teacher, Predictor) else teacher
+        if reg:
+            raise ValueError('train: teacher= excludes task="reg" (distillation is the classification job\'s loss)')
+        if graph:
+            raise ValueError("train: teacher= excludes graph=True (the captured step builds its own TrainStep)")
+        if getattr(teacher_mod, "generate", False):
+            raise ValueError("train: teacher= needs a classifier, got a model built with generate=True")
+        distill_kw = {"alpha": float(distill_kw.get("alpha", 0.5)), "temperature": float(distill_kw.get("temperature", 1.0)),
+                      "mode": distill_kw.get("mode", "soft"), "teacher_graph": bool(distill_kw.get("graph", False))}
+        if distill_kw["mode"] not in ("soft", "hard"):
+            raise ValueError(f'train: distill["mode"] is "soft" or "hard", got {distill_kw["mode"]!r}')
+        if not 0.0 <= distill_kw["alpha"] <= 1.0:
+            raise ValueError(f'train: distill["alpha"] lies in [0, 1], got {distill_kw["alpha"]!r}')
+        if not (distill_kw["temperature"] > 0.0 and math.isfinite(distill_kw["temperature"])):
+            raise ValueError(f'train: distill["temperature"] is a positive finite number, got {distill_kw["temperature"]!r}')
     if device_metrics and not (use_gpu and _backend.get_loss_kernels()):
         raise ValueError("device_metrics=True needs use_gpu=True and the loss kernels switched on "
                          "(backend.set_loss_kernels(True) or CALM_LOSS_KERNELS=1)")
@@ -2710,6 +2862,12 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     elif scheduler is False:
         scheduler = None
     sync_module_states(model)
+    dmetrics = None
+    if teacher_mod is not None:
+        teacher_home = (next(iter(teacher_mod.parameters())).device, teacher_mod.training)
+        teacher_mod.to(device).eval()
+        sync_module_states(teacher_mod)
+        dmetrics = DistillMetrics(device) if _backend.get_loss_kernels() else None
     ema_obj = ModelEMA(model, **ema_kw) if ema is not None else None
     reducer = (HeldGradReducer(model) if accumulate > 1 else BucketedGradReducer(model)) if world > 1 else None
     if world > 1:
@@ -2741,6 +2899,12 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             step = AccumRegTrainStep(model, optimizer, reducer, accumulate=accumulate, kl_weight=kl_weight, **step_kw)
         else:
             step = RegTrainStep(model, optimizer, reducer, kl_weight=kl_weight, **step_kw)
+    elif teacher is not None:
+        step_kw.update(distill_kw, distill_metrics=dmetrics)
+        if accumulate > 1:
+            step = AccumDistillTrainStep(model, optimizer, teacher, reducer, accumulate=accumulate, **step_kw)
+        else:
+            step = DistillTrainStep(model, optimizer, teacher, reducer, **step_kw)
     elif accumulate > 1:
         step = AccumTrainStep(model, optimizer, reducer, accumulate=accumulate, **step_kw)
     else:
@@ -2858,6 +3022,12 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                 if rank == 0 and local_rank == 0:
                     print(f"Epoch: {epoch + 1}, Device: [{rank}, {local_rank}], Mean loss: {loss_sum / max(rows, 1)}, "
                           f"Dominant-class accuracy: {100.0 * agree / max(rows, 1):.4f}%")
+            if dmetrics is not None:
+                ce_sum, d_sum, t_agree, t_rows = dmetrics.read()   # one device-to-host copy per epoch
+                dmetrics.reset()
+                if rank == 0 and local_rank == 0 and t_rows > 0:
+                    print(f"Epoch: {epoch + 1}, Device: [{rank}, {local_rank}], Mean CE: {ce_sum / t_rows}, "
+                          f"Mean distillation term: {d_sum / t_rows}, Teacher agreement: {100.0 * t_agree / t_rows:.4f}%")
             if rank == 0 and local_rank == 0 and checkpoint_path:
                 os.makedirs(os.path.dirname(os.path.abspath(checkpoint_path)), exist_ok=True)
                 torch.save(model.state_dict(), checkpoint_path)                                            # cls:105-107
@@ -2888,6 +3058,10 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             torch.cuda.synchronize()
         if isinstance(optimizer, FusedClipAdamW):
             optimizer.close()
+        if teacher_mod is not None:        # handed back where and as it came in
+            if isinstance(step.teacher, Predictor) and step.teacher is not teacher:
+                step.teacher.close()
+            teacher_mod.to(teacher_home[0]).train(teacher_home[1])
     model = model.to("cpu")                                                                                # cls:112
     if ema_obj is not None:
         ema_obj.rebind()                   # the averages follow the parameters to the CPU

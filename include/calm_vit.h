@@ -186,9 +186,10 @@ int calm_gemm_describe(const calm_gemm_args* args, calm_gemm_plan* plan);
  *   CALM_RED_HUBER            B*S                  3S
  *   CALM_RED_EVAL             B                    C            (calm_eval_metrics: one 16-byte record per row)
  *   CALM_RED_RECON            B                    S            (calm_recon_metrics: one 32-byte record per workgroup)
+ *   CALM_RED_DISTILL          B                    C            (calm_distill_fwd: five sums per row)
  * ------------------------------------------------------------------------------------- */
 enum { CALM_RED_LAYERNORM_BWD = 0, CALM_RED_ROPE_BWD = 1, CALM_RED_LATENT_FWD = 2, CALM_RED_COLSUM = 3, CALM_RED_CNN_BWD = 4,
-       CALM_RED_SOFT_CE = 5, CALM_RED_HUBER = 6, CALM_RED_EVAL = 7, CALM_RED_RECON = 8 };
+       CALM_RED_SOFT_CE = 5, CALM_RED_HUBER = 6, CALM_RED_EVAL = 7, CALM_RED_RECON = 8, CALM_RED_DISTILL = 9 };
 int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols);
 
 /* ---------------------------------------------------------------------------------------
@@ -962,6 +963,55 @@ int calm_recon_huber_rows_bwd(const float* tokens, const float* target, float de
 int calm_recon_metrics(const void* tokens, int32_t tokens_type, const float* target, int32_t target_layout,
                        const float* mean /* host [3] */, const float* std /* host [3] */, float delta, int32_t want_ssim,
                        double* sums /* device [8] */, int32_t B, int32_t S, float* partials, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Knowledge distillation (additions to ABI v7 — no existing signature or struct changes, so the version number stays):
+ * the loss of a student trained against a frozen teacher's logits, cross-entropy with the CutMix / MixUp labels and the
+ * distillation term in ONE pass per direction.  Per row b, with z the student logits (fp32, row stride ld), t the teacher
+ * logits (teacher_type CALM_ST_F32 or CALM_ST_BF16, row stride tld; bf16 widens exactly), y the soft targets (fp32, row
+ * stride td; they need not sum to one), T = temperature, a = alpha:
+ *     p1 = softmax(z)      pT = softmax(z / T)      q = softmax(t / T)
+ *     CE_b = sum_c y_c (max z - z_c) + log(sum exp(z - max z)) * sum_c y_c          (the form of calm_soft_ce_fwd)
+ *     CALM_DISTILL_SOFT:  D_b = sum_c q_c (log q_c - log pT_c), a class with q_c == 0 adds 0 (F.kl_div);   w = a T^2
+ *     CALM_DISTILL_HARD:  D_b = -log p1_k, k = argmax_c t_c (lowest index among equals); T is not used;    w = a
+ *     loss = 1/B sum_b [(1 - a) CE_b + w D_b]
+ *     soft: dlogits[b,c] = dloss/B [(1 - a)(p1_c sum_c y - y_c) + a T (pT_c - q_c)]
+ *     hard: dlogits[b,c] = dloss/B [(1 - a)(p1_c sum_c y - y_c) + a (p1_c - [c == k])]
+ * Every row maximum is subtracted before every exponential in both directions; pT and q come out of one expression
+ * (exp((x - max x) * (1/T) - log sum exp((x - max x) * (1/T)))), so identical student and teacher rows give a distillation
+ * gradient of exactly zero.  A NaN anywhere in a row (z, t or y; in hard mode as well) makes the loss NaN.  Rows are read
+ * in groups of eight elements, each input as 16-byte vectors where its base is 16-byte aligned and its stride a multiple
+ * of one vector (4 fp32 / 8 bf16 elements), element by element otherwise; dlogits likewise.  One workgroup per row; up
+ * to C = 2048 a row of all three inputs stays in registers between the passes, beyond that it is read again (from cache).
+ *
+ * row_stats [B, CALM_DISTILL_ROW_STATS] fp32 — what the backward needs besides its inputs:
+ *     [0] max_c z        [1] log sum exp(z - max z)        [2] log sum exp((z - max z) / T)
+ *     [3] max_c t        [4] log sum exp((t - max t) / T)  [5] argmax_c t as a float (exact: C <= 65536)
+ *     [6] sum_c y        [7] 0; NaN in hard mode when the teacher row holds a NaN (the argmax skips it: the backward
+ *                            adds [7] to the row's gradient, so that a NaN loss comes with a NaN gradient)
+ * partials: calm_reduce_scratch_floats(CALM_RED_DISTILL, B, C) floats, 16-byte aligned: five values per row (total, CE_b,
+ *   D_b, agreement with y, agreement with t); one final workgroup adds them in a fixed order.  No atomics: results repeat
+ *   bit for bit.
+ * metrics (nullable): the float[4] of calm_soft_ce_fwd with its meaning — [0] += sum of the total row losses, [1] +=
+ *   #{b : argmax z == argmax y} (a NaN in z or y: no agreement), [2] += B, [3] += 1.
+ * dmetrics (nullable): device float[4]:  [0] += sum_b CE_b   [1] += sum_b D_b (unweighted)
+ *   [2] += #{b : argmax z == argmax t} (ties to the lowest index; a NaN in z or t: no agreement)   [3] += B.
+ *   Both are updated by one thread of the last launch with a plain read-modify-write.
+ * CALM_E_INVAL: a null logits / teacher / targets / row_stats / loss (dloss, dlogits) / partials, B <= 0, C <= 0, a row
+ * stride below C, T <= 0 or not finite, alpha outside [0, 1] or NaN, an unknown mode, a teacher storage type other than
+ * the two above;  CALM_E_UNSUPP: C > 65536;  CALM_E_LAYOUT: partials not 16-byte aligned.  All of them before any launch.
+ * ------------------------------------------------------------------------------------- */
+enum { CALM_DISTILL_SOFT = 0, CALM_DISTILL_HARD = 1 };
+#define CALM_DISTILL_ROW_STATS 8
+int calm_distill_fwd(const float* logits, int64_t ld, const void* teacher, int64_t tld, int32_t teacher_type,
+                     const float* targets, int64_t td, float temperature, float alpha, int32_t mode,
+                     float* row_stats /* [B, CALM_DISTILL_ROW_STATS] */, float* loss /* scalar, overwritten */,
+                     float* metrics /* nullable, [4] */, float* dmetrics /* nullable, [4] */, int32_t B, int32_t C,
+                     float* partials, void* stream);
+int calm_distill_bwd(const float* logits, int64_t ld, const void* teacher, int64_t tld, int32_t teacher_type,
+                     const float* targets, int64_t td, float temperature, float alpha, int32_t mode,
+                     const float* row_stats, const float* dloss /* device scalar */, float* dlogits /* [B,C] contiguous */,
+                     int32_t B, int32_t C, void* stream);
 
 #ifdef __cplusplus
 }
