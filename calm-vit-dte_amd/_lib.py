@@ -79,9 +79,14 @@ class SnBwdEntry(C.Structure):
 
 
 class OptimTensor(C.Structure):
-    """struct calm_optim_tensor (64 bytes)."""
+    """struct calm_optim_tensor (80 bytes); `group`: the parameter group calm_optim_step_groups reads."""
     _fields_ = [("param", _p), ("grad", _p), ("exp_avg", _p), ("exp_avg_sq", _p), ("sn_u", _p), ("sn_v", _p),
-                ("sn_sigma", _p), ("numel", _i64), ("rows", _i32), ("cols", _i32), ("chunk0", _i32), ("reserved", _i32)]
+                ("sn_sigma", _p), ("numel", _i64), ("rows", _i32), ("cols", _i32), ("chunk0", _i32), ("group", _i32)]
+
+
+class OptimGroup(C.Structure):
+    """struct calm_optim_group (8 bytes, one per parameter group of calm_optim_step_groups)."""
+    _fields_ = [("lr", _f32), ("weight_decay", _f32)]
 
 
 class OptimHparams(C.Structure):
@@ -198,6 +203,7 @@ SIGNATURES = {
     "calm_sn_weight_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _p, _p]),
     "calm_optim_chunk_elems": (_i32, []),
     "calm_optim_step": (_i32, [_p, _i32, _p, _i32, _p, C.POINTER(OptimHparams), _p, _p, _p, _p, _p]),
+    "calm_optim_step_groups": (_i32, [_p, _i32, _p, _i32, _p, C.POINTER(OptimHparams), _p, _i32, _p, _p, _p, _p]),
     "calm_grad_accum": (_i32, [_p, _i32, _p, _i32, _p, _p, _i32, _p]),
     "calm_ema_chunk_elems": (_i32, []),
     "calm_ema_update": (_i32, [_p, _i32, _p, _i32, _f32, _i32, _p, _p, _p, _p]),

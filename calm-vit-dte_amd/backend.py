@@ -233,8 +233,50 @@ class ChunkPlan:
         self.chunk_dev = torch.tensor(chunk_entry, dtype=torch.int32, device=dev)
 
 
+class GroupTable:
+    """The (lr, weight_decay) of every parameter group in device memory (`dev`: float32 [n_groups, 2], the
+    calm_optim_group records calm_optim_step_groups reads) and the host values last uploaded (`host`).  Plans that step
+    the same parameters share one table (FusedClipAdamWindow's two plans).
+
+    `set()` uploads only when a value differs from `host`, and never while the stream is capturing: a captured step
+    reads whatever the table holds when it is replayed.  The values travel through a ring of pinned buffers, each
+    guarded by an event behind its copy, for the reason OptimPlan's docstring gives."""
+    RING = 4
+
+    def __init__(self, n_groups, dev):
+        self.n = int(n_groups)
+        self.dev = torch.zeros(self.n, 2, dtype=torch.float32, device=dev)
+        self.host = np.zeros((self.n, 2), dtype=np.float32)
+        self.stage = [torch.empty(self.n, 2, dtype=torch.float32).pin_memory() for _ in range(self.RING)]
+        self.events = [None] * self.RING
+        self.slot = 0
+
+    def set(self, group_hp):
+        """group_hp: one (lr, weight_decay) per group.  True when the device table was rewritten."""
+        vals = np.asarray(group_hp, dtype=np.float32).reshape(-1, 2)
+        if vals.shape[0] != self.n:
+            raise ValueError(f"the plan has {self.n} parameter groups, {vals.shape[0]} (lr, weight_decay) pairs given")
+        if not np.all(vals[:, 0] >= 0):                     # (also refuses NaN)
+            raise ValueError("a parameter group's learning rate is negative")
+        if np.array_equal(vals, self.host) or torch.cuda.is_current_stream_capturing():
+            return False
+        k = self.slot
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        self.stage[k].numpy()[:] = vals
+        self.dev.copy_(self.stage[k], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[k] = ev
+        self.slot = (k + 1) % self.RING
+        self.host = vals.copy()
+        return True
+
+
 class OptimPlan(ChunkPlan):
     """Device table of calm_optim_tensor records for calm_optim_step; only the gradient pointers change per step.
+    A record's optional "group" (default 0) is the tensor's parameter group for calm_optim_step_groups, below `n_groups`;
+    `groups` is the plan's GroupTable.
 
     The pointers travel through a RING of pinned staging buffers, each guarded by an event recorded behind its
     host-to-device copy: an asynchronous copy from pinned memory reads the host bytes when the DMA runs, not when it is
@@ -243,13 +285,17 @@ class OptimPlan(ChunkPlan):
     upload (gradients kept in the all-reduce buckets, `BucketedGradReducer`) uploads nothing."""
     RING = 4
 
-    def __init__(self, be, records):
+    def __init__(self, be, records, n_groups=1):
         rec = np.zeros(len(records), dtype=np.dtype(_lib.OptimTensor))
         for i, r in enumerate(records):
             p = r["param"]
             if not p.is_contiguous():
                 raise TypeError("optimizer-side step expects contiguous parameters")
             e = rec[i]
+            g = r.get("group", 0)
+            if int(g) != g or not 0 <= g < n_groups:
+                raise ValueError(f"record {i}: parameter group {g!r} outside 0 .. {n_groups - 1}")
+            e["group"] = int(g)
             e["param"], e["exp_avg"], e["exp_avg_sq"] = _ptr(p), _ptr(r["exp_avg"]), _ptr(r["exp_avg_sq"])
             if r["exp_avg"].shape != p.shape or r["exp_avg_sq"].shape != p.shape:
                 raise ValueError("optimizer state shape mismatch")
@@ -271,6 +317,20 @@ class OptimPlan(ChunkPlan):
         self.scratch = torch.empty(6 * self.n + 4 + 3 * self.n_chunks, dtype=torch.float32, device=dev)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)      # advanced by the device, not on skipped steps
         self.param_ptrs = rec["param"].copy()
+        self.n_groups, self._groups = int(n_groups), None
+
+    @property
+    def groups(self):
+        """The plan's GroupTable, made at its first use (a plan stepped through calm_optim_step alone never has one)."""
+        if self._groups is None:
+            self._groups = GroupTable(self.n_groups, self.table_dev.device)
+        return self._groups
+
+    @groups.setter
+    def groups(self, table):
+        if table.n != self.n_groups:
+            raise ValueError(f"the plan has {self.n_groups} parameter groups, the table {table.n}")
+        self._groups = table
 
     def upload(self, grad_ptrs):
         """Stage this step's gradient pointers (numpy uint64 array) and enqueue their copy on the current stream."""
@@ -784,9 +844,10 @@ class HipBackend:
                                               kind, cm, cs, _stream()), "calm_resized_crop")
 
     # ---- optimizer-side step ------------------------------------------------------------
-    def optim_plan(self, records):
-        """records: one dict per parameter — param, exp_avg, exp_avg_sq, sn (None or (u, v, sigma, rows, cols))."""
-        return OptimPlan(self, records)
+    def optim_plan(self, records, n_groups=1):
+        """records: one dict per parameter — param, exp_avg, exp_avg_sq, sn (None or (u, v, sigma, rows, cols)) and,
+        optionally, group (the parameter group of optim_step_groups, below n_groups; default 0)."""
+        return OptimPlan(self, records, n_groups)
 
     def optim_step(self, plan, grads, hp, grad_scale, stats_out, lr_dev=None):
         """hp = (lr, beta1, beta2, eps, weight_decay, max_norm, step); stats_out[2] <- grad norm, found_inf.
@@ -797,6 +858,23 @@ class HipBackend:
         _lib.check(self.lib.calm_optim_step(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
                                             _ptr(plan.scratch), C.byref(h), _ptr(grad_scale, True), _ptr(stats_out),
                                             plan.step_dev.data_ptr(), _ptr(lr_dev, True), _stream()), "calm_optim_step")
+
+    def optim_step_groups(self, plan, grads, hp, group_hp, grad_scale, stats_out):
+        """calm_optim_step_groups: optim_step with the (lr, weight_decay) of every tensor taken from its parameter
+        group.  hp as for optim_step (its lr and weight_decay are ignored); group_hp: one (lr, weight_decay) per group
+        of the plan, written to the plan's device table when a value changed since the last upload — never while the
+        stream is capturing: a captured step reads the table as it is at replay (GroupTable.set between replays).
+        CAUTION: a call inside a capture whose group_hp differs from the values last uploaded therefore steps with the
+        uploaded ones, silently; upload the rates in front of the capture (plan.groups.set / sync_lr_to_device), as
+        GraphedTrainStep does."""
+        plan.upload(np.asarray([_ptr(g) for g in grads], dtype=np.uint64))
+        plan.groups.set(group_hp)
+        h = _lib.OptimHparams(*hp)
+        _lib.check(self.lib.calm_optim_step_groups(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(),
+                                                   plan.n_chunks, _ptr(plan.scratch), C.byref(h),
+                                                   plan.groups.dev.data_ptr(), plan.groups.n, _ptr(grad_scale, True),
+                                                   _ptr(stats_out), plan.step_dev.data_ptr(), _stream()),
+                   "calm_optim_step_groups")
 
     def grad_accum(self, plan, grads, acc_ptrs_dev, first):
         """calm_grad_accum over the table of `plan` (the optimizer's deferred plan, this micro-batch's gradient pointers

@@ -14,6 +14,7 @@
 //   pass 3  optim_update    g' = ((G - c u_i v_j)/sigma) * clip / grad_scale; AdamW exactly as torch.optim.AdamW:
 //                           p *= 1 - lr*wd; m = b1 m + (1-b1) g'; v = b2 v + (1-b2) g'^2;
 //                           p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps);   skipped entirely if found_inf
+//           optim_update_groups  the same update with lr and wd of the tensor's parameter group (calm_optim_step_groups)
 // Work item = chunk of CHUNK consecutive elements of one tensor (table built by the host).
 #include "chunk_table.h"
 
@@ -111,20 +112,15 @@ __global__ __launch_bounds__(NT) void optim_finalize(const calm_optim_tensor* __
     }
 }
 
-__global__ __launch_bounds__(NT) void optim_update(const calm_optim_tensor* __restrict__ T, const int* __restrict__ chunk_tensor,
-                                                   const float* __restrict__ stats, const Globals* __restrict__ G,
-                                                   calm_optim_hparams hp, const int* __restrict__ step_dev,
-                                                   const float* __restrict__ lr_dev) {
-    if (G->found_inf != 0.f) return;          // the reference's scaler.step() skips optimizer.step() on inf/NaN
-    if (step_dev) hp.step = step_dev[0];      // already advanced by optim_finalize for this (un-skipped) step
-    if (lr_dev) hp.lr = lr_dev[0];            // a captured step follows the LR schedule through this device scalar
-    const int t = chunk_tensor[blockIdx.x];
-    const calm_optim_tensor e = T[t];
-    const auto [i0, i1] = chunk_span(blockIdx.x, CHUNK, e.chunk0, e.numel);
+// The update of one chunk with the tensor's rate and weight decay: shared by both update kernels, so that equal
+// hyper-parameters give equal bits whichever of them runs.
+__device__ __forceinline__ void update_chunk(const calm_optim_tensor& e, int t, int chunk, const float* __restrict__ stats,
+                                             const Globals* __restrict__ G, const calm_optim_hparams& hp, float lr, float wd) {
+    const auto [i0, i1] = chunk_span(chunk, CHUNK, e.chunk0, e.numel);
     const float mul = G->clip;
-    const float decay = 1.0f - hp.lr * hp.weight_decay;
+    const float decay = 1.0f - lr * wd;
     const float bc1 = 1.0f - powf(hp.beta1, (float)hp.step), bc2 = 1.0f - powf(hp.beta2, (float)hp.step);
-    const float step_size = hp.lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
+    const float step_size = lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
     const bool sn = e.sn_sigma != nullptr;
     const float c = sn ? stats[ST * t + 5] : 0.f, inv_sg = sn ? 1.0f / e.sn_sigma[0] : 1.f;
     for (long i = i0 + threadIdx.x; i < i1; i += NT) {
@@ -143,6 +139,51 @@ __global__ __launch_bounds__(NT) void optim_update(const calm_optim_tensor* __re
     }
 }
 
+__global__ __launch_bounds__(NT) void optim_update(const calm_optim_tensor* __restrict__ T, const int* __restrict__ chunk_tensor,
+                                                   const float* __restrict__ stats, const Globals* __restrict__ G,
+                                                   calm_optim_hparams hp, const int* __restrict__ step_dev,
+                                                   const float* __restrict__ lr_dev) {
+    if (G->found_inf != 0.f) return;          // the reference's scaler.step() skips optimizer.step() on inf/NaN
+    if (step_dev) hp.step = step_dev[0];      // already advanced by optim_finalize for this (un-skipped) step
+    if (lr_dev) hp.lr = lr_dev[0];            // a captured step follows the LR schedule through this device scalar
+    const int t = chunk_tensor[blockIdx.x];
+    const calm_optim_tensor e = T[t];
+    update_chunk(e, t, blockIdx.x, stats, G, hp, hp.lr, hp.weight_decay);
+}
+
+// Pass 3 with parameter groups: the rate and the weight decay are those of the tensor's group, read from the device
+// table once per workgroup (the index is uniform: a scalar load); hp.lr and hp.weight_decay are not read.
+__global__ __launch_bounds__(NT) void optim_update_groups(const calm_optim_tensor* __restrict__ T, const int* __restrict__ chunk_tensor,
+                                                          const float* __restrict__ stats, const Globals* __restrict__ G,
+                                                          calm_optim_hparams hp, const int* __restrict__ step_dev,
+                                                          const calm_optim_group* __restrict__ groups) {
+    if (G->found_inf != 0.f) return;
+    if (step_dev) hp.step = step_dev[0];
+    const int t = chunk_tensor[blockIdx.x];
+    const calm_optim_tensor e = T[t];
+    const calm_optim_group gr = groups[e.group];
+    update_chunk(e, t, blockIdx.x, stats, G, hp, gr.lr, gr.weight_decay);
+}
+
+// passes 1 and 2 of both entry points: scratch cleared, per-chunk partials, the norm / clip / found_inf / step count
+int stats_and_finalize(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev, int32_t n_chunks,
+                       float* scratch, float max_norm, const float* grad_scale, float* stats_out, int32_t* step_dev, void* stream) {
+    const size_t scratch_bytes = sizeof(float) * ST * (size_t)n_tensors + sizeof(Globals);
+    if (hipError_t e = hipMemsetAsync(scratch, 0, scratch_bytes, as_stream(stream))) return (int)e;
+    Globals* G = reinterpret_cast<Globals*>(scratch + ST * (size_t)n_tensors);
+    float* chunk_part = scratch + ST * (size_t)n_tensors + sizeof(Globals) / sizeof(float);     // every entry is written
+    if (int e = calm_launch(optim_stats, n_chunks, NT, 0, stream, tensors_dev, chunk_tensor_dev, scratch, G, chunk_part))
+        return e;
+    return calm_launch(optim_finalize, 1, NT, 0, stream, tensors_dev, n_tensors, scratch, G, max_norm, grad_scale,
+                       stats_out, chunk_part, step_dev);
+}
+
+bool bad_step_args(const void* tensors_dev, int32_t n_tensors, const void* chunk_tensor_dev, int32_t n_chunks, const void* scratch,
+                   const calm_optim_hparams* hp, const void* stats_out, const void* step_dev) {
+    if (!tensors_dev || !chunk_tensor_dev || !scratch || !hp || !stats_out || n_tensors <= 0 || n_chunks <= 0) return true;
+    return (!step_dev && hp->step < 1) || hp->beta1 < 0.f || hp->beta1 >= 1.f || hp->beta2 < 0.f || hp->beta2 >= 1.f;
+}
+
 }  // namespace
 
 extern "C" {
@@ -152,20 +193,27 @@ int32_t calm_optim_chunk_elems(void) { return CHUNK; }
 int calm_optim_step(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev,
                     int32_t n_chunks, float* scratch, const calm_optim_hparams* hp, const float* grad_scale,
                     float* stats_out, int32_t* step_dev, const float* lr_dev, void* stream) {
-    if (!tensors_dev || !chunk_tensor_dev || !scratch || !hp || !stats_out || n_tensors <= 0 || n_chunks <= 0)
+    if (bad_step_args(tensors_dev, n_tensors, chunk_tensor_dev, n_chunks, scratch, hp, stats_out, step_dev) || hp->lr < 0.f)
         return CALM_E_INVAL;
-    if ((!step_dev && hp->step < 1) || hp->lr < 0.f || hp->beta1 < 0.f || hp->beta1 >= 1.f || hp->beta2 < 0.f || hp->beta2 >= 1.f)
-        return CALM_E_INVAL;
-    const size_t scratch_bytes = sizeof(float) * ST * (size_t)n_tensors + sizeof(Globals);
-    if (hipError_t e = hipMemsetAsync(scratch, 0, scratch_bytes, as_stream(stream))) return (int)e;
-    Globals* G = reinterpret_cast<Globals*>(scratch + ST * (size_t)n_tensors);
-    float* chunk_part = scratch + ST * (size_t)n_tensors + sizeof(Globals) / sizeof(float);     // every entry is written
-    if (int e = calm_launch(optim_stats, n_chunks, NT, 0, stream, tensors_dev, chunk_tensor_dev, scratch, G, chunk_part))
+    if (int e = stats_and_finalize(tensors_dev, n_tensors, chunk_tensor_dev, n_chunks, scratch, hp->max_norm, grad_scale,
+                                   stats_out, step_dev, stream))
         return e;
-    if (int e = calm_launch(optim_finalize, 1, NT, 0, stream, tensors_dev, n_tensors, scratch, G, hp->max_norm, grad_scale,
-                            stats_out, chunk_part, step_dev))
-        return e;
+    const Globals* G = reinterpret_cast<const Globals*>(scratch + ST * (size_t)n_tensors);
     return calm_launch(optim_update, n_chunks, NT, 0, stream, tensors_dev, chunk_tensor_dev, scratch, G, *hp, step_dev, lr_dev);
+}
+
+int calm_optim_step_groups(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev,
+                           int32_t n_chunks, float* scratch, const calm_optim_hparams* hp, const calm_optim_group* groups_dev,
+                           int32_t n_groups, const float* grad_scale, float* stats_out, int32_t* step_dev, void* stream) {
+    if (bad_step_args(tensors_dev, n_tensors, chunk_tensor_dev, n_chunks, scratch, hp, stats_out, step_dev) || !groups_dev ||
+        n_groups <= 0)
+        return CALM_E_INVAL;
+    if (int e = stats_and_finalize(tensors_dev, n_tensors, chunk_tensor_dev, n_chunks, scratch, hp->max_norm, grad_scale,
+                                   stats_out, step_dev, stream))
+        return e;
+    const Globals* G = reinterpret_cast<const Globals*>(scratch + ST * (size_t)n_tensors);
+    return calm_launch(optim_update_groups, n_chunks, NT, 0, stream, tensors_dev, chunk_tensor_dev, scratch, G, *hp, step_dev,
+                       groups_dev);
 }
 
 }  // extern "C"

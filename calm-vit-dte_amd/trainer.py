@@ -1481,12 +1481,112 @@ def save_samples(imgs, out_dir, prefix="sample_"):
     return paths
 
 
-def make_optimizer(model, lr=3.1e-3, weight_decay=0.02, betas=(0.9, 0.98), capturable=False):
-    """optim.AdamW(model.parameters(), lr=3.1e-3, weight_decay=0.02, betas=(0.9, 0.98)) (cls:146,158)."""
+def make_optimizer(model, lr=3.1e-3, weight_decay=0.02, betas=(0.9, 0.98), capturable=False, groups=None):
+    """optim.AdamW(model.parameters(), lr=3.1e-3, weight_decay=0.02, betas=(0.9, 0.98)) (cls:146,158).
+    groups: the parameter groups FusedClipAdamW(groups=) takes (e.g. from `param_groups`), laid out the same way — the
+    base group first — so that a torch run and a fused run share them."""
     params = [p for p in model.parameters() if p.requires_grad]
     fused = params[0].is_cuda
+    if groups is not None:
+        params = _optimizer_groups(model, params, groups, lr, weight_decay)[0]
     return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay, betas=betas, fused=fused,
                              capturable=capturable and fused)
+
+
+def _optimizer_groups(model, params, groups, lr, weight_decay):
+    """torch-style `groups` ({"params": [...], "lr": ..., "weight_decay": ...}, optionally "names") over `params` (the
+    trainable parameters of `model`, in model order) -> (param groups, group index per parameter of `params`).  Group 0
+    is the base group — every parameter no group names, with `lr` / `weight_decay`; it may be empty."""
+    index = {id(p): i for i, p in enumerate(params)}
+    owned = {id(p) for p in model.parameters()}
+    group_of = [0] * len(params)
+    taken = set()
+    out = [{"params": [], "lr": lr, "weight_decay": weight_decay}]
+    for k, g in enumerate(groups, start=1):
+        if not isinstance(g, dict) or "params" not in g:
+            raise ValueError(f'parameter group {k}: a dict with "params" (and "lr" / "weight_decay") is expected')
+        extra = set(g) - {"params", "lr", "weight_decay", "names"}
+        if extra & {"betas", "eps"}:
+            raise ValueError(f"parameter group {k} sets {sorted(extra & {'betas', 'eps'})}: betas and eps are shared by all "
+                             "groups (one hyper-parameter block per optimizer step)")
+        if extra:
+            raise ValueError(f"parameter group {k}: unknown keys {sorted(extra)}")
+        glr, gwd = float(g.get("lr", lr)), float(g.get("weight_decay", weight_decay))
+        if not glr >= 0.0:
+            raise ValueError(f"parameter group {k}: negative learning rate {glr!r}")
+        members = [g["params"]] if isinstance(g["params"], torch.Tensor) else list(g["params"])
+        for p in members:
+            if id(p) not in owned:
+                raise ValueError(f"parameter group {k} holds a tensor that is not a parameter of the model")
+            if not p.requires_grad:
+                raise ValueError(f"parameter group {k} holds a parameter with requires_grad=False (leave frozen "
+                                 "parameters out of every group)")
+            if id(p) in taken:
+                raise ValueError(f"parameter group {k} holds a parameter that is in another group (or twice in this one)")
+            taken.add(id(p))
+            group_of[index[id(p)]] = k
+        d = {"params": members, "lr": glr, "weight_decay": gwd}
+        if "names" in g:
+            d["names"] = list(g["names"])
+        out.append(d)
+    out[0]["params"] = [p for p in params if id(p) not in taken]
+    return out, group_of
+
+
+def param_groups(model, rules, lr=3.1e-3, weight_decay=0.02):
+    """Parameter groups from name rules -> (groups, frozen_params), for FusedClipAdamW(groups=) / make_optimizer(groups=).
+
+    rules: an ordered list of (pattern, options).  pattern: an `fnmatch` pattern on the `named_parameters()` name, or a
+    callable (name, param) -> bool; the FIRST rule that matches a parameter decides, a parameter no rule matches goes to
+    the base group (the optimizer's own lr / weight_decay; it is not listed here).  options: a subset of "lr",
+    "lr_scale" (times the base `lr`; not together with "lr"), "weight_decay", "frozen" (True: the parameter is returned in
+    frozen_params and is in no group — the caller sets requires_grad_(False) before building the optimizer).  Rules that
+    end at the same (lr, weight_decay) share one group, so there are as many groups as distinct pairs (a pair equal to
+    the base one stays in the base group); every group lists its "names" beside its "params".  A rule that matches no
+    parameter is an error.  The preset rules="no_decay": weight_decay = 0 for every parameter with ndim <= 1 — biases,
+    LayerNorm weight / bias, ls_att / ls_mlp, the RoPE inv_freq; a spectral-normed `weight_orig` is 2-d and keeps its
+    decay."""
+    import fnmatch
+    if isinstance(rules, str):
+        if rules != "no_decay":
+            raise ValueError(f'param_groups: the only preset is "no_decay", got {rules!r}')
+        rules = [(lambda name, p: p.ndim <= 1, {"weight_decay": 0.0})]
+    rules = list(rules)
+    for k, (pattern, options) in enumerate(rules):
+        if not (callable(pattern) or isinstance(pattern, str)):
+            raise ValueError(f"param_groups: rule {k}: the pattern is an fnmatch string or a callable (name, param) -> bool")
+        if not set(options) <= {"lr", "lr_scale", "weight_decay", "frozen"}:
+            raise ValueError(f'param_groups: rule {k} takes "lr", "lr_scale", "weight_decay", "frozen", got {sorted(options)}')
+        if "lr" in options and "lr_scale" in options:
+            raise ValueError(f'param_groups: rule {k} sets both "lr" and "lr_scale"')
+    hits = [0] * len(rules)
+    by_pair, frozen = {}, []
+    for name, p in model.named_parameters():
+        for k, (pattern, options) in enumerate(rules):
+            if pattern(name, p) if callable(pattern) else fnmatch.fnmatchcase(name, pattern):
+                break
+        else:
+            continue
+        hits[k] += 1
+        if options.get("frozen"):
+            frozen.append(p)
+            continue
+        if not p.requires_grad:
+            continue
+        glr = float(options["lr"]) if "lr" in options else lr * float(options.get("lr_scale", 1.0))
+        pair = (glr, float(options.get("weight_decay", weight_decay)))
+        if pair == (lr, weight_decay):
+            continue
+        g = by_pair.setdefault(pair, {"params": [], "names": [], "lr": pair[0], "weight_decay": pair[1]})
+        g["params"].append(p)
+        g["names"].append(name)
+    for k, n in enumerate(hits):
+        if n == 0:
+            raise ValueError(f"param_groups: rule {k} ({rules[k][0]!r}) matches no parameter of the model")
+    return list(by_pair.values()), frozen
+
+
+_build_param_groups = param_groups              # (train() has an argument of that name)
 
 
 def _clear_deferred(refs, attr, token):
@@ -1515,17 +1615,33 @@ class FusedClipAdamW(torch.optim.Optimizer):
     u, v, sigma, W are replicated), so the BucketedGradReducer / DDP run unchanged in between.  close() restores the
     in-backward correction.  Same update rule, hyper-parameters and state names as torch.optim.AdamW.
 
-    It IS a torch.optim.Optimizer (one param group): `CosineAnnealingLR(optimizer, T_max=epochs, eta_min=1e-6)` of the
-    reference's train() (cls:52,108-109) wraps it, and the learning rate a step uses is `param_groups[0]["lr"]`."""
+    It IS a torch.optim.Optimizer: `CosineAnnealingLR(optimizer, T_max=epochs, eta_min=1e-6)` of the reference's
+    train() (cls:52,108-109) wraps it, and the learning rate a step uses is `param_groups[0]["lr"]`.
 
-    def __init__(self, model, lr=3.1e-3, weight_decay=0.02, betas=(0.9, 0.98), eps=1e-8, max_norm=1.0, defer_sn=True):
+    groups=None (the reference's own call): one param group, calm_optim_step.  groups=[{"params": [...], "lr": ...,
+    "weight_decay": ...}, ...] (torch's form; `param_groups()` builds them from name rules): the parameters no group
+    names form the base group with the constructor's lr / weight_decay — group 0, first in `param_groups`, possibly
+    empty; betas and eps are shared.  With more than one group the step is calm_optim_step_groups: the same three
+    launches, the norm / clip / inf check / step count over ALL parameters, and pass 3 reading every tensor's
+    `param_groups[g]["lr"]` / `["weight_decay"]` from a device table that is rewritten only when a value changed — so a
+    torch scheduler drives every group, also through a captured step.  `params`, `exp_avg`, `exp_avg_sq` keep the order of
+    model.parameters() whatever the grouping.  Refused: a group that sets betas or eps, a parameter in two groups, one
+    that is not the model's or has requires_grad=False, a negative lr."""
+
+    def __init__(self, model, lr=3.1e-3, weight_decay=0.02, betas=(0.9, 0.98), eps=1e-8, max_norm=1.0, defer_sn=True,
+                 groups=None):
         from . import ops
         from .backend import get_backend
         from .spectral_norm import SpectralWeight
         self.be = get_backend()
         self.max_norm = max_norm
         params = [p for p in model.parameters() if p.requires_grad]
-        super().__init__(params, dict(lr=lr, weight_decay=weight_decay, betas=tuple(betas), eps=eps))
+        group_of = [0] * len(params)
+        if groups is None:
+            super().__init__(params, dict(lr=lr, weight_decay=weight_decay, betas=tuple(betas), eps=eps))
+        else:
+            pg, group_of = _optimizer_groups(model, params, groups, lr, weight_decay)
+            super().__init__(pg, dict(lr=lr, weight_decay=weight_decay, betas=tuple(betas), eps=eps))
         self.params = params
         self.exp_avg = [torch.zeros_like(p) for p in self.params]
         self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
@@ -1535,7 +1651,7 @@ class FusedClipAdamW(torch.optim.Optimizer):
                 if isinstance(m, SpectralWeight) and not getattr(m, "layer_scaled", False):
                     sn[id(m.weight_orig)] = m
         self._records, self._deferred, self._sn_tensors = [], [], []
-        for p, ea, eas in zip(self.params, self.exp_avg, self.exp_avg_sq):
+        for p, ea, eas, grp in zip(self.params, self.exp_avg, self.exp_avg_sq, group_of):
             m = sn.get(id(p))
             info = None
             if m is not None:
@@ -1543,7 +1659,9 @@ class FusedClipAdamW(torch.optim.Optimizer):
                 self._deferred.append(p)
                 self._sn_tensors.append((m, m.weight_u.data_ptr(), m.weight_v.data_ptr(), m._sigma.data_ptr()))
             self._records.append({"param": p.data, "exp_avg": ea, "exp_avg_sq": eas, "sn": info})
-        self._plan = self.be.optim_plan(self._records)
+            if self.grouped:
+                self._records[-1]["group"] = grp
+        self._plan = self._make_plan(self._records)
         # the deferral is a mark on the PARAMETER OBJECT (ops reads it in forward), not a set of raw addresses: it
         # survives a re-materialised buffer and cannot be inherited by an unrelated tensor at a recycled address
         # The mark carries its owner: a second optimizer built over the same model takes the marks over, and the first
@@ -1558,14 +1676,34 @@ class FusedClipAdamW(torch.optim.Optimizer):
         self._finalizer = weakref.finalize(self, _clear_deferred, [weakref.ref(p) for p in self._deferred], ops.DEFER_ATTR,
                                            self._token)
         self.stats = torch.zeros(2, dtype=torch.float32, device=self.params[0].device)   # [grad norm, found_inf]
+        # (with parameter groups the rates always live on the device, in the plan's group table)
         # learning rate as a device scalar for captured steps (GraphedTrainStep sets lr_on_device and refreshes it from
         # param_groups[0]["lr"] before a replay whenever a scheduler has changed it); eager steps pass the host value
         self.lr_on_device = False
         self._lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=self.params[0].device)
         self._lr_dev_value = float(lr)
 
+    @property
+    def grouped(self):
+        """More than one param group: the step goes through calm_optim_step_groups."""
+        return len(self.param_groups) > 1
+
+    def _make_plan(self, records):
+        if self.grouped and hasattr(self.be, "optim_step_groups"):
+            return self.be.optim_plan(records, n_groups=len(self.param_groups))
+        return self.be.optim_plan(records)
+
+    def group_hparams(self):
+        """[(lr, weight_decay)] of every param group as they are now (what the next step uses)."""
+        return [(float(g["lr"]), float(g["weight_decay"])) for g in self.param_groups]
+
     def sync_lr_to_device(self):
-        """Write param_groups[0]["lr"] to the device scalar a captured step reads (no-op when unchanged)."""
+        """Write param_groups[0]["lr"] to the device scalar a captured step reads (no-op when unchanged); with parameter
+        groups, the whole (lr, weight_decay) table when any value changed."""
+        if self.grouped:
+            if hasattr(self.be, "optim_step_groups"):
+                self._plan.groups.set(self.group_hparams())
+            return
         lr = float(self.lr)
         if lr != self._lr_dev_value:
             self._lr_dev.fill_(lr)
@@ -1577,7 +1715,7 @@ class FusedClipAdamW(torch.optim.Optimizer):
         inf/NaN gradient skips the update — torch.optim.AdamW under a GradScaler.  Reading it synchronises."""
         return int(self._plan.step_dev.item())
 
-    # the hyper-parameters live in the (single) param group, where LR schedulers read and write them
+    # the hyper-parameters live in the param groups, where LR schedulers read and write them (these: group 0's)
     lr = property(lambda self: self.param_groups[0]["lr"], lambda self, v: self.param_groups[0].__setitem__("lr", v))
     weight_decay = property(lambda self: self.param_groups[0]["weight_decay"])
     betas = property(lambda self: self.param_groups[0]["betas"])
@@ -1618,10 +1756,20 @@ class FusedClipAdamW(torch.optim.Optimizer):
             grads.append(g)
         return grads
 
-    def _launch(self, plan, grads, divisor):
-        """calm_optim_step over `plan` with `grads` divided by `divisor` (a device scalar, or None); every `.grad` is
-        released afterwards.  Returns the stats tensor."""
+    def _launch(self, plan, grads, divisor, records=None):
+        """calm_optim_step (calm_optim_step_groups with more than one param group) over `plan` — whose records are
+        `records`, default the deferred plan's — with `grads` divided by `divisor` (a device scalar, or None); every
+        `.grad` is released afterwards.  Returns the stats tensor."""
         hp = (float(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.max_norm or 0.0, 0)
+        if self.grouped:
+            if hasattr(self.be, "optim_step_groups"):
+                self.be.optim_step_groups(plan, grads, hp, self.group_hparams(), divisor, self.stats)
+            else:                               # a backend without the entry point (CPU parameters)
+                optim_step_groups_torch(self._records if records is None else records, plan.step_dev, grads, hp,
+                                        self.group_hparams(), divisor, self.stats)
+            for p in self.params:
+                p.grad = None
+            return self.stats
         if self.lr_on_device and not torch.cuda.is_current_stream_capturing():
             self.sync_lr_to_device()
         self.be.optim_step(plan, grads, hp, divisor, self.stats, lr_dev=self._lr_dev if self.lr_on_device else None)
@@ -1643,18 +1791,62 @@ class FusedClipAdamW(torch.optim.Optimizer):
             p.grad = None
 
     def state_dict(self):
-        return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
-                "hparams": dict(lr=self.lr, weight_decay=self.weight_decay, betas=self.betas, eps=self.eps,
-                                max_norm=self.max_norm)}
+        hparams = dict(lr=self.lr, weight_decay=self.weight_decay, betas=self.betas, eps=self.eps, max_norm=self.max_norm)
+        if self.grouped:
+            hparams["groups"] = [list(pair) for pair in self.group_hparams()]
+        return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "hparams": hparams}
 
     def load_state_dict(self, sd):
         if "hparams" in sd:
+            saved = sd["hparams"].get("groups")
+            if (len(saved) if saved is not None else 1) != len(self.param_groups):
+                raise ValueError(f"FusedClipAdamW.load_state_dict: the state holds {len(saved) if saved is not None else 1} "
+                                 f"parameter group(s), this optimizer has {len(self.param_groups)}")
             self.lr = sd["hparams"]["lr"]
+            if saved is not None:
+                for g, (glr, gwd) in zip(self.param_groups, saved):
+                    g["lr"], g["weight_decay"] = glr, gwd
         self._plan.step_dev.fill_(int(sd["step"]))
         for dst, src in zip(self.exp_avg, sd["exp_avg"]):
             dst.copy_(src)
         for dst, src in zip(self.exp_avg_sq, sd["exp_avg_sq"]):
             dst.copy_(src)
+
+
+def optim_step_groups_torch(records, step_dev, grads, hp, group_hp, grad_scale, stats_out):
+    """calm_optim_step_groups in torch, for a backend without `optim_step_groups` (CPU parameters): the deferred
+    spectral-norm correction of a record with `sn`, the norm / clip / inf check over ALL records, then torch.optim.AdamW's
+    update of every record with the (lr, weight_decay) of `group_hp[record["group"]]`.  hp as for optim_step (its lr and
+    weight_decay are ignored); step_dev: the int32 step count, advanced unless the step is skipped for inf/NaN."""
+    f32 = lambda x: float(torch.tensor(float(x), dtype=torch.float32))        # the ABI's hyper-parameters are fp32  # noqa: E731
+    _, b1, b2, eps, _, max_norm, _ = (f32(x) for x in hp)
+    group_hp = [(f32(lr), f32(wd)) for lr, wd in group_hp]
+    fixed = []
+    for r, g in zip(records, grads):
+        if r["sn"] is not None:
+            u, v, sigma, rows, cols = r["sn"]
+            G = g.reshape(rows, cols)
+            c = (G * r["param"].reshape(rows, cols)).sum() / sigma
+            g = ((G - (c * u)[:, None] * v[None, :]) * (1.0 / sigma)).reshape(g.shape)
+        fixed.append(g)
+    inv = 1.0 / float(grad_scale) if grad_scale is not None else 1.0
+    norm = torch.sqrt(sum((g.double() ** 2).sum() for g in fixed)).float() * inv
+    bad = not bool(torch.isfinite(norm))
+    stats_out[0], stats_out[1] = norm, float(bad)
+    if bad:
+        return
+    step_dev += 1
+    step = int(step_dev)
+    mul = (min(1.0, max_norm / (float(norm) + 1e-6)) if max_norm > 0 else 1.0) * inv
+    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+    for r, g in zip(records, fixed):
+        lr, wd = group_hp[r.get("group", 0)]
+        g = g * mul
+        p, m, v = r["param"], r["exp_avg"], r["exp_avg_sq"]
+        p.mul_(1 - lr * wd)
+        m.lerp_(g, 1 - b1)
+        v.mul_(b2).addcmul_(g, g, value=1 - b2)
+        p.addcdiv_(m, (v.sqrt() / (bc2 ** 0.5)).add_(eps), value=-lr / bc1)
 
 
 def grad_accum_torch(records, grads, accs, first):
@@ -1682,7 +1874,8 @@ class FusedClipAdamWindow(FusedClipAdamW):
     over several forwards could not be corrected once at the end — and adds the finished gradients to fp32 accumulators
     (`first = 1` at the start of a window: written without being read, they may hold NaN from a skipped window).  Every
     `.grad` is then released: the next backward finds the gradient tail armable and autograd adopts fresh buffers.
-    `step()` with `window > 0` runs calm_optim_step over a second, "plain" plan — the same parameters, moments and device
+    `step()` with `window > 0` runs calm_optim_step (calm_optim_step_groups with parameter groups: the plain plan carries
+    the same group indices and shares the group table) over a second, "plain" plan — the same parameters, moments and device
     step counter, no correction, gradients = the accumulators, whose addresses are fixed, so its table is uploaded once
     — with `grad_scale * window` (or `window`) as the divisor: the mean over the micro-batches costs no pass.  `step()`
     with `window == 0` is FusedClipAdamW.step()."""
@@ -1690,7 +1883,7 @@ class FusedClipAdamWindow(FusedClipAdamW):
     def __init__(self, model, *args, **kw):
         super().__init__(model, *args, **kw)
         self.window = 0                         # micro-batches accumulated since the last step
-        self._acc = self._acc_plan = self._acc_ptrs = self._acc_ptrs_dev = None
+        self._acc = self._acc_plan = self._acc_records = self._acc_ptrs = self._acc_ptrs_dev = None
         self._window_divisors = {}
 
     def bind_accumulators(self, accs=None):
@@ -1707,8 +1900,11 @@ class FusedClipAdamWindow(FusedClipAdamW):
                                                 or not a.is_contiguous() for a, p in zip(accs, self.params)):
             raise ValueError("FusedClipAdamWindow.bind_accumulators: one contiguous fp32 tensor per parameter, of its shape "
                              "and on its device")
-        plan = self.be.optim_plan([dict(r, sn=None) for r in self._records])
+        self._acc_records = [dict(r, sn=None) for r in self._records]        # (the group indices travel with them)
+        plan = self._make_plan(self._acc_records)
         plan.step_dev = self._plan.step_dev     # one counter: snapshots and step_count see every step
+        if self.grouped and hasattr(self.be, "optim_step_groups"):
+            plan.groups = self._plan.groups     # one (lr, weight_decay) table: both plans step the same groups
         self._acc, self._acc_plan = accs, plan
         self._acc_ptrs = np.asarray([a.data_ptr() for a in accs], dtype=np.uint64)
         self._acc_ptrs_dev = torch.from_numpy(self._acc_ptrs.view(np.int64).copy()).to(self.params[0].device)
@@ -1755,7 +1951,7 @@ class FusedClipAdamWindow(FusedClipAdamW):
             if p.grad is not None and p.grad.data_ptr() != a.data_ptr():
                 raise RuntimeError("FusedClipAdamWindow.step: a window is open and a parameter has a gradient outside it; "
                                    "accumulate() takes gradients into the window")
-        stats = self._launch(self._acc_plan, self._acc, self._window_divisor(grad_scale))
+        stats = self._launch(self._acc_plan, self._acc, self._window_divisor(grad_scale), self._acc_records)
         self.window = 0
         return stats
 
@@ -1979,7 +2175,8 @@ def _unb64(text):
 class TrainState:
     """The whole state of a training run as ONE file, written without stalling the training thread, and resumed from
     exactly: parameters and buffers, the optimizer's moments and step count, the weight EMA and its update count, the
-    step metrics, the GradScaler's scale and the growth count of the fused step, the scheduler, the learning rate, the
+    step metrics, the GradScaler's scale and the growth count of the fused step, the scheduler, the learning rate (a
+    FusedClipAdamW with more than one param group: every group's, as "lrs"; a file of another group count is refused), the
     torch CPU / CUDA RNG states, the numpy generators of the device collate / augmentation and the position in the run.
     The tensor set is the one GraphedTrainStep(restore_after_warmup=True) puts back, which
     tests/test_determinism_gpu.py shows to be sufficient bit for bit.
@@ -2137,6 +2334,8 @@ class TrainState:
              "rng": {"torch_cpu": _b64(torch.get_rng_state()),
                      "cuda": _b64(torch.cuda.get_rng_state(self.device)) if self.on_gpu else None},
              "generators": {n: g.bit_generator.state for n, g in self.generators.items()}}
+        if self.fused and len(self.opt.param_groups) > 1:     # (a torch optimizer's groups travel in its own state dict)
+            h["lrs"] = [g["lr"] for g in self.opt.param_groups]
         if not self.fused and self.payload:
             h["optimizer"] = self._optim_desc
             if self.scaler is not None:            # torch's own GradScaler policy: its growth count (reading it synchronises)
@@ -2298,6 +2497,10 @@ class TrainState:
             host.update({k: side[k] for k in self._PER_RANK})
         if set(host["generators"]) != set(self.generators):
             raise ValueError(f"{path}: generators {sorted(host['generators'])} in the file, {sorted(self.generators)} given")
+        n_groups = len(host["lrs"]) if "lrs" in host else 1
+        if self.fused and n_groups != len(self.opt.param_groups):
+            raise ValueError(f"{path}: written with {n_groups} parameter group(s), this optimizer has "
+                             f"{len(self.opt.param_groups)}")
         # the entries: everything but a torch optimizer's state must be the live set, name by name
         head, optim, tail = self._fixed_entries()
         live = head + optim + tail
@@ -2368,6 +2571,9 @@ class TrainState:
                 self.scaler.load_state_dict(sd)
             self._plan_key = None                 # the tensors made above are now the optimizer's (or copies of them)
         self.opt.param_groups[0]["lr"] = host["lr"]
+        if self.fused:
+            for g, glr in zip(self.opt.param_groups, host.get("lrs", ())):
+                g["lr"] = glr
         if self.scheduler is not None:
             if host["scheduler"] is None:
                 raise ValueError(f"{path}: written without a scheduler, this run has one")
@@ -2393,7 +2599,9 @@ class GraphedTrainStep:
     capture-compatible form, see BucketedGradReducer._launch); without one the constructor refuses a world of more than
     one rank.  Inputs are copied into static buffers.  A learning-rate scheduler acts on replays: FusedClipAdamW reads
     the rate from a device scalar (calm_optim_step's lr_dev, ABI v7) that __call__ refreshes from
-    param_groups[0]["lr"] before the replay; capturable torch optimizers keep theirs on the device already.
+    param_groups[0]["lr"] before the replay — with parameter groups, the (lr, weight_decay) table of
+    calm_optim_step_groups, rewritten when any group's value changed; capturable torch optimizers keep theirs on the
+    device already.
 
     The warm-up steps in front of the capture (allocator, lazy plans) are real training steps on the example batch.
     restore_after_warmup=True (FusedClipAdamW only) undoes them: parameters, buffers (spectral-norm u / v), optimizer
@@ -2435,6 +2643,8 @@ class GraphedTrainStep:
                 self.inner(self.x, self.y)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        if isinstance(optimizer, FusedClipAdamW):
+            optimizer.sync_lr_to_device()          # nothing is written to the rates during the capture
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss, self.y_hat = self.inner(self.x, self.y)
@@ -2626,7 +2836,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None,
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
           val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
-          teacher=None, distill=None):
+          teacher=None, distill=None, param_groups=None, scheduler_step="epoch"):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -2756,9 +2966,34 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     cross-entropy, mean distillation term, agreement with the teacher (of the batches since the epoch began or the run was
     resumed).  The log_every line is unchanged; its loss is the total.  accumulate, ema, device_collate and its
     companions, val_dataset and snapshots work as before.  task="reg", graph=True (the captured step builds its own
-    TrainStep), a `generate=True` teacher and distill without teacher are refused."""
+    TrainStep), a `generate=True` teacher and distill without teacher are refused.
+
+    param_groups (needs optimizer="fused"): the rules of `param_groups()` — an ordered list of (fnmatch pattern or
+    callable, {"lr" | "lr_scale", "weight_decay", "frozen"}) — or the preset "no_decay" (no weight decay on biases, norms,
+    scales and inv_freq).  The frozen parameters get requires_grad_(False) before the reducer, the optimizer and the EMA
+    are built, so none of the three sees them; FusedClipAdamW / FusedClipAdamWindow is built with the groups and steps
+    through calm_optim_step_groups, the scheduler drives every group's rate, and rank 0 prints one line per group
+    (tensors, elements, lr, weight decay).  Works with accumulate, ema, graph=True, snapshots / resume= (a snapshot of
+    another group count is refused), teacher= and task="reg".  With an optimizer OBJECT it is refused: build the groups
+    into the optimizer you hand in (`FusedClipAdamW(groups=)`, `make_optimizer(groups=)`).  Freezing saves no backward
+    work: the weight-gradient GEMMs of frozen layers are still computed and autograd drops the result, and the
+    spectral-norm power iteration of a frozen layer still advances at every training forward (as torch's does), so its
+    u / v / sigma buffers move although `weight_orig` does not.
+
+    scheduler_step="epoch" (the reference: scheduler.step() once per epoch) | "step": scheduler.step() right behind every
+    optimizer step — where the step count advances, the end-of-epoch flush of an accumulation window included — and in
+    front of that step's snapshot, so a snapshot holds the schedule's position and resume= stays exact; it is then not
+    called at the epoch end.  A scheduler built here is CosineAnnealingLR(T_max = epochs * optimizer steps per epoch,
+    eta_min=1e-6).  A step skipped for inf/NaN gradients still advances the schedule (torch under a GradScaler: the
+    host does not know)."""
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
+    if scheduler_step not in ("epoch", "step"):
+        raise ValueError(f'train: scheduler_step is "epoch" or "step", got {scheduler_step!r}')
+    per_step = scheduler_step == "step"
+    if param_groups is not None and not (isinstance(optimizer, str) and optimizer == "fused"):
+        raise ValueError('train: param_groups= needs optimizer="fused"; build the groups into the optimizer you hand in '
+                         "(FusedClipAdamW(groups=) / make_optimizer(groups=))")
     if task not in ("cls", "reg"):
         raise ValueError(f'train: task is "cls" or "reg", got {task!r}')
     reg = task == "reg"
@@ -2855,9 +3090,19 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             be._selfcheck_done = True
             torch.cuda.empty_cache()
     model = initializer.to(device)
-    if optimizer == "fused":
-        optimizer = FusedClipAdamWindow(model) if accumulate > 1 else FusedClipAdamW(model)
-    if scheduler is None or scheduler is True:
+    if isinstance(optimizer, str) and optimizer == "fused":
+        group_kw = {}
+        if param_groups is not None:
+            groups, frozen = _build_param_groups(model, param_groups)
+            for p in frozen:                # before the reducer, the optimizer and the EMA: all three filter on it
+                p.requires_grad_(False)
+            group_kw = {"groups": groups}
+        optimizer = FusedClipAdamWindow(model, **group_kw) if accumulate > 1 else FusedClipAdamW(model, **group_kw)
+        if param_groups is not None and rank == 0 and local_rank == 0:
+            for k, g in enumerate(optimizer.param_groups):
+                print(f"Parameter group {k}: {len(g['params'])} tensors, {sum(p.numel() for p in g['params'])} elements, "
+                      f"lr {g['lr']}, weight decay {g['weight_decay']}")
+    if (scheduler is None or scheduler is True) and not per_step:
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=epochs, eta_min=1e-6)      # cls:52
     elif scheduler is False:
         scheduler = None
@@ -2889,6 +3134,9 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         collate_fn = None if reg else SoftMixCollate(num_classes=num_classes, seed=2006 + rank)      # reg:58
     loader = DataLoader(dataset, batch_size=batch_size, sampler=sampler, collate_fn=collate_fn, num_workers=num_workers,
                         pin_memory=use_gpu, persistent_workers=num_workers > 0, drop_last=bool(graph))
+    if per_step and (scheduler is None or scheduler is True):       # one schedule position per optimizer step
+        steps_per_epoch = -(-len(loader) // accumulate)
+        scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=max(epochs * steps_per_epoch, 1), eta_min=1e-6)
     scaler = torch.amp.GradScaler("cuda", enabled=use_gpu)                                                 # cls:64
     metrics = StepMetrics(device) if device_metrics else None
     step_kw = dict(max_norm=1.0, scaler=scaler if use_gpu else None, autocast_dtype=torch.bfloat16 if use_gpu else None,
@@ -2997,6 +3245,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                     loss, y_hat = step(x, y)
                 stepped = accumulate == 1 or step.boundary          # accumulate > 1: a window's last micro-batch steps
                 n_steps += int(stepped)
+                if stepped and per_step and scheduler is not None:
+                    scheduler.step()                # in front of this step's snapshot: it holds the schedule's position
                 done = stepped and max_steps is not None and n_steps >= max_steps
                 if st is not None:                  # right behind the step, before anything else touches state
                     if stepped and snapshot_path is not None and ((snapshot_every and n_steps % int(snapshot_every) == 0)
@@ -3016,6 +3266,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                     break
             if accumulate > 1 and step.flush():     # the epoch's last, incomplete window: stepped before the checkpoint
                 n_steps += 1
+                if per_step and scheduler is not None:
+                    scheduler.step()
             if metrics is not None:
                 loss_sum, agree, rows, _ = metrics.read()          # the epoch's one device-to-host copy
                 metrics.reset()
@@ -3042,7 +3294,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                                 val_log if rank == 0 and local_rank == 0 else None, val_best,
                                 verbose=rank == 0 and local_rank == 0, recon=reg,
                                 transform_out="tokens" if dcoll is not None or not reg else "image")
-            if scheduler is not None:
+            if scheduler is not None and not per_step:
                 scheduler.step()                                                                           # cls:108-109
             if st is not None and snapshot_path is not None and i + 1 >= n_batches:     # the epoch ran to its end
                 st.save_async(snapshot_path, {"epoch": epoch + 1, "batch": 0, "step": n_steps})

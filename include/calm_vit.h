@@ -517,7 +517,8 @@ typedef struct calm_optim_tensor {
     const float* sn_sigma;    /* [1] */
     int64_t numel;
     int32_t rows, cols;       /* rows*cols == numel for deferred spectral-norm weights */
-    int32_t chunk0, reserved;
+    int32_t chunk0;
+    int32_t group;            /* parameter group, read by calm_optim_step_groups only (0 from a zeroed table) */
 } calm_optim_tensor;
 
 typedef struct calm_optim_hparams {
@@ -532,6 +533,30 @@ int calm_optim_step(const calm_optim_tensor* tensors_dev, int32_t n_tensors, con
                     const float* lr_dev /* ABI v7: device scalar overriding hparams->lr, or NULL — lets a captured
                                            (hipGraph) step follow an LR schedule without re-capture */,
                     void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * calm_optim_step with parameter groups (addition to ABI v7): tensor t is updated with the learning rate and the weight
+ * decay of groups_dev[tensors_dev[t].group]; hparams->lr and hparams->weight_decay are ignored, beta1, beta2, eps,
+ * max_norm and step / step_dev mean what they mean to calm_optim_step.  Passes 1 and 2 are calm_optim_step's own
+ * kernels on the same scratch layout: the norm, the clip coefficient, found_inf and the step counter are taken over ALL
+ * tensors of the table, whatever their group (clip_grad_norm_(model.parameters()) and torch's fused AdamW with several
+ * param groups).  Pass 3 reads its group once per workgroup and then performs calm_optim_step's fp32 operations in
+ * calm_optim_step's order: equal (lr, weight_decay) give equal bits.  An lr of 0 freezes a group's parameters while
+ * its moments keep moving.
+ * groups_dev: n_groups records in DEVICE memory, always — there is no lr_dev: a captured (hipGraph) step follows a
+ * schedule of every group by the host rewriting this table between replays.
+ * The entry point cannot see the device tables: the caller guarantees 0 <= group < n_groups for every tensor and
+ * lr >= 0 for every group (backend.OptimPlan checks both on the host).
+ * Three launches, no atomics, a fixed result per element; does not allocate or synchronise; captures into a hipGraph.
+ * CALM_E_INVAL, before any launch: everything calm_optim_step refuses (hparams->lr aside), a null groups_dev,
+ * n_groups <= 0.
+ * ------------------------------------------------------------------------------------- */
+typedef struct calm_optim_group { float lr, weight_decay; } calm_optim_group;   /* 8 bytes */
+int calm_optim_step_groups(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev,
+                           int32_t n_chunks, float* scratch, const calm_optim_hparams* hparams,
+                           const calm_optim_group* groups_dev, int32_t n_groups,
+                           const float* grad_scale /* device scalar or NULL */, float* stats_out, int32_t* step_dev,
+                           void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Gradient accumulation over micro-batches (addition to ABI v7), between a backward and calm_optim_step:
