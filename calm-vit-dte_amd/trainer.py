@@ -792,12 +792,7 @@ class DistillTrainStep(TrainStep):
     def __init__(self, model, optimizer, teacher, reducer=None, alpha=0.5, temperature=1.0, mode="soft", teacher_graph=False,
                  distill_metrics=None, **kw):
         super().__init__(model, optimizer, reducer, **kw)
-        if mode not in ("soft", "hard"):
-            raise ValueError(f'DistillTrainStep: mode is "soft" or "hard", got {mode!r}')
-        if not 0.0 <= float(alpha) <= 1.0:
-            raise ValueError(f"DistillTrainStep: alpha lies in [0, 1], got {alpha!r}")
-        if not (float(temperature) > 0.0 and math.isfinite(float(temperature))):
-            raise ValueError(f"DistillTrainStep: temperature is a positive finite number, got {temperature!r}")
+        _check_distill("DistillTrainStep: %s", mode, alpha, temperature)
         self.alpha, self.temperature, self.mode = float(alpha), float(temperature), mode
         self.distill_metrics = distill_metrics
         self.teacher = teacher if isinstance(teacher, Predictor) else Predictor(teacher, autocast_dtype=self.autocast_dtype)
@@ -823,6 +818,16 @@ class DistillTrainStep(TrainStep):
     def _loss(self, y_hat, y_soft):
         return distillation_loss(y_hat.squeeze(), self._teacher_logits.squeeze(), y_soft, self.alpha, self.temperature,
                                  self.mode, self.metrics, self.distill_metrics)
+
+
+def _check_distill(label, mode, alpha, temperature):
+    """The refusals DistillTrainStep and train() share; `label % name` is how the caller names a hyper-parameter."""
+    if mode not in ("soft", "hard"):
+        raise ValueError(f'{label % "mode"} is "soft" or "hard", got {mode!r}')
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"{label % 'alpha'} lies in [0, 1], got {alpha!r}")
+    if not (float(temperature) > 0.0 and math.isfinite(float(temperature))):
+        raise ValueError(f"{label % 'temperature'} is a positive finite number, got {temperature!r}")
 
 
 class AccumDistillTrainStep(AccumTrainStep, DistillTrainStep):
@@ -2736,37 +2741,90 @@ class SoftMixCollate:
         return self.mix(x, labels, mode, lam, box)
 
 
+def _improves(best, name, value, lower):
+    """The selection rule of the best checkpoints: True, and best[name] = value, when value strictly beats best[name] —
+    lies below it with lower=True, above it otherwise."""
+    if (value < best.get(name, float("inf"))) if lower else (value > best.get(name, -1.0)):
+        best[name] = value
+        return True
+    return False
+
+
 def _val_best_so_far(val_log, key="top1", lower=False):
     """{"top1": best live top-1, "ema_top1": best averaged top-1} from the lines of an existing validation log; with
     key="huber", lower=True the lowest validation Huber of a generative run under "huber" / "ema_huber"."""
     import json
     best = {}
-    if lower:
-        if os.path.exists(val_log):
-            with open(val_log) as f:
-                for rec in (json.loads(line) for line in f if line.strip()):
-                    for name, r in ((key, rec), ("ema_" + key, rec.get("ema"))):
-                        if r is not None and key in r and r[key] < best.get(name, float("inf")):
-                            best[name] = r[key]
-        return best
     if os.path.exists(val_log):
         with open(val_log) as f:
-            for line in f:
-                if not line.strip():
-                    continue
-                rec = json.loads(line)
-                for key, rep in (("top1", rec), ("ema_top1", rec.get("ema"))):
-                    if rep is not None and "top1" in rep and rep["top1"] > best.get(key, -1.0):
-                        best[key] = rep["top1"]
+            for rec in (json.loads(line) for line in f if line.strip()):
+                for name, r in ((key, rec), ("ema_" + key, rec.get("ema"))):
+                    if r is not None and key in r:
+                        _improves(best, name, r[key], lower)
     return best
 
 
-def _validate_epoch(model, ema, val_dataset, rank, world, device, batch_size, transform, topk, epoch, n_steps,
-                    checkpoint_path, val_log, best, verbose, recon=False, transform_out="tokens"):
+class _ClsTask:
+    """What train() asks of its job, for the classification job (distillation included: it is this task with another
+    step): the step's own keywords, the text of a log_every line behind "Device: [r, l], ", the keywords of the validation
+    `evaluate`, its printed report and `best` = (report key, lower is better), the rule of the best checkpoints."""
+    name, reg, best = "cls", False, ("top1", False)
+
+    def __init__(self, metrics, topk):
+        self.step_kw, self.topk = {"metrics": metrics}, topk
+        self.eval_kw = dict(report=True, topk=topk)
+
+    def log_text(self, loss, y_hat, y):                    # (one host read of the accuracy: only on log_every batches)
+        correct = (y_hat.reshape(y.shape[0], -1).argmax(1) == y.argmax(1)).sum().item()
+        return f"Loss: {float(loss)}, Accuracy: {100.0 * correct / y.size(0):.4f}%"
+
+    def val_text(self, r):
+        tops = ", ".join(f"top-{k}: {100.0 * r[f'top{k}']:.4f}%" for k in self.topk)
+        return (f"{tops}, Loss: {r['loss']}, Mean per-class accuracy: {100.0 * r['mean_per_class_accuracy']:.4f}%, "
+                f"Samples: {r['n']}")
+
+
+class _RegTask:
+    """_ClsTask's counterpart for task="reg": no step metrics, the loss alone in a log line (reg:100), `ReconMetrics` for a
+    report and the strictly lower validation Huber for the best checkpoints."""
+    name, reg, best = "reg", True, ("huber", True)
+    eval_kw = dict(recon=True)
+
+    def __init__(self, kl_weight):
+        self.step_kw = {"kl_weight": kl_weight}
+
+    def log_text(self, loss, y_hat, y):
+        return f"Loss: {float(loss)}"
+
+    def val_text(self, r):
+        return (f"Huber: {r['huber']}, MAE: {r['mae']}, MSE: {r['mse']}, PSNR: {r['psnr']:.4f} dB, SSIM: {r['ssim']}, "
+                f"Samples: {r['n']}, Non-finite: {r['nonfinite']}")
+
+
+_STEP_CLASSES = {("cls", False): TrainStep, ("cls", True): AccumTrainStep, ("reg", False): RegTrainStep,
+                 ("reg", True): AccumRegTrainStep, ("distill", False): DistillTrainStep, ("distill", True): AccumDistillTrainStep}
+
+
+def _make_step(task, model, optimizer, reducer, accumulate, teacher, distill_kw, **kw):
+    """The step of train(): (the task, or "distill" with a teacher) x (accumulate > 1) picks the class; kw are the
+    keywords every class takes, the task adds its own, a teacher adds distill_kw, a window adds accumulate=."""
+    kw.update(task.step_kw)
+    args = (model, optimizer, reducer)
+    if teacher is not None:
+        args = (model, optimizer, teacher, reducer)
+        kw.update(distill_kw)
+    if accumulate > 1:
+        kw["accumulate"] = accumulate
+    return _STEP_CLASSES["distill" if teacher is not None else task.name, accumulate > 1](*args, **kw)
+
+
+def _validate_epoch(task, model, ema, val_dataset, rank, world, device, batch_size, transform, epoch, n_steps,
+                    checkpoint_path, val_log, best, verbose, transform_out="tokens"):
     """One validation pass of train(): every rank evaluates its shard (live weights, then the averaged ones), the reports
     are all-reduced inside evaluate; the caller's rank 0 passes checkpoint_path / val_log / verbose and does the writing.
-    The RNG states and the training flag are as before when it returns.  recon=True: the generative job — the samples'
-    labels are ignored, the report is ReconMetrics.read() and the best checkpoint follows the strictly lower Huber."""
+    The RNG states and the training flag are as before when it returns.  The task decides what is measured (for "reg" the
+    samples' labels are ignored and the report is ReconMetrics.read()), how it is printed and, with task.best, which
+    report value the best checkpoint follows."""
     import json
     from torch.utils.data import DataLoader
     use_gpu = device.type == "cuda"
@@ -2782,11 +2840,10 @@ def _validate_epoch(model, ema, val_dataset, rank, world, device, batch_size, tr
                 yield batch                                   # (packed, meta, labels): evaluate moves and transforms it
             else:
                 x, labels = batch if isinstance(batch, (tuple, list)) else (batch, None)
-                yield x.to(device, non_blocking=True), None if labels is None or recon else labels.to(device, non_blocking=True)
+                yield x.to(device, non_blocking=True), None if labels is None or task.reg else labels.to(device, non_blocking=True)
     try:
         kw = dict(lean=True, autocast_dtype=torch.bfloat16 if use_gpu else None, transform=transform,
-                  transform_out=transform_out)
-        kw.update(dict(recon=True) if recon else dict(report=True, topk=topk))
+                  transform_out=transform_out, **task.eval_kw)
         rep = evaluate(model, batches(), **kw)
         rep_ema = evaluate(model, batches(), ema=ema, **kw) if ema is not None else None
     finally:
@@ -2800,34 +2857,259 @@ def _validate_epoch(model, ema, val_dataset, rank, world, device, batch_size, tr
         line["ema"] = scalars(rep_ema)
     if verbose:
         for tag, r in (("", rep), (" (EMA)", rep_ema)):
-            if r is not None and recon:
-                print(f"Epoch: {epoch + 1}, Validation{tag}: Huber: {r['huber']}, MAE: {r['mae']}, MSE: {r['mse']}, "
-                      f"PSNR: {r['psnr']:.4f} dB, SSIM: {r['ssim']}, Samples: {r['n']}, Non-finite: {r['nonfinite']}")
-            elif r is not None:
-                tops = ", ".join(f"top-{k}: {100.0 * r[f'top{k}']:.4f}%" for k in topk)
-                print(f"Epoch: {epoch + 1}, Validation{tag}: {tops}, Loss: {r['loss']}, "
-                      f"Mean per-class accuracy: {100.0 * r['mean_per_class_accuracy']:.4f}%, Samples: {r['n']}")
+            if r is not None:
+                print(f"Epoch: {epoch + 1}, Validation{tag}: {task.val_text(r)}")
     if val_log is not None:
         os.makedirs(os.path.dirname(os.path.abspath(val_log)), exist_ok=True)
         with open(val_log, "a") as f:
             f.write(json.dumps(line) + "\n")
     if checkpoint_path:
         stem, ext = os.path.splitext(checkpoint_path)
-        if recon:
-            if rep["huber"] < best.get("huber", float("inf")):
-                best["huber"] = rep["huber"]
-                torch.save(model.state_dict(), stem + "_best" + ext)
-            if rep_ema is not None and rep_ema["huber"] < best.get("ema_huber", float("inf")):
-                best["ema_huber"] = rep_ema["huber"]
-                torch.save(ema.model_state_dict(), stem + "_ema_best" + ext)
-            return line
-        if rep["top1"] > best.get("top1", -1.0):
-            best["top1"] = rep["top1"]
+        key, lower = task.best
+        if _improves(best, key, rep[key], lower):
             torch.save(model.state_dict(), stem + "_best" + ext)
-        if rep_ema is not None and rep_ema["top1"] > best.get("ema_top1", -1.0):
-            best["ema_top1"] = rep_ema["top1"]
+        if rep_ema is not None and _improves(best, "ema_" + key, rep_ema[key], lower):
             torch.save(ema.model_state_dict(), stem + "_ema_best" + ext)
     return line
+
+
+def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_collate, crop, graph, device_metrics,
+                      device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path, snapshot_every,
+                      accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task, teacher, distill,
+                      param_groups, scheduler_step):
+    """Every refusal train() makes from its arguments alone: it touches no device and no process group, so a bad call
+    fails before either exists.  Returns the normalised values the job is assembled from: accumulate (int), ema_kw
+    (None without ema), distill_kw (DistillTrainStep's keywords, {} without a teacher), teacher_mod, resize (the
+    DeviceResize or None), window (the DeviceResizedCrop.window or None), reg, per_step."""
+    from . import backend as _backend
+    from types import SimpleNamespace
+    if scheduler_step not in ("epoch", "step"):
+        raise ValueError(f'train: scheduler_step is "epoch" or "step", got {scheduler_step!r}')
+    if param_groups is not None and not (isinstance(optimizer, str) and optimizer == "fused"):
+        raise ValueError('train: param_groups= needs optimizer="fused"; build the groups into the optimizer you hand in '
+                         "(FusedClipAdamW(groups=) / make_optimizer(groups=))")
+    if task not in ("cls", "reg"):
+        raise ValueError(f'train: task is "cls" or "reg", got {task!r}')
+    reg = task == "reg"
+    if reg and graph:
+        raise ValueError('train: task="reg" excludes graph=True (GraphedTrainStep captures the classification step)')
+    if reg and device_metrics:
+        raise ValueError('train: task="reg" excludes device_metrics=True (StepMetrics belongs to the classification loss)')
+    generates = getattr(initializer, "generate", None)
+    if generates is not None and bool(generates) != reg:
+        raise ValueError(f'train: task="{task}" needs a model built with generate={reg}, got generate={bool(generates)}')
+    distill_kw = {}
+    if distill is not None:
+        if teacher is None:
+            raise ValueError("train: distill= sets the loss against a teacher; it needs teacher=")
+        distill_kw = dict(distill)
+        if not set(distill_kw) <= {"alpha", "temperature", "mode", "graph"}:
+            raise ValueError(f'train: distill takes the keys "alpha", "temperature", "mode", "graph", got {sorted(distill_kw)}')
+    teacher_mod = None
+    if teacher is not None:
+        teacher_mod = teacher.model if isinstance(teacher, Predictor) else teacher
+        if reg:
+            raise ValueError('train: teacher= excludes task="reg" (distillation is the classification job\'s loss)')
+        if graph:
+            raise ValueError("train: teacher= excludes graph=True (the captured step builds its own TrainStep)")
+        if getattr(teacher_mod, "generate", False):
+            raise ValueError("train: teacher= needs a classifier, got a model built with generate=True")
+        distill_kw = {"alpha": float(distill_kw.get("alpha", 0.5)), "temperature": float(distill_kw.get("temperature", 1.0)),
+                      "mode": distill_kw.get("mode", "soft"), "teacher_graph": bool(distill_kw.get("graph", False))}
+        _check_distill('train: distill["%s"]', distill_kw["mode"], distill_kw["alpha"], distill_kw["temperature"])
+    if device_metrics and not (use_gpu and _backend.get_loss_kernels()):
+        raise ValueError("device_metrics=True needs use_gpu=True and the loss kernels switched on "
+                         "(backend.set_loss_kernels(True) or CALM_LOSS_KERNELS=1)")
+    if device_collate and not use_gpu:
+        raise ValueError("device_collate=True needs use_gpu=True (the collate is a HIP kernel)")
+    if device_augment and not device_collate:
+        raise ValueError("device_augment=True needs device_collate=True (the augmentation is part of the collate kernel)")
+    resize = window = None
+    if device_resize is not None:
+        if not device_collate:
+            raise ValueError("device_resize=(oh, ow) needs device_collate=True (the resized uint8 batch feeds the collate kernel)")
+        resize = DeviceResize(device_resize)               # (refuses a size that is not a pair of sides within 1 .. 16384)
+    if resize_window:
+        if device_resize is None or crop is None:
+            raise ValueError("resize_window=True needs device_resize=(oh, ow) and crop=(H, W): it resizes only the crop window")
+        window = DeviceResizedCrop.window(resize.size, crop)    # (refuses a crop that does not fit the resized size)
+    if random_resized_crop is not None:
+        if not isinstance(random_resized_crop, DeviceResizedCrop) or random_resized_crop.kind != "random_resized":
+            raise ValueError("random_resized_crop takes a DeviceResizedCrop.random_resized(...)")
+        if not device_collate:
+            raise ValueError("random_resized_crop needs device_collate=True (the cropped uint8 batch feeds the collate kernel)")
+        if device_resize is not None or crop is not None:
+            raise ValueError("random_resized_crop excludes device_resize and crop: it is the crop and the resize")
+    if graph and not (use_gpu and (optimizer == "fused" or isinstance(optimizer, FusedClipAdamW))):
+        raise ValueError('graph=True needs use_gpu=True and optimizer="fused" (FusedClipAdamW)')
+    if int(accumulate) != accumulate or accumulate < 1:
+        raise ValueError(f"train: accumulate counts micro-batches per optimizer step (>= 1), got {accumulate!r}")
+    accumulate = int(accumulate)
+    if accumulate > 1 and graph:
+        raise ValueError("train: accumulate > 1 excludes graph=True (capturing an accumulation window is not supported)")
+    if accumulate > 1 and isinstance(optimizer, FusedClipAdamW) and not isinstance(optimizer, FusedClipAdamWindow):
+        raise ValueError('train: accumulate > 1 needs optimizer="fused" or a FusedClipAdamWindow, not a FusedClipAdamW')
+    if snapshot_every is not None and (snapshot_path is None or int(snapshot_every) < 1):
+        raise ValueError("snapshot_every counts steps (>= 1) between the snapshots written to snapshot_path")
+    ema_kw = None
+    if ema is not None:
+        ema_kw = dict(ema) if isinstance(ema, dict) else {"decay": float(ema)}
+        if not set(ema_kw) <= {"decay", "warmup"} or not 0.0 <= float(ema_kw.get("decay", 0.9999)) < 1.0:
+            raise ValueError(f'train: ema takes a decay in [0, 1) or a dict with "decay" / "warmup", got {ema!r}')
+    if int(val_every) != val_every or val_every < 1:
+        raise ValueError(f"train: val_every counts epochs between validation passes (>= 1), got {val_every!r}")
+    if val_transform is not None and not use_gpu:
+        raise ValueError("train: val_transform needs use_gpu=True (the validation transform is a HIP kernel)")
+    if val_dataset is not None:
+        if val_batch_size is not None and (int(val_batch_size) != val_batch_size or val_batch_size < 1):
+            raise ValueError(f"train: val_batch_size counts samples (>= 1), got {val_batch_size!r}")
+        if not reg and 1 not in tuple(val_topk):
+            raise ValueError(f"train: val_topk must contain 1 (the best checkpoint follows top-1), got {val_topk!r}")
+        if not reg:
+            EvalMetrics(num_classes, topk=val_topk)         # (refuses a malformed val_topk here, not after the first epoch)
+    return SimpleNamespace(accumulate=accumulate, ema_kw=ema_kw, distill_kw=distill_kw, teacher_mod=teacher_mod, resize=resize,
+                           window=window, reg=reg, per_step=scheduler_step == "step")
+
+
+class _TrainInput:
+    """The input side of train(): owns the DeviceCollate and the DeviceAugment (seeded 2006 + rank) and turns a batch of
+    the DataLoader into (x, y) on the device; y is None for reg.  `collate_fn` is what the DataLoader gets: the caller's
+    own, SoftMixCollate for "mix" under cls, None (default_collate) for "mix" under reg and for a stacked uint8 batch,
+    RaggedU8Collate in front of a resize stage.
+
+    The draw order is the contract (resume= and the bit-for-bit runs rest on it): the decisions come from
+    `DeviceCollate.draw` first and the crop corners second — with a window from `draw_corners` here, otherwise inside
+    the collate call.  Under reg the draw is made all the same and then mapped to decisions that mix nothing (MixUp with
+    lam = 1), so the generators advance as under cls; the collate gets zero labels and its soft labels are dropped."""
+
+    def __init__(self, device_collate, device_augment, resize, window, random_resized_crop, crop, collate_fn, num_classes,
+                 rank, reg, device):
+        self.resize, self.window, self.resized_crop, self.crop = resize, window, random_resized_crop, crop
+        self.reg, self.device = reg, device
+        self.collate = self.augment = None
+        if device_collate:
+            self.collate = DeviceCollate(num_classes=num_classes, seed=2006 + rank)
+            self.augment = DeviceAugment(seed=2006 + rank) if device_augment else None
+            collate_fn = None                               # default_collate: stack uint8 images and labels
+            if resize is not None or random_resized_crop is not None:
+                collate_fn = RaggedU8Collate()              # images of any size: one packed buffer and its table
+        elif collate_fn == "mix":
+            collate_fn = None if reg else SoftMixCollate(num_classes=num_classes, seed=2006 + rank)      # reg:58
+        self.collate_fn = collate_fn
+
+    def generators(self, num_workers):
+        """The numpy generators a snapshot has to hold (TrainState's `generators`)."""
+        gens = {}
+        if self.collate is not None:
+            gens["collate"] = self.collate.rng
+            if self.augment is not None:
+                gens["augment"] = self.augment.rng
+            if self.resized_crop is not None:
+                gens["resized_crop"] = self.resized_crop.rng
+        elif isinstance(self.collate_fn, SoftMixCollate) and num_workers == 0:
+            gens["mix"] = self.collate_fn.rng
+        return gens
+
+    def __call__(self, batch):
+        dcoll, device, decisions, crop = self.collate, self.device, None, self.crop
+        if self.window is not None:
+            packed, meta, y = batch
+            decisions = dcoll.draw(len(meta), *self.window.size)       # the order of DeviceCollate.__call__: decisions,
+            corners = dcoll.draw_corners(len(meta), *self.resize.size, *self.window.size)      # then corners
+            x = self.window(packed.to(device, non_blocking=True), meta, corners=corners)    # only the crop window, uint8
+            crop = None                                                # the batch is at the crop size already
+        elif self.resized_crop is not None:
+            packed, meta, y = batch
+            x = self.resized_crop(packed.to(device, non_blocking=True), meta)               # box -> [B,3,H,W] uint8
+        elif self.resize is not None:
+            packed, meta, y = batch
+            x = self.resize(packed.to(device, non_blocking=True), meta)    # packed originals -> [B,3,oh,ow] uint8
+        else:
+            x, y = batch if isinstance(batch, (tuple, list)) else (batch, None)
+            x = x.to(device, non_blocking=True)
+        if self.reg:                                                   # the labels are ignored (reg:74-77)
+            if dcoll is not None:                                      # uint8 batch -> row tokens; the draws as for "cls"
+                if decisions is None:
+                    decisions = dcoll.draw(x.shape[0], *(crop if crop is not None else x.shape[-2:]))
+                x, _ = dcoll(x, torch.zeros(x.shape[0], dtype=torch.int64, device=device),
+                             decisions=(1, 1.0, None, decisions[3]), crop=crop, tokens=True, augment=self.augment)
+            return x, None
+        y = y.to(device, non_blocking=True)
+        if dcoll is not None:                                          # uint8 batch -> row tokens + soft labels
+            x, y = dcoll(x, y.long(), decisions=decisions, crop=crop, tokens=True, augment=self.augment)
+        return x, y
+
+
+def _fused_optimizer(model, param_groups, accumulate, verbose):
+    """train(optimizer="fused"): FusedClipAdamW (FusedClipAdamWindow for an accumulation window) over the model on its
+    device, with the groups of param_groups=; the frozen parameters lose requires_grad here, before the reducer and the EMA
+    are built.  verbose: print one line per group."""
+    group_kw = {}
+    if param_groups is not None:
+        groups, frozen = _build_param_groups(model, param_groups)
+        for p in frozen:                    # before the reducer, the optimizer and the EMA: all three filter on it
+            p.requires_grad_(False)
+        group_kw = {"groups": groups}
+    optimizer = FusedClipAdamWindow(model, **group_kw) if accumulate > 1 else FusedClipAdamW(model, **group_kw)
+    if param_groups is not None and verbose:
+        for k, g in enumerate(optimizer.param_groups):
+            print(f"Parameter group {k}: {len(g['params'])} tensors, {sum(p.numel() for p in g['params'])} elements, "
+                  f"lr {g['lr']}, weight decay {g['weight_decay']}")
+    return optimizer
+
+
+def _capture_step(step, st, model, optimizer, x, y, **kw):
+    """The first batch of train(graph=True): the step captured at its shape (the capture's warm-up steps are undone).
+    With snapshots, the eager step's growth count moves into the captured one, which keeps its own, and the TrainState
+    follows the captured step from here on."""
+    gstep = GraphedTrainStep(model, optimizer, x, y, max_norm=1.0, autocast_dtype=torch.bfloat16, restore_after_warmup=True,
+                             **kw)
+    if st is not None:
+        if step._clean_steps is not None:                   # (then the captured step, built alike, has one too)
+            gstep.inner._clean_steps.copy_(step._clean_steps)
+        st.bind_step(gstep)
+    return gstep
+
+
+def _end_epoch(epoch, i, n_batches, n_steps, y_hat, *, task, model, step, accumulate, scheduler, per_step, ema, metrics,
+               dmetrics, who, checkpoint_path, samples_dir, validate, st, snapshot_path):
+    """What train() does between the last batch of an epoch and the next epoch, in this order: the incomplete
+    accumulation window stepped, the StepMetrics and DistillMetrics lines, the checkpoint (and the EMA's), the samples,
+    validation, the per-epoch scheduler step, the epoch-end snapshot.  i: the index of the last batch run (skip - 1 when
+    there was none), who: (rank, local_rank, main), validate: (epoch, n_steps) -> None when this epoch is validated.
+    Returns n_steps."""
+    rank, local_rank, main = who
+    if accumulate > 1 and step.flush():     # the epoch's last, incomplete window: stepped before the checkpoint
+        n_steps += 1
+        if per_step and scheduler is not None:
+            scheduler.step()
+    if metrics is not None:
+        loss_sum, agree, rows, _ = metrics.read()          # the epoch's one device-to-host copy
+        metrics.reset()
+        if main:
+            print(f"Epoch: {epoch + 1}, Device: [{rank}, {local_rank}], Mean loss: {loss_sum / max(rows, 1)}, "
+                  f"Dominant-class accuracy: {100.0 * agree / max(rows, 1):.4f}%")
+    if dmetrics is not None:
+        ce_sum, d_sum, t_agree, t_rows = dmetrics.read()   # one device-to-host copy per epoch
+        dmetrics.reset()
+        if main and t_rows > 0:
+            print(f"Epoch: {epoch + 1}, Device: [{rank}, {local_rank}], Mean CE: {ce_sum / t_rows}, "
+                  f"Mean distillation term: {d_sum / t_rows}, Teacher agreement: {100.0 * t_agree / t_rows:.4f}%")
+    if main and checkpoint_path:
+        os.makedirs(os.path.dirname(os.path.abspath(checkpoint_path)), exist_ok=True)
+        torch.save(model.state_dict(), checkpoint_path)                                            # cls:105-107
+        if ema is not None:
+            stem, ext = os.path.splitext(checkpoint_path)
+            torch.save(ema.model_state_dict(), stem + "_ema" + ext)
+    if task.reg and samples_dir and main and i >= 0:
+        save_samples(y_hat, samples_dir)                                                           # reg:103
+    if validate is not None:
+        validate(epoch, n_steps)
+    if scheduler is not None and not per_step:
+        scheduler.step()                                                                           # cls:108-109
+    if st is not None and snapshot_path is not None and i + 1 >= n_batches:     # the epoch ran to its end
+        st.save_async(snapshot_path, {"epoch": epoch + 1, "batch": 0, "step": n_steps})
+    return n_steps
 
 
 def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, epochs=15, batch_size=128,
@@ -2986,122 +3268,30 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     called at the epoch end.  A scheduler built here is CosineAnnealingLR(T_max = epochs * optimizer steps per epoch,
     eta_min=1e-6).  A step skipped for inf/NaN gradients still advances the schedule (torch under a GradScaler: the
     host does not know)."""
+    from functools import partial
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
-    if scheduler_step not in ("epoch", "step"):
-        raise ValueError(f'train: scheduler_step is "epoch" or "step", got {scheduler_step!r}')
-    per_step = scheduler_step == "step"
-    if param_groups is not None and not (isinstance(optimizer, str) and optimizer == "fused"):
-        raise ValueError('train: param_groups= needs optimizer="fused"; build the groups into the optimizer you hand in '
-                         "(FusedClipAdamW(groups=) / make_optimizer(groups=))")
-    if task not in ("cls", "reg"):
-        raise ValueError(f'train: task is "cls" or "reg", got {task!r}')
-    reg = task == "reg"
-    if reg and graph:
-        raise ValueError('train: task="reg" excludes graph=True (GraphedTrainStep captures the classification step)')
-    if reg and device_metrics:
-        raise ValueError('train: task="reg" excludes device_metrics=True (StepMetrics belongs to the classification loss)')
-    generates = getattr(initializer, "generate", None)
-    if generates is not None and bool(generates) != reg:
-        raise ValueError(f'train: task="{task}" needs a model built with generate={reg}, got generate={bool(generates)}')
-    distill_kw = {}
-    if distill is not None:
-        if teacher is None:
-            raise ValueError("train: distill= sets the loss against a teacher; it needs teacher=")
-        distill_kw = dict(distill)
-        if not set(distill_kw) <= {"alpha", "temperature", "mode", "graph"}:
-            raise ValueError(f'train: distill takes the keys "alpha", "temperature", "mode", "graph", got {sorted(distill_kw)}')
-    teacher_mod = None
-    if teacher is not None:
-        teacher_mod = teacher.model if isinstance(teacher, Predictor) else teacher
-        if reg:
-            raise ValueError('train: teacher= excludes task="reg" (distillation is the classification job\'s loss)')
-        if graph:
-            raise ValueError("train: teacher= excludes graph=True (the captured step builds its own TrainStep)")
-        if getattr(teacher_mod, "generate", False):
-            raise ValueError("train: teacher= needs a classifier, got a model built with generate=True")
-        distill_kw = {"alpha": float(distill_kw.get("alpha", 0.5)), "temperature": float(distill_kw.get("temperature", 1.0)),
-                      "mode": distill_kw.get("mode", "soft"), "teacher_graph": bool(distill_kw.get("graph", False))}
-        if distill_kw["mode"] not in ("soft", "hard"):
-            raise ValueError(f'train: distill["mode"] is "soft" or "hard", got {distill_kw["mode"]!r}')
-        if not 0.0 <= distill_kw["alpha"] <= 1.0:
-            raise ValueError(f'train: distill["alpha"] lies in [0, 1], got {distill_kw["alpha"]!r}')
-        if not (distill_kw["temperature"] > 0.0 and math.isfinite(distill_kw["temperature"])):
-            raise ValueError(f'train: distill["temperature"] is a positive finite number, got {distill_kw["temperature"]!r}')
-    if device_metrics and not (use_gpu and _backend.get_loss_kernels()):
-        raise ValueError("device_metrics=True needs use_gpu=True and the loss kernels switched on "
-                         "(backend.set_loss_kernels(True) or CALM_LOSS_KERNELS=1)")
-    if device_collate and not use_gpu:                     # (argument errors before any process group exists)
-        raise ValueError("device_collate=True needs use_gpu=True (the collate is a HIP kernel)")
-    if device_augment and not device_collate:
-        raise ValueError("device_augment=True needs device_collate=True (the augmentation is part of the collate kernel)")
-    if device_resize is not None:
-        if not device_collate:
-            raise ValueError("device_resize=(oh, ow) needs device_collate=True (the resized uint8 batch feeds the collate kernel)")
-        dres = DeviceResize(device_resize)                 # (refuses a size that is not a pair of sides within 1 .. 16384)
-    if resize_window:
-        if device_resize is None or crop is None:
-            raise ValueError("resize_window=True needs device_resize=(oh, ow) and crop=(H, W): it resizes only the crop window")
-        dwin = DeviceResizedCrop.window(dres.size, crop)    # (refuses a crop that does not fit the resized size)
-    if random_resized_crop is not None:
-        if not isinstance(random_resized_crop, DeviceResizedCrop) or random_resized_crop.kind != "random_resized":
-            raise ValueError("random_resized_crop takes a DeviceResizedCrop.random_resized(...)")
-        if not device_collate:
-            raise ValueError("random_resized_crop needs device_collate=True (the cropped uint8 batch feeds the collate kernel)")
-        if device_resize is not None or crop is not None:
-            raise ValueError("random_resized_crop excludes device_resize and crop: it is the crop and the resize")
-    if graph and not (use_gpu and (optimizer == "fused" or isinstance(optimizer, FusedClipAdamW))):
-        raise ValueError('graph=True needs use_gpu=True and optimizer="fused" (FusedClipAdamW)')
-    if int(accumulate) != accumulate or accumulate < 1:
-        raise ValueError(f"train: accumulate counts micro-batches per optimizer step (>= 1), got {accumulate!r}")
-    accumulate = int(accumulate)
-    if accumulate > 1 and graph:
-        raise ValueError("train: accumulate > 1 excludes graph=True (capturing an accumulation window is not supported)")
-    if accumulate > 1 and isinstance(optimizer, FusedClipAdamW) and not isinstance(optimizer, FusedClipAdamWindow):
-        raise ValueError('train: accumulate > 1 needs optimizer="fused" or a FusedClipAdamWindow, not a FusedClipAdamW')
-    if snapshot_every is not None and (snapshot_path is None or int(snapshot_every) < 1):
-        raise ValueError("snapshot_every counts steps (>= 1) between the snapshots written to snapshot_path")
-    if ema is not None:
-        ema_kw = dict(ema) if isinstance(ema, dict) else {"decay": float(ema)}
-        if not set(ema_kw) <= {"decay", "warmup"} or not 0.0 <= float(ema_kw.get("decay", 0.9999)) < 1.0:
-            raise ValueError(f'train: ema takes a decay in [0, 1) or a dict with "decay" / "warmup", got {ema!r}')
-    if int(val_every) != val_every or val_every < 1:
-        raise ValueError(f"train: val_every counts epochs between validation passes (>= 1), got {val_every!r}")
-    if val_transform is not None and not use_gpu:
-        raise ValueError("train: val_transform needs use_gpu=True (the validation transform is a HIP kernel)")
-    if val_dataset is not None:
-        if val_batch_size is not None and (int(val_batch_size) != val_batch_size or val_batch_size < 1):
-            raise ValueError(f"train: val_batch_size counts samples (>= 1), got {val_batch_size!r}")
-        if not reg and 1 not in tuple(val_topk):
-            raise ValueError(f"train: val_topk must contain 1 (the best checkpoint follows top-1), got {val_topk!r}")
-        if not reg:
-            EvalMetrics(num_classes, topk=val_topk)         # (refuses a malformed val_topk here, not after the first epoch)
+    args = _check_train_args(initializer, optimizer, use_gpu, num_classes, device_collate, crop, graph, device_metrics,
+                          device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path,
+                          snapshot_every, accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task,
+                          teacher, distill, param_groups, scheduler_step)
+    accumulate, per_step, teacher_mod = args.accumulate, args.per_step, args.teacher_mod
     rank, local_rank, world = init_distributed(use_gpu)
+    main = rank == 0 and local_rank == 0                    # the one process that prints and writes
     if val_dataset is not None and len(val_dataset) < world:
         raise ValueError(f"train: val_dataset holds {len(val_dataset)} samples, fewer than the {world} ranks")
     device = torch.device(f"cuda:{local_rank}" if use_gpu else "cpu")
     if use_gpu:
         torch.cuda.set_device(device)
     if use_gpu and selfcheck:
-        from .backend import get_backend
-        be = get_backend()
+        be = _backend.get_backend()
         if not getattr(be, "_selfcheck_done", False):
             be.selfcheck_bf16_gemm(on_mismatch=selfcheck)
             be._selfcheck_done = True
             torch.cuda.empty_cache()
     model = initializer.to(device)
     if isinstance(optimizer, str) and optimizer == "fused":
-        group_kw = {}
-        if param_groups is not None:
-            groups, frozen = _build_param_groups(model, param_groups)
-            for p in frozen:                # before the reducer, the optimizer and the EMA: all three filter on it
-                p.requires_grad_(False)
-            group_kw = {"groups": groups}
-        optimizer = FusedClipAdamWindow(model, **group_kw) if accumulate > 1 else FusedClipAdamW(model, **group_kw)
-        if param_groups is not None and rank == 0 and local_rank == 0:
-            for k, g in enumerate(optimizer.param_groups):
-                print(f"Parameter group {k}: {len(g['params'])} tensors, {sum(p.numel() for p in g['params'])} elements, "
-                      f"lr {g['lr']}, weight decay {g['weight_decay']}")
+        optimizer = _fused_optimizer(model, param_groups, accumulate, verbose=main)
     if (scheduler is None or scheduler is True) and not per_step:
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=epochs, eta_min=1e-6)      # cls:52
     elif scheduler is False:
@@ -3113,75 +3303,46 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         teacher_mod.to(device).eval()
         sync_module_states(teacher_mod)
         dmetrics = DistillMetrics(device) if _backend.get_loss_kernels() else None
-    ema_obj = ModelEMA(model, **ema_kw) if ema is not None else None
+    ema_obj = ModelEMA(model, **args.ema_kw) if ema is not None else None
     reducer = (HeldGradReducer(model) if accumulate > 1 else BucketedGradReducer(model)) if world > 1 else None
     if world > 1:
         sampler = DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=True, seed=2006)       # cls:56
     else:
         sampler = DistributedSampler(dataset, num_replicas=1, rank=0, shuffle=True, seed=2006)
     sampler.set_epoch(0)
-    dcoll = None
-    no_mix = (lambda d: (1, 1.0, None, d[3])) if reg else (lambda d: d)     # MixUp with lam = 1: nothing is mixed
-    if device_collate:
-        if not use_gpu:
-            raise ValueError("device_collate=True needs use_gpu=True (the collate is a HIP kernel)")
-        dcoll = DeviceCollate(num_classes=num_classes, seed=2006 + rank)
-        daug = DeviceAugment(seed=2006 + rank) if device_augment else None
-        collate_fn = None                                   # default_collate: stack uint8 images and labels
-        if device_resize is not None or random_resized_crop is not None:
-            collate_fn = RaggedU8Collate()                  # images of any size: one packed buffer and its table
-    elif collate_fn == "mix":
-        collate_fn = None if reg else SoftMixCollate(num_classes=num_classes, seed=2006 + rank)      # reg:58
-    loader = DataLoader(dataset, batch_size=batch_size, sampler=sampler, collate_fn=collate_fn, num_workers=num_workers,
-                        pin_memory=use_gpu, persistent_workers=num_workers > 0, drop_last=bool(graph))
+    inp = _TrainInput(device_collate, device_augment, args.resize, args.window, random_resized_crop, crop, collate_fn, num_classes,
+                      rank, args.reg, device)
+    loader_kw = dict(batch_size=batch_size, collate_fn=inp.collate_fn, num_workers=num_workers, pin_memory=use_gpu,
+                     drop_last=bool(graph))
+    loader = DataLoader(dataset, sampler=sampler, persistent_workers=num_workers > 0, **loader_kw)
     if per_step and (scheduler is None or scheduler is True):       # one schedule position per optimizer step
         steps_per_epoch = -(-len(loader) // accumulate)
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=max(epochs * steps_per_epoch, 1), eta_min=1e-6)
     scaler = torch.amp.GradScaler("cuda", enabled=use_gpu)                                                 # cls:64
     metrics = StepMetrics(device) if device_metrics else None
-    step_kw = dict(max_norm=1.0, scaler=scaler if use_gpu else None, autocast_dtype=torch.bfloat16 if use_gpu else None,
-                   metrics=metrics, ema=ema_obj)
-    if reg:
-        del step_kw["metrics"]
-        if accumulate > 1:
-            step = AccumRegTrainStep(model, optimizer, reducer, accumulate=accumulate, kl_weight=kl_weight, **step_kw)
-        else:
-            step = RegTrainStep(model, optimizer, reducer, kl_weight=kl_weight, **step_kw)
-    elif teacher is not None:
-        step_kw.update(distill_kw, distill_metrics=dmetrics)
-        if accumulate > 1:
-            step = AccumDistillTrainStep(model, optimizer, teacher, reducer, accumulate=accumulate, **step_kw)
-        else:
-            step = DistillTrainStep(model, optimizer, teacher, reducer, **step_kw)
-    elif accumulate > 1:
-        step = AccumTrainStep(model, optimizer, reducer, accumulate=accumulate, **step_kw)
-    else:
-        step = TrainStep(model, optimizer, reducer, **step_kw)
+    job = _RegTask(kl_weight) if args.reg else _ClsTask(metrics, val_topk)
+    step = _make_step(job, model, optimizer, reducer, accumulate, teacher, {**args.distill_kw, "distill_metrics": dmetrics},
+                      max_norm=1.0, scaler=scaler if use_gpu else None, autocast_dtype=torch.bfloat16 if use_gpu else None,
+                      ema=ema_obj)
     model.train()
     n_steps = 0
     gstep = None
     st = None
     start_epoch = start_batch = 0
     if snapshot_path is not None or resume is not None:
-        gens = {}
-        if dcoll is not None:
-            gens["collate"] = dcoll.rng
-            if daug is not None:
-                gens["augment"] = daug.rng
-            if random_resized_crop is not None:
-                gens["resized_crop"] = random_resized_crop.rng
-        elif isinstance(collate_fn, SoftMixCollate) and num_workers == 0:
-            gens["mix"] = collate_fn.rng
         st = TrainState(model, optimizer, scaler=scaler if use_gpu else None, scheduler=scheduler, ema=ema_obj, step=step,
-                        metrics=metrics, generators=gens, payload=rank == 0 and local_rank == 0,
+                        metrics=metrics, generators=inp.generators(num_workers), payload=main,
                         sidecar_rank=rank if world > 1 else None)
-    val_log = val_best = None
+    validate = None
     if val_dataset is not None:
         val_log = os.path.splitext(checkpoint_path)[0] + "_val.jsonl" if checkpoint_path else None
-        val_best = (_val_best_so_far(val_log, *(("huber", True) if reg else ()))
-                    if resume is not None and val_log else {})
-        if resume is None and val_log and rank == 0 and local_rank == 0 and os.path.exists(val_log):
+        val_best = _val_best_so_far(val_log, *job.best) if resume is not None and val_log else {}
+        if resume is None and val_log and main and os.path.exists(val_log):
             os.remove(val_log)                              # a new run starts its own log; a resumed one appends
+        validate = partial(_validate_epoch, job, model, ema_obj, val_dataset, rank, world, device,
+                           val_batch_size or batch_size, val_transform, checkpoint_path=checkpoint_path if main else None,
+                           val_log=val_log if main else None, best=val_best, verbose=main,
+                           transform_out="tokens" if device_collate or not args.reg else "image")
     try:
         if resume is not None:
             progress = st.load(resume)
@@ -3193,53 +3354,18 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             skip = start_batch if epoch == start_epoch else 0
             epoch_loader = loader
             if skip:                                # the rest of the epoch the saved run was in: indices dropped, not data
-                epoch_loader = DataLoader(dataset, batch_size=batch_size, sampler=resume_tail(sampler, skip, batch_size),
-                                          collate_fn=collate_fn, num_workers=num_workers, pin_memory=use_gpu,
-                                          drop_last=bool(graph))
+                epoch_loader = DataLoader(dataset, sampler=resume_tail(sampler, skip, batch_size), **loader_kw)
             batches = iter(epoch_loader)
             if skip:
                 st.reapply_rng()                    # (the iterator drew its base seed; the saved run had drawn it before)
             n_batches = skip + len(epoch_loader)
-            i = skip - 1
+            i, y_hat = skip - 1, None
             for i, batch in enumerate(batches, start=skip):
-                decisions, window = None, crop
-                if resize_window:
-                    packed, meta, y = batch
-                    decisions = no_mix(dcoll.draw(len(meta), *dwin.size))  # the order of DeviceCollate.__call__: decisions,
-                    corners = dcoll.draw_corners(len(meta), *dres.size, *dwin.size)    # then corners
-                    x = dwin(packed.to(device, non_blocking=True), meta, corners=corners)   # only the crop window, uint8
-                    window = None                                          # the batch is at the crop size already
-                elif random_resized_crop is not None:
-                    packed, meta, y = batch
-                    x = random_resized_crop(packed.to(device, non_blocking=True), meta)     # box -> [B,3,H,W] uint8
-                elif device_resize is not None:
-                    packed, meta, y = batch
-                    x = dres(packed.to(device, non_blocking=True), meta)   # packed originals -> [B,3,oh,ow] uint8
-                else:
-                    x, y = batch if isinstance(batch, (tuple, list)) else (batch, None)
-                    x = x.to(device, non_blocking=True)
-                if reg:                                                    # the labels are ignored (reg:74-77)
-                    y = None
-                    if dcoll is not None:                                  # uint8 batch -> row tokens; the draws as for "cls"
-                        if decisions is None:
-                            decisions = no_mix(dcoll.draw(x.shape[0], *(window if window is not None else x.shape[-2:])))
-                        x, _ = dcoll(x, torch.zeros(x.shape[0], dtype=torch.int64, device=device), decisions=decisions,
-                                     crop=window, tokens=True, augment=daug)
-                else:
-                    y = y.to(device, non_blocking=True)
-                    if dcoll is not None:                                  # uint8 batch -> row tokens + soft labels
-                        x, y = dcoll(x, y.long(), decisions=decisions, crop=window, tokens=True, augment=daug)
+                x, y = inp(batch)
                 if graph and gstep is None:
-                    gstep = GraphedTrainStep(model, optimizer, x, y, max_norm=1.0, scaler=scaler,
-                                             autocast_dtype=torch.bfloat16, reducer=reducer, restore_after_warmup=True,
-                                             metrics=metrics, ema=ema_obj)
-                    if st is not None:              # the captured step keeps its own growth count: the current one moves in
-                        if step._clean_steps is not None:       # (then the captured step, built alike, has one too)
-                            gstep.inner._clean_steps.copy_(step._clean_steps)
-                        st.bind_step(gstep)
-                if reg:
-                    loss, y_hat = step(x)
-                elif gstep is not None and x.shape == gstep.x.shape and y.shape == gstep.y.shape:
+                    gstep = _capture_step(step, st, model, optimizer, x, y, scaler=scaler, reducer=reducer, metrics=metrics,
+                                          ema=ema_obj)
+                if gstep is not None and x.shape == gstep.x.shape and y.shape == gstep.y.shape:
                     loss, y_hat = gstep(x, y)
                 else:
                     loss, y_hat = step(x, y)
@@ -3255,49 +3381,17 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                     st.poll()
                 if metrics is None:
                     epoch_loss += loss.item()                                                              # cls:97
-                if reg:
-                    if rank == 0 and local_rank == 0 and i % log_every == 0:                               # reg:100
-                        print(f"Epoch: {epoch + 1}, Batch: {i + 1}, Device: [{rank}, {local_rank}], Loss: {float(loss)}")
-                elif rank == 0 and local_rank == 0 and i % log_every == 0:
-                    correct = (y_hat.reshape(y.shape[0], -1).argmax(1) == y.argmax(1)).sum().item()
-                    print(f"Epoch: {epoch + 1}, Batch: {i + 1}, Device: [{rank}, {local_rank}], Loss: {float(loss)}, "
-                          f"Accuracy: {100.0 * correct / y.size(0):.4f}%")
+                if main and i % log_every == 0:                                                    # cls:98-104, reg:100
+                    print(f"Epoch: {epoch + 1}, Batch: {i + 1}, Device: [{rank}, {local_rank}], "
+                          f"{job.log_text(loss, y_hat, y)}")
                 if done:
                     break
-            if accumulate > 1 and step.flush():     # the epoch's last, incomplete window: stepped before the checkpoint
-                n_steps += 1
-                if per_step and scheduler is not None:
-                    scheduler.step()
-            if metrics is not None:
-                loss_sum, agree, rows, _ = metrics.read()          # the epoch's one device-to-host copy
-                metrics.reset()
-                if rank == 0 and local_rank == 0:
-                    print(f"Epoch: {epoch + 1}, Device: [{rank}, {local_rank}], Mean loss: {loss_sum / max(rows, 1)}, "
-                          f"Dominant-class accuracy: {100.0 * agree / max(rows, 1):.4f}%")
-            if dmetrics is not None:
-                ce_sum, d_sum, t_agree, t_rows = dmetrics.read()   # one device-to-host copy per epoch
-                dmetrics.reset()
-                if rank == 0 and local_rank == 0 and t_rows > 0:
-                    print(f"Epoch: {epoch + 1}, Device: [{rank}, {local_rank}], Mean CE: {ce_sum / t_rows}, "
-                          f"Mean distillation term: {d_sum / t_rows}, Teacher agreement: {100.0 * t_agree / t_rows:.4f}%")
-            if rank == 0 and local_rank == 0 and checkpoint_path:
-                os.makedirs(os.path.dirname(os.path.abspath(checkpoint_path)), exist_ok=True)
-                torch.save(model.state_dict(), checkpoint_path)                                            # cls:105-107
-                if ema_obj is not None:
-                    stem, ext = os.path.splitext(checkpoint_path)
-                    torch.save(ema_obj.model_state_dict(), stem + "_ema" + ext)
-            if reg and samples_dir and rank == 0 and local_rank == 0 and i >= 0:
-                save_samples(y_hat, samples_dir)                                                           # reg:103
-            if val_dataset is not None and (epoch + 1) % int(val_every) == 0:
-                _validate_epoch(model, ema_obj, val_dataset, rank, world, device, val_batch_size or batch_size, val_transform,
-                                val_topk, epoch, n_steps, checkpoint_path if rank == 0 and local_rank == 0 else None,
-                                val_log if rank == 0 and local_rank == 0 else None, val_best,
-                                verbose=rank == 0 and local_rank == 0, recon=reg,
-                                transform_out="tokens" if dcoll is not None or not reg else "image")
-            if scheduler is not None and not per_step:
-                scheduler.step()                                                                           # cls:108-109
-            if st is not None and snapshot_path is not None and i + 1 >= n_batches:     # the epoch ran to its end
-                st.save_async(snapshot_path, {"epoch": epoch + 1, "batch": 0, "step": n_steps})
+            validating = validate is not None and (epoch + 1) % int(val_every) == 0
+            n_steps = _end_epoch(epoch, i, n_batches, n_steps, y_hat, task=job, model=model, step=step,
+                                 accumulate=accumulate, scheduler=scheduler, per_step=per_step, ema=ema_obj, metrics=metrics,
+                                 dmetrics=dmetrics, who=(rank, local_rank, main), checkpoint_path=checkpoint_path,
+                                 samples_dir=samples_dir, validate=validate if validating else None, st=st,
+                                 snapshot_path=snapshot_path)
             if max_steps is not None and n_steps >= max_steps:
                 break
     finally:
