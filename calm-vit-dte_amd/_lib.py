@@ -95,6 +95,12 @@ class OptimHparams(C.Structure):
                 ("max_norm", _f32), ("step", _i32)]
 
 
+class GradStat(C.Structure):
+    """struct calm_grad_stat (32 bytes, one per tensor of calm_grad_stats; np.dtype(GradStat) is the numpy record)."""
+    _fields_ = [("grad_sq", _f32), ("grad_absmax", _f32), ("param_sq", _f32), ("param_absmax", _f32), ("dir_sq", _f32),
+                ("nonfinite", _i32), ("bad_calls", _i32), ("first_bad_call", _i32)]
+
+
 class CastEntry(C.Structure):
     """struct calm_cast_entry."""
     _fields_ = [("src", _p), ("dst", _p), ("numel", _i64), ("chunk0", _i32), ("reserved", _i32)]
@@ -205,6 +211,8 @@ SIGNATURES = {
     "calm_optim_step": (_i32, [_p, _i32, _p, _i32, _p, C.POINTER(OptimHparams), _p, _p, _p, _p, _p]),
     "calm_optim_step_groups": (_i32, [_p, _i32, _p, _i32, _p, C.POINTER(OptimHparams), _p, _i32, _p, _p, _p, _p]),
     "calm_grad_accum": (_i32, [_p, _i32, _p, _i32, _p, _p, _i32, _p]),
+    "calm_grad_stats_scratch_floats": (_i64, [_i32, _i32]),
+    "calm_grad_stats": (_i32, [_p, _i32, _p, _i32, C.POINTER(OptimHparams), _p, _p, _p, _p, _p, _p]),
     "calm_ema_chunk_elems": (_i32, []),
     "calm_ema_update": (_i32, [_p, _i32, _p, _i32, _f32, _i32, _p, _p, _p, _p]),
     "calm_ema_swap": (_i32, [_p, _i32, _p, _i32, _p]),

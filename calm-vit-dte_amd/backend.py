@@ -887,6 +887,28 @@ class HipBackend:
                                             acc_ptrs_dev.data_ptr(), _ptr(plan.scratch), int(bool(first)), _stream()),
                    "calm_grad_accum")
 
+    def grad_stats_scratch_floats(self, plan):
+        """calm_grad_stats_scratch_floats for the table of `plan` (host only)."""
+        return int(self.lib.calm_grad_stats_scratch_floats(plan.n, plan.n_chunks))
+
+    def grad_stats(self, plan, grads, hp, grad_scale, out, summary, scratch):
+        """calm_grad_stats over the table of `plan` with this step's gradient pointers, uploaded as for optim_step (the
+        optim_step that follows with the same gradients then uploads nothing).  hp as for optim_step (beta1, beta2, eps
+        are read; the step count is plan.step_dev).  out: uint8 device tensor of plan.n calm_grad_stat records, summary:
+        int32[4], both initialised by the caller (counts 0, firsts -1); scratch: the caller's OWN float32 buffer of
+        grad_stats_scratch_floats(plan) elements — never plan.scratch, which belongs to the step."""
+        if out.numel() != plan.n * C.sizeof(_lib.GradStat) or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError("grad_stats expects one 32-byte calm_grad_stat record per tensor of the plan (uint8)")
+        if summary.numel() != 4 or summary.dtype != torch.int32:
+            raise ValueError("grad_stats expects an int32[4] summary")
+        if scratch.dtype != torch.float32 or scratch.numel() < self.grad_stats_scratch_floats(plan):
+            raise ValueError("grad_stats: scratch smaller than calm_grad_stats_scratch_floats answers")
+        plan.upload(np.asarray([_ptr(g) for g in grads], dtype=np.uint64))
+        h = _lib.OptimHparams(*hp)
+        _lib.check(self.lib.calm_grad_stats(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
+                                            C.byref(h), plan.step_dev.data_ptr(), _ptr(grad_scale, True), out.data_ptr(),
+                                            summary.data_ptr(), _ptr(scratch), _stream()), "calm_grad_stats")
+
     # ---- weight EMA ---------------------------------------------------------------------
     def ema_plan(self, pairs):
         """pairs: [(fp32 parameter, its fp32 average of the same shape)] -> plan for ema_update / ema_swap."""

@@ -1631,7 +1631,12 @@ class FusedClipAdamW(torch.optim.Optimizer):
     `param_groups[g]["lr"]` / `["weight_decay"]` from a device table that is rewritten only when a value changed — so a
     torch scheduler drives every group, also through a captured step.  `params`, `exp_avg`, `exp_avg_sq` keep the order of
     model.parameters() whatever the grouping.  Refused: a group that sets betas or eps, a parameter in two groups, one
-    that is not the model's or has requires_grad=False, a negative lr."""
+    that is not the model's or has requires_grad=False, a negative lr.
+
+    `monitor`: None, or the attached `GradMonitor` (`GradMonitor.attach()`), whose `observe()` every step — eager,
+    windowed or captured — calls on the step's gradients in front of the update."""
+
+    monitor = None
 
     def __init__(self, model, lr=3.1e-3, weight_decay=0.02, betas=(0.9, 0.98), eps=1e-8, max_norm=1.0, defer_sn=True,
                  groups=None):
@@ -1761,11 +1766,17 @@ class FusedClipAdamW(torch.optim.Optimizer):
             grads.append(g)
         return grads
 
+    def _hparams(self):
+        """(lr, beta1, beta2, eps, weight_decay, max_norm, step) as the backend's optimizer-side entry points take them."""
+        return (float(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.max_norm or 0.0, 0)
+
     def _launch(self, plan, grads, divisor, records=None):
         """calm_optim_step (calm_optim_step_groups with more than one param group) over `plan` — whose records are
         `records`, default the deferred plan's — with `grads` divided by `divisor` (a device scalar, or None); every
         `.grad` is released afterwards.  Returns the stats tensor."""
-        hp = (float(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.max_norm or 0.0, 0)
+        hp = self._hparams()
+        if self.monitor is not None:            # a GradMonitor: this step's gradients, in front of the step
+            self.monitor.observe(plan, grads, divisor, self._records if records is None else records)
         if self.grouped:
             if hasattr(self.be, "optim_step_groups"):
                 self.be.optim_step_groups(plan, grads, hp, self.group_hparams(), divisor, self.stats)
@@ -1964,6 +1975,169 @@ class FusedClipAdamWindow(FusedClipAdamW):
         """Release every `.grad` and discard an open window."""
         super().zero_grad(set_to_none)
         self.window = 0
+
+
+def grad_stats_torch(records, step_dev, grads, hp, grad_scale, out, summary):
+    """calm_grad_stats in torch, for a backend without `grad_stats` (CPU parameters), with the header's semantics in fp32:
+    g' = G / grad_scale, for a record with `sn` g' = ((G - <G, W_orig>/sigma u v^T) * (1/sigma)) / grad_scale; grad_sq and
+    grad_absmax over the elements whose g' is finite, param_sq / param_absmax, dir_sq of the Adam direction
+    (1/bc1) m / (sqrt(v) / sqrt(bc2) + eps) at t = step_dev (0 while t < 1), nonfinite = the inf / NaN elements of the RAW
+    gradient, and the sticky fields.  out: numpy record array of `_lib.GradStat` (one per record), summary: numpy
+    int32[4] = calls, bad_calls, first_bad_call, first_bad_tensor; both initialised by the caller (counts 0, firsts -1)."""
+    f32 = lambda x: torch.tensor(float(x), dtype=torch.float32)               # noqa: E731
+    b1, b2, eps = f32(hp[1]), f32(hp[2]), f32(hp[3])
+    inv = 1.0 / f32(float(grad_scale)) if grad_scale is not None else f32(1.0)
+    t = int(step_dev)
+    if t >= 1:
+        inv_bc1 = 1.0 / (1.0 - torch.pow(b1, float(t)))
+        inv_sqrt_bc2 = 1.0 / torch.sqrt(1.0 - torch.pow(b2, float(t)))
+    call, first = int(summary[0]), -1
+    for k, (r, g) in enumerate(zip(records, grads)):
+        g = g.detach().float().reshape(-1)
+        p = r["param"].detach().reshape(-1)
+        bad = int((~torch.isfinite(g)).sum())
+        if r["sn"] is not None:
+            u, v, sigma, rows, cols = r["sn"]
+            G = g.reshape(rows, cols)
+            c = (G * p.reshape(rows, cols)).sum() / sigma
+            g = ((G - (c * u)[:, None] * v[None, :]) * (1.0 / sigma)).reshape(-1)
+        g = g * inv
+        g = g[torch.isfinite(g)]
+        e = out[k]
+        e["grad_sq"], e["grad_absmax"] = float((g * g).sum()), float(g.abs().max()) if g.numel() else 0.0
+        e["param_sq"], e["param_absmax"] = float((p * p).sum()), float(p.abs().max())
+        e["dir_sq"] = 0.0
+        if t >= 1:
+            d = inv_bc1 * (r["exp_avg"].reshape(-1) / (r["exp_avg_sq"].reshape(-1).sqrt() * inv_sqrt_bc2 + eps))
+            e["dir_sq"] = float((d * d).sum())
+        e["nonfinite"] = bad
+        if bad:
+            e["bad_calls"] += 1
+            if e["first_bad_call"] < 0:
+                e["first_bad_call"] = call
+            if first < 0:
+                first = k
+    summary[0] = call + 1
+    if first >= 0:
+        summary[1] += 1
+        if summary[2] < 0:
+            summary[2], summary[3] = call, first
+
+
+class GradMonitor:
+    """Per-tensor statistics of the gradients a FusedClipAdamW / FusedClipAdamWindow steps on, kept on the device.
+
+    `GradMonitor(model, optimizer).attach()` arms it: every optimizer step — the eager one, the step that closes an
+    accumulation window (then on the window's mean gradient) and a captured one — runs calm_grad_stats over the
+    optimizer's own table in front of the update: three launches, no host synchronisation.  The statistics are of the TRUE
+    gradient: corrected for the deferred spectral-norm layers, whose `.grad` between backward and step is not the
+    gradient, and divided by the GradScaler's scale; clipping is not applied.  A step that the optimizer skips for an
+    inf / NaN gradient is counted, with the tensors that held the values.  The trained parameters are those of the run
+    without a monitor, bit for bit: the call writes only its own buffers.
+
+    `read()` is the one host synchronisation (one device-to-host copy) and returns
+      norm       the gradient norm of the last observed step over the finite elements (root of the float64 sum of grad_sq)
+      calls      steps observed since the last reset();  skipped: those with a non-finite gradient
+      first_bad  None, or {"call": 0-based index of the first such step, "tensor": the lowest tensor's name}
+      groups     per param group: lr (the group's current rate), tensors, grad_norm, weight_norm, update_ratio =
+                 lr * sqrt(sum dir_sq / sum param_sq), nonfinite (names of the tensors with a non-finite gradient in the
+                 last observed step)
+      tensors    name -> the calm_grad_stat fields, group, and grad_norm, weight_norm, update_ratio derived likewise
+    dir_sq is the squared norm of the Adam direction of the moments as they were in front of the step — the update of the
+    last applied step divided by its rate, without weight decay; it is 0 until a step has been applied.
+    `reset()` clears the counters.  Under GraphedTrainStep attach before the capture: the kernels are captured with the
+    step, and the counters then count replays (and the warm-up steps, until reset()).  With CPU parameters, or a backend
+    without the entry point, `grad_stats_torch` computes the same report.  Names come from model.named_parameters().
+    The monitor's state is not part of TrainState: a resumed run counts anew."""
+
+    def __init__(self, model, optimizer):
+        import numpy as np
+        from . import _lib
+        if not isinstance(optimizer, FusedClipAdamW):
+            raise ValueError("GradMonitor reads the table of the fused optimizer: it needs a FusedClipAdamW or a "
+                             f"FusedClipAdamWindow, got {type(optimizer).__name__}")
+        names = {id(p): n for n, p in model.named_parameters()}
+        missing = [k for k, p in enumerate(optimizer.params) if id(p) not in names]
+        if missing:
+            raise ValueError(f"GradMonitor: {len(missing)} parameters of the optimizer are not parameters of this model")
+        self.optimizer = optimizer
+        self.names = [names[id(p)] for p in optimizer.params]
+        self.group_of = [int(r.get("group", 0)) for r in optimizer._records]
+        self.n = len(self.names)
+        self.dtype = np.dtype(_lib.GradStat)
+        dev = optimizer.params[0].device
+        self.native = dev.type == "cuda" and hasattr(optimizer.be, "grad_stats")
+        init = np.zeros(self.n, dtype=self.dtype)
+        init["first_bad_call"] = -1
+        self._init = np.concatenate([init.view(np.uint8), np.asarray([0, 0, -1, -1], dtype=np.int32).view(np.uint8)])
+        if self.native:
+            # one buffer, so that read() is one copy: the records, then the summary
+            self._buf = torch.empty(self._init.size, dtype=torch.uint8, device=dev)
+            self._init_dev = torch.from_numpy(self._init.copy()).to(dev)
+            self._out, self._summary = self._buf[:self.n * self.dtype.itemsize], self._buf[self.n * self.dtype.itemsize:].view(torch.int32)
+            self._scratch = torch.empty(optimizer.be.grad_stats_scratch_floats(optimizer._plan), dtype=torch.float32, device=dev)
+        else:
+            self._host = self._init.copy()
+        self.reset()
+
+    def attach(self):
+        """Arm the monitor: the optimizer's steps call observe() from now on.  Returns self."""
+        self.optimizer.monitor = self
+        return self
+
+    def detach(self):
+        if self.optimizer.monitor is self:
+            self.optimizer.monitor = None
+
+    def reset(self):
+        """Clear the statistics and the sticky state: counts 0, firsts -1."""
+        if self.native:
+            self._buf.copy_(self._init_dev)
+        else:
+            self._host[:] = self._init
+
+    def _views(self, host):
+        import numpy as np
+        nb = self.n * self.dtype.itemsize
+        return host[:nb].view(self.dtype), host[nb:].view(np.int32)
+
+    @torch.no_grad()
+    def observe(self, plan, grads, divisor, records):
+        """Called by FusedClipAdamW._launch in front of the step over `plan` (records `records`) with `grads` / `divisor`."""
+        opt = self.optimizer
+        hp = opt._hparams()
+        if self.native:
+            opt.be.grad_stats(plan, grads, hp, divisor, self._out, self._summary, self._scratch)
+        else:
+            out, summary = self._views(self._host)
+            grad_stats_torch(records, plan.step_dev, grads, hp, divisor, out, summary)
+
+    def read(self):
+        import math
+        rec, summary = self._views(self._buf.cpu().numpy() if self.native else self._host.copy())
+        root = lambda x: math.sqrt(x) if x >= 0 else math.nan                 # noqa: E731  (inf stays inf, NaN stays NaN)
+        ratio = lambda lr, d2, p2: lr * root(d2 / p2) if p2 > 0 else 0.0      # noqa: E731
+        rates = [lr for lr, _ in self.optimizer.group_hparams()]
+        tensors = {}
+        groups = [dict(group=g, lr=lr, tensors=0, grad_sq=0.0, param_sq=0.0, dir_sq=0.0, nonfinite=[]) for g, lr in enumerate(rates)]
+        for name, g, r in zip(self.names, self.group_of, rec):
+            t = {k: (int(r[k]) if k in ("nonfinite", "bad_calls", "first_bad_call") else float(r[k])) for k in self.dtype.names}
+            t.update(group=g, grad_norm=root(t["grad_sq"]), weight_norm=root(t["param_sq"]),
+                     update_ratio=ratio(rates[g], t["dir_sq"], t["param_sq"]))
+            tensors[name] = t
+            G = groups[g]
+            G["tensors"] += 1
+            for k in ("grad_sq", "param_sq", "dir_sq"):
+                G[k] += t[k]                                # (float64 sums of the fp32 per-tensor values)
+            if t["nonfinite"] > 0:
+                G["nonfinite"].append(name)
+        for G in groups:
+            g2, p2, d2 = G.pop("grad_sq"), G.pop("param_sq"), G.pop("dir_sq")
+            G.update(grad_norm=root(g2), weight_norm=root(p2), update_ratio=ratio(G["lr"], d2, p2))
+        calls, skipped, first_call, first_tensor = (int(x) for x in summary)
+        return dict(norm=root(sum(t["grad_sq"] for t in tensors.values())), calls=calls, skipped=skipped,
+                    first_bad=None if first_call < 0 else {"call": first_call, "tensor": self.names[first_tensor]},
+                    groups=groups, tensors=tensors)
 
 
 def ema_weight(decay, schedule, n):
@@ -2876,11 +3050,12 @@ def _validate_epoch(task, model, ema, val_dataset, rank, world, device, batch_si
 def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_collate, crop, graph, device_metrics,
                       device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path, snapshot_every,
                       accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task, teacher, distill,
-                      param_groups, scheduler_step):
+                      param_groups, scheduler_step, monitor=None):
     """Every refusal train() makes from its arguments alone: it touches no device and no process group, so a bad call
     fails before either exists.  Returns the normalised values the job is assembled from: accumulate (int), ema_kw
     (None without ema), distill_kw (DistillTrainStep's keywords, {} without a teacher), teacher_mod, resize (the
-    DeviceResize or None), window (the DeviceResizedCrop.window or None), reg, per_step."""
+    DeviceResize or None), window (the DeviceResizedCrop.window or None), reg, per_step, monitor_kw (None without
+    monitor=; "every" None: log_every)."""
     from . import backend as _backend
     from types import SimpleNamespace
     if scheduler_step not in ("epoch", "step"):
@@ -2888,6 +3063,23 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
     if param_groups is not None and not (isinstance(optimizer, str) and optimizer == "fused"):
         raise ValueError('train: param_groups= needs optimizer="fused"; build the groups into the optimizer you hand in '
                          "(FusedClipAdamW(groups=) / make_optimizer(groups=))")
+    monitor_kw = None
+    if monitor is not None and monitor is not False:
+        if not ((isinstance(optimizer, str) and optimizer == "fused") or isinstance(optimizer, FusedClipAdamW)):
+            raise ValueError('train: monitor= needs optimizer="fused" or a FusedClipAdamW (the monitor reads the fused '
+                             "optimizer's table)")
+        if monitor is not True and not isinstance(monitor, dict):
+            raise ValueError(f'train: monitor is None, True or a dict with "every" / "top" / "per_tensor", got {monitor!r}')
+        monitor_kw = {"every": None, "top": 8, "per_tensor": False, **({} if monitor is True else monitor)}
+        if set(monitor_kw) != {"every", "top", "per_tensor"}:
+            raise ValueError(f'train: monitor takes the keys "every", "top", "per_tensor", got {sorted(monitor)}')
+        for key in ("every", "top"):
+            v = monitor_kw[key]
+            if v is not None and (isinstance(v, bool) or int(v) != v or v < (1 if key == "every" else 0)):
+                raise ValueError(f'train: monitor["{key}"] counts {"optimizer steps (>= 1)" if key == "every" else "tensors (>= 0)"}, got {v!r}')
+        if monitor_kw["top"] is None:
+            raise ValueError('train: monitor["top"] counts tensors (>= 0), got None')
+        monitor_kw["per_tensor"] = bool(monitor_kw["per_tensor"])
     if task not in ("cls", "reg"):
         raise ValueError(f'train: task is "cls" or "reg", got {task!r}')
     reg = task == "reg"
@@ -2968,7 +3160,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
         if not reg:
             EvalMetrics(num_classes, topk=val_topk)         # (refuses a malformed val_topk here, not after the first epoch)
     return SimpleNamespace(accumulate=accumulate, ema_kw=ema_kw, distill_kw=distill_kw, teacher_mod=teacher_mod, resize=resize,
-                           window=window, reg=reg, per_step=scheduler_step == "step")
+                           window=window, reg=reg, per_step=scheduler_step == "step", monitor_kw=monitor_kw)
 
 
 class _TrainInput:
@@ -3112,13 +3304,65 @@ def _end_epoch(epoch, i, n_batches, n_steps, y_hat, *, task, model, step, accumu
     return n_steps
 
 
+class _MonitorLog:
+    """Rank 0's side of train(monitor=): one read of the GradMonitor per line, printed and appended to `path` (None:
+    printed only).  A run without resume= starts the file anew."""
+
+    def __init__(self, monitor, path, top, who, fresh=True):
+        self.monitor, self.path, self.top, self.who = monitor, path, int(top), who
+        self.skipped, self.bad = 0, {}
+        if path and fresh and os.path.exists(path):
+            os.remove(path)
+
+    @staticmethod
+    def _json(v):
+        """Strict JSON: a non-finite float becomes null."""
+        if isinstance(v, float):
+            return v if v == v and abs(v) != float("inf") else None
+        if isinstance(v, dict):
+            return {k: _MonitorLog._json(x) for k, x in v.items()}
+        if isinstance(v, (list, tuple)):
+            return [_MonitorLog._json(x) for x in v]
+        return v
+
+    def line(self, epoch, n_steps, per_tensor=False):
+        import json
+        rep = self.monitor.read()
+        tensors = rep["tensors"]
+        key = lambda k: lambda n: tensors[n][k] if tensors[n][k] == tensors[n][k] else float("inf")       # noqa: E731
+        top = lambda k: [{"name": n, k: tensors[n][k]} for n in sorted(tensors, key=key(k), reverse=True)[:self.top]]  # noqa: E731
+        grew = [n for n, t in tensors.items() if t["bad_calls"] > self.bad.get(n, 0)]
+        out = dict(epoch=epoch + 1, step=n_steps, norm=rep["norm"], calls=rep["calls"], skipped=rep["skipped"],
+                   first_bad=rep["first_bad"], groups=rep["groups"], top_grad_norm=top("grad_norm"),
+                   top_update_ratio=top("update_ratio"),
+                   nonfinite=[{"name": n, "bad_calls": tensors[n]["bad_calls"], "first_bad_call": tensors[n]["first_bad_call"]}
+                              for n in grew])
+        if per_tensor:
+            out["tensors"] = tensors
+        if self.path:
+            os.makedirs(os.path.dirname(os.path.abspath(self.path)), exist_ok=True)
+            with open(self.path, "a") as f:
+                f.write(json.dumps(self._json(out), allow_nan=False) + "\n")
+        text = f"Epoch: {epoch + 1}, Step: {n_steps}, Device: [{self.who[0]}, {self.who[1]}], Gradient norm: {rep['norm']:.6g}, " \
+               f"Skipped steps: {rep['skipped']}"
+        worst = out["top_update_ratio"][:1]
+        if worst:
+            text += f", Largest update ratio: {worst[0]['update_ratio']:.3g} ({worst[0]['name']})"
+        if rep["skipped"] > self.skipped:
+            text += f", Non-finite gradient in: {', '.join(grew)}"
+        print(text)
+        self.skipped = rep["skipped"]
+        self.bad = {n: t["bad_calls"] for n, t in tensors.items()}
+        return out
+
+
 def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, epochs=15, batch_size=128,
           checkpoint_path=None, num_classes=1000, num_workers=0, collate_fn="mix", log_every=100, max_steps=None,
           destroy_process_group=True, device_collate=False, crop=None, graph=False, selfcheck="raise",
           device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None,
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
           val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
-          teacher=None, distill=None, param_groups=None, scheduler_step="epoch"):
+          teacher=None, distill=None, param_groups=None, scheduler_step="epoch", monitor=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -3267,14 +3511,28 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     front of that step's snapshot, so a snapshot holds the schedule's position and resume= stays exact; it is then not
     called at the epoch end.  A scheduler built here is CosineAnnealingLR(T_max = epochs * optimizer steps per epoch,
     eta_min=1e-6).  A step skipped for inf/NaN gradients still advances the schedule (torch under a GradScaler: the
-    host does not know)."""
+    host does not know).
+
+    monitor=True | {"every": n, "top": k, "per_tensor": bool} (needs optimizer="fused" or a FusedClipAdamW; unknown keys
+    and every < 1 are refused): a `GradMonitor` is attached to the optimizer, so every optimizer step — eager, windowed
+    (then on the window's mean gradient) or captured — runs calm_grad_stats in front of the update on EVERY rank (the
+    gradients are equal behind the all-reduce, so the ranks stay in step), without a host synchronisation.  Rank 0 reads it
+    every `every` optimizer steps (default: log_every) and at every epoch end, prints one line (gradient norm, skipped
+    steps, the largest update-to-weight ratio; when the skipped count grew, the tensors responsible) and appends one JSON
+    line to `<checkpoint stem>_grad.jsonl` (checkpoint_path=None: printed only): epoch, step, norm, calls, skipped,
+    first_bad, the per-group table, the `top` (default 8) tensors by gradient norm and by update ratio, every tensor with a
+    non-finite gradient since the last line, and at the epoch end, with per_tensor, the whole per-tensor table.  A run
+    without resume= starts the file anew; the counters are not part of a snapshot, so a resumed run counts anew.  With
+    graph=True the counters are cleared behind the capture (its warm-up steps are undone).  The returned model carries the
+    monitor as `model._calm_monitor`.  The run's parameters equal those of the same run without monitor=, bit for bit.
+    Works with accumulate, param_groups, ema, teacher=, task="reg", graph=True and snapshots / resume=."""
     from functools import partial
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
     args = _check_train_args(initializer, optimizer, use_gpu, num_classes, device_collate, crop, graph, device_metrics,
                           device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path,
                           snapshot_every, accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task,
-                          teacher, distill, param_groups, scheduler_step)
+                          teacher, distill, param_groups, scheduler_step, monitor)
     accumulate, per_step, teacher_mod = args.accumulate, args.per_step, args.teacher_mod
     rank, local_rank, world = init_distributed(use_gpu)
     main = rank == 0 and local_rank == 0                    # the one process that prints and writes
@@ -3297,6 +3555,12 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     elif scheduler is False:
         scheduler = None
     sync_module_states(model)
+    mon = mon_log = None
+    if args.monitor_kw is not None:
+        mon = GradMonitor(model, optimizer).attach()        # every rank runs the kernels; rank 0 alone reads
+        mon_every = int(args.monitor_kw["every"] or log_every)
+        mon_log = _MonitorLog(mon, os.path.splitext(checkpoint_path)[0] + "_grad.jsonl" if checkpoint_path else None,
+                              args.monitor_kw["top"], (rank, local_rank), fresh=resume is None) if main else None
     dmetrics = None
     if teacher_mod is not None:
         teacher_home = (next(iter(teacher_mod.parameters())).device, teacher_mod.training)
@@ -3365,6 +3629,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                 if graph and gstep is None:
                     gstep = _capture_step(step, st, model, optimizer, x, y, scaler=scaler, reducer=reducer, metrics=metrics,
                                           ema=ema_obj)
+                    if mon is not None:
+                        mon.reset()                 # the capture's warm-up steps were undone: they are not counted
                 if gstep is not None and x.shape == gstep.x.shape and y.shape == gstep.y.shape:
                     loss, y_hat = gstep(x, y)
                 else:
@@ -3373,6 +3639,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                 n_steps += int(stepped)
                 if stepped and per_step and scheduler is not None:
                     scheduler.step()                # in front of this step's snapshot: it holds the schedule's position
+                if mon_log is not None and stepped and n_steps % mon_every == 0:
+                    mon_log.line(epoch, n_steps)
                 done = stepped and max_steps is not None and n_steps >= max_steps
                 if st is not None:                  # right behind the step, before anything else touches state
                     if stepped and snapshot_path is not None and ((snapshot_every and n_steps % int(snapshot_every) == 0)
@@ -3392,6 +3660,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                                  dmetrics=dmetrics, who=(rank, local_rank, main), checkpoint_path=checkpoint_path,
                                  samples_dir=samples_dir, validate=validate if validating else None, st=st,
                                  snapshot_path=snapshot_path)
+            if mon_log is not None:                 # behind the flushed window: the epoch's last step is in the report
+                mon_log.line(epoch, n_steps, per_tensor=args.monitor_kw["per_tensor"])
             if max_steps is not None and n_steps >= max_steps:
                 break
     finally:
@@ -3412,6 +3682,9 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     if ema_obj is not None:
         ema_obj.rebind()                   # the averages follow the parameters to the CPU
         model._calm_ema = ema_obj
+    if mon is not None:
+        mon.detach()
+        model._calm_monitor = mon
     if destroy_process_group and dist.is_initialized():
         dist.destroy_process_group()
     return model

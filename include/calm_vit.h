@@ -581,6 +581,56 @@ int calm_grad_accum(const calm_optim_tensor* tensors_dev, int32_t n_tensors, con
                     int32_t n_chunks, float* const* acc_dev, float* scratch, int32_t first, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Gradient monitor (addition to ABI v7), in front of calm_optim_step over the same table (tensors_dev / chunk_tensor_dev
+ * exactly as handed to it, gradient pointers of THIS step): one calm_grad_stat per tensor, of the gradient the step is
+ * about to apply before clipping, of the weights and of the Adam direction of the moments as they are now.  All in fp32:
+ *   inv = grad_scale ? 1.0f / grad_scale[0] : 1.0f
+ *   plain tensor:               g' = G[i] * inv
+ *   tensor with sn_sigma != 0:  c = (sum over chunks of <G, W_orig>) / sigma, the per-chunk partials summed in the
+ *                               thread / block order of calm_optim_step's first pass and then in chunk order (the bits
+ *                               calm_optim_step and calm_grad_accum give c);
+ *                               g' = ((G[i] - c * u[r] * v[col]) * (1.0f / sigma)) * inv
+ *   grad_sq, param_sq, dir_sq:  a thread's serial sum over its (at most 64) elements of a chunk, the block sum (six
+ *                               shuffle levels, three adds of the wave sums), then the tensor's chunks in chunk order.
+ *                               g'^2 is summed element by element, never in the expanded |G|^2 - 2 c u^T G v + ... form
+ *   grad_absmax, param_absmax:  exact maxima of the fp32 values
+ *   nonfinite:                  the number of RAW G[i] with !(fabsf(G[i]) <= FLT_MAX).  An element whose g' is not finite is
+ *                               left out of grad_sq and grad_absmax; a spectral-norm tensor with a non-finite G has a
+ *                               non-finite c, so all of its elements are left out (grad_sq = grad_absmax = 0)
+ *   dir_sq:                     t = step_dev ? step_dev[0] : hparams->step.  t < 1: 0, and the moments are not read.
+ *                               Otherwise bc1 = 1.0f - powf(beta1, (float)t), bc2 likewise, and
+ *                               d = (1.0f / bc1) * (m / (sqrtf(v) * (1.0f / sqrtf(bc2)) + eps)):
+ *                               the AdamW update of the last applied step divided by its learning rate, without the
+ *                               weight-decay term.  lr * sqrt(dir_sq / param_sq) is a tensor's update-to-weight ratio.
+ * A chunk whose four operand addresses are 16-byte aligned is read as 16-byte vectors, any other as single words; the
+ * thread that owns an element differs between the two, the summation depth does not.
+ * Sticky fields and summary_dev[4] = {calls, bad_calls, first_bad_call, first_bad_tensor}: the last launch is one
+ * workgroup.  calls += 1; if any tensor has nonfinite > 0, bad_calls += 1 and, the first time, first_bad_call = this
+ * call's 0-based index and first_bad_tensor = the lowest such tensor; each such tensor's own bad_calls / first_bad_call
+ * likewise.  The HOST initialises and resets them: counts 0, firsts -1 (in out_dev and in summary_dev).
+ * Reads param, grad, exp_avg, exp_avg_sq, sn_*; writes out_dev, summary_dev and scratch
+ * (calm_grad_stats_scratch_floats(n_tensors, n_chunks) floats, host-only query) and nothing else.  Three launches, no
+ * atomics, no result depends on the grid; does not allocate or synchronise (capturable).  hparams: beta1, beta2, eps and
+ * step are read.
+ * CALM_E_INVAL, before any launch: a null tensors_dev / chunk_tensor_dev / hparams / out_dev / summary_dev / scratch,
+ * n_tensors <= 0, n_chunks <= 0, a beta outside [0, 1).
+ * ------------------------------------------------------------------------------------- */
+typedef struct calm_grad_stat {      /* 32 bytes, one per tensor of the table */
+    float   grad_sq;        /* sum g'^2 over the elements whose g' is finite                      (this call) */
+    float   grad_absmax;    /* max |g'| over the same elements, 0 if none                         (this call) */
+    float   param_sq;       /* sum p^2                                                            (this call) */
+    float   param_absmax;   /* max |p|                                                            (this call) */
+    float   dir_sq;         /* sum d^2, d = Adam direction of the moments as they are now         (this call) */
+    int32_t nonfinite;      /* elements of the RAW gradient G that are inf / NaN                  (this call) */
+    int32_t bad_calls;      /* calls so far in which nonfinite > 0                                (sticky)    */
+    int32_t first_bad_call; /* 0-based index of the first such call, -1 until then                (sticky)    */
+} calm_grad_stat;
+int64_t calm_grad_stats_scratch_floats(int32_t n_tensors, int32_t n_chunks);
+int calm_grad_stats(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev,
+                    int32_t n_chunks, const calm_optim_hparams* hparams, const int32_t* step_dev, const float* grad_scale,
+                    calm_grad_stat* out_dev, int32_t* summary_dev, float* scratch, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Exponential moving average of ALL parameters (additions to ABI v7), a launch of its own behind calm_optim_step — the
  * weight EMA every ImageNet ViT recipe evaluates and checkpoints with (timm's ModelEmaV2 / torch's AveragedModel):
  *   ema += w * (src - ema),  w = 1 - d,  d = decay (CALM_EMA_CONSTANT) | min(decay, (1 + n) / (10 + n)) (CALM_EMA_WARMUP)
