@@ -141,6 +141,11 @@ class AugSample(C.Structure):
                 ("solarize_thr", _f32), ("blur_sigma", _f32), ("reserved", _f32 * 2)]
 
 
+class EraseBox(C.Structure):
+    """struct calm_erase_box (16 bytes, one per sample of calm_augment_collate_erase): a box in output coordinates."""
+    _fields_ = [("y", _i32), ("x", _i32), ("h", _i32), ("w", _i32)]
+
+
 class ResizeSample(C.Structure):
     """struct calm_resize_sample (16 bytes, one per image of calm_resize_u8)."""
     _fields_ = [("offset", _i64), ("h", _i32), ("w", _i32)]
@@ -222,6 +227,8 @@ SIGNATURES = {
     "calm_collate_mix": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_collate_crop_mix": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
     "calm_augment_collate": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p]),
+    "calm_augment_collate_erase": (_i32, [_p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p, _i32, _p,
+                                          C.c_uint64, C.c_uint64, _p]),
     "calm_resize_coeffs": (_i32, [_i32, _i32, _p, _p, _i32]),
     "calm_resize_u8": (_i32, [_p, _i64, _p, _p, _i32, _i32, _i32, _p]),
     "calm_resized_crop": (_i32, [_p, _i64, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),

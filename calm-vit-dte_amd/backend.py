@@ -777,26 +777,50 @@ class HipBackend:
         Normalize (calm_augment_collate).  img_u8 [B,3,Hs,Ws] uint8; samples: the device array of B calm_aug_sample
         records as a contiguous uint8 CUDA tensor [B,48] (trainer.DeviceAugment.pack: crop corners and flips are in it);
         gray_mean [B] fp32 CUDA, written (the contrast means); out [B,3,H,W] or, tokens=True, [B,H,3W] fp32."""
+        args = self._augment_args("augment_collate", img_u8, samples, gray_mean, out, mode, lam, box, mean, std, tokens)
+        _lib.check(self.lib.calm_augment_collate(*args, _stream()), "calm_augment_collate")
+
+    @staticmethod
+    def _augment_args(who, img_u8, samples, gray_mean, out, mode, lam, box, mean, std, tokens):
+        """The tensor checks and the C arguments, up to std, that calm_augment_collate and calm_augment_collate_erase share."""
         if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or not img_u8.is_contiguous():
-            raise TypeError("augment_collate expects a contiguous uint8 CUDA image batch")
+            raise TypeError(f"{who} expects a contiguous uint8 CUDA image batch")
         B, _, Hs, Ws = img_u8.shape
         if tokens:
             H, W = out.shape[1], out.shape[2] // 3
         else:
             H, W = out.shape[2], out.shape[3]
         if out.shape[0] != B or out.numel() != B * 3 * H * W or not out.is_contiguous():
-            raise TypeError("augment_collate: out must be contiguous [B,3,H,W] or, tokens=True, [B,H,3W]")
+            raise TypeError(f"{who}: out must be contiguous [B,3,H,W] or, tokens=True, [B,H,3W]")
         if (samples.dtype != torch.uint8 or not samples.is_cuda or not samples.is_contiguous()
                 or tuple(samples.shape) != (B, C.sizeof(_lib.AugSample))):
-            raise TypeError("augment_collate: samples must be a contiguous uint8 CUDA tensor [B,48] (calm_aug_sample records)")
+            raise TypeError(f"{who}: samples must be a contiguous uint8 CUDA tensor [B,48] (calm_aug_sample records)")
         if (gray_mean.dtype != torch.float32 or not gray_mean.is_cuda or not gray_mean.is_contiguous()
                 or gray_mean.numel() != B):
-            raise TypeError("augment_collate: gray_mean must be a contiguous fp32 CUDA tensor [B]")
+            raise TypeError(f"{who}: gray_mean must be a contiguous fp32 CUDA tensor [B]")
         cbox = (C.c_int32 * 4)(*box) if box is not None else None
         cm, cs = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-        _lib.check(self.lib.calm_augment_collate(img_u8.data_ptr(), Hs, Ws, samples.data_ptr(), gray_mean.data_ptr(),
-                                                 _ptr(out), B, H, W, int(tokens), mode, float(lam), cbox, cm, cs, _stream()),
-                   "calm_augment_collate")
+        return (img_u8.data_ptr(), Hs, Ws, samples.data_ptr(), gray_mean.data_ptr(), _ptr(out), B, H, W, int(tokens), mode,
+                float(lam), cbox, cm, cs)
+
+    def augment_collate_erase(self, img_u8, samples, gray_mean, out, mode, lam, box, mean, std, boxes, value, key,
+                              tokens=False):
+        """augment_collate with RandomErasing between Normalize and the mix (calm_augment_collate_erase).  boxes: the
+        device array of B calm_erase_box records as a contiguous uint8 CUDA tensor [B,16] (trainer.DeviceErase.pack;
+        output coordinates, h == 0 or w == 0: not erased — the caller has checked them, DeviceErase.check); value: None
+        for per-pixel standard normal noise, or three floats in normalised space; key: (seed, offset), the noise key,
+        integers below 2^64.  The other arguments as augment_collate."""
+        args = self._augment_args("augment_collate_erase", img_u8, samples, gray_mean, out, mode, lam, box, mean, std, tokens)
+        if (boxes.dtype != torch.uint8 or not boxes.is_cuda or not boxes.is_contiguous()
+                or tuple(boxes.shape) != (img_u8.shape[0], C.sizeof(_lib.EraseBox))):
+            raise TypeError("augment_collate_erase: boxes must be a contiguous uint8 CUDA tensor [B,16] (calm_erase_box records)")
+        seed, offset = (int(k) for k in key)
+        if not (0 <= seed < 2 ** 64 and 0 <= offset < 2 ** 64):
+            raise ValueError("augment_collate_erase: key is (seed, offset), two integers in [0, 2^64)")
+        cv = (C.c_float * 3)(*value) if value is not None else None
+        _lib.check(self.lib.calm_augment_collate_erase(*args, boxes.data_ptr(), 0 if value is not None else 1, cv, seed,
+                                                       offset, _stream()),
+                   "calm_augment_collate_erase")
 
     def resize_u8(self, packed, samples, out):
         """PIL's antialiased bilinear Image.resize over a ragged batch, bit for bit (calm_resize_u8).  packed: 1-D uint8

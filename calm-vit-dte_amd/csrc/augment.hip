@@ -8,7 +8,12 @@
 // stands when the sample's contrast operation runs (the operations in front of it applied on the fly), summed in a fixed
 // order.  augment_collate_kernel: one workgroup per 16 x 64 tile of output pixels; the tile and a one-pixel halo go through
 // the pointwise chain once per pixel into LDS, the 3 x 3 blur reads LDS, then Normalize, the mix and the store.
+//
+// calm_augment_collate_erase is the same pass with RandomErasing between Normalize and the mix (the ERASE instantiations of
+// the collate kernel): a sample's box is four integers read with its record, a predicate on the output pixels a thread
+// owns, and the fill is a constant or counter-based noise — no extra LDS, no atomics, nothing addressed through the box.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -160,12 +165,55 @@ __device__ __forceinline__ void blur4(const float* __restrict__ p, int ly, int l
 
 struct AugNorm { float mean[3], inv[3]; };
 
-template <bool TOKENS, bool VEC>
+// RandomErasing (calm_augment_collate_erase): the per-sample boxes, the fill and the noise key.  Without ERASE the kernel
+// reads none of it.
+struct AugErase {
+    const calm_erase_box* boxes;                   // DEVICE [B]
+    int noise;                                     // value_mode: 0 constant, 1 standard normal noise
+    float value[3];
+    PhiloxKey key;
+};
+
+__device__ __forceinline__ bool in_box(const calm_erase_box& e, int y, int x) {
+    return y >= e.y && y < e.y + e.h && x >= e.x && x < e.x + e.w;
+}
+
+// The fill of source sample s at output pixel (y, x), three channels: a function of (key, s, y, x) alone.  Box-Muller on
+// one Philox call (include/calm_vit.h has the definition); the precise logf / sincospif / cospif, no fast intrinsics.
+__device__ __forceinline__ void erase_fill(const AugErase& er, int s, int y, int x, int H, int W, float& f0, float& f1,
+                                           float& f2) {
+    if (!er.noise) {
+        f0 = er.value[0]; f1 = er.value[1]; f2 = er.value[2];
+        return;
+    }
+    const u32x4 w = philox4x32_10(((uint64_t)s * (uint64_t)H + (uint64_t)y) * (uint64_t)W + (uint64_t)x, er.key);
+    const float ulp = 5.9604644775390625e-8f;                            // 2^-24: every product below is exact
+    const float u1 = (float)((w[0] >> 8) + 1u) * ulp, u2 = (float)(w[1] >> 8) * ulp;
+    const float u3 = (float)((w[2] >> 8) + 1u) * ulp, u4 = (float)(w[3] >> 8) * ulp;
+    const float r1 = sqrtf(-2.0f * logf(u1)), r3 = sqrtf(-2.0f * logf(u3));
+    float sn, cs;
+    sincospif(2.0f * u2, &sn, &cs);
+    f0 = r1 * cs; f1 = r1 * sn; f2 = r3 * cospif(2.0f * u4);
+}
+
+// The fills of a thread's four pixels of sample s where its box covers them (Philox runs only there)
+__device__ __forceinline__ void erase_fill4(const AugErase& er, const calm_erase_box& e, int s, int y, int x, int H, int W,
+                                            bool in[4], float f[3][4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        in[k] = in_box(e, y, x + k);
+        f[0][k] = f[1][k] = f[2][k] = 0.0f;
+        if (in[k]) erase_fill(er, s, y, x + k, H, W, f[0][k], f[1][k], f[2][k]);
+    }
+}
+
+template <bool TOKENS, bool VEC, bool ERASE>
 __global__ __launch_bounds__(NT) void augment_collate_kernel(const unsigned char* __restrict__ img, int Hs, int Ws,
                                                              const calm_aug_sample* __restrict__ samples,
                                                              const float* __restrict__ gray_mean,
                                                              float* __restrict__ out, int B, int H, int W, int mode,
-                                                             float lam, int y1, int y2, int x1, int x2, AugNorm nm) {
+                                                             float lam, int y1, int y2, int x1, int x2, AugNorm nm,
+                                                             AugErase er) {
     __shared__ float tile[2][3 * PLANE];
     const int b = blockIdx.z, ty0 = blockIdx.y * TH, tx0 = blockIdx.x * TW;
     const int pb = b == 0 ? B - 1 : b - 1;
@@ -193,6 +241,14 @@ __global__ __launch_bounds__(NT) void augment_collate_kernel(const unsigned char
         const float w1 = expf(-0.5f / (sp.blur_sigma * sp.blur_sigma));
         wc_p = 1.0f / (1.0f + 2.0f * w1); we_p = w1 / (1.0f + 2.0f * w1);
     }
+    // ERASE: each sample's box replaces its normalised pixels by its fill in front of the mix — the own sample's with
+    // the own box, the partner's with the partner's box and the partner's noise
+    bool in_o[4], in_p[4];
+    float fill_o[3][4], fill_p[3][4];
+    if constexpr (ERASE) {
+        erase_fill4(er, er.boxes[b], b, y, x, H, W, in_o, fill_o);
+        if (partner) erase_fill4(er, er.boxes[pb], pb, y, x, H, W, in_p, fill_p);
+    }
     float v[3][4];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -200,12 +256,17 @@ __global__ __launch_bounds__(NT) void augment_collate_kernel(const unsigned char
         blur4(tile[0] + c * PLANE, ly, lx, blur_o, wc_o, we_o, own);
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[c][k] = (own[k] - nm.mean[c]) * nm.inv[c];
+        if constexpr (ERASE) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[c][k] = in_o[k] ? fill_o[c][k] : v[c][k];
+        }
         if (partner) {
             float oth[4];
             blur4(tile[1] + c * PLANE, ly, lx, blur_p, wc_p, we_p, oth);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float o = (oth[k] - nm.mean[c]) * nm.inv[c];
+                float o = (oth[k] - nm.mean[c]) * nm.inv[c];
+                if constexpr (ERASE) o = in_p[k] ? fill_p[c][k] : o;
                 if (mode == 1) v[c][k] = v[c][k] * lam + o * (1.0f - lam);          // MixUp: x.roll(1,0)*(1-lam) + x*lam
                 else if (y >= y1 && y < y2 && x + k >= x1 && x + k < x2) v[c][k] = o;   // CutMix box
             }
@@ -246,13 +307,10 @@ __global__ __launch_bounds__(NT) void augment_collate_kernel(const unsigned char
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int calm_augment_collate(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const calm_aug_sample* samples_dev,
-                         float* gray_mean, float* out, int32_t B, int32_t H, int32_t W, int32_t out_tokens, int32_t mode,
-                         float lam, const int32_t* box, const float* mean, const float* std, void* stream) {
+// Both entry points: the argument checks, the statistics launch and the collate launch; erase: null = ERASE off
+int augment_collate(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const calm_aug_sample* samples_dev, float* gray_mean,
+                    float* out, int32_t B, int32_t H, int32_t W, int32_t out_tokens, int32_t mode, float lam,
+                    const int32_t* box, const float* mean, const float* std, const AugErase* erase, void* stream) {
     if (!img_u8 || !out || !mean || !std || B <= 0 || H <= 0 || W <= 0 || Hs < H || Ws < W || mode < 0 || mode > 2) return CALM_E_INVAL;
     if (!samples_dev || !gray_mean) return CALM_E_INVAL;
     if (mode == 2 && !box) return CALM_E_INVAL;
@@ -264,12 +322,42 @@ int calm_augment_collate(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const ca
     int rc = calm_launch(augment_stats_kernel, B, NT, 0, stream, img_u8, Hs, Ws, samples_dev, gray_mean, H, W);
     if (rc != 0) return rc;
     const bool vec = W % 4 == 0 && aligned16(out);
+    const AugErase er = erase ? *erase : AugErase{};
     return with_bool(out_tokens != 0, [&](auto tokens) {
         return with_bool(vec, [&](auto v) {
-            return calm_launch(augment_collate_kernel<decltype(tokens)::value, decltype(v)::value>, dim3(tiles_x, tiles_y, B), NT,
-                               0, stream, img_u8, Hs, Ws, samples_dev, gray_mean, out, B, H, W, mode, lam, y1, y2, x1, x2, nm);
+            return with_bool(erase != nullptr, [&](auto e) {
+                return calm_launch(augment_collate_kernel<decltype(tokens)::value, decltype(v)::value, decltype(e)::value>,
+                                   dim3(tiles_x, tiles_y, B), NT, 0, stream, img_u8, Hs, Ws, samples_dev, gray_mean, out, B, H,
+                                   W, mode, lam, y1, y2, x1, x2, nm, er);
+            });
         });
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int calm_augment_collate(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const calm_aug_sample* samples_dev,
+                         float* gray_mean, float* out, int32_t B, int32_t H, int32_t W, int32_t out_tokens, int32_t mode,
+                         float lam, const int32_t* box, const float* mean, const float* std, void* stream) {
+    return augment_collate(img_u8, Hs, Ws, samples_dev, gray_mean, out, B, H, W, out_tokens, mode, lam, box, mean, std,
+                           nullptr, stream);
+}
+
+int calm_augment_collate_erase(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const calm_aug_sample* samples_dev,
+                               float* gray_mean, float* out, int32_t B, int32_t H, int32_t W, int32_t out_tokens,
+                               int32_t mode, float lam, const int32_t* box, const float* mean, const float* std,
+                               const calm_erase_box* boxes_dev, int32_t value_mode, const float* value, uint64_t seed,
+                               uint64_t offset, void* stream) {
+    if (!boxes_dev || value_mode < 0 || value_mode > 1 || (value_mode == 0 && !value)) return CALM_E_INVAL;
+    AugErase er{};
+    er.boxes = boxes_dev;
+    er.noise = value_mode;
+    for (int c = 0; c < 3; ++c) er.value[c] = value_mode == 0 ? value[c] : 0.0f;
+    er.key = philox_key(seed, offset);
+    return augment_collate(img_u8, Hs, Ws, samples_dev, gray_mean, out, B, H, W, out_tokens, mode, lam, box, mean, std, &er,
+                           stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 // result.  It is a multiply, not a select: a dropped NaN / inf yields NaN.  y may alias x (each element is read by the
 // thread that writes it, before it writes it).  No LDS, no atomics.
 #include "common.h"
+#include "philox.h"
 
 // The multiply and the add round separately.  hipcc compiles with fp-contract=fast, and __fmul_rn / __fadd_rn are plain
 // operators in the HIP headers — compiled there, they keep the `contract` flag and are fused into one fma all the same —
@@ -34,33 +35,11 @@ inline int grid_for(int64_t work_items, int per_block) {
 }
 bool st_ok(int t) { return t == CALM_ST_F32 || t == CALM_ST_BF16; }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-struct DropKey { uint32_t k0, k1, c2, c3; };        // key words and the upper counter words: the same for every element
+typedef PhiloxKey DropKey;                          // key words and the upper counter words: the same for every element
 
-__device__ __forceinline__ DropKey drop_key(const uint64_t* key) {
-    const uint64_t seed = key[0], offset = key[1];
-    return {(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
-}
-
-// Philox4x32-10 of counter (lo32(group), hi32(group), k.c2, k.c3); each 32 x 32 -> 64-bit product is one v_mad_u64_u32
-__device__ __forceinline__ u32x4 philox4x32_10(uint64_t group, const DropKey& k) {
-    uint32_t c0 = (uint32_t)group, c1 = (uint32_t)(group >> 32), c2 = k.c2, c3 = k.c3;
-    uint32_t k0 = k.k0, k1 = k.k1;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return (u32x4){c0, c1, c2, c3};
-}
+__device__ __forceinline__ DropKey drop_key(const uint64_t* key) { return philox_key(key[0], key[1]); }
 
 __device__ __forceinline__ float drop_one(float x, uint32_t word, uint32_t thr, float scale) {
     return x * (word >= thr ? scale : 0.0f);

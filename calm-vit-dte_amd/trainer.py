@@ -873,7 +873,8 @@ class DeviceCollate:
         import numpy as np
         return np.stack([self.rng.integers(0, Hs - H + 1, B), self.rng.integers(0, Ws - W + 1, B)], axis=1).astype("int32")
 
-    def __call__(self, img_u8, labels, decisions=None, crop=None, tokens=False, augment=None, aug_table=None):
+    def __call__(self, img_u8, labels, decisions=None, crop=None, tokens=False, augment=None, aug_table=None, erase=None,
+                 erase_table=None):
         """crop=(H, W): RandomCrop of every sample to H x W inside the (resized) source, corners drawn uniformly as
         torchvision's RandomCrop.get_params does (cls:130); tokens=True: the batch comes out as the row tokens
         [B, H, 3W] of the first Block (Vi_Tools_CNN_less_V2.py:389-391) — feed it to `model.autoencoder` / a ViT whose
@@ -881,7 +882,14 @@ class DeviceCollate:
         augment: a DeviceAugment — ColorJitter / solarize / grayscale / blur of cls:131-135 run in the same pass
         (calm_augment_collate) with parameters from the augment object's own generator, so the draws made here (mode,
         lam, box, flips, corners) are the ones made without it; aug_table: that per-sample table given instead of drawn
-        (DeviceAugment.draw's format).  None (the default) is the plain collate."""
+        (DeviceAugment.draw's format).  None (the default) is the plain collate.
+        erase: a DeviceErase — RandomErasing behind Normalize and in front of the mix, in the same pass
+        (calm_augment_collate_erase), with boxes and noise key from the erase object's own generator, drawn after
+        everything else, so the draws made here and by `augment` are the ones made without it; erase_table: a
+        (table, (seed, offset)) pair in DeviceErase.draw's format given instead of drawn (`erase` then only supplies the
+        fill; without it the fill is noise).  Erasing lives in the augmenting kernel: without augment / aug_table the call
+        runs it on DeviceAugment.identity(B) with the corners and flips filled in, so the plain-collate user then pays
+        the augment kernel's LDS staging of every tile.  Without either argument nothing changes."""
         from .backend import get_backend
         B, _, Hs, Ws = img_u8.shape
         H, W = crop if crop is not None else (Hs, Ws)
@@ -891,13 +899,23 @@ class DeviceCollate:
             corners_host = self.draw_corners(B, Hs, Ws, H, W)
             corners = torch.from_numpy(corners_host).to(img_u8.device)
         out = torch.empty((B, H, 3 * W) if tokens else (B, 3, H, W), dtype=torch.float32, device=img_u8.device)
-        if augment is not None or aug_table is not None:
-            table = aug_table if aug_table is not None else augment.draw(B)
+        erasing = erase is not None or erase_table is not None
+        if augment is not None or aug_table is not None or erasing:
+            table = aug_table if aug_table is not None else augment.draw(B) if augment is not None else DeviceAugment.identity(B)
             DeviceAugment.check_window(table, H, W)
             samples = DeviceAugment.pack(table, corners_host, flips, device=img_u8.device)
             self.last_gray_mean = torch.empty(B, dtype=torch.float32, device=img_u8.device)
-            get_backend().augment_collate(img_u8, samples, self.last_gray_mean, out, mode, lam, box, self.MEAN, self.STD,
-                                          tokens=tokens)
+            if erasing:
+                boxes, key = erase_table if erase_table is not None else erase.draw(B, H, W)
+                if len(boxes) != B:
+                    raise ValueError(f"DeviceCollate: the erase table holds {len(boxes)} boxes for a batch of {B}")
+                DeviceErase.check(boxes, H, W)
+                get_backend().augment_collate_erase(img_u8, samples, self.last_gray_mean, out, mode, lam, box, self.MEAN,
+                                                    self.STD, DeviceErase.pack(boxes, device=img_u8.device),
+                                                    erase.value if erase is not None else None, key, tokens=tokens)
+            else:
+                get_backend().augment_collate(img_u8, samples, self.last_gray_mean, out, mode, lam, box, self.MEAN,
+                                              self.STD, tokens=tokens)
         elif crop is None and not tokens:
             get_backend().collate_mix(img_u8, flips.to(img_u8.device), out, mode, lam, box, self.MEAN, self.STD)
         else:
@@ -991,6 +1009,95 @@ class DeviceAugment:
         if flips is not None:
             f = np.asarray(flips).astype(bool)
             t["flags"] = (t["flags"] & ~np.uint32(_lib.AUG_FLIP)) | np.where(f, _lib.AUG_FLIP, 0).astype(np.uint32)
+        host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
+        return host.to(device)
+
+
+class DeviceErase:
+    """The per-sample boxes of RandomErasing (Zhong et al.; torchvision.transforms.v2.RandomErasing, timm's "pixel" mode)
+    for the device pass calm_augment_collate_erase: with probability p a sample gets one rectangle of the OUTPUT window
+    — after crop and flip, behind Normalize, in front of CutMix / MixUp — replaced by `value`:
+      "random": per-pixel, per-channel standard normal noise drawn on the device from the batch's (seed, offset) key;
+      a float or three floats: that constant per channel, in normalised space (0.0 is the dataset mean).
+    The box follows torchvision's RandomErasing.get_params, restated (torchvision is not installed in the build image):
+    up to 10 attempts of area = H W U(scale), aspect = exp(U(ln ratio[0], ln ratio[1])), h = round(sqrt(area aspect)),
+    w = round(sqrt(area / aspect)), accepted when 0 < h < H and 0 < w < W, then the corner uniform over the positions that
+    keep the box inside; a sample for which no attempt fits is not erased.  The draws are numpy's, from this object's own
+    generator: bit-parity of the draws with torchvision (torch's generator) is not claimed, and the draws of DeviceCollate
+    and DeviceAugment do not shift when the object is used."""
+
+    def __init__(self, p=0.25, scale=(0.02, 1.0 / 3.0), ratio=(0.3, 3.3), value="random", seed=None):
+        import numpy as np
+        if not 0.0 <= float(p) <= 1.0:
+            raise ValueError(f"DeviceErase: p is a probability, got {p!r}")
+        if not (len(scale) == 2 and 0.0 < scale[0] <= scale[1] <= 1.0):
+            raise ValueError(f"DeviceErase: scale is a range of area shares within (0, 1], got {scale!r}")
+        if not (len(ratio) == 2 and 0.0 < ratio[0] <= ratio[1]):
+            raise ValueError(f"DeviceErase: ratio is a range of positive aspect ratios, got {ratio!r}")
+        if isinstance(value, str):
+            if value != "random":
+                raise ValueError(f'DeviceErase: value is "random", a float or three floats, got {value!r}')
+            self.value = None
+        else:
+            v = tuple(float(c) for c in np.atleast_1d(np.asarray(value, dtype=np.float64)))
+            if len(v) not in (1, 3) or not all(np.isfinite(v)):
+                raise ValueError(f'DeviceErase: value is "random", a float or three floats, got {value!r}')
+            self.value = v * 3 if len(v) == 1 else v
+        self.p, self.scale, self.ratio = float(p), (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1]))
+        self.rng = np.random.default_rng(seed)
+        self.seed = int(self.rng.integers(0, 2 ** 64, dtype=np.uint64))     # the noise key's seed: fixed for the object
+
+    @staticmethod
+    def dtype():
+        """The numpy record of struct calm_erase_box."""
+        import numpy as np
+        from . import _lib
+        return np.dtype(_lib.EraseBox)
+
+    @classmethod
+    def identity(cls, B):
+        """A table of B samples none of which is erased."""
+        import numpy as np
+        return np.zeros(B, dtype=cls.dtype())
+
+    def draw(self, B, H, W):
+        """(table, (seed, offset)): the boxes of one batch (a numpy record array of calm_erase_box) and its noise key —
+        the samples in order, then one 64-bit offset for the batch."""
+        import math
+        import numpy as np
+        rng = self.rng
+        t = self.identity(B)
+        log_ratio = (math.log(self.ratio[0]), math.log(self.ratio[1]))
+        for b in range(B):
+            if not rng.random() < self.p:
+                continue
+            for _ in range(10):
+                area = H * W * rng.uniform(self.scale[0], self.scale[1])
+                aspect = math.exp(rng.uniform(log_ratio[0], log_ratio[1]))
+                h, w = int(round(math.sqrt(area * aspect))), int(round(math.sqrt(area / aspect)))
+                if not (0 < h < H and 0 < w < W):
+                    continue
+                t[b] = (int(rng.integers(0, H - h + 1)), int(rng.integers(0, W - w + 1)), h, w)
+                break
+        offset = int(rng.integers(0, 2 ** 64, dtype=np.uint64))
+        return t, (self.seed, offset)
+
+    @staticmethod
+    def check(table, H, W):
+        """Refuses a table the kernel must not get: a negative field, or a box that leaves the H x W window."""
+        import numpy as np
+        t = np.asarray(table)
+        y, x, h, w = (t[f].astype(np.int64) for f in ("y", "x", "h", "w"))
+        if bool(((y < 0) | (x < 0) | (h < 0) | (w < 0)).any()):
+            raise ValueError("DeviceErase: a box has a negative field")
+        if bool(((y + h > H) | (x + w > W)).any()):
+            raise ValueError(f"DeviceErase: a box leaves the {H} x {W} window")
+
+    @staticmethod
+    def pack(table, device="cuda"):
+        """The device array of calm_erase_box records, [B,16] uint8, in one host-to-device copy."""
+        import numpy as np
+        t = np.array(table, dtype=DeviceErase.dtype(), copy=True)
         host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
         return host.to(device)
 
@@ -3050,12 +3157,13 @@ def _validate_epoch(task, model, ema, val_dataset, rank, world, device, batch_si
 def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_collate, crop, graph, device_metrics,
                       device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path, snapshot_every,
                       accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task, teacher, distill,
-                      param_groups, scheduler_step, monitor=None):
+                      param_groups, scheduler_step, monitor=None, random_erasing=None, label_smoothing=0.0):
     """Every refusal train() makes from its arguments alone: it touches no device and no process group, so a bad call
     fails before either exists.  Returns the normalised values the job is assembled from: accumulate (int), ema_kw
     (None without ema), distill_kw (DistillTrainStep's keywords, {} without a teacher), teacher_mod, resize (the
     DeviceResize or None), window (the DeviceResizedCrop.window or None), reg, per_step, monitor_kw (None without
-    monitor=; "every" None: log_every)."""
+    monitor=; "every" None: log_every), erase (None, a DeviceErase, or the dict of arguments one is built from),
+    label_smoothing (float)."""
     from . import backend as _backend
     from types import SimpleNamespace
     if scheduler_step not in ("epoch", "step"):
@@ -3132,6 +3240,29 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
             raise ValueError("random_resized_crop needs device_collate=True (the cropped uint8 batch feeds the collate kernel)")
         if device_resize is not None or crop is not None:
             raise ValueError("random_resized_crop excludes device_resize and crop: it is the crop and the resize")
+    erase = None
+    if random_erasing is not None and random_erasing is not False:
+        if not device_collate:
+            raise ValueError("random_erasing needs device_collate=True (the erasing is part of the collate kernel)")
+        if reg:
+            raise ValueError('train: random_erasing excludes task="reg" (the row tokens are also the Huber target)')
+        if isinstance(random_erasing, DeviceErase):
+            erase = random_erasing
+        elif isinstance(random_erasing, dict):
+            erase = dict(random_erasing)
+            if not set(erase) <= {"p", "scale", "ratio", "value", "seed"}:
+                raise ValueError(f'train: random_erasing takes the keys "p", "scale", "ratio", "value", "seed", got {sorted(erase)}')
+            DeviceErase(**erase)                            # (refuses malformed ranges here, not at the first batch)
+        elif not isinstance(random_erasing, bool) and isinstance(random_erasing, (int, float)):
+            erase = {"p": float(random_erasing)}
+            DeviceErase(**erase)
+        else:
+            raise ValueError("train: random_erasing is a probability, a dict of DeviceErase's arguments or a DeviceErase, "
+                             f"got {random_erasing!r}")
+    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)) or not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"train: label_smoothing is an epsilon in [0, 1), got {label_smoothing!r}")
+    if label_smoothing > 0.0 and reg:
+        raise ValueError('train: label_smoothing excludes task="reg" (the generative job has no class targets)')
     if graph and not (use_gpu and (optimizer == "fused" or isinstance(optimizer, FusedClipAdamW))):
         raise ValueError('graph=True needs use_gpu=True and optimizer="fused" (FusedClipAdamW)')
     if int(accumulate) != accumulate or accumulate < 1:
@@ -3160,12 +3291,14 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
         if not reg:
             EvalMetrics(num_classes, topk=val_topk)         # (refuses a malformed val_topk here, not after the first epoch)
     return SimpleNamespace(accumulate=accumulate, ema_kw=ema_kw, distill_kw=distill_kw, teacher_mod=teacher_mod, resize=resize,
-                           window=window, reg=reg, per_step=scheduler_step == "step", monitor_kw=monitor_kw)
+                           window=window, reg=reg, per_step=scheduler_step == "step", monitor_kw=monitor_kw, erase=erase,
+                           label_smoothing=float(label_smoothing))
 
 
 class _TrainInput:
-    """The input side of train(): owns the DeviceCollate and the DeviceAugment (seeded 2006 + rank) and turns a batch of
-    the DataLoader into (x, y) on the device; y is None for reg.  `collate_fn` is what the DataLoader gets: the caller's
+    """The input side of train(): owns the DeviceCollate, the DeviceAugment and the DeviceErase (seeded 2006 + rank) and
+    turns a batch of the DataLoader into (x, y) on the device; y is None for reg, and under cls it is smoothed here
+    (label_smoothing) behind whichever collate made it.  `collate_fn` is what the DataLoader gets: the caller's
     own, SoftMixCollate for "mix" under cls, None (default_collate) for "mix" under reg and for a stacked uint8 batch,
     RaggedU8Collate in front of a resize stage.
 
@@ -3175,13 +3308,20 @@ class _TrainInput:
     lam = 1), so the generators advance as under cls; the collate gets zero labels and its soft labels are dropped."""
 
     def __init__(self, device_collate, device_augment, resize, window, random_resized_crop, crop, collate_fn, num_classes,
-                 rank, reg, device):
+                 rank, reg, device, random_erasing=None, label_smoothing=0.0):
         self.resize, self.window, self.resized_crop, self.crop = resize, window, random_resized_crop, crop
         self.reg, self.device = reg, device
-        self.collate = self.augment = None
+        self.num_classes, self.label_smoothing = num_classes, float(label_smoothing)
+        # eps / K as a 0-dim host tensor (it broadcasts against a batch on any device); None: no smoothing, no extra op
+        self._smooth = torch.tensor(self.label_smoothing / num_classes, dtype=torch.float32) if self.label_smoothing > 0.0 else None
+        self.collate = self.augment = self.erase = None
         if device_collate:
             self.collate = DeviceCollate(num_classes=num_classes, seed=2006 + rank)
             self.augment = DeviceAugment(seed=2006 + rank) if device_augment else None
+            if isinstance(random_erasing, DeviceErase):
+                self.erase = random_erasing
+            elif random_erasing is not None:               # a dict of DeviceErase's arguments (_check_train_args made it)
+                self.erase = DeviceErase(**{"seed": 2006 + rank, **random_erasing})
             collate_fn = None                               # default_collate: stack uint8 images and labels
             if resize is not None or random_resized_crop is not None:
                 collate_fn = RaggedU8Collate()              # images of any size: one packed buffer and its table
@@ -3198,6 +3338,8 @@ class _TrainInput:
                 gens["augment"] = self.augment.rng
             if self.resized_crop is not None:
                 gens["resized_crop"] = self.resized_crop.rng
+            if self.erase is not None:
+                gens["erase"] = self.erase.rng
         elif isinstance(self.collate_fn, SoftMixCollate) and num_workers == 0:
             gens["mix"] = self.collate_fn.rng
         return gens
@@ -3228,7 +3370,12 @@ class _TrainInput:
             return x, None
         y = y.to(device, non_blocking=True)
         if dcoll is not None:                                          # uint8 batch -> row tokens + soft labels
-            x, y = dcoll(x, y.long(), decisions=decisions, crop=crop, tokens=True, augment=self.augment)
+            x, y = dcoll(x, y.long(), decisions=decisions, crop=crop, tokens=True, augment=self.augment, erase=self.erase)
+        if self._smooth is not None:                                   # y (1 - eps) + eps / K on the soft targets: one op
+            if not (y.is_floating_point() and y.dim() == 2 and y.shape[1] == self.num_classes):
+                raise ValueError(f"train: label_smoothing acts on soft targets [B, {self.num_classes}], the collate gave "
+                                 f"{y.dtype} {tuple(y.shape)}")
+            y = torch.add(self._smooth, y, alpha=1.0 - self.label_smoothing)
         return x, y
 
 
@@ -3362,7 +3509,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           device_metrics=False, device_augment=False, device_resize=None, resize_window=False, random_resized_crop=None,
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
           val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
-          teacher=None, distill=None, param_groups=None, scheduler_step="epoch", monitor=None):
+          teacher=None, distill=None, param_groups=None, scheduler_step="epoch", monitor=None, random_erasing=None,
+          label_smoothing=0.0):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -3525,14 +3673,29 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     without resume= starts the file anew; the counters are not part of a snapshot, so a resumed run counts anew.  With
     graph=True the counters are cleared behind the capture (its warm-up steps are undone).  The returned model carries the
     monitor as `model._calm_monitor`.  The run's parameters equal those of the same run without monitor=, bit for bit.
-    Works with accumulate, param_groups, ema, teacher=, task="reg", graph=True and snapshots / resume=."""
+    Works with accumulate, param_groups, ema, teacher=, task="reg", graph=True and snapshots / resume=.
+
+    random_erasing (needs device_collate=True; refused under task="reg", whose tokens are also the Huber target) and
+    label_smoothing, the regularisers DeiT-style recipes pair with CutMix / MixUp; both default to off.  random_erasing:
+    a probability p, a dict of `DeviceErase`'s arguments (p, scale, ratio, value, seed) or a `DeviceErase`; built here it is
+    seeded 2006 + rank and owns its generator, so no other draw shifts.  The erasing runs inside the collate kernel
+    (calm_augment_collate_erase) behind Normalize and in front of CutMix / MixUp, each partner erased with its own box and
+    its own noise, on boxes in the coordinates of the batch the model sees — so it is the same with device_augment,
+    device_resize, resize_window and random_resized_crop; without device_augment the collate then runs the augmenting
+    kernel on an identity table.  A teacher sees the erased batch the student sees.  The generator is part of a snapshot
+    ("erase"), so resume= continues bit for bit, and a snapshot written without random_erasing is refused by a run with it
+    (and the other way round).  label_smoothing=eps in [0, 1) (task="cls" only): the soft targets of either collate become
+    y (1 - eps) + eps / num_classes — what torch.nn.CrossEntropyLoss(label_smoothing=eps) does to probability targets —
+    in one op in front of the step; the loss kernels and the distillation CE take them as they take any soft target, the
+    log line's dominant-class accuracy does not move (the argmax is the same), the validation loss is not smoothed, and
+    eps = 0 adds no op."""
     from functools import partial
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
     args = _check_train_args(initializer, optimizer, use_gpu, num_classes, device_collate, crop, graph, device_metrics,
                           device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path,
                           snapshot_every, accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task,
-                          teacher, distill, param_groups, scheduler_step, monitor)
+                          teacher, distill, param_groups, scheduler_step, monitor, random_erasing, label_smoothing)
     accumulate, per_step, teacher_mod = args.accumulate, args.per_step, args.teacher_mod
     rank, local_rank, world = init_distributed(use_gpu)
     main = rank == 0 and local_rank == 0                    # the one process that prints and writes
@@ -3575,7 +3738,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         sampler = DistributedSampler(dataset, num_replicas=1, rank=0, shuffle=True, seed=2006)
     sampler.set_epoch(0)
     inp = _TrainInput(device_collate, device_augment, args.resize, args.window, random_resized_crop, crop, collate_fn, num_classes,
-                      rank, args.reg, device)
+                      rank, args.reg, device, random_erasing=args.erase, label_smoothing=args.label_smoothing)
     loader_kw = dict(batch_size=batch_size, collate_fn=inp.collate_fn, num_workers=num_workers, pin_memory=use_gpu,
                      drop_last=bool(graph))
     loader = DataLoader(dataset, sampler=sampler, persistent_workers=num_workers > 0, **loader_kw)

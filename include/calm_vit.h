@@ -764,6 +764,40 @@ int calm_augment_collate(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const ca
                          const float* std, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * RandomErasing inside the augmenting collate (an addition to ABI v7 — no existing signature or struct changes, so the
+ * version number stays).  calm_augment_collate with one more per-sample step between Normalize and the batch mix:
+ *   e_s(c, y, x) = inside(box_s, y, x) ? fill_s(c, y, x) : normalised_s(c, y, x)
+ * for every source sample s, where normalised_s is what calm_augment_collate computes for s up to and including
+ * Normalize.  The box is in OUTPUT coordinates — rows y .. y + h - 1, columns x .. x + w - 1 of the H x W window, after
+ * crop and flip; h == 0 or w == 0: the sample is not erased.  Erasing comes after the blur: an erased pixel is not
+ * blurred, a pixel beside the box still blurs over the un-erased neighbours.  The mix then runs on e: MixUp is
+ * e_b lam + e_pb (1 - lam), CutMix takes e_pb inside the CutMix box, pb = (b - 1) mod B — the partner is erased with ITS
+ * box and ITS fill.
+ *   value_mode 0: fill_s(c, y, x) = value[c] (host float[3], in normalised space)
+ *   value_mode 1: per-pixel, per-channel standard normal noise (value is not read): with p = (s H + y) W + x,
+ *     (w0, w1, w2, w3) = Philox4x32-10 of the counter (lo32(p), hi32(p), lo32(offset), hi32(offset)) under the key
+ *     (lo32(seed), hi32(seed)) — the generator of calm_dropout —
+ *       u1 = ((w0 >> 8) + 1) 2^-24,  u2 = (w1 >> 8) 2^-24,  u3 = ((w2 >> 8) + 1) 2^-24,  u4 = (w3 >> 8) 2^-24
+ *       channel 0 = sqrt(-2 ln u1) cos(2 pi u2),  channel 1 = sqrt(-2 ln u1) sin(2 pi u2),  channel 2 = sqrt(-2 ln u3) cos(2 pi u4)
+ *     in fp32 with the precise logf / sincospif / cospif; |n| <= sqrt(48 ln 2) = 5.77.  The fill is a function of
+ *     (seed, offset, s, c, y, x) alone: not of the output sample that reads it, the tile, the store path or the layout.
+ * boxes_dev: DEVICE array [B].  A box is only a predicate on output pixels: whatever a record holds, the kernel addresses
+ * nothing outside `out`; it clips and checks nothing (the caller checks: 0 <= y, 0 <= x, y + h <= H, x + w <= W).  With
+ * no box in the table the output and gray_mean equal calm_augment_collate's bit for bit.
+ * CALM_E_INVAL / CALM_E_UNSUPP as calm_augment_collate, and CALM_E_INVAL for a null boxes_dev, a value_mode outside
+ * {0, 1} and a null value in mode 0 — all before any launch.
+ * ------------------------------------------------------------------------------------- */
+typedef struct calm_erase_box {    /* 16 bytes */
+    int32_t y, x, h, w;            /* top-left corner and size in output coordinates; h == 0 || w == 0: not erased */
+} calm_erase_box;
+
+int calm_augment_collate_erase(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const calm_aug_sample* samples_dev,
+                               float* gray_mean /* DEVICE [B], written */, float* out, int32_t B, int32_t H, int32_t W,
+                               int32_t out_tokens, int32_t mode, float lam, const int32_t* box, const float* mean,
+                               const float* std, const calm_erase_box* boxes_dev, int32_t value_mode, const float* value,
+                               uint64_t seed, uint64_t offset, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Device resize over a ragged uint8 batch (an addition to ABI v7 — no existing signature or struct changes, so the
  * version number stays).  The first transform of the reference's list, transforms.Resize((256, 256)) on a PIL image
  * (distributed_trainer_cls.py:129), is Image.resize((ow, oh), BILINEAR): antialiased, a horizontal pass and then a
