@@ -199,6 +199,7 @@ SIGNATURES = {
     "calm_attention_bwd_front": (_i32, [_p] * 5 + [_i32] * 5 + [_p]),
     "calm_attention_bwd_back": (_i32, [_p] * 9 + [_i32] * 5 + [_p]),
     "calm_attention_bwd_fold_preferred": (_i32, [_i32, _i32, _i32, _i32]),
+    "calm_attention_set_option": (C.c_int, [_i32, _i32]),
     "calm_attention_fwd_lse": (_i32, [_p] * 15 + [_i32] * 5 + [_p]),
     "calm_attention_bwd_lse_scratch_bytes": (_i64, [_i32] * 5),
     "calm_attention_bwd_lse": (_i32, [_p] * 7 + [_i64] + [_p] * 4 + [_i32] * 5 + [_p]),

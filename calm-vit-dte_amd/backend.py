@@ -1085,6 +1085,17 @@ class HipBackend:
                                                     _ptr(dk), _ptr(dv), B, Sq, Skv, H, hd, _stream()),
                    "calm_attention_bwd_back")
 
+    ATTN_OPT_BACK = 0
+    ATTN_BACK_TABLE, ATTN_BACK_STRIPE, ATTN_BACK_RING = 0, 1, 2
+
+    def attn_set_option(self, option, value):
+        """calm_attention_set_option: ATTN_OPT_BACK = how the kernels of attn_bwd_back stage a head's stripe — the
+        per-geometry table (default), the whole stripe, or the slab ring.  Returns the previous value."""
+        prev = self.lib.calm_attention_set_option(int(option), int(value))
+        if prev < 0:
+            raise ValueError(f"calm_attention_set_option({option}, {value}) -> {prev}")
+        return prev
+
     def attn_fwd_lse(self, q, k, v, w1, b1, s1, w2, b2, s2, out, R, hp, hg, Mk, lse, B, Sq, Skv, H, hd):
         _lib.check(self.lib.calm_attention_fwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(w1), _ptr(b1), _ptr(s1), _ptr(w2),
                                                    _ptr(b2), _ptr(s2), _ptr(out), _ptr(R), _ptr(hp), _ptr(hg),

@@ -17,6 +17,8 @@
 // land 16 banks apart (conflict-free); global->LDS staging is register-prefetched one chunk ahead.
 #include "common.h"
 
+#include <atomic>
+
 #ifndef ATT_TR_ROWFAST
 #define ATT_TR_ROWFAST 1   // W1-chunk staging: hidden rows fastest over lanes (16-way LDS write conflict otherwise)
 #endif
@@ -151,6 +153,13 @@ struct AttGeo {
     // folded route: the front kernel stages no stripe, the dQ kernel nothing but the K_h stripe
     static constexpr size_t bwd_front_bytes() { return sizeof(float) * (size_t)V_OFF; }
     static constexpr size_t bwd_dq_bytes(int hd) { return sizeof(float) * (size_t)at(hd).stripe; }
+    // ring form of the two back kernels: the stripe goes through LDS as [SKV][32]-column slabs (two d-tiles, the unit
+    // of the contraction's d loop), two slots — whatever the head dim
+    static constexpr int SLAB_COLS = 32, LDS_SLAB = SLAB_COLS + 4, SLAB = SKV * LDS_SLAB;
+    static_assert(4 * LDS_SLAB % 32 == 16, "slab row stride: the residue rule of the stripe stride LDV");
+    __device__ static float* slab_slot(float* smem, int i) { return smem + (i & 1) * SLAB; }
+    static_assert(sizeof(float) * (size_t)(2 * SLAB) <= LDS_MAX, "the slab ring fits at every head dim");
+    static constexpr size_t bwd_ring_bytes() { return sizeof(float) * (size_t)(2 * SLAB); }
 };
 
 // LEAN (calm_attention_infer): the forward of a model that will run no backward.  R, hp, hg, P and lse are absent — their
@@ -924,6 +933,221 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnBwdP p) 
     }
 }
 
+// =====================================================================================================
+// Ring form of the two back kernels of the folded route.  In the stripe form above a head's whole [S][hd + 4] stripe sits
+// in one LDS buffer that cannot be refilled while the contraction reads it: stage, barrier, contract, barrier — the
+// global loads of every stripe are exposed.  Here the stripe goes through LDS in the unit the contraction's d loop consumes
+// anyway, a slab of 32 columns (two d-tiles; the last slab of an odd DT holds one, with the stripe form's d2 = 0 for the
+// second chain), and the slabs of ALL stripes of the workgroup form one sequence — key side: dO_0, Q_0, dO_1, Q_1, ...;
+// dQ side: K_0, K_1, ... — that runs through two slots.  Step s:
+//   1. request slab s + 1 from global memory into registers (4 or 2 float4 per thread)
+//   2. contract slab s out of slot s & 1
+//   3. write the registers to slot (s + 1) & 1
+//   4. one barrier
+// The slot written in step s was last read in step s - 1, behind that step's barrier, so one barrier per step is enough.
+// Each output element is the same chain of MFMAs over the same operands in the same order as in the stripe form: dq, dk
+// and dv are bit-identical to it.  The register tiles (P / dS / dR) keep their loads and their place in the head.
+// =====================================================================================================
+template <int NTH, class G>
+struct Slab {
+    static constexpr int V_TOTAL = 8 * G::SKV;                 // a slab row is 8 float4: row = f >> 3, cq = f & 7
+    static constexpr int NV = V_TOTAL / NTH;
+    static_assert(V_TOTAL % NTH == 0, "every thread moves the same number of float4: no bounds test on f");
+    f32x4v v[NV];
+    // columns c0 .. c0 + 31 of the [SKV x hd] stripe at src (row stride D).  No branch around a load (the compiler
+    // drains the whole memory queue where loads sit in conditional blocks): a column >= hd requests column 0 of its row
+    // instead, and store() writes the zero
+    __device__ __forceinline__ void load(const float* __restrict__ src, int D, int hd, int c0) {
+#pragma unroll
+        for (int u = 0; u < NV; ++u) {
+            const int f = threadIdx.x + u * NTH;
+            const int row = f >> 3, c = c0 + 4 * (f & 7);
+            v[u] = *reinterpret_cast<const f32x4v*>(src + (long)row * D + (c < hd ? c : 0));
+        }
+    }
+    __device__ __forceinline__ void store(float* slot, int hd, int c0) const {
+#pragma unroll
+        for (int u = 0; u < NV; ++u) {
+            const int f = threadIdx.x + u * NTH;
+            const int row = f >> 3, cq = f & 7;
+            const f32x4v zero = {0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4v*>(slot + row * G::LDS_SLAB + 4 * cq) = c0 + 4 * cq < hd ? v[u] : zero;
+        }
+    }
+};
+
+// out^T[d .. d + 1 tiles, lane] = sum_i slab[i, .] X[i, lane]: the body of the stripe form's d loop on one slab, in two
+// halves — the caller writes the next slab to LDS between them, so that the write waits for the slab's loads alone and
+// not for the output stores behind them in the memory queue
+struct SlabAcc { f32x4v o, o2; };
+template <class G>
+__device__ __forceinline__ SlabAcc slab_contract(const float* slot, const f32x4v (&X)[G::NJ], int d, int DT, int r16, int g) {
+    constexpr int LD = G::LDS_SLAB;
+    f32x4v accO = {0.f, 0.f, 0.f, 0.f}, accO2 = {0.f, 0.f, 0.f, 0.f};
+    const float* col = slot + r16;
+    const int d2 = (d + 1 < DT) ? 16 : 0;
+#pragma unroll
+    for (int t = 0; t < G::NJ; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            accO = MFMA16(col[(16 * t + 4 * g + r) * LD], X[t][r], accO);
+            accO2 = MFMA16(col[(16 * t + 4 * g + r) * LD + d2], X[t][r], accO2);
+        }
+    return {accO, accO2};
+}
+__device__ __forceinline__ void slab_out(const SlabAcc& a, float* out_row, int d, int DT, int hd, int g) {
+    if (16 * d + 4 * g < hd) *reinterpret_cast<f32x4v*>(out_row + 16 * d + 4 * g) = a.o;
+    if (d + 1 < DT && 16 * (d + 1) + 4 * g < hd) *reinterpret_cast<f32x4v*>(out_row + 16 * (d + 1) + 4 * g) = a.o2;
+}
+
+// attn_bwd_kv_kernel<NI, NW, FOLD = true> with the dO_h / Q_h stripes through the slab ring
+template <int NI, int NW>
+__global__ __launch_bounds__(64 * NW) void attn_bwd_kv_ring_kernel(const AttnBwdP p) {
+    constexpr int NTH = 64 * NW;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    typedef AttGeo<NI, NW> G;                                   // the same geometry with the axes swapped
+    static_assert(NI % NW == 0, "Skv = 16 NI keys in whole workgroups: every wave has a key tile");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, g = lane >> 4;
+    const int b = blockIdx.y;
+    const int jk = blockIdx.x * G::TQ + 16 * wave + r16;        // this lane's key
+    const int D = p.H * p.hd;
+    const int hd = p.hd;
+    const int DT = G::at(hd).DT, NS = (DT + 1) >> 1;            // slabs per stripe
+    const float* qb = p.q + (long)b * p.Sq * D;
+    const float* dob = p.dout + (long)b * p.Sq * D;
+
+    // the opaque row index of the stripe form: the 4 NI tile offsets are rebuilt per load, not held across the head loop
+    const unsigned col = jk, skv = p.Skv;
+    auto rows = [&]() -> unsigned {
+        unsigned g4 = 4 * g;
+        asm volatile("" : "+v"(g4));
+        return g4;
+    };
+    auto at = [&](const float* __restrict__ base, int t, int r, unsigned g4) -> float {
+        return base[(16 * t + r + g4) * skv + col];
+    };
+    f32x4v dR[NI];
+    {
+        const float* __restrict__ dRb = p.dR + (long)b * p.Sq * p.Skv;
+        const unsigned g4 = rows();
+#pragma unroll
+        for (int t = 0; t < NI; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dR[t][r] = at(dRb, t, r, g4);
+    }
+
+    Slab<NTH, G> rs;
+    int s = 0;                                                  // step = slab in the workgroup's sequence
+    // the NS slabs of the stripe `cur`; the last step requests the first slab of `nxt`.  The very last step of the
+    // workgroup has no next stripe and is handed `cur` again: one slab goes to the free slot unread, and the loop keeps a
+    // single shape
+    auto walk = [&](f32x4v (&X)[NI], const float* cur, const float* nxt, float* out_row, auto fold) {
+#pragma unroll 1
+        for (int sl = 0; sl < NS; ++sl, ++s) {
+            const bool last = sl + 1 == NS;
+            const int c0 = last ? 0 : 32 * (sl + 1);
+            rs.load(last ? nxt : cur, D, hd, c0);
+            __builtin_amdgcn_sched_barrier(0);                  // the requests leave ahead of the contraction ...
+            if constexpr (decltype(fold)::value) {
+                if (sl == 0) {
+#pragma unroll
+                    for (int t = 0; t < NI; ++t)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) X[t][r] = fmaf(p.scale, X[t][r], dR[t][r]);
+                }
+            }
+            const SlabAcc acc = slab_contract<G>(G::slab_slot(smem, s), X, 2 * sl, DT, r16, g);
+            __builtin_amdgcn_sched_barrier(0);                  // ... and are waited for behind it
+            rs.store(G::slab_slot(smem, s + 1), hd, c0);
+            slab_out(acc, out_row, 2 * sl, DT, hd, g);
+            __syncthreads();
+        }
+    };
+
+    rs.load(dob, D, hd, 0);
+    rs.store(G::slab_slot(smem, 0), hd, 0);
+    __syncthreads();
+#pragma unroll 1
+    for (int h = 0; h < p.H; ++h) {
+        const float* __restrict__ Ph = p.P + ((long)b * p.H + h) * p.Sq * p.Skv;
+        const float* __restrict__ dSh = p.dS + ((long)b * p.H + h) * p.Sq * p.Skv;
+        const long orow = ((long)b * p.Skv + jk) * D + h * hd;
+        f32x4v X[NI];
+        unsigned g4 = rows();
+#pragma unroll
+        for (int t = 0; t < NI; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) X[t][r] = at(Ph, t, r, g4);
+        walk(X, dob + h * hd, qb + h * hd, p.dv + orow, std::false_type{});
+        g4 = rows();
+#pragma unroll
+        for (int t = 0; t < NI; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) X[t][r] = at(dSh, t, r, g4);
+        walk(X, qb + h * hd, h + 1 < p.H ? dob + (h + 1) * hd : qb + h * hd, p.dk + orow, std::true_type{});
+    }
+}
+
+// attn_bwd_dq_kernel<NJ, NW> with the K_h stripes through the slab ring
+template <int NJ, int NW>
+__global__ __launch_bounds__(64 * NW) void attn_bwd_dq_ring_kernel(const AttnBwdP p) {
+    constexpr int NTH = 64 * NW;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    typedef AttGeo<NJ, NW> G;
+    static_assert(NJ % NW == 0, "Sq = 16 NJ queries in whole workgroups: every wave has a query tile");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, g = lane >> 4;
+    const int b = blockIdx.y;
+    const int iq = blockIdx.x * G::TQ + 16 * wave + r16;
+    const int D = p.H * p.hd;
+    const int hd = p.hd;
+    const int DT = G::at(hd).DT, NS = (DT + 1) >> 1;            // slabs per stripe
+    const float* kb = p.k + (long)b * p.Skv * D;
+
+    const float* __restrict__ dRrow = p.dR + ((long)b * p.Sq + iq) * p.Skv + 4 * g;
+    f32x4v accR[NJ];
+#pragma unroll
+    for (int t = 0; t < NJ; ++t) accR[t] = *reinterpret_cast<const f32x4v*>(dRrow + 16 * t);
+
+    Slab<NTH, G> rs;
+    rs.load(kb, D, hd, 0);
+    rs.store(G::slab_slot(smem, 0), hd, 0);
+    __syncthreads();
+    int s = 0;                                                  // step = slab in the workgroup's sequence
+#pragma unroll 1
+    for (int h = 0; h < p.H; ++h) {
+        const long prow = (((long)b * p.H + h) * p.Sq + iq) * p.Skv;
+        const float* __restrict__ dSrow = p.dS + prow + 4 * g;
+        float* qrow = p.dq + ((long)b * p.Sq + iq) * D + h * hd;
+        const float* cur = kb + h * hd;
+        const float* nxt = h + 1 < p.H ? cur + hd : cur;        // the workgroup's last step: one slab to the free slot, unread
+        f32x4v accD[NJ];
+#pragma unroll
+        for (int t = 0; t < NJ; ++t) accD[t] = *reinterpret_cast<const f32x4v*>(dSrow + 16 * t);
+        __builtin_amdgcn_sched_barrier(0);                      // the requests leave before the slab's, not after them
+#pragma unroll 1
+        for (int sl = 0; sl < NS; ++sl, ++s) {
+            const bool last = sl + 1 == NS;
+            const int c0 = last ? 0 : 32 * (sl + 1);
+            rs.load(last ? nxt : cur, D, hd, c0);
+            __builtin_amdgcn_sched_barrier(0);                  // the requests leave ahead of the contraction ...
+            if (sl == 0) {
+#pragma unroll
+                for (int t = 0; t < NJ; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) accD[t][r] = fmaf(p.scale, accD[t][r], accR[t][r]);
+            }
+            // dQ^T[d,i] = sum_j K_h[j,d] (scale dS + dR)^T[j,i]
+            const SlabAcc acc = slab_contract<G>(G::slab_slot(smem, s), accD, 2 * sl, DT, r16, g);
+            __builtin_amdgcn_sched_barrier(0);                  // ... and are waited for behind it
+            rs.store(G::slab_slot(smem, s + 1), hd, c0);
+            slab_out(acc, qrow, 2 * sl, DT, hd, g);
+            __syncthreads();
+        }
+    }
+}
+
 // set the dynamic-LDS limit of a kernel, launch it, check the launch
 template <class P>
 int launch(void (*kernel)(const P), dim3 grid, int threads, size_t lds, hipStream_t s, const P& p) {
@@ -953,13 +1177,34 @@ int launch_bwd_front(const AttnBwdP& p, hipStream_t s) {
     dim3 grid((p.Sq / 16 + NW - 1) / NW, p.B);
     return launch(&attn_bwd_q_kernel<NJ, NW, false, false>, grid, 64 * NW, G::bwd_front_bytes(), s, p);
 }
+// Staging form of the two back kernels (calm_attention_set_option): the table below, or one form forced everywhere.
+std::atomic<int>& back_option() {
+    static std::atomic<int> opt{CALM_ATTN_BACK_TABLE};
+    return opt;
+}
+// The table: ring where it is measured faster than the stripe at that stage (MI355X, B = 256, kernel trace of both forms in
+// one process, us per launch at H = 6; DESIGN.md section 7 "slab ring in the attention backward" has H = 12 as well):
+//   key tiles (S, hd)     KV stripe -> ring     dQ stripe -> ring
+//   14 (224, 112)            656 -> 473            344 -> 242         ring
+//   11 (176, 88)             330 -> 242            172 -> 126         ring
+//    8 (128, 64)             114 ->  88             63 ->  50         ring
+//    5 (80, 40)               59 ->  44             32 ->  25         ring
+//    2, 3 (32, 48)         no stage of a measured model has them: not measured, stripe
+template <int NJ> constexpr bool ring_kv_preferred() { return NJ >= 5; }
+template <int NJ> constexpr bool ring_dq_preferred() { return NJ >= 5; }
+
 template <class G>
 int launch_bwd_back(const AttnBwdP& p, hipStream_t s) {
     constexpr int NJ = G::NJ, NW = G::NW;
     dim3 grid((p.Sq / 16 + NW - 1) / NW, p.B);
-    const int e = launch(&attn_bwd_kv_kernel<NJ, NW, true>, grid, 64 * NW, G::bwd_kv_bytes(p.hd), s, p);
+    const int mode = back_option().load(std::memory_order_relaxed);
+    const bool ring_kv = mode == CALM_ATTN_BACK_TABLE ? ring_kv_preferred<NJ>() : mode == CALM_ATTN_BACK_RING;
+    const bool ring_dq = mode == CALM_ATTN_BACK_TABLE ? ring_dq_preferred<NJ>() : mode == CALM_ATTN_BACK_RING;
+    const int e = ring_kv ? launch(&attn_bwd_kv_ring_kernel<NJ, NW>, grid, 64 * NW, G::bwd_ring_bytes(), s, p)
+                          : launch(&attn_bwd_kv_kernel<NJ, NW, true>, grid, 64 * NW, G::bwd_kv_bytes(p.hd), s, p);
     if (e) return e;
-    return launch(&attn_bwd_dq_kernel<NJ, NW>, grid, 64 * NW, G::bwd_dq_bytes(p.hd), s, p);
+    return ring_dq ? launch(&attn_bwd_dq_ring_kernel<NJ, NW>, grid, 64 * NW, G::bwd_ring_bytes(), s, p)
+                   : launch(&attn_bwd_dq_kernel<NJ, NW>, grid, 64 * NW, G::bwd_dq_bytes(p.hd), s, p);
 }
 
 template <class G, bool LEAN>
@@ -1101,6 +1346,13 @@ int calm_attention_bwd_back(const float* q, const float* k, const float* dout, c
                1.0f / sqrtf((float)hd), nullptr, nullptr, dR};
     hipStream_t s = as_stream(stream);
     return with_geo(Skv / 16, [&](auto g) -> int { return launch_bwd_back<decltype(g)>(p, s); });
+}
+
+// Process-wide switches of the attention launchers, in the style of calm_gemm_set_option: returns the previous value.
+int calm_attention_set_option(int32_t option, int32_t value) {
+    if (option != CALM_ATTN_OPT_BACK) return CALM_E_INVAL;
+    if (value != CALM_ATTN_BACK_TABLE && value != CALM_ATTN_BACK_STRIPE && value != CALM_ATTN_BACK_RING) return CALM_E_INVAL;
+    return back_option().exchange(value);
 }
 
 // Measured on MI355X (scripts/ab_attn_bwd.py, same process, B = 256; ms per attention block, core + the two dR products,

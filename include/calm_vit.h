@@ -331,6 +331,20 @@ int calm_attention_bwd_back(const float* q, const float* k, const float* dout, c
                             int32_t H, int32_t hd, void* stream);
 int calm_attention_bwd_fold_preferred(int32_t Sq, int32_t Skv, int32_t H, int32_t hd);
 
+/* Process-wide switches of the attention launchers, in the style of calm_gemm_set_option (addition to ABI v7 — no
+ * existing signature or struct changes, so the version number stays).  Returns the previous value, CALM_E_INVAL for an
+ * unknown option or value.
+ *   CALM_ATTN_OPT_BACK  how the two kernels of calm_attention_bwd_back bring a head's dO_h / Q_h / K_h stripe into LDS:
+ *       CALM_ATTN_BACK_TABLE  (default) per compiled geometry, whichever form is measured faster on MI355X
+ *       CALM_ATTN_BACK_STRIPE the whole [S][hd] stripe at once: stage, barrier, contract, barrier
+ *       CALM_ATTN_BACK_RING   32-column slabs through a two-slot ring, the next slab requested under the contraction
+ *     Both forms run the same MFMA chains in the same order: dq, dk and dv are bit-identical (tests, same-process A/B). */
+#define CALM_ATTN_OPT_BACK    0
+#define CALM_ATTN_BACK_TABLE  0
+#define CALM_ATTN_BACK_STRIPE 1
+#define CALM_ATTN_BACK_RING   2
+int calm_attention_set_option(int32_t option, int32_t value);
+
 /* Row-LSE mode of the fp32 attention (Vi_Tools:288-299; additions to ABI v7 — no existing signature or struct
  * changes, so the version number stays): train without the saved probabilities.
  *   calm_attention_fwd_lse: calm_attention_fwd with P left out and lse [B,H,Sq] written instead,
