@@ -160,6 +160,18 @@ class RCropSample(C.Structure):
                 ("vh", _i32), ("vw", _i32), ("wy0", _i32), ("wx0", _i32)]
 
 
+RA_MAX_OPS, RA_MAX_SIDE = 4, 4096                                                  # CALM_RA_MAX_OPS, CALM_RA_MAX_SIDE
+(RA_OP_IDENTITY, RA_OP_AFFINE, RA_OP_BRIGHTNESS, RA_OP_COLOR, RA_OP_CONTRAST, RA_OP_SHARPNESS, RA_OP_POSTERIZE,
+ RA_OP_SOLARIZE, RA_OP_AUTOCONTRAST, RA_OP_EQUALIZE) = range(10)                    # CALM_RA_OP_*
+RA_STATS_OPS = (RA_OP_CONTRAST, RA_OP_AUTOCONTRAST, RA_OP_EQUALIZE)                 # the slots a statistics launch precedes
+
+
+class RaSample(C.Structure):
+    """struct calm_ra_sample (160 bytes, one per sample of calm_randaugment_u8)."""
+    _fields_ = [("y0", _i32), ("x0", _i32), ("flip", C.c_uint32), ("n_ops", _i32), ("op", _i32 * 4), ("factor", _f32 * 4),
+                ("param", _i32 * 4), ("coef", (_i32 * 6) * 4)]
+
+
 # name -> (restype, argtypes); every symbol include/calm_vit.h declares
 SIGNATURES = {
     "calm_abi_version": (_i32, []),
@@ -234,6 +246,8 @@ SIGNATURES = {
     "calm_resize_u8": (_i32, [_p, _i64, _p, _p, _i32, _i32, _i32, _p]),
     "calm_resized_crop": (_i32, [_p, _i64, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),
     "calm_resized_crop_check": (_i32, [C.POINTER(RCropSample), _i64, _i32, _i32]),
+    "calm_randaugment_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "calm_randaugment_u8": (_i32, [_p, _i32, _i32, _p, _p, _i32, _i32, _i32, _i32, C.c_uint32, _p, _p, _i64, _p]),
     "calm_image_to_rows": (_i32, [_p, _p, _i32, _i32, _p]),
     "calm_rows_to_image": (_i32, [_p, _p, _i32, _i32, _p]),
     "calm_grid_transpose": (_i32, [_p, _p, _i32, _i32, _p]),

@@ -867,6 +867,44 @@ class HipBackend:
         _lib.check(self.lib.calm_resized_crop(packed.data_ptr(), packed.numel(), samples.data_ptr(), out.data_ptr(), B, H, W,
                                               kind, cm, cs, _stream()), "calm_resized_crop")
 
+    def randaugment_scratch_bytes(self, B, H, W):
+        """Bytes of scratch randaugment_u8 needs for a [B,3,H,W] output (calm_randaugment_scratch_bytes)."""
+        n = self.lib.calm_randaugment_scratch_bytes(B, H, W)
+        if n < 0:
+            _lib.check(int(n), "calm_randaugment_scratch_bytes")
+        return int(n)
+
+    def randaugment_u8(self, img_u8, samples, out, n_slots, stats_mask, fill=None, scratch=None):
+        """The uint8 RandAugment stage (calm_randaugment_u8): per sample the crop window and the flip, then up to four
+        PIL-exact uint8 operations.  img_u8 [B,3,Hs,Ws] uint8; samples: the device array of B calm_ra_sample records as a
+        contiguous uint8 CUDA tensor [B,160] (trainer.DeviceRandAugment.pack: corners and flips are in it); out
+        [B,3,H,W] uint8, written; n_slots: the slot passes to run (the batch's largest n_ops); stats_mask: bit k set when
+        some sample's slot k is Contrast, AutoContrast or Equalize; fill: three integers 0 .. 255 (None: black);
+        scratch: a uint8 CUDA tensor of at least randaugment_scratch_bytes(B, H, W) bytes (None: allocated here)."""
+        if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[1] != 3 or not img_u8.is_contiguous():
+            raise TypeError("randaugment_u8 expects a contiguous uint8 CUDA image batch [B,3,Hs,Ws]")
+        B, _, Hs, Ws = img_u8.shape
+        if (not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 4 or out.shape[0] != B or out.shape[1] != 3
+                or not out.is_contiguous()):
+            raise TypeError("randaugment_u8: out must be a contiguous uint8 CUDA tensor [B,3,H,W]")
+        H, W = out.shape[2], out.shape[3]
+        if (samples.dtype != torch.uint8 or not samples.is_cuda or not samples.is_contiguous()
+                or tuple(samples.shape) != (B, C.sizeof(_lib.RaSample))):
+            raise TypeError("randaugment_u8: samples must be a contiguous uint8 CUDA tensor [B,160] (calm_ra_sample records)")
+        need = self.randaugment_scratch_bytes(B, H, W)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.uint8, device=img_u8.device)
+        if not scratch.is_cuda or scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
+            raise TypeError(f"randaugment_u8: scratch must be a contiguous uint8 CUDA tensor of at least {need} bytes")
+        cf = None
+        if fill is not None:
+            if len(fill) != 3 or not all(int(v) == v and 0 <= v <= 255 for v in fill):
+                raise ValueError(f"randaugment_u8: fill is three integers in 0 .. 255, got {fill!r}")
+            cf = (C.c_uint8 * 3)(*(int(v) for v in fill))
+        _lib.check(self.lib.calm_randaugment_u8(img_u8.data_ptr(), Hs, Ws, samples.data_ptr(), out.data_ptr(), B, H, W,
+                                                int(n_slots), int(stats_mask), cf, scratch.data_ptr(), scratch.numel(),
+                                                _stream()), "calm_randaugment_u8")
+
     # ---- optimizer-side step ------------------------------------------------------------
     def optim_plan(self, records, n_groups=1):
         """records: one dict per parameter — param, exp_avg, exp_avg_sq, sn (None or (u, v, sigma, rows, cols)) and,

@@ -1102,6 +1102,234 @@ class DeviceErase:
         return host.to(device)
 
 
+class DeviceRandAugment:
+    """RandAugment (Cubuk et al.; torchvision.transforms.v2.RandAugment on a PIL image, restated — torchvision is not
+    installed in the build image) as a uint8 -> uint8 device stage in front of the collate (calm_randaugment_u8): per
+    sample the RandomCrop window and the flip, then `num_ops` operations drawn uniformly from `ops`, every one rounded to
+    uint8 as PIL rounds it — the batch equals the PIL chain byte for byte (tests/test_randaug_cpu.py, test_randaug_gpu.py).
+
+    The augmentation space is torchvision's 14 operations, magnitude bin `magnitude` of `num_bins`:
+      Identity; ShearX, ShearY linspace(0, 0.3); TranslateX, TranslateY int(linspace(0, 150 / 331 * side)) pixels, side = W
+      for X and H for Y; Rotate linspace(0, 30) degrees; Brightness, Color, Contrast, Sharpness factor 1 +- linspace(0, 0.9);
+      Posterize 8 - round(i / ((num_bins - 1) / 4)) bits; Solarize threshold linspace(255, 0); AutoContrast; Equalize.
+    The signed operations (shears, translations, rotation, the four enhances) flip their sign with probability 1/2.
+    `fill`: one integer or three, 0 .. 255, the colour of the pixels a warp brings in from outside the window.
+    `trivial_wide(...)` is TrivialAugmentWide on the same kernel: one operation, a uniformly drawn bin, the wide ranges
+    (shear 0.99, translation 32 pixels, rotation 135 degrees, enhances 0.99, posterize 8 - round(i / ((num_bins - 1) / 6))).
+    The draws are numpy's, from this object's own generator: bit-parity of the draws with torchvision (torch's generator)
+    is not claimed, and the draws of DeviceCollate, DeviceAugment, DeviceErase and DeviceResizedCrop do not shift when the
+    object is used."""
+
+    OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast", "Sharpness",
+           "Posterize", "Solarize", "AutoContrast", "Equalize")
+    SIGNED = frozenset(("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast", "Sharpness"))
+
+    def __init__(self, num_ops=2, magnitude=9, num_bins=31, fill=0, ops=None, seed=None, _wide=False):
+        import numpy as np
+        from . import _lib
+        if isinstance(num_ops, bool) or int(num_ops) != num_ops or not 0 <= num_ops <= _lib.RA_MAX_OPS:
+            raise ValueError(f"DeviceRandAugment: num_ops counts operations per sample, 0 .. {_lib.RA_MAX_OPS}, got {num_ops!r}")
+        if isinstance(num_bins, bool) or int(num_bins) != num_bins or num_bins < 2:
+            raise ValueError(f"DeviceRandAugment: num_bins counts magnitude bins (>= 2), got {num_bins!r}")
+        if isinstance(magnitude, bool) or int(magnitude) != magnitude or not 0 <= magnitude < num_bins:
+            raise ValueError(f"DeviceRandAugment: magnitude is a bin, 0 .. num_bins - 1 = {int(num_bins) - 1}, got {magnitude!r}")
+        ops = tuple(self.OPS if ops is None else ops)
+        if not ops or any(o not in self.OPS for o in ops):
+            raise ValueError(f"DeviceRandAugment: ops is a non-empty selection of {self.OPS}, got {ops!r}")
+        f = tuple(np.atleast_1d(np.asarray(fill)).tolist())
+        f = f * 3 if len(f) == 1 else f
+        if len(f) != 3 or not all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= 255 for v in f):
+            raise ValueError(f"DeviceRandAugment: fill is one integer or three in 0 .. 255, got {fill!r}")
+        self.num_ops, self.magnitude, self.num_bins, self.fill, self.ops = int(num_ops), int(magnitude), int(num_bins), f, ops
+        self.wide = bool(_wide)
+        self.rng = np.random.default_rng(seed)
+        self._scratch = None
+
+    @classmethod
+    def trivial_wide(cls, num_bins=31, fill=0, ops=None, seed=None):
+        """TrivialAugmentWide: one operation per sample with a uniformly drawn magnitude bin over the wide ranges."""
+        return cls(num_ops=1, magnitude=0, num_bins=num_bins, fill=fill, ops=ops, seed=seed, _wide=True)
+
+    @staticmethod
+    def dtype():
+        """The numpy record of struct calm_ra_sample."""
+        import numpy as np
+        from . import _lib
+        return np.dtype(_lib.RaSample)
+
+    @classmethod
+    def identity(cls, B):
+        """A table of B samples with no operation, no flip and the corner (0, 0); the unused slots hold the identity."""
+        import numpy as np
+        t = np.zeros(B, dtype=cls.dtype())
+        t["factor"] = 1.0
+        t["coef"] = (65536, 0, 32768, 0, 65536, 32768)
+        return t
+
+    def magnitudes(self, name, H, W):
+        """The magnitude of every bin for operation `name` on an H x W window, float64 [num_bins] (None: the operation has
+        none): the table of torchvision's _augmentation_space, RandAugment's or TrivialAugmentWide's."""
+        import numpy as np
+        n, wide = self.num_bins, self.wide
+        if name in ("Identity", "AutoContrast", "Equalize"):
+            return None
+        if name in ("ShearX", "ShearY"):
+            return np.linspace(0.0, 0.99 if wide else 0.3, n)
+        if name in ("TranslateX", "TranslateY"):
+            return np.linspace(0.0, 32.0 if wide else 150.0 / 331.0 * (W if name == "TranslateX" else H), n)
+        if name == "Rotate":
+            return np.linspace(0.0, 135.0 if wide else 30.0, n)
+        if name in ("Brightness", "Color", "Contrast", "Sharpness"):
+            return np.linspace(0.0, 0.99 if wide else 0.9, n)
+        if name == "Posterize":
+            return 8.0 - np.round(np.arange(n) / ((n - 1) / (6.0 if wide else 4.0)))
+        return np.linspace(255.0, 0.0, n)                                    # Solarize
+
+    @staticmethod
+    def fixed_coeffs(a):
+        """(A0 .. A5): the six doubles of an inverse affine map in PIL's 16.16 fixed point (the header's FIX)."""
+        import math
+        fix = lambda v: int(math.floor(v * 65536.0 + 0.5))
+        a = [float(v) for v in a]
+        return (fix(a[0]), fix(a[1]), fix(a[2] + a[0] * 0.5 + a[1] * 0.5), fix(a[3]), fix(a[4]), fix(a[5] + a[3] * 0.5 + a[4] * 0.5))
+
+    @classmethod
+    def slot(cls, name, value, H, W):
+        """(op id, factor, param, coef) of operation `name` with the signed magnitude `value` on an H x W window."""
+        import math
+        import numpy as np
+        from . import _lib
+        ident = (65536, 0, 32768, 0, 65536, 32768)
+        if name in ("Identity", "AutoContrast", "Equalize"):
+            return {"Identity": _lib.RA_OP_IDENTITY, "AutoContrast": _lib.RA_OP_AUTOCONTRAST,
+                    "Equalize": _lib.RA_OP_EQUALIZE}[name], 1.0, 0, ident
+        if name in ("Brightness", "Color", "Contrast", "Sharpness"):
+            op = {"Brightness": _lib.RA_OP_BRIGHTNESS, "Color": _lib.RA_OP_COLOR, "Contrast": _lib.RA_OP_CONTRAST,
+                  "Sharpness": _lib.RA_OP_SHARPNESS}[name]
+            return op, float(np.float32(1.0 + value)), 0, ident
+        if name == "Posterize":
+            return _lib.RA_OP_POSTERIZE, 1.0, int(value), ident
+        if name == "Solarize":                                               # i < threshold on integers i
+            return _lib.RA_OP_SOLARIZE, 1.0, int(math.ceil(value)), ident
+        if name == "ShearX":
+            a = (1.0, float(value), 0.0, 0.0, 1.0, 0.0)
+        elif name == "ShearY":
+            a = (1.0, 0.0, 0.0, float(value), 1.0, 0.0)
+        elif name == "TranslateX":
+            a = (1.0, 0.0, -float(int(value)), 0.0, 1.0, 0.0)
+        elif name == "TranslateY":
+            a = (1.0, 0.0, 0.0, 0.0, 1.0, -float(int(value)))
+        elif name == "Rotate":                                               # Image.rotate's matrix about (W / 2, H / 2)
+            r = -math.radians(value % 360.0)
+            m = [round(math.cos(r), 15), round(math.sin(r), 15), 0.0, round(-math.sin(r), 15), round(math.cos(r), 15), 0.0]
+            cx, cy = W / 2.0, H / 2.0
+            m[2] = m[0] * -cx + m[1] * -cy + m[2]
+            m[5] = m[3] * -cx + m[4] * -cy + m[5]
+            m[2] += cx
+            m[5] += cy
+            a = m
+        else:
+            raise ValueError(f"DeviceRandAugment: no operation {name!r}")
+        return _lib.RA_OP_AFFINE, 1.0, 0, cls.fixed_coeffs(a)
+
+    def draw(self, B, H, W):
+        """The record table of one batch (a numpy record array of calm_ra_sample; corners and flips are DeviceCollate's
+        and are filled in by pack).  Per batch, in this order: the operation indices [B, num_ops], the sign decisions
+        [B, num_ops] (drawn for every slot, used by the signed operations) and, for trivial_wide, the bins [B, num_ops]."""
+        rng, k = self.rng, self.num_ops
+        t = self.identity(B)
+        which = rng.integers(0, len(self.ops), (B, k))
+        negate = rng.random((B, k)) < 0.5
+        bins = rng.integers(0, self.num_bins, (B, k)) if self.wide else None
+        mags = {name: self.magnitudes(name, H, W) for name in self.ops}
+        t["n_ops"] = k
+        for b in range(B):
+            for j in range(k):
+                name = self.ops[which[b, j]]
+                m = mags[name]
+                value = 0.0 if m is None else float(m[bins[b, j] if self.wide else self.magnitude])
+                if name in self.SIGNED and negate[b, j]:
+                    value = -value
+                t["op"][b, j], t["factor"][b, j], t["param"][b, j], t["coef"][b, j] = self.slot(name, value, H, W)
+        return t
+
+    @staticmethod
+    def check(table, H, W):
+        """Refuses a table the stage must not get: n_ops outside 0 .. 4, an operation id outside the table, posterize bits
+        outside 0 .. 8, a non-finite factor, or affine coefficients outside the bounds under which the kernel's 32-bit
+        sums cannot overflow (|A0|, |A1|, |A3|, |A4| <= 2^17, |A2|, |A5| <= 2^30; H, W <= 4096)."""
+        import numpy as np
+        from . import _lib
+        t = np.asarray(table)
+        if H > _lib.RA_MAX_SIDE or W > _lib.RA_MAX_SIDE or H < 1 or W < 1:
+            raise ValueError(f"DeviceRandAugment: the window's sides are 1 .. {_lib.RA_MAX_SIDE}, got {H} x {W}")
+        n = t["n_ops"].astype(np.int64)
+        if bool(((n < 0) | (n > _lib.RA_MAX_OPS)).any()):
+            raise ValueError(f"DeviceRandAugment: n_ops is 0 .. {_lib.RA_MAX_OPS}")
+        used = np.arange(_lib.RA_MAX_OPS)[None, :] < n[:, None]
+        op = t["op"].astype(np.int64)
+        if bool((used & ((op < 0) | (op > _lib.RA_OP_EQUALIZE))).any()):
+            raise ValueError("DeviceRandAugment: an operation id outside the table")
+        if bool((used & (op == _lib.RA_OP_POSTERIZE) & ((t["param"] < 0) | (t["param"] > 8))).any()):
+            raise ValueError("DeviceRandAugment: posterize keeps 0 .. 8 bits")
+        if bool((used & ~np.isfinite(t["factor"])).any()):
+            raise ValueError("DeviceRandAugment: a factor is not finite")
+        c = np.abs(t["coef"].astype(np.int64))
+        big = (c[:, :, [0, 1, 3, 4]] > 2 ** 17).any(axis=2) | (c[:, :, [2, 5]] > 2 ** 30).any(axis=2)
+        if bool((used & (op == _lib.RA_OP_AFFINE) & big).any()):
+            raise ValueError("DeviceRandAugment: affine coefficients outside |A0, A1, A3, A4| <= 2^17, |A2, A5| <= 2^30")
+
+    @staticmethod
+    def launch_plan(table):
+        """(n_slots, stats_mask) of a table: the slot passes the batch needs and, bit k, whether some sample's slot k needs
+        the statistics launch (Contrast, AutoContrast, Equalize)."""
+        import numpy as np
+        from . import _lib
+        t = np.asarray(table)
+        n = np.clip(t["n_ops"].astype(np.int64), 0, _lib.RA_MAX_OPS)
+        n_slots = int(n.max()) if len(n) else 0
+        used = np.arange(_lib.RA_MAX_OPS)[None, :] < n[:, None]
+        need = used & np.isin(t["op"], _lib.RA_STATS_OPS)
+        return n_slots, sum(1 << k for k in range(_lib.RA_MAX_OPS) if bool(need[:, k].any()))
+
+    @staticmethod
+    def pack(table, corners=None, flips=None, device="cuda"):
+        """The device array of calm_ra_sample records, [B,160] uint8, in one host-to-device copy: `table` with the crop
+        corners ([B,2] integers, None = keep the table's) and the flip decisions ([B], None = keep) filled in."""
+        import numpy as np
+        t = np.array(table, dtype=DeviceRandAugment.dtype(), copy=True)
+        if corners is not None:
+            c = np.asarray(corners)
+            t["y0"], t["x0"] = c[:, 0], c[:, 1]
+        if flips is not None:
+            t["flip"] = np.asarray(flips).astype(bool).astype(np.uint32)
+        host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
+        return host.to(device)
+
+    def __call__(self, img_u8, corners=None, flips=None, crop=None, table=None):
+        """img_u8 [B,3,Hs,Ws] uint8 on the device -> [B,3,H,W] uint8: the window crop=(H, W) at `corners` ([B,2] host
+        integers; None: (0, 0), and crop=None: the whole image), the flips ([B], None: none), then the drawn chain —
+        or `table`, draw()'s format, given instead of drawn.  The collate behind it takes the batch with crop=None and
+        no flips."""
+        from .backend import get_backend
+        B, _, Hs, Ws = img_u8.shape
+        H, W = crop if crop is not None else (Hs, Ws)
+        if table is None:
+            table = self.draw(B, H, W)
+        if len(table) != B:
+            raise ValueError(f"DeviceRandAugment: the table holds {len(table)} records for a batch of {B}")
+        self.check(table, H, W)
+        n_slots, stats_mask = self.launch_plan(table)
+        be = get_backend()
+        out = torch.empty((B, 3, H, W), dtype=torch.uint8, device=img_u8.device)
+        need = be.randaugment_scratch_bytes(B, H, W)
+        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != img_u8.device:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=img_u8.device)
+        be.randaugment_u8(img_u8, self.pack(table, corners, flips, device=img_u8.device), out, n_slots, stats_mask,
+                          fill=self.fill, scratch=self._scratch)
+        return out
+
+
 class RaggedU8Collate:
     """DataLoader collate_fn for decoded images of different sizes: samples `(uint8 [h, w, 3], label)` — the array
     np.asarray(pil_image) gives, or a tensor of that shape — become
@@ -3157,13 +3385,13 @@ def _validate_epoch(task, model, ema, val_dataset, rank, world, device, batch_si
 def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_collate, crop, graph, device_metrics,
                       device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path, snapshot_every,
                       accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task, teacher, distill,
-                      param_groups, scheduler_step, monitor=None, random_erasing=None, label_smoothing=0.0):
+                      param_groups, scheduler_step, monitor=None, random_erasing=None, label_smoothing=0.0, rand_augment=None):
     """Every refusal train() makes from its arguments alone: it touches no device and no process group, so a bad call
     fails before either exists.  Returns the normalised values the job is assembled from: accumulate (int), ema_kw
     (None without ema), distill_kw (DistillTrainStep's keywords, {} without a teacher), teacher_mod, resize (the
     DeviceResize or None), window (the DeviceResizedCrop.window or None), reg, per_step, monitor_kw (None without
     monitor=; "every" None: log_every), erase (None, a DeviceErase, or the dict of arguments one is built from),
-    label_smoothing (float)."""
+    label_smoothing (float), rand_augment (None, a DeviceRandAugment, or the dict of arguments one is built from)."""
     from . import backend as _backend
     from types import SimpleNamespace
     if scheduler_step not in ("epoch", "step"):
@@ -3259,6 +3487,25 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
         else:
             raise ValueError("train: random_erasing is a probability, a dict of DeviceErase's arguments or a DeviceErase, "
                              f"got {random_erasing!r}")
+    randaug = None
+    if rand_augment is not None and rand_augment is not False:
+        if not device_collate:
+            raise ValueError("rand_augment needs device_collate=True (the stage feeds the collate kernel its uint8 batch)")
+        if isinstance(rand_augment, DeviceRandAugment):
+            randaug = rand_augment
+        elif rand_augment is True or isinstance(rand_augment, dict):
+            randaug = {} if rand_augment is True else dict(rand_augment)
+            if not set(randaug) <= {"num_ops", "magnitude", "num_bins", "fill", "ops", "seed"}:
+                raise ValueError('train: rand_augment takes the keys "num_ops", "magnitude", "num_bins", "fill", "ops", "seed", '
+                                 f"got {sorted(randaug)}")
+            DeviceRandAugment(**randaug)                    # (refuses malformed arguments here, not at the first batch)
+        else:
+            raise ValueError("train: rand_augment is None, True, a dict of DeviceRandAugment's arguments or a DeviceRandAugment, "
+                             f"got {rand_augment!r}")
+        side = crop if crop is not None else device_resize if device_resize is not None else \
+            random_resized_crop.size if random_resized_crop is not None else None
+        if side is not None and max(side) > 4096:
+            raise ValueError(f"train: rand_augment works on windows of at most 4096 x 4096, got {tuple(side)}")
     if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)) or not 0.0 <= label_smoothing < 1.0:
         raise ValueError(f"train: label_smoothing is an epsilon in [0, 1), got {label_smoothing!r}")
     if label_smoothing > 0.0 and reg:
@@ -3292,7 +3539,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
             EvalMetrics(num_classes, topk=val_topk)         # (refuses a malformed val_topk here, not after the first epoch)
     return SimpleNamespace(accumulate=accumulate, ema_kw=ema_kw, distill_kw=distill_kw, teacher_mod=teacher_mod, resize=resize,
                            window=window, reg=reg, per_step=scheduler_step == "step", monitor_kw=monitor_kw, erase=erase,
-                           label_smoothing=float(label_smoothing))
+                           label_smoothing=float(label_smoothing), rand_augment=randaug)
 
 
 class _TrainInput:
@@ -3308,13 +3555,13 @@ class _TrainInput:
     lam = 1), so the generators advance as under cls; the collate gets zero labels and its soft labels are dropped."""
 
     def __init__(self, device_collate, device_augment, resize, window, random_resized_crop, crop, collate_fn, num_classes,
-                 rank, reg, device, random_erasing=None, label_smoothing=0.0):
+                 rank, reg, device, random_erasing=None, label_smoothing=0.0, rand_augment=None):
         self.resize, self.window, self.resized_crop, self.crop = resize, window, random_resized_crop, crop
         self.reg, self.device = reg, device
         self.num_classes, self.label_smoothing = num_classes, float(label_smoothing)
         # eps / K as a 0-dim host tensor (it broadcasts against a batch on any device); None: no smoothing, no extra op
         self._smooth = torch.tensor(self.label_smoothing / num_classes, dtype=torch.float32) if self.label_smoothing > 0.0 else None
-        self.collate = self.augment = self.erase = None
+        self.collate = self.augment = self.erase = self.randaug = None
         if device_collate:
             self.collate = DeviceCollate(num_classes=num_classes, seed=2006 + rank)
             self.augment = DeviceAugment(seed=2006 + rank) if device_augment else None
@@ -3322,6 +3569,10 @@ class _TrainInput:
                 self.erase = random_erasing
             elif random_erasing is not None:               # a dict of DeviceErase's arguments (_check_train_args made it)
                 self.erase = DeviceErase(**{"seed": 2006 + rank, **random_erasing})
+            if isinstance(rand_augment, DeviceRandAugment):
+                self.randaug = rand_augment
+            elif rand_augment is not None:                  # a dict of DeviceRandAugment's arguments (_check_train_args made it)
+                self.randaug = DeviceRandAugment(**{"seed": 2006 + rank, **rand_augment})
             collate_fn = None                               # default_collate: stack uint8 images and labels
             if resize is not None or random_resized_crop is not None:
                 collate_fn = RaggedU8Collate()              # images of any size: one packed buffer and its table
@@ -3340,6 +3591,8 @@ class _TrainInput:
                 gens["resized_crop"] = self.resized_crop.rng
             if self.erase is not None:
                 gens["erase"] = self.erase.rng
+            if self.randaug is not None:
+                gens["rand_augment"] = self.randaug.rng
         elif isinstance(self.collate_fn, SoftMixCollate) and num_workers == 0:
             gens["mix"] = self.collate_fn.rng
         return gens
@@ -3361,6 +3614,16 @@ class _TrainInput:
         else:
             x, y = batch if isinstance(batch, (tuple, list)) else (batch, None)
             x = x.to(device, non_blocking=True)
+        if self.randaug is not None:
+            # the decisions and the corners in the collate's own order, then the stage's draws: it crops and flips, and the
+            # collate takes its uint8 batch with crop=None and no flips
+            B, (Hs, Ws) = x.shape[0], x.shape[-2:]
+            H, W = crop if crop is not None else (Hs, Ws)
+            if decisions is None:
+                decisions = dcoll.draw(B, H, W)
+            corners = dcoll.draw_corners(B, Hs, Ws, H, W) if crop is not None else None
+            x = self.randaug(x, corners, decisions[3], crop)
+            decisions, crop = (*decisions[:3], torch.zeros_like(decisions[3])), None
         if self.reg:                                                   # the labels are ignored (reg:74-77)
             if dcoll is not None:                                      # uint8 batch -> row tokens; the draws as for "cls"
                 if decisions is None:
@@ -3510,7 +3773,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
           val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
           teacher=None, distill=None, param_groups=None, scheduler_step="epoch", monitor=None, random_erasing=None,
-          label_smoothing=0.0):
+          label_smoothing=0.0, rand_augment=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -3688,14 +3951,26 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     y (1 - eps) + eps / num_classes — what torch.nn.CrossEntropyLoss(label_smoothing=eps) does to probability targets —
     in one op in front of the step; the loss kernels and the distillation CE take them as they take any soft target, the
     log line's dominant-class accuracy does not move (the argmax is the same), the validation loss is not smoothed, and
-    eps = 0 adds no op."""
+    eps = 0 adds no op.
+
+    rand_augment=True | a dict of `DeviceRandAugment`'s arguments (num_ops, magnitude, num_bins, fill, ops, seed) | a
+    `DeviceRandAugment` (`DeviceRandAugment.trivial_wide(...)` for TrivialAugmentWide); needs device_collate=True.  The
+    RandAugment of the DeiT / timm recipe as a uint8 -> uint8 device stage (calm_randaugment_u8, PIL-exact bytes) between
+    the uint8 batch — the dataset's, or the output of device_resize / resize_window / random_resized_crop — and the
+    collate.  Built here it is seeded 2006 + rank and owns its generator.  Per batch the collate's decisions and the crop
+    corners are drawn first, in the order they are drawn without the stage, then the stage's own draws; the stage crops
+    and flips (the reference's order: crop, flip, then the operations) and the collate — with device_augment and
+    random_erasing as before — takes its batch with crop=None and no flips.  The generator is part of a snapshot
+    ("rand_augment"), so resume= continues bit for bit.  Works with both tasks, accumulate and graph= (the stage runs in
+    front of the captured step).  With num_ops=0 the run equals the one without the argument bit for bit; without the
+    argument nothing changes."""
     from functools import partial
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
     args = _check_train_args(initializer, optimizer, use_gpu, num_classes, device_collate, crop, graph, device_metrics,
                           device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path,
                           snapshot_every, accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task,
-                          teacher, distill, param_groups, scheduler_step, monitor, random_erasing, label_smoothing)
+                          teacher, distill, param_groups, scheduler_step, monitor, random_erasing, label_smoothing, rand_augment)
     accumulate, per_step, teacher_mod = args.accumulate, args.per_step, args.teacher_mod
     rank, local_rank, world = init_distributed(use_gpu)
     main = rank == 0 and local_rank == 0                    # the one process that prints and writes
@@ -3738,7 +4013,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         sampler = DistributedSampler(dataset, num_replicas=1, rank=0, shuffle=True, seed=2006)
     sampler.set_epoch(0)
     inp = _TrainInput(device_collate, device_augment, args.resize, args.window, random_resized_crop, crop, collate_fn, num_classes,
-                      rank, args.reg, device, random_erasing=args.erase, label_smoothing=args.label_smoothing)
+                      rank, args.reg, device, random_erasing=args.erase, label_smoothing=args.label_smoothing,
+                      rand_augment=args.rand_augment)
     loader_kw = dict(batch_size=batch_size, collate_fn=inp.collate_fn, num_workers=num_workers, pin_memory=use_gpu,
                      drop_last=bool(graph))
     loader = DataLoader(dataset, sampler=sampler, persistent_workers=num_workers > 0, **loader_kw)

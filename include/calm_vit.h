@@ -895,6 +895,81 @@ int calm_resized_crop(const uint8_t* packed, int64_t nbytes, const calm_rcrop_sa
 int calm_resized_crop_check(const calm_rcrop_sample* sample /* HOST */, int64_t nbytes, int32_t H, int32_t W);  /* 1 valid, 0 not */
 
 /* ---------------------------------------------------------------------------------------
+ * Device RandAugment (an addition to ABI v7 — no existing signature or struct changes, so the version number stays): a
+ * uint8 -> uint8 stage between the uint8 batch and the collate.  img_u8 [B,3,Hs,Ws] -> out [B,3,H,W]; per sample the
+ * RandomCrop window (corner clamped into [0, Hs-H] x [0, Ws-W] as calm_augment_collate clamps it) and the horizontal
+ * flip first — the order of the reference's transform list — then a chain of up to CALM_RA_MAX_OPS operations, each
+ * rounded to uint8 as PIL rounds it: the output equals, byte for byte, what PIL 12 gives for the same chain on
+ * Image.fromarray(window).  The semantics are torchvision.transforms.v2.RandAugment's on a PIL image, restated.
+ *
+ * CALM_RA_OP_AFFINE (ShearX, ShearY, TranslateX, TranslateY, Rotate): nearest-neighbour affine in PIL's 16.16 fixed
+ *   point on the H x W window, never on source pixels outside the crop.  The host has six doubles a[0..5], the inverse
+ *   map (output -> input): ShearX s (1, s, 0, 0, 1, 0); ShearY s (1, 0, 0, s, 1, 0); TranslateX by an integer t
+ *   (1, 0, -t, 0, 1, 0); TranslateY (1, 0, 0, 0, 1, -t); Rotate by `angle` degrees counter-clockwise about (W/2, H/2),
+ *   Image.rotate's matrix: r = -radians(angle % 360), m = (round(cos r, 15), round(sin r, 15), 0, round(-sin r, 15),
+ *   round(cos r, 15), 0), m[2] = m[0] (-W/2) + m[1] (-H/2) + W/2, m[5] = m[3] (-W/2) + m[4] (-H/2) + H/2.  It converts
+ *   them with FIX(v) = floor(v * 65536 + 0.5): coef = (FIX(a0), FIX(a1), FIX(a2 + a0 * 0.5 + a1 * 0.5), FIX(a3), FIX(a4),
+ *   FIX(a5 + a3 * 0.5 + a4 * 0.5)) = (A0 .. A5), and the device computes
+ *     xin = (A2 + A1 y + A0 x) >> 16,  yin = (A5 + A4 y + A3 x) >> 16      (arithmetic shift)
+ *     out[c][y][x] = 0 <= xin < W && 0 <= yin < H ? window[c][yin][xin] : fill[c]
+ *   Integer translations and the identity agree with PIL's separate scale-only path; bit parity with non-integer
+ *   translations is not claimed.  32 bits suffice: x, y < 4096 = 2^12, so with |A0|, |A1|, |A3|, |A4| <= 2^17 (|a| <= 2:
+ *   every shear, rotation and translation) and |A2|, |A5| <= 2^30 (an offset below 16384 pixels) each sum stays below
+ *   2^29 + 2^29 + 2^30 = 2^31.  trainer.DeviceRandAugment.check refuses a record outside those bounds; the device
+ *   evaluates the sums in wrapping 32-bit arithmetic, so any other record still gives a defined pixel or the fill.
+ * blend(d, s, f) is Image.blend: in fp32, t = d + f * (s - d), every operation one IEEE rounding and no fused
+ *   multiply-add; for 0 <= f <= 1 the result is (uint8)(int)t, otherwise 0 for t <= 0, 255 for t >= 255, (int)t between.
+ *   L(R, G, B) = (19595 R + 38470 G + 7471 B + 32768) >> 16.
+ *   CALM_RA_OP_BRIGHTNESS blend(0, x, f);  CALM_RA_OP_COLOR blend(L, x, f) per channel;
+ *   CALM_RA_OP_CONTRAST blend(m, x, f), m = floor((2 sum L + n) / (2 n)) over the n window pixels as the image stands
+ *     when the operation runs (= int(mean + 0.5));
+ *   CALM_RA_OP_SHARPNESS blend(smooth(x), x, f), smooth = ImageFilter.SMOOTH: on interior pixels acc = 0.5f, then
+ *     acc += p * k for the nine taps in row-major order with k = (1,1,1,1,5,1,1,1,1), each entry divided by 13 in fp32,
+ *     result clamp((int)acc, 0, 255); the outermost rows and columns are copied; a window with H < 3 or W < 3 is copied.
+ * CALM_RA_OP_POSTERIZE v & (0xFF << (8 - param)), param = bits; bits outside 0 .. 8 are treated as 8.
+ * CALM_RA_OP_SOLARIZE  v < param ? v : 255 - v.
+ * CALM_RA_OP_AUTOCONTRAST per channel: lo, hi = the channel's min and max; hi <= lo: unchanged; otherwise in IEEE
+ *   double, single operations, a correctly rounded division: scale = 255.0 / (hi - lo), off = -lo * scale,
+ *   lut[i] = clamp((int)(i * scale + off), 0, 255).
+ * CALM_RA_OP_EQUALIZE per channel, h the 256-bin histogram: fewer than two non-empty bins: unchanged;
+ *   step = (sum h - h[last non-empty]) / 255 in integers, step == 0: unchanged; otherwise
+ *   lut[i] = min((step / 2 + sum_{j < i} h[j]) / step, 255) in integers.
+ * CALM_RA_OP_IDENTITY and every id outside the table: the slot is skipped.
+ *
+ * samples_dev: DEVICE array [B].  A sample runs its first min(n_ops, n_slots) slots (n_ops < 0 counts as 0).  The records
+ * live on the device, so the host says what the batch needs: n_slots (0 .. CALM_RA_MAX_OPS) is the number of slot passes
+ * launched, and bit k of stats_mask says that some sample has CONTRAST, AUTOCONTRAST or EQUALIZE in slot k — that slot is
+ * then preceded by a statistics launch (R / G / B / L histograms per sample: LDS-private counts, then integer atomics,
+ * so the result repeats bit for bit; there is no floating-point atomic anywhere).  One of those three operations in a
+ * slot whose bit is not set is skipped.  Whatever a record holds, the kernels address nothing outside their buffers.
+ * fill: HOST uint8[3], NULL = (0, 0, 0).  scratch: DEVICE, at least calm_randaugment_scratch_bytes(B, H, W) bytes, 16-byte
+ * aligned: two ping-pong images [B,3,H,W] and 4 x 256 int32 histograms per sample.  out must not overlap img_u8.
+ *   CALM_E_INVAL: a null img_u8 / samples_dev / out / scratch, B <= 0, H or W <= 0, H > Hs or W > Ws, n_slots outside
+ *     0 .. CALM_RA_MAX_OPS, scratch_bytes below calm_randaugment_scratch_bytes(B, H, W);
+ *   CALM_E_UNSUPP: B > 65535, H or W above CALM_RA_MAX_SIDE.  All of them before any launch.
+ *   calm_randaugment_scratch_bytes: the size, or CALM_E_INVAL / CALM_E_UNSUPP for the same B, H, W.
+ * ------------------------------------------------------------------------------------- */
+#define CALM_RA_MAX_OPS 4
+#define CALM_RA_MAX_SIDE 4096
+enum { CALM_RA_OP_IDENTITY = 0, CALM_RA_OP_AFFINE = 1, CALM_RA_OP_BRIGHTNESS = 2, CALM_RA_OP_COLOR = 3, CALM_RA_OP_CONTRAST = 4,
+       CALM_RA_OP_SHARPNESS = 5, CALM_RA_OP_POSTERIZE = 6, CALM_RA_OP_SOLARIZE = 7, CALM_RA_OP_AUTOCONTRAST = 8,
+       CALM_RA_OP_EQUALIZE = 9 };
+typedef struct calm_ra_sample {    /* 160 bytes */
+    int32_t  y0, x0;                        /* crop corner */
+    uint32_t flip;                          /* != 0: horizontal flip of the window */
+    int32_t  n_ops;                         /* slots in use, 0 .. CALM_RA_MAX_OPS */
+    int32_t  op[CALM_RA_MAX_OPS];           /* CALM_RA_OP_* per slot */
+    float    factor[CALM_RA_MAX_OPS];       /* f of the four blends */
+    int32_t  param[CALM_RA_MAX_OPS];        /* posterize bits, solarize threshold */
+    int32_t  coef[CALM_RA_MAX_OPS][6];      /* A0 .. A5 of CALM_RA_OP_AFFINE */
+} calm_ra_sample;
+
+int64_t calm_randaugment_scratch_bytes(int32_t B, int32_t H, int32_t W);
+int calm_randaugment_u8(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const calm_ra_sample* samples_dev,
+                        uint8_t* out /* [B,3,H,W] */, int32_t B, int32_t H, int32_t W, int32_t n_slots, uint32_t stats_mask,
+                        const uint8_t* fill /* HOST [3] or NULL */, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Tokenisation (bit-exact index work).
  * image_to_rows : rows[b,i,3j+c] = img[b,c,i,j]           (Vi_Tools:389-391); rows_to_image inverse.
  * grid_transpose: out[b,j,3i+c]  = in[b,i,3j+c]           (Vi_Tools:394-395,397-398; self-inverse)
