@@ -190,6 +190,32 @@ def act_dtype(last_dim):
     return torch.bfloat16 if bf16_pipeline() and last_dim % 8 == 0 else torch.float32
 
 
+# ---- argument checks the device input entry points share (collate, augment, resize, resized crop, RandAugment) ----
+_RECORD_NAMES = {_lib.AugSample: "calm_aug_sample", _lib.EraseBox: "calm_erase_box", _lib.ResizeSample: "calm_resize_sample",
+                 _lib.RCropSample: "calm_rcrop_sample", _lib.RaSample: "calm_ra_sample"}
+
+
+def _u8_image_batch(who, img_u8, planar=False):
+    """img_u8 is a contiguous uint8 CUDA image batch (planar=True: of shape [B,3,Hs,Ws]); returns its shape."""
+    ok = img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.is_contiguous()
+    if not ok or (planar and (img_u8.dim() != 4 or img_u8.shape[1] != 3)):
+        raise TypeError(f"{who} expects a contiguous uint8 CUDA image batch" + (" [B,3,Hs,Ws]" if planar else ""))
+    return img_u8.shape
+
+
+def _records(who, t, B, struct, what="samples"):
+    """t is the device array of B `struct` records as a contiguous uint8 CUDA tensor [B, sizeof(struct)]; its pointer."""
+    size = C.sizeof(struct)
+    if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (B, size):
+        raise TypeError(f"{who}: {what} must be a contiguous uint8 CUDA tensor [B,{size}] ({_RECORD_NAMES[struct]} records)")
+    return t.data_ptr()
+
+
+def _out_hw(out, tokens):
+    """(H, W) of an output [B,3,H,W] or, tokens=True, [B,H,3W]."""
+    return (out.shape[1], out.shape[2] // 3) if tokens else (out.shape[2], out.shape[3])
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _cur_device = getattr(torch._C, "_cuda_getDevice", None)
 
@@ -744,9 +770,7 @@ class HipBackend:
     # ---- device-side collate -------------------------------------------------------------
     def collate_mix(self, img_u8, flip, out, mode, lam, box, mean, std):
         """img_u8 [B,3,H,W] uint8, flip [B] uint8 or None, out [B,3,H,W] fp32; mode 0/1/2 = none/MixUp/CutMix."""
-        if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or not img_u8.is_contiguous():
-            raise TypeError("collate_mix expects a contiguous uint8 CUDA image batch")
-        B, _, H, W = img_u8.shape
+        B, _, H, W = _u8_image_batch("collate_mix", img_u8)
         cbox = (C.c_int32 * 4)(*box) if box is not None else None
         cm, cs = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
         fp = flip.data_ptr() if flip is not None else None
@@ -756,13 +780,8 @@ class HipBackend:
     def collate_crop_mix(self, img_u8, crop_yx, flip, out, mode, lam, box, mean, std, tokens=False):
         """img_u8 [B,3,Hs,Ws] uint8; crop_yx [B,2] int32 on the device (or None); out [B,3,H,W] or, tokens=True,
         [B,H,3W] fp32 (the row tokens of the first Block)."""
-        if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or not img_u8.is_contiguous():
-            raise TypeError("collate_crop_mix expects a contiguous uint8 CUDA image batch")
-        B, _, Hs, Ws = img_u8.shape
-        if tokens:
-            H, W = out.shape[1], out.shape[2] // 3
-        else:
-            H, W = out.shape[2], out.shape[3]
+        B, _, Hs, Ws = _u8_image_batch("collate_crop_mix", img_u8)
+        H, W = _out_hw(out, tokens)
         if crop_yx is not None and (crop_yx.dtype != torch.int32 or not crop_yx.is_cuda or not crop_yx.is_contiguous()):
             raise TypeError("collate_crop_mix: crop_yx must be a contiguous int32 CUDA tensor [B,2]")
         cbox = (C.c_int32 * 4)(*box) if box is not None else None
@@ -783,24 +802,17 @@ class HipBackend:
     @staticmethod
     def _augment_args(who, img_u8, samples, gray_mean, out, mode, lam, box, mean, std, tokens):
         """The tensor checks and the C arguments, up to std, that calm_augment_collate and calm_augment_collate_erase share."""
-        if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or not img_u8.is_contiguous():
-            raise TypeError(f"{who} expects a contiguous uint8 CUDA image batch")
-        B, _, Hs, Ws = img_u8.shape
-        if tokens:
-            H, W = out.shape[1], out.shape[2] // 3
-        else:
-            H, W = out.shape[2], out.shape[3]
+        B, _, Hs, Ws = _u8_image_batch(who, img_u8)
+        H, W = _out_hw(out, tokens)
         if out.shape[0] != B or out.numel() != B * 3 * H * W or not out.is_contiguous():
             raise TypeError(f"{who}: out must be contiguous [B,3,H,W] or, tokens=True, [B,H,3W]")
-        if (samples.dtype != torch.uint8 or not samples.is_cuda or not samples.is_contiguous()
-                or tuple(samples.shape) != (B, C.sizeof(_lib.AugSample))):
-            raise TypeError(f"{who}: samples must be a contiguous uint8 CUDA tensor [B,48] (calm_aug_sample records)")
+        samples_ptr = _records(who, samples, B, _lib.AugSample)
         if (gray_mean.dtype != torch.float32 or not gray_mean.is_cuda or not gray_mean.is_contiguous()
                 or gray_mean.numel() != B):
             raise TypeError(f"{who}: gray_mean must be a contiguous fp32 CUDA tensor [B]")
         cbox = (C.c_int32 * 4)(*box) if box is not None else None
         cm, cs = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-        return (img_u8.data_ptr(), Hs, Ws, samples.data_ptr(), gray_mean.data_ptr(), _ptr(out), B, H, W, int(tokens), mode,
+        return (img_u8.data_ptr(), Hs, Ws, samples_ptr, gray_mean.data_ptr(), _ptr(out), B, H, W, int(tokens), mode,
                 float(lam), cbox, cm, cs)
 
     def augment_collate_erase(self, img_u8, samples, gray_mean, out, mode, lam, box, mean, std, boxes, value, key,
@@ -811,14 +823,12 @@ class HipBackend:
         for per-pixel standard normal noise, or three floats in normalised space; key: (seed, offset), the noise key,
         integers below 2^64.  The other arguments as augment_collate."""
         args = self._augment_args("augment_collate_erase", img_u8, samples, gray_mean, out, mode, lam, box, mean, std, tokens)
-        if (boxes.dtype != torch.uint8 or not boxes.is_cuda or not boxes.is_contiguous()
-                or tuple(boxes.shape) != (img_u8.shape[0], C.sizeof(_lib.EraseBox))):
-            raise TypeError("augment_collate_erase: boxes must be a contiguous uint8 CUDA tensor [B,16] (calm_erase_box records)")
+        boxes_ptr = _records("augment_collate_erase", boxes, img_u8.shape[0], _lib.EraseBox, "boxes")
         seed, offset = (int(k) for k in key)
         if not (0 <= seed < 2 ** 64 and 0 <= offset < 2 ** 64):
             raise ValueError("augment_collate_erase: key is (seed, offset), two integers in [0, 2^64)")
         cv = (C.c_float * 3)(*value) if value is not None else None
-        _lib.check(self.lib.calm_augment_collate_erase(*args, boxes.data_ptr(), 0 if value is not None else 1, cv, seed,
+        _lib.check(self.lib.calm_augment_collate_erase(*args, boxes_ptr, 0 if value is not None else 1, cv, seed,
                                                        offset, _stream()),
                    "calm_augment_collate_erase")
 
@@ -832,10 +842,8 @@ class HipBackend:
         if not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 4 or out.shape[1] != 3 or not out.is_contiguous():
             raise TypeError("resize_u8: out must be a contiguous uint8 CUDA tensor [B,3,oh,ow]")
         B, _, oh, ow = out.shape
-        if (samples.dtype != torch.uint8 or not samples.is_cuda or not samples.is_contiguous()
-                or tuple(samples.shape) != (B, C.sizeof(_lib.ResizeSample))):
-            raise TypeError("resize_u8: samples must be a contiguous uint8 CUDA tensor [B,16] (calm_resize_sample records)")
-        _lib.check(self.lib.calm_resize_u8(packed.data_ptr(), packed.numel(), samples.data_ptr(), out.data_ptr(), B, oh, ow,
+        samples_ptr = _records("resize_u8", samples, B, _lib.ResizeSample)
+        _lib.check(self.lib.calm_resize_u8(packed.data_ptr(), packed.numel(), samples_ptr, out.data_ptr(), B, oh, ow,
                                            _stream()), "calm_resize_u8")
 
     def resized_crop(self, packed, samples, out, mean=None, std=None, tokens=False):
@@ -851,20 +859,19 @@ class HipBackend:
         if tokens:
             if out.dtype != torch.float32 or out.dim() != 3 or out.shape[2] % 3 != 0:
                 raise TypeError("resized_crop: tokens=True writes a contiguous fp32 CUDA tensor [B,H,3W]")
-            kind, (B, H, W) = _lib.RCROP_TOKENS, (out.shape[0], out.shape[1], out.shape[2] // 3)
+            kind = _lib.RCROP_TOKENS
         else:
             if out.dim() != 4 or out.shape[1] != 3:
                 raise TypeError("resized_crop: out must be a contiguous uint8 or fp32 CUDA tensor [B,3,H,W]")
-            kind, (B, _, H, W) = (_lib.RCROP_U8 if out.dtype == torch.uint8 else _lib.RCROP_IMAGE), out.shape
-        if (samples.dtype != torch.uint8 or not samples.is_cuda or not samples.is_contiguous()
-                or tuple(samples.shape) != (B, C.sizeof(_lib.RCropSample))):
-            raise TypeError("resized_crop: samples must be a contiguous uint8 CUDA tensor [B,48] (calm_rcrop_sample records)")
+            kind = _lib.RCROP_U8 if out.dtype == torch.uint8 else _lib.RCROP_IMAGE
+        B, (H, W) = out.shape[0], _out_hw(out, tokens)
+        samples_ptr = _records("resized_crop", samples, B, _lib.RCropSample)
         cm = cs = None
         if kind != _lib.RCROP_U8:
             if mean is None or std is None or len(mean) != 3 or len(std) != 3:
                 raise TypeError("resized_crop: an fp32 output needs mean and std, three floats each")
             cm, cs = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-        _lib.check(self.lib.calm_resized_crop(packed.data_ptr(), packed.numel(), samples.data_ptr(), out.data_ptr(), B, H, W,
+        _lib.check(self.lib.calm_resized_crop(packed.data_ptr(), packed.numel(), samples_ptr, out.data_ptr(), B, H, W,
                                               kind, cm, cs, _stream()), "calm_resized_crop")
 
     def randaugment_scratch_bytes(self, B, H, W):
@@ -881,16 +888,12 @@ class HipBackend:
         [B,3,H,W] uint8, written; n_slots: the slot passes to run (the batch's largest n_ops); stats_mask: bit k set when
         some sample's slot k is Contrast, AutoContrast or Equalize; fill: three integers 0 .. 255 (None: black);
         scratch: a uint8 CUDA tensor of at least randaugment_scratch_bytes(B, H, W) bytes (None: allocated here)."""
-        if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[1] != 3 or not img_u8.is_contiguous():
-            raise TypeError("randaugment_u8 expects a contiguous uint8 CUDA image batch [B,3,Hs,Ws]")
-        B, _, Hs, Ws = img_u8.shape
+        B, _, Hs, Ws = _u8_image_batch("randaugment_u8", img_u8, planar=True)
         if (not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 4 or out.shape[0] != B or out.shape[1] != 3
                 or not out.is_contiguous()):
             raise TypeError("randaugment_u8: out must be a contiguous uint8 CUDA tensor [B,3,H,W]")
         H, W = out.shape[2], out.shape[3]
-        if (samples.dtype != torch.uint8 or not samples.is_cuda or not samples.is_contiguous()
-                or tuple(samples.shape) != (B, C.sizeof(_lib.RaSample))):
-            raise TypeError("randaugment_u8: samples must be a contiguous uint8 CUDA tensor [B,160] (calm_ra_sample records)")
+        samples_ptr = _records("randaugment_u8", samples, B, _lib.RaSample)
         need = self.randaugment_scratch_bytes(B, H, W)
         if scratch is None:
             scratch = torch.empty(need, dtype=torch.uint8, device=img_u8.device)
@@ -901,7 +904,7 @@ class HipBackend:
             if len(fill) != 3 or not all(int(v) == v and 0 <= v <= 255 for v in fill):
                 raise ValueError(f"randaugment_u8: fill is three integers in 0 .. 255, got {fill!r}")
             cf = (C.c_uint8 * 3)(*(int(v) for v in fill))
-        _lib.check(self.lib.calm_randaugment_u8(img_u8.data_ptr(), Hs, Ws, samples.data_ptr(), out.data_ptr(), B, H, W,
+        _lib.check(self.lib.calm_randaugment_u8(img_u8.data_ptr(), Hs, Ws, samples_ptr, out.data_ptr(), B, H, W,
                                                 int(n_slots), int(stats_mask), cf, scratch.data_ptr(), scratch.numel(),
                                                 _stream()), "calm_randaugment_u8")
 

@@ -14,6 +14,7 @@
 // owns, and the fill is a constant or counter-based noise — no extra LDS, no atomics, nothing addressed through the box.
 #include "common.h"
 #include "philox.h"
+#include "pixel_quad.h"
 
 namespace {
 
@@ -74,8 +75,6 @@ __device__ __forceinline__ void jitter(float& r, float& g, float& b, const calm_
         }
     }
 }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // index of the sample's (first) contrast operation in its order, 4 = none
 __device__ __forceinline__ int contrast_slot(const calm_aug_sample& s) {
@@ -163,8 +162,6 @@ __device__ __forceinline__ void blur4(const float* __restrict__ p, int ly, int l
     for (int k = 0; k < 4; ++k) out[k] = we * h[0][k] + wc * h[1][k] + we * h[2][k];
 }
 
-struct AugNorm { float mean[3], inv[3]; };
-
 // RandomErasing (calm_augment_collate_erase): the per-sample boxes, the fill and the noise key.  Without ERASE the kernel
 // reads none of it.
 struct AugErase {
@@ -212,7 +209,7 @@ __global__ __launch_bounds__(NT) void augment_collate_kernel(const unsigned char
                                                              const calm_aug_sample* __restrict__ samples,
                                                              const float* __restrict__ gray_mean,
                                                              float* __restrict__ out, int B, int H, int W, int mode,
-                                                             float lam, int y1, int y2, int x1, int x2, AugNorm nm,
+                                                             float lam, int y1, int y2, int x1, int x2, Norm3 nm,
                                                              AugErase er) {
     __shared__ float tile[2][3 * PLANE];
     const int b = blockIdx.z, ty0 = blockIdx.y * TH, tx0 = blockIdx.x * TW;
@@ -272,39 +269,8 @@ __global__ __launch_bounds__(NT) void augment_collate_kernel(const unsigned char
             }
         }
     }
-    if (TOKENS) {                                   // out[b, y, 3 x + c]: 12 consecutive floats
-        float* dst = out + ((long)b * H + y) * 3 * W + 3 * x;
-        if (VEC) {                                  // W % 4 == 0: x + 3 < W and dst is 16-byte aligned
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                f32x4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = v[(4 * q + j) % 3][(4 * q + j) / 3];
-                *reinterpret_cast<f32x4*>(dst + 4 * q) = o;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (x + k < W) {
-                    dst[3 * k] = v[0][k]; dst[3 * k + 1] = v[1][k]; dst[3 * k + 2] = v[2][k];
-                }
-        }
-    } else {                                        // out[b, c, y, x]
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float* dst = out + (((long)b * 3 + c) * H + y) * W + x;
-            if (VEC) {
-                f32x4 o;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) o[k] = v[c][k];
-                *reinterpret_cast<f32x4*>(dst) = o;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (x + k < W) dst[k] = v[c][k];
-            }
-        }
-    }
+    if (TOKENS) store_quad_tokens<VEC>(out, b, H, W, y, x, v);
+    else store_quad_f32<VEC>(out, b, H, W, y, x, v);
 }
 
 // Both entry points: the argument checks, the statistics launch and the collate launch; erase: null = ERASE off
@@ -317,8 +283,7 @@ int augment_collate(const uint8_t* img_u8, int32_t Hs, int32_t Ws, const calm_au
     const int tiles_y = (H + TH - 1) / TH, tiles_x = (W + TW - 1) / TW;
     if (B > 65535 || tiles_y > 65535 || (int64_t)H * W > (1 << 30)) return CALM_E_UNSUPP;   // grid dimensions y and z; int pixel index
     const int y1 = box ? box[0] : 0, y2 = box ? box[1] : 0, x1 = box ? box[2] : 0, x2 = box ? box[3] : 0;
-    AugNorm nm;
-    for (int c = 0; c < 3; ++c) { nm.mean[c] = mean[c]; nm.inv[c] = 1.0f / std[c]; }
+    const Norm3 nm = norm3(mean, std);
     int rc = calm_launch(augment_stats_kernel, B, NT, 0, stream, img_u8, Hs, Ws, samples_dev, gray_mean, H, W);
     if (rc != 0) return rc;
     const bool vec = W % 4 == 0 && aligned16(out);

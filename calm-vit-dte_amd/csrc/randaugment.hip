@@ -47,8 +47,6 @@ struct RaSrc {
     }
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
 __device__ __forceinline__ RaSrc ra_source(const uint8_t* src, int Hs, int Ws, int first, const calm_ra_sample* s, int b, int H,
                                            int W) {
     RaSrc r;

@@ -927,6 +927,24 @@ class DeviceCollate:
         return out, y
 
 
+def _records_to_device(t, device):
+    """A numpy record array as the uint8 tensor [B, itemsize] of its bytes on `device`: one host-to-device copy."""
+    import numpy as np
+    return torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize)).to(device)
+
+
+def _meta_columns(who, meta, max_side):
+    """(offset, h, w), int64 [B] each, of a RaggedU8Collate meta table; the sides are checked against 1 .. max_side."""
+    import numpy as np
+    m = np.asarray(meta.cpu() if isinstance(meta, torch.Tensor) else meta, dtype=np.int64)
+    if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] < 1:
+        raise ValueError(f"{who}: meta must be [B, 3] (offset, h, w), got shape {m.shape}")
+    off, h, w = m[:, 0], m[:, 1], m[:, 2]
+    if (h < 1).any() or (w < 1).any() or (h > max_side).any() or (w > max_side).any():
+        raise ValueError(f"{who}: source sides must be within 1 .. {max_side}")
+    return off, h, w
+
+
 class DeviceAugment:
     """The per-sample random parameters of the reference's colour augmentations (distributed_trainer_cls.py:131-135,
     defaults from there) for the device pass calm_augment_collate:
@@ -1009,8 +1027,7 @@ class DeviceAugment:
         if flips is not None:
             f = np.asarray(flips).astype(bool)
             t["flags"] = (t["flags"] & ~np.uint32(_lib.AUG_FLIP)) | np.where(f, _lib.AUG_FLIP, 0).astype(np.uint32)
-        host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
-        return host.to(device)
+        return _records_to_device(t, device)
 
 
 class DeviceErase:
@@ -1097,9 +1114,7 @@ class DeviceErase:
     def pack(table, device="cuda"):
         """The device array of calm_erase_box records, [B,16] uint8, in one host-to-device copy."""
         import numpy as np
-        t = np.array(table, dtype=DeviceErase.dtype(), copy=True)
-        host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
-        return host.to(device)
+        return _records_to_device(np.array(table, dtype=DeviceErase.dtype(), copy=True), device)
 
 
 class DeviceRandAugment:
@@ -1303,8 +1318,7 @@ class DeviceRandAugment:
             t["y0"], t["x0"] = c[:, 0], c[:, 1]
         if flips is not None:
             t["flip"] = np.asarray(flips).astype(bool).astype(np.uint32)
-        host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
-        return host.to(device)
+        return _records_to_device(t, device)
 
     def __call__(self, img_u8, corners=None, flips=None, crop=None, table=None):
         """img_u8 [B,3,Hs,Ws] uint8 on the device -> [B,3,H,W] uint8: the window crop=(H, W) at `corners` ([B,2] host
@@ -1389,24 +1403,17 @@ class DeviceResize:
         """The host array of calm_resize_sample records for a meta table, checked against a buffer of nbytes bytes (the
         kernel would write zeros for a record it cannot read; here it is an error)."""
         import numpy as np
-        m = np.asarray(meta.cpu() if isinstance(meta, torch.Tensor) else meta, dtype=np.int64)
-        if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] < 1:
-            raise ValueError(f"DeviceResize: meta must be [B, 3] (offset, h, w), got shape {m.shape}")
-        off, h, w = m[:, 0], m[:, 1], m[:, 2]
-        if (h < 1).any() or (w < 1).any() or (h > cls.MAX_SIDE).any() or (w > cls.MAX_SIDE).any():
-            raise ValueError(f"DeviceResize: source sides must be within 1 .. {cls.MAX_SIDE}")
+        off, h, w = _meta_columns("DeviceResize", meta, cls.MAX_SIDE)
         if (off < 0).any() or (off + 3 * h * w > nbytes).any():
             raise ValueError("DeviceResize: an image lies outside the packed buffer")
-        t = np.zeros(len(m), dtype=cls.dtype())
+        t = np.zeros(len(off), dtype=cls.dtype())
         t["offset"], t["h"], t["w"] = off, h, w
         return t
 
     @classmethod
     def pack(cls, meta, nbytes, device="cuda"):
         """The device array of calm_resize_sample records, [B,16] uint8, in one host-to-device copy."""
-        import numpy as np
-        t = cls.records(meta, nbytes)
-        return torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize)).to(device)
+        return _records_to_device(cls.records(meta, nbytes), device)
 
     def __call__(self, packed_dev, meta):
         from .backend import get_backend
@@ -1539,13 +1546,8 @@ class DeviceResizedCrop:
         """The host array of calm_rcrop_sample records for a meta table ([B, 3] of (offset, h, w)), checked against a
         buffer of nbytes bytes: what the kernel would answer with zeros is an error here.  .random_resized draws here."""
         import numpy as np
-        m = np.asarray(meta.cpu() if isinstance(meta, torch.Tensor) else meta, dtype=np.int64)
-        if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] < 1:
-            raise ValueError(f"DeviceResizedCrop: meta must be [B, 3] (offset, h, w), got shape {m.shape}")
-        B, (H, W) = len(m), self.size
-        off, h, w = m[:, 0], m[:, 1], m[:, 2]
-        if (h < 1).any() or (w < 1).any() or (h > self.MAX_SIDE).any() or (w > self.MAX_SIDE).any():
-            raise ValueError(f"DeviceResizedCrop: source sides must be within 1 .. {self.MAX_SIDE}")
+        off, h, w = _meta_columns("DeviceResizedCrop", meta, self.MAX_SIDE)
+        B, (H, W) = len(off), self.size
         if (corners is not None) != (self.kind == "window"):
             raise ValueError("DeviceResizedCrop: corners ([B, 2] of (y0, x0)) are given to .window and to nothing else")
         t = np.zeros(B, dtype=self.dtype())
@@ -1585,9 +1587,7 @@ class DeviceResizedCrop:
 
     def pack(self, meta, nbytes, corners=None, device="cuda"):
         """The device array of calm_rcrop_sample records, [B,48] uint8, in one host-to-device copy."""
-        import numpy as np
-        t = self.records(meta, nbytes, corners)
-        return torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize)).to(device)
+        return _records_to_device(self.records(meta, nbytes, corners), device)
 
     def __call__(self, packed_dev, meta, corners=None, out="u8"):
         from .backend import get_backend

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is the device code of two versions of the HIP sources the same?  (No GPU needed.)
 
-    compare_device_asm.py OLD NEW [--jobs N] [--only norm_act.hip ...]
+    compare_device_asm.py OLD NEW [--jobs N] [--only norm_act.hip ...] [--rename FROM=TO ...]
 
 OLD and NEW are two assembly files, two directories of `<source>.s` files, or two checkouts of this repository; a
 checkout's SOURCES (calm-vit-dte_amd/build.py) are compiled with the build's FLAGS plus `--cuda-device-only -S` into a
@@ -11,6 +11,8 @@ The comparison is per function symbol, not per file: comments, debug / `.file` d
 and local labels are renumbered in order of appearance, so moving or reordering host code, or code of OTHER kernels,
 does not show.  What remains has to match exactly — instructions, registers, and the kernel descriptor
 (`.amdhsa_*`: registers, LDS, scratch).  Exit status 0: the same kernels in every file, each with identical text.
+A kernel's symbol holds the mangled types of its parameters, so renaming a parameter's struct renames the kernel:
+--rename FROM=TO replaces FROM in OLD's text first (--rename NS_7AugNormE=5Norm3), and the kernels pair up again.
 """
 import argparse
 import importlib.util
@@ -25,10 +27,12 @@ DROP = re.compile(r"\s*\.(file|loc|cfi_\w+|ident|addrsig\w*|p2align|section|text
 LOCAL = re.compile(r"\.L[A-Za-z_]*\d+(?:_\d+)?")
 
 
-def functions(path):
+def functions(path, rename=()):
     """{symbol: normalised text}, set of kernel symbols."""
     funcs, kernels, cur, name = {}, set(), None, None
     for raw in open(path, errors="replace"):
+        for old, new in rename:
+            raw = raw.replace(old, new)
         line = raw.split(";", 1)[0].rstrip()
         if not line.strip():
             continue
@@ -88,6 +92,7 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--only", nargs="*", default=[])
+    ap.add_argument("--rename", nargs="*", default=[], metavar="FROM=TO")
     a = ap.parse_args()
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
@@ -102,7 +107,7 @@ def main():
                 bad += 1
             pairs = [(f, old[f], new[f]) for f in sorted(set(old) & set(new))]
         for f, po, pn in pairs:
-            (fo, ko), (fn, kn) = functions(po), functions(pn)
+            (fo, ko), (fn, kn) = functions(po, [r.split("=", 1) for r in a.rename]), functions(pn)
             differ = sorted(s for s in set(fo) & set(fn) if fo[s] != fn[s])
             gone, added = sorted(set(fo) - set(fn)), sorted(set(fn) - set(fo))
             print(f"{f}: {len(kn)} kernels ({len(fn)} symbols); {len(differ)} differ, {len(gone)} gone, {len(added)} new")
