@@ -101,6 +101,11 @@ class GradStat(C.Structure):
                 ("nonfinite", _i32), ("bad_calls", _i32), ("first_bad_call", _i32)]
 
 
+class SamHparams(C.Structure):
+    """struct calm_sam_hparams (16 bytes)."""
+    _fields_ = [("rho", _f32), ("eps", _f32), ("eta", _f32), ("adaptive", _i32)]
+
+
 class CastEntry(C.Structure):
     """struct calm_cast_entry."""
     _fields_ = [("src", _p), ("dst", _p), ("numel", _i64), ("chunk0", _i32), ("reserved", _i32)]
@@ -231,6 +236,9 @@ SIGNATURES = {
     "calm_grad_accum": (_i32, [_p, _i32, _p, _i32, _p, _p, _i32, _p]),
     "calm_grad_stats_scratch_floats": (_i64, [_i32, _i32]),
     "calm_grad_stats": (_i32, [_p, _i32, _p, _i32, C.POINTER(OptimHparams), _p, _p, _p, _p, _p, _p]),
+    "calm_sam_scratch_floats": (_i64, [_i32, _i32]),
+    "calm_sam_perturb": (_i32, [_p, _i32, _p, _i32, C.POINTER(SamHparams), _p, _p, _p, _p, _p]),
+    "calm_sam_restore": (_i32, [_p, _i32, _p, _i32, _p, _p]),
     "calm_ema_chunk_elems": (_i32, []),
     "calm_ema_update": (_i32, [_p, _i32, _p, _i32, _f32, _i32, _p, _p, _p, _p]),
     "calm_ema_swap": (_i32, [_p, _i32, _p, _i32, _p]),

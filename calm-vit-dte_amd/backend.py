@@ -974,6 +974,36 @@ class HipBackend:
                                             C.byref(h), plan.step_dev.data_ptr(), _ptr(grad_scale, True), out.data_ptr(),
                                             summary.data_ptr(), _ptr(scratch), _stream()), "calm_grad_stats")
 
+    def sam_scratch_floats(self, plan):
+        """calm_sam_scratch_floats for the table of `plan` (host only)."""
+        return int(self.lib.calm_sam_scratch_floats(plan.n, plan.n_chunks))
+
+    def sam_perturb(self, plan, grads, hp, grad_scale, backup_ptrs_dev, scratch, stats_out):
+        """calm_sam_perturb over the table of `plan` with the gradient pointers of the first pass, uploaded as for
+        optim_step.  hp = (rho, eps, eta, adaptive); grad_scale: device scalar or None; backup_ptrs_dev: int64 device
+        tensor of plan.n addresses of fp32 storage shaped like the parameters; scratch: the caller's OWN float32 buffer of
+        sam_scratch_floats(plan) elements — never plan.scratch, which belongs to the step; stats_out[3] <- norm,
+        found_inf, scale."""
+        if backup_ptrs_dev.numel() != plan.n or backup_ptrs_dev.dtype != torch.int64 or not backup_ptrs_dev.is_cuda:
+            raise ValueError("sam_perturb expects one int64 backup address per tensor of the plan, on the device")
+        if scratch.dtype != torch.float32 or scratch.numel() < self.sam_scratch_floats(plan):
+            raise ValueError("sam_perturb: scratch smaller than calm_sam_scratch_floats answers")
+        if stats_out.dtype != torch.float32 or stats_out.numel() != 3:
+            raise ValueError("sam_perturb expects a float32[3] stats_out")
+        plan.upload(np.asarray([_ptr(g) for g in grads], dtype=np.uint64))
+        rho, eps, eta, adaptive = hp
+        h = _lib.SamHparams(rho, eps, eta, int(adaptive))
+        _lib.check(self.lib.calm_sam_perturb(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
+                                             C.byref(h), _ptr(grad_scale, True), backup_ptrs_dev.data_ptr(), _ptr(scratch),
+                                             _ptr(stats_out), _stream()), "calm_sam_perturb")
+
+    def sam_restore(self, plan, backup_ptrs_dev):
+        """calm_sam_restore: the bits calm_sam_perturb saved, back into the parameters of `plan`."""
+        if backup_ptrs_dev.numel() != plan.n or backup_ptrs_dev.dtype != torch.int64 or not backup_ptrs_dev.is_cuda:
+            raise ValueError("sam_restore expects one int64 backup address per tensor of the plan, on the device")
+        _lib.check(self.lib.calm_sam_restore(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
+                                             backup_ptrs_dev.data_ptr(), _stream()), "calm_sam_restore")
+
     # ---- weight EMA ---------------------------------------------------------------------
     def ema_plan(self, pairs):
         """pairs: [(fp32 parameter, its fp32 average of the same shape)] -> plan for ema_update / ema_swap."""

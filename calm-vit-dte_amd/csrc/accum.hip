@@ -29,9 +29,7 @@ __global__ __launch_bounds__(NT) void accum_gw(const calm_optim_tensor* __restri
     const calm_optim_tensor e = T[chunk_tensor[blockIdx.x]];
     if (!e.sn_sigma) return;
     const auto [i0, i1] = chunk_span(blockIdx.x, CHUNK, e.chunk0, e.numel);
-    float gw = 0.f;
-    for (long i = i0 + threadIdx.x; i < i1; i += NT) gw += e.grad[i] * e.param[i];
-    gw = block_sum_256(gw, red);
+    const float gw = chunk_gw_partial(e, i0, i1, red);
     if (threadIdx.x == 0) chunk_part[blockIdx.x] = gw;
 }
 
@@ -93,14 +91,8 @@ __global__ __launch_bounds__(NT) void accum_apply(const calm_optim_tensor* __res
     gf32* a = (gf32*)acc[t];
     if (e.sn_sigma) {                                            // (uniform over the workgroup)
         const float sg = e.sn_sigma[0];
-        if (threadIdx.x == 0) {
-            const int nch = chunk_count(CHUNK, e.numel);
-            float gw = 0.f;
-            for (int k = 0; k < nch; ++k) gw += chunk_part[e.chunk0 + k];      // fixed order: chunk 0, 1, 2, ...
-            c_lds = gw / sg;                                     // <G, W_orig / sigma>, as optim_finalize forms it
-        }
-        __syncthreads();
-        accum_span<FIRST, true>(e, g, a, i0, i1, c_lds, 1.0f / sg);
+        const float c = tensor_sn_c(e, chunk_part, sg, &c_lds);
+        accum_span<FIRST, true>(e, g, a, i0, i1, c, 1.0f / sg);
     } else {
         accum_span<FIRST, false>(e, g, a, i0, i1, 0.f, 1.f);
     }

@@ -32,6 +32,30 @@ __device__ __forceinline__ ChunkSpan chunk_span(Index chunk, int chunk_len, int 
 // chunks of an entry of `len` elements: what the host counted from chunk0 on
 __device__ __forceinline__ int chunk_count(int chunk_len, long len) { return (int)((len + chunk_len - 1) / chunk_len); }
 
+// The deferred spectral-norm coefficient c = <G, W_orig> / sigma of a tensor of calm_optim_step's table, in the two steps
+// calm_grad_accum, calm_grad_stats and calm_sam_perturb share, so that c has in all of them the bits calm_optim_step gives
+// it (optim_stats forms the same partial next to its other sums).  256-thread workgroups.
+// Step 1, one workgroup per chunk [i0, i1): thread t adds the elements i0 + t, i0 + t + 256, ... serially, then
+// block_sum_256 (red: four floats of LDS); every thread returns the chunk's partial.
+__device__ __forceinline__ float chunk_gw_partial(const calm_optim_tensor& e, long i0, long i1, float* red) {
+    float gw = 0.f;
+    for (long i = i0 + threadIdx.x; i < i1; i += 256) gw += e.grad[i] * e.param[i];
+    return block_sum_256(gw, red);
+}
+// Step 2, any workgroup: one thread adds the tensor's partials in chunk order (chunks^2 serial loads per tensor when
+// every workgroup of the tensor does it) and divides by sigma; broadcast through *c_lds.
+__device__ __forceinline__ float tensor_sn_c(const calm_optim_tensor& e, const float* __restrict__ chunk_gw, float sg,
+                                             float* c_lds) {
+    if (threadIdx.x == 0) {
+        const int nch = chunk_count(CHUNK_ELEMS, e.numel);
+        float gw = 0.f;
+        for (int k = 0; k < nch; ++k) gw += chunk_gw[e.chunk0 + k];        // fixed order: chunk 0, 1, 2, ...
+        *c_lds = gw / sg;                                    // <G, W_orig / sigma>, as optim_finalize forms it
+    }
+    __syncthreads();
+    return *c_lds;
+}
+
 // The loop of a kernel whose pointers come out of a table, so that the compiler cannot know that they do not alias and
 // will not move a load across a store: a thread issues the loads of U accesses of W elements each ahead of the first
 // store.  Over [i0, end), a span of at most one chunk with end - i0 a multiple of W (end <= i0: nothing); load(i) returns

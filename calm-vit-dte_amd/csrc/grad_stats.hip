@@ -41,9 +41,7 @@ __global__ __launch_bounds__(NT) void gstat_gw(const calm_optim_tensor* __restri
     const calm_optim_tensor e = T[chunk_tensor[blockIdx.x]];
     if (!e.sn_sigma) return;
     const auto [i0, i1] = chunk_span(blockIdx.x, CHUNK, e.chunk0, e.numel);
-    float gw = 0.f;
-    for (long i = i0 + threadIdx.x; i < i1; i += NT) gw += e.grad[i] * e.param[i];
-    gw = block_sum_256(gw, red);
+    const float gw = chunk_gw_partial(e, i0, i1, red);
     if (threadIdx.x == 0) chunk_gw[blockIdx.x] = gw;
 }
 
@@ -125,14 +123,7 @@ __global__ __launch_bounds__(NT) void gstat_chunks(const calm_optim_tensor* __re
     Acc a;
     if (e.sn_sigma) {                                            // (uniform over the workgroup)
         const float sg = e.sn_sigma[0];
-        if (threadIdx.x == 0) {
-            const int nch = chunk_count(CHUNK, e.numel);
-            float gw = 0.f;
-            for (int k = 0; k < nch; ++k) gw += chunk_gw[e.chunk0 + k];        // fixed order: chunk 0, 1, 2, ...
-            c_lds = gw / sg;                                     // <G, W_orig / sigma>, as optim_finalize forms it
-        }
-        __syncthreads();
-        const float c = c_lds, inv_sg = 1.0f / sg;
+        const float c = tensor_sn_c(e, chunk_gw, sg, &c_lds), inv_sg = 1.0f / sg;
         a = dir ? stats_span<true, true>(e, i0, i1, c, inv_sg, inv, inv_bc1, inv_sqrt_bc2, dp.eps)
                 : stats_span<true, false>(e, i0, i1, c, inv_sg, inv, 0.f, 0.f, 0.f);
     } else {

@@ -27,6 +27,10 @@ as set by torchrun):
         the generative job: Huber + kl_weight * kl on the image or on the device collate's row tokens, and Huber / MAE /
         MSE / PSNR / SSIM of held-out data tallied on the device (calm_recon_metrics); the best checkpoint follows the
         lowest validation Huber.
+  * `SharpnessAware` / `SamTrainStep` / `SamRegTrainStep` / `train(sam=)`   (no counterpart: the reference has no SAM)
+        sharpness-aware minimisation: calm_sam_perturb behind a first backward (in place, along the true gradient, the
+        bits saved), a second pass at the perturbed weights whose gradients calm_grad_accum finishes there,
+        calm_sam_restore, then the unchanged optimizer-side step.
 
 The model also works under stock `torch.nn.parallel.DistributedDataParallel` (that is what the
 reference's train() does with it); the reducer here is the MI355X-tuned equivalent.  Under DDP the step
@@ -1969,9 +1973,14 @@ class FusedClipAdamW(torch.optim.Optimizer):
     that is not the model's or has requires_grad=False, a negative lr.
 
     `monitor`: None, or the attached `GradMonitor` (`GradMonitor.attach()`), whose `observe()` every step — eager,
-    windowed or captured — calls on the step's gradients in front of the update."""
+    windowed or captured — calls on the step's gradients in front of the update.
+
+    `perturbed_by`: None, or the `SharpnessAware` whose perturbation the parameters carry right now: until its restore()
+    it stands in front of step() and refuses it (an attribute of the INSTANCE that perturb() sets and restore() removes,
+    so step() itself has no branch for it)."""
 
     monitor = None
+    perturbed_by = None
 
     def __init__(self, model, lr=3.1e-3, weight_decay=0.02, betas=(0.9, 0.98), eps=1e-8, max_norm=1.0, defer_sn=True,
                  groups=None):
@@ -2473,6 +2482,256 @@ class GradMonitor:
         return dict(norm=root(sum(t["grad_sq"] for t in tensors.values())), calls=calls, skipped=skipped,
                     first_bad=None if first_call < 0 else {"call": first_call, "tensor": self.names[first_tensor]},
                     groups=groups, tensors=tensors)
+
+
+def sam_perturb_torch(records, grads, hp, grad_scale, backups, stats_out):
+    """calm_sam_perturb in torch, for a backend without `sam_perturb` (CPU parameters), with the header's fp32 formula:
+    g' = G / grad_scale, for a record with `sn` g' = ((G - <G, W_orig>/sigma u v^T) * (1/sigma)) / grad_scale; s = g', or
+    with adaptive t = |w| + eta and s = t g'; norm = sqrt(sum s^2) over ALL records; found_inf when a RAW gradient element
+    is inf / NaN or the norm is not finite; scale = found_inf ? 0 : rho / (norm + eps).  Every backup receives its
+    parameter's bits; unless found_inf, w += (scale t) s.  hp = (rho, eps, eta, adaptive); stats_out[3] <- norm,
+    found_inf, scale."""
+    f32 = lambda x: torch.tensor(float(x), dtype=torch.float32)               # the ABI's hyper-parameters are fp32  # noqa: E731
+    rho, eps, eta = f32(hp[0]), f32(hp[1]), f32(hp[2])
+    adaptive = bool(hp[3])
+    inv = 1.0 / f32(float(grad_scale)) if grad_scale is not None else f32(1.0)
+    bad, total, dirs = False, torch.zeros((), dtype=torch.float32), []
+    for r, g in zip(records, grads):
+        g = g.detach().float().reshape(-1)
+        p = r["param"].detach().reshape(-1)
+        bad = bad or not bool(torch.isfinite(g).all())
+        if r["sn"] is not None:
+            u, v, sigma, rows, cols = r["sn"]
+            G = g.reshape(rows, cols)
+            c = (G * p.reshape(rows, cols)).sum() / sigma
+            g = ((G - (c * u)[:, None] * v[None, :]) * (1.0 / sigma)).reshape(-1)
+        g = g * inv
+        t = p.abs() + eta if adaptive else None
+        s = t * g if adaptive else g
+        total = total + (s * s).sum()
+        dirs.append((s, t))
+    norm = torch.sqrt(total)
+    bad = bad or not bool(torch.isfinite(norm))
+    scale = torch.zeros((), dtype=torch.float32) if bad else rho / (norm + eps)
+    stats_out[0], stats_out[1], stats_out[2] = norm, float(bad), scale
+    for r, b, (s, t) in zip(records, backups, dirs):
+        b.copy_(r["param"])
+        if not bad:
+            r["param"].add_(((scale * t) * s if adaptive else scale * s).reshape(r["param"].shape))
+
+
+def sam_restore_torch(records, backups):
+    """calm_sam_restore in torch: every parameter receives the bits of its backup."""
+    for r, b in zip(records, backups):
+        r["param"].copy_(b)
+
+
+class SharpnessAware:
+    """Sharpness-aware minimisation (SAM; adaptive=True: ASAM) on the table of a FusedClipAdamW / FusedClipAdamWindow.
+
+    `perturb()` behind the first backward moves every parameter IN PLACE by rho along the normalised TRUE gradient —
+    calm_sam_perturb corrects the `.grad` of the deferred spectral-norm layers, which between backward and step is not the
+    gradient, and divides by the GradScaler's scale — after saving its bits; `restore()` behind the second backward puts
+    the saved bits back (calm_sam_restore), so the addresses the optimizer plan, the EMA plan and the bf16 weight copies
+    cache stay valid and the weights return exactly, on every rank alike.  Four launches and one, no host synchronisation.
+    With adaptive=True the step of an element is rho t^2 g' / ||t g'||, t = |w| + eta.
+
+    `perturb()` reads the current `.grad`s (a parameter without one contributes zeros) and then sets EVERY `.grad` to None.
+    The second backward must start with no `.grad` left: then the gradient tail arms, the reducer's pack sees fresh
+    buffers, and autograd adopts the new gradients instead of adding them into the first pass's.  A non-finite gradient in
+    the first pass makes the perturbation zero (found_inf = 1, scale = 0, no parameter written); nothing else follows from
+    it here.  While the weights are perturbed the optimizer refuses to step.  The second pass's `.grad`s of the deferred
+    layers are gradients w.r.t. the weight normalised at w + e(w): finish them BEFORE restore() —
+    `FusedClipAdamWindow.accumulate()`, as SamTrainStep does — because the correction reads the weights through the table.
+
+    `read()` is the one host synchronisation: {"norm", "found_inf", "scale"} of the last perturb().  With CPU parameters,
+    or a backend without the entry points, `sam_perturb_torch` / `sam_restore_torch` do the same.  SAM keeps no state
+    between steps: nothing of it belongs to a TrainState."""
+
+    def __init__(self, model, optimizer, rho=0.05, adaptive=False, eta=0.01, eps=1e-12):
+        import numpy as np
+        if not isinstance(optimizer, FusedClipAdamW):
+            raise ValueError("SharpnessAware walks the table of the fused optimizer: it needs a FusedClipAdamW or a "
+                             f"FusedClipAdamWindow, got {type(optimizer).__name__}")
+        own = {id(p) for p in model.parameters()}
+        missing = [k for k, p in enumerate(optimizer.params) if id(p) not in own]
+        if missing:
+            raise ValueError(f"SharpnessAware: {len(missing)} parameters of the optimizer are not parameters of this model")
+        rho, eta, eps = float(rho), float(eta), float(eps)
+        if not (rho > 0.0 and math.isfinite(rho)):
+            raise ValueError(f"SharpnessAware: rho is a positive finite radius, got {rho!r}")
+        if not (eps > 0.0 and math.isfinite(eps)) or float(torch.tensor(eps, dtype=torch.float32)) <= 0.0:
+            raise ValueError(f"SharpnessAware: eps is a positive fp32 number, got {eps!r}")
+        if not (eta >= 0.0 and math.isfinite(eta)):
+            raise ValueError(f"SharpnessAware: eta is a non-negative finite number, got {eta!r}")
+        self.optimizer = optimizer
+        self.rho, self.adaptive, self.eta, self.eps = rho, bool(adaptive), eta, eps
+        dev = optimizer.params[0].device
+        self.native = dev.type == "cuda" and hasattr(optimizer.be, "sam_perturb")
+        self.backups = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in optimizer.params]
+        self.stats = torch.zeros(3, dtype=torch.float32, device=dev)         # [norm, found_inf, scale]
+        self._step_attr = None
+        if self.native:
+            ptrs = np.asarray([b.data_ptr() for b in self.backups], dtype=np.uint64)
+            self._backup_ptrs_dev = torch.from_numpy(ptrs.view(np.int64).copy()).to(dev)
+            self._scratch = torch.empty(optimizer.be.sam_scratch_floats(optimizer._plan), dtype=torch.float32, device=dev)
+
+    @property
+    def perturbed(self):
+        return self.optimizer.perturbed_by is self
+
+    def _hparams(self):
+        return (self.rho, self.eps, self.eta, int(self.adaptive))
+
+    @torch.no_grad()
+    def perturb(self, grad_scale=None):
+        """w -> w + e(w) from the current `.grad`s; grad_scale: the device scalar the loss was multiplied by, or None.
+        Every `.grad` is None afterwards."""
+        opt = self.optimizer
+        if opt.perturbed_by is not None:
+            raise RuntimeError("SharpnessAware.perturb: the parameters are already perturbed; restore() first")
+        opt._check_owner()                      # (with _check_plan: parameters / spectral-norm buffers moved since construction)
+        grads = opt._contiguous_grads(keep=False)
+        if self.native:
+            opt.be.sam_perturb(opt._plan, grads, self._hparams(), grad_scale, self._backup_ptrs_dev, self._scratch, self.stats)
+        else:
+            sam_perturb_torch(opt._records, grads, self._hparams(), grad_scale, self.backups, self.stats)
+        for p in opt.params:
+            p.grad = None
+        opt.perturbed_by = self
+        # the guard of optimizer.step(): an instance attribute in front of the method (and of a scheduler's counting
+        # wrapper, which is one too and is put back by restore())
+        self._step_attr = opt.__dict__.get("step")
+        opt.step = self._refuse_step
+
+    def _refuse_step(self, *args, **kw):
+        raise RuntimeError("FusedClipAdamW.step: the parameters carry a SharpnessAware perturbation; restore() comes "
+                           "before the step (the update belongs to the unperturbed weights)")
+
+    @torch.no_grad()
+    def restore(self):
+        """The bits perturb() saved, back into the parameters."""
+        opt = self.optimizer
+        if opt.perturbed_by is not self:
+            raise RuntimeError("SharpnessAware.restore: the parameters are not perturbed (perturb() comes first)")
+        opt._check_plan()
+        if self.native:
+            opt.be.sam_restore(opt._plan, self._backup_ptrs_dev)
+        else:
+            sam_restore_torch(opt._records, self.backups)
+        opt.perturbed_by = None
+        if self._step_attr is not None:
+            opt.step = self._step_attr
+        else:
+            del opt.step
+        self._step_attr = None
+
+    def read(self):
+        norm, found_inf, scale = (float(v) for v in self.stats.cpu())
+        return {"norm": norm, "found_inf": found_inf, "scale": scale}
+
+
+class SamTrainStep(TrainStep):
+    """TrainStep with sharpness-aware minimisation: two passes over the same batch per optimizer step.
+
+      1. forward, loss, backward at w (same autocast, same GradScaler scale), the gradient exchange held;
+      2. `sam.perturb(grad_scale=the current scale, read on the device as _optimizer_step reads it)`: w -> w + e(w),
+         every `.grad` released;
+      3. forward, loss, backward at w + e(w), then `optimizer.accumulate()`: the second pass's gradients are FINISHED here
+         (calm_grad_accum, a window of one), while the parameters still hold w + e(w) — the deferred spectral-norm
+         correction <G, W_orig / sigma> u v^T needs the W_orig, u, v, sigma of the forward that produced G, and behind the
+         restore the table would point at w instead;
+      4. `sam.restore()`: the saved bits of w; then the exchange of the finished gradients (`reduce_held()`);
+      5. TrainStep's unchanged optimizer-side sequence, which steps the window of one.
+
+    optimizer: a FusedClipAdamWindow (for step 3).  The step returns the loss and the output of the FIRST pass, and a
+    metrics object is fed by the first pass only.  EMA, the GradScaler bookkeeping and a GradMonitor (it observes the second
+    pass's gradients, those the step applies) are untouched.  A non-finite gradient in the first pass makes the
+    perturbation zero, so the second pass is an ordinary pass at w; nothing is skipped on its account: only the
+    optimizer's own found_inf, of the second pass's gradients, skips the update and backs the scale off.
+
+    In a world of more than one rank (reducer: a HeldGradReducer, whose bucket views become the window's accumulators) the
+    default (sync=False) is the per-rank perturbation of the SAM paper's m-sharpness: the first pass's gradients are NOT
+    exchanged, so the perturbed weights differ between the ranks and half the communication is saved; every rank finishes
+    its second-pass gradient with its own perturbed weights before the exchange, and restore() brings every rank back to
+    identical bits (saved bits, not a subtraction), so the parameters never drift.  The spectral-norm buffers u, v, sigma
+    do become rank-local then: the second forward iterates them on the rank's own perturbed weights (as BatchNorm
+    statistics are rank-local under data parallelism; a checkpoint holds rank 0's).  sync=True exchanges the first pass
+    through the reducer as well: one perturbation for all ranks, and the buffers stay replicated.  With sync=False a
+    model that is, or contains, a stock DistributedDataParallel is refused: it would all-reduce both backwards.
+
+    Two consequences of running the model twice: spectral norm's power iteration advances at both training forwards (as
+    torch's would under a two-pass closure), so the second pass's u, v, sigma are one iteration further; and dropout and
+    latent-noise keys are drawn in both passes, so the two passes see different masks / noise."""
+
+    def __init__(self, model, optimizer, reducer=None, sam=None, sync=False, **kw):
+        if not isinstance(sam, SharpnessAware) or sam.optimizer is not optimizer:
+            raise ValueError("SamTrainStep needs sam=SharpnessAware(model, optimizer) over this step's optimizer")
+        if not isinstance(optimizer, FusedClipAdamWindow):
+            raise TypeError("SamTrainStep needs a FusedClipAdamWindow: the second pass's gradients are finished by "
+                            "accumulate() while the weights are still perturbed (FusedClipAdamW.step would correct the "
+                            "spectral-norm gradients against the restored weights)")
+        if optimizer.window > 0:
+            raise RuntimeError("SamTrainStep: the optimizer has an open accumulation window")
+        self.sync = bool(sync)
+        if not self.sync and any(isinstance(mod, torch.nn.parallel.DistributedDataParallel) for mod in model.modules()):
+            raise TypeError("SamTrainStep(sync=False): DistributedDataParallel all-reduces every backward, the first "
+                            "pass's too; use the bare model with a HeldGradReducer, or sync=True")
+        if reducer is not None and reducer.enabled and not isinstance(reducer, HeldGradReducer):
+            raise TypeError("SamTrainStep needs a HeldGradReducer (BucketedGradReducer all-reduces every backward)")
+        super().__init__(model, optimizer, reducer=reducer, **kw)
+        self.sam = sam
+        self._second = False
+        self._batch = None
+        self._held = reducer is not None and reducer.enabled
+        if self._held:
+            reducer.hold = True
+            optimizer.bind_accumulators(reducer.views_of(optimizer.params))      # the finished gradients ARE the buckets
+
+    def __call__(self, x, y=None):
+        self._batch = (x, y)
+        try:
+            return super().__call__(x, y)
+        finally:
+            self._batch, self._second = None, False
+
+    def _finish(self, loss, y_hat):
+        if self._second:                        # the second pass: its backward, and its gradients finished at w + e(w)
+            self._backward(loss)
+            self.opt.accumulate()
+            return None
+        if self._held:
+            self.reducer.hold = not self.sync   # sync: the hooks launch the first pass's buckets
+        try:
+            self._backward(loss)
+            if self._held and self.sync:
+                self.reducer.finish()
+        finally:
+            if self._held:
+                self.reducer.hold = True
+        scale = self.scaler.scale(self._one) if self._clean_steps is not None else None
+        self.sam.perturb(grad_scale=scale)
+        metrics, self.metrics, self._second = self.metrics, None, True
+        try:
+            super().__call__(*self._batch)      # forward and loss of the task's step at w + e(w); re-enters _finish above
+        except BaseException:
+            self.opt.zero_grad()                # (discards the window, if the failure left one open)
+            raise
+        finally:
+            self.metrics, self._second = metrics, False
+            if self.sam.perturbed:
+                self.sam.restore()
+        if self._held:
+            self.reducer.reduce_held()
+        self._optimizer_step()
+        return loss.detach(), y_hat.detach()
+
+
+class SamRegTrainStep(SamTrainStep, RegTrainStep):
+    """RegTrainStep (the generative trainer's forward and loss) with SamTrainStep's two passes."""
+
+    def __init__(self, model, optimizer, reducer=None, sam=None, sync=False, kl_weight=0.1, **kw):
+        super().__init__(model, optimizer, reducer, sam=sam, sync=sync, kl_weight=kl_weight, **kw)
 
 
 def ema_weight(decay, schedule, n):
@@ -3311,13 +3570,21 @@ class _RegTask:
 
 
 _STEP_CLASSES = {("cls", False): TrainStep, ("cls", True): AccumTrainStep, ("reg", False): RegTrainStep,
-                 ("reg", True): AccumRegTrainStep, ("distill", False): DistillTrainStep, ("distill", True): AccumDistillTrainStep}
+                 ("reg", True): AccumRegTrainStep, ("distill", False): DistillTrainStep, ("distill", True): AccumDistillTrainStep,
+                 ("cls", "sam"): SamTrainStep, ("reg", "sam"): SamRegTrainStep}
 
 
-def _make_step(task, model, optimizer, reducer, accumulate, teacher, distill_kw, **kw):
+def _make_step(task, model, optimizer, reducer, accumulate, teacher, distill_kw, sam_kw=None, **kw):
     """The step of train(): (the task, or "distill" with a teacher) x (accumulate > 1) picks the class; kw are the
-    keywords every class takes, the task adds its own, a teacher adds distill_kw, a window adds accumulate=."""
+    keywords every class takes, the task adds its own, a teacher adds distill_kw, a window adds accumulate=.  sam_kw (the
+    normalised sam= of train(), which excludes a teacher and a window): the SharpnessAware is built here and the class is
+    the task's two-pass step."""
     kw.update(task.step_kw)
+    if sam_kw is not None:
+        sam_kw = dict(sam_kw)
+        sync = sam_kw.pop("sync")
+        return _STEP_CLASSES[task.name, "sam"](model, optimizer, reducer, sam=SharpnessAware(model, optimizer, **sam_kw),
+                                               sync=sync, **kw)
     args = (model, optimizer, reducer)
     if teacher is not None:
         args = (model, optimizer, teacher, reducer)
@@ -3385,13 +3652,15 @@ def _validate_epoch(task, model, ema, val_dataset, rank, world, device, batch_si
 def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_collate, crop, graph, device_metrics,
                       device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path, snapshot_every,
                       accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task, teacher, distill,
-                      param_groups, scheduler_step, monitor=None, random_erasing=None, label_smoothing=0.0, rand_augment=None):
+                      param_groups, scheduler_step, monitor=None, random_erasing=None, label_smoothing=0.0, rand_augment=None,
+                      sam=None):
     """Every refusal train() makes from its arguments alone: it touches no device and no process group, so a bad call
     fails before either exists.  Returns the normalised values the job is assembled from: accumulate (int), ema_kw
     (None without ema), distill_kw (DistillTrainStep's keywords, {} without a teacher), teacher_mod, resize (the
     DeviceResize or None), window (the DeviceResizedCrop.window or None), reg, per_step, monitor_kw (None without
     monitor=; "every" None: log_every), erase (None, a DeviceErase, or the dict of arguments one is built from),
-    label_smoothing (float), rand_augment (None, a DeviceRandAugment, or the dict of arguments one is built from)."""
+    label_smoothing (float), rand_augment (None, a DeviceRandAugment, or the dict of arguments one is built from), sam_kw
+    (None without sam=; SharpnessAware's keywords and "sync")."""
     from . import backend as _backend
     from types import SimpleNamespace
     if scheduler_step not in ("epoch", "step"):
@@ -3416,6 +3685,32 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
         if monitor_kw["top"] is None:
             raise ValueError('train: monitor["top"] counts tensors (>= 0), got None')
         monitor_kw["per_tensor"] = bool(monitor_kw["per_tensor"])
+    sam_kw = None
+    if sam is not None and sam is not False:
+        if isinstance(sam, dict):
+            sam_kw = dict(sam)
+        elif not isinstance(sam, bool) and isinstance(sam, (int, float)):
+            sam_kw = {"rho": sam}
+        else:
+            raise ValueError(f'train: sam is None, a radius rho or a dict with "rho" / "adaptive" / "eta" / "eps" / "sync", got {sam!r}')
+        if not set(sam_kw) <= {"rho", "adaptive", "eta", "eps", "sync"}:
+            raise ValueError(f'train: sam takes the keys "rho", "adaptive", "eta", "eps", "sync", got {sorted(sam_kw)}')
+        sam_kw = {"rho": 0.05, "adaptive": False, "eta": 0.01, "eps": 1e-12, "sync": False, **sam_kw}
+        rho = sam_kw["rho"]
+        if isinstance(rho, bool) or not isinstance(rho, (int, float)) or not (rho > 0.0 and math.isfinite(rho)):
+            raise ValueError(f'train: sam["rho"] is a positive finite radius, got {rho!r}')
+        if not (isinstance(optimizer, FusedClipAdamW) or (isinstance(optimizer, str) and optimizer == "fused")):
+            raise ValueError('train: sam= needs optimizer="fused" or a FusedClipAdamWindow (the perturbation walks the fused '
+                             "optimizer's table; a torch optimizer's `.grad`s are not corrected for it)")
+        if isinstance(optimizer, FusedClipAdamW) and not isinstance(optimizer, FusedClipAdamWindow):
+            raise ValueError('train: sam= needs optimizer="fused" or a FusedClipAdamWindow, not a FusedClipAdamW (the second '
+                             "pass's gradients are finished in a window of one while the weights are still perturbed)")
+        if graph:
+            raise ValueError("train: sam= excludes graph=True (a captured two-pass step is not supported)")
+        if int(accumulate) == accumulate and accumulate > 1:
+            raise ValueError("train: sam= excludes accumulate > 1 (SAM under an accumulation window is not supported)")
+        if teacher is not None:
+            raise ValueError("train: sam= excludes teacher= (SAM under distillation is not supported)")
     if task not in ("cls", "reg"):
         raise ValueError(f'train: task is "cls" or "reg", got {task!r}')
     reg = task == "reg"
@@ -3539,7 +3834,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
             EvalMetrics(num_classes, topk=val_topk)         # (refuses a malformed val_topk here, not after the first epoch)
     return SimpleNamespace(accumulate=accumulate, ema_kw=ema_kw, distill_kw=distill_kw, teacher_mod=teacher_mod, resize=resize,
                            window=window, reg=reg, per_step=scheduler_step == "step", monitor_kw=monitor_kw, erase=erase,
-                           label_smoothing=float(label_smoothing), rand_augment=randaug)
+                           label_smoothing=float(label_smoothing), rand_augment=randaug, sam_kw=sam_kw)
 
 
 class _TrainInput:
@@ -3642,8 +3937,9 @@ class _TrainInput:
         return x, y
 
 
-def _fused_optimizer(model, param_groups, accumulate, verbose):
-    """train(optimizer="fused"): FusedClipAdamW (FusedClipAdamWindow for an accumulation window) over the model on its
+def _fused_optimizer(model, param_groups, accumulate, verbose, window=False):
+    """train(optimizer="fused"): FusedClipAdamW (FusedClipAdamWindow for an accumulation window, or with `window`: sam=
+    finishes its second pass's gradients in a window of one) over the model on its
     device, with the groups of param_groups=; the frozen parameters lose requires_grad here, before the reducer and the EMA
     are built.  verbose: print one line per group."""
     group_kw = {}
@@ -3652,7 +3948,7 @@ def _fused_optimizer(model, param_groups, accumulate, verbose):
         for p in frozen:                    # before the reducer, the optimizer and the EMA: all three filter on it
             p.requires_grad_(False)
         group_kw = {"groups": groups}
-    optimizer = FusedClipAdamWindow(model, **group_kw) if accumulate > 1 else FusedClipAdamW(model, **group_kw)
+    optimizer = FusedClipAdamWindow(model, **group_kw) if accumulate > 1 or window else FusedClipAdamW(model, **group_kw)
     if param_groups is not None and verbose:
         for k, g in enumerate(optimizer.param_groups):
             print(f"Parameter group {k}: {len(g['params'])} tensors, {sum(p.numel() for p in g['params'])} elements, "
@@ -3773,7 +4069,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
           val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
           teacher=None, distill=None, param_groups=None, scheduler_step="epoch", monitor=None, random_erasing=None,
-          label_smoothing=0.0, rand_augment=None):
+          label_smoothing=0.0, rand_augment=None, sam=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -3963,14 +4259,32 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     random_erasing as before — takes its batch with crop=None and no flips.  The generator is part of a snapshot
     ("rand_augment"), so resume= continues bit for bit.  Works with both tasks, accumulate and graph= (the stage runs in
     front of the captured step).  With num_ops=0 the run equals the one without the argument bit for bit; without the
-    argument nothing changes."""
+    argument nothing changes.
+
+    sam=rho | {"rho": 0.05, "adaptive": False, "eta": 0.01, "eps": 1e-12, "sync": False} (sharpness-aware minimisation; needs
+    optimizer="fused", which then builds a FusedClipAdamWindow, or such an object): the step is a `SamTrainStep`
+    (`SamRegTrainStep` under task="reg") over a `SharpnessAware` — per batch a first forward / backward at w,
+    calm_sam_perturb (w += rho s / ||s|| along the TRUE gradient, in place, the bits saved; adaptive: ASAM's
+    s = (|w| + eta) g), a second forward / backward at the perturbed weights whose gradients calm_grad_accum finishes
+    there (a window of one), calm_sam_restore, and the unchanged optimizer-side sequence on those gradients: about two
+    plain steps of time.  The loss and output of the log lines, and the device metrics, are the first pass's; EMA, monitor= (it
+    sees the second pass's gradients, those applied), val_dataset, param_groups, device_collate and its companions work as
+    before.  In a world of more than one rank the reducer is a `HeldGradReducer`: with sync=False (default) the first
+    pass's gradients stay on their rank, so each rank perturbs along its own gradient and only the second pass is
+    exchanged (the spectral-norm buffers u, v, sigma are then rank-local); sync=True exchanges both.  Either way the
+    restored weights are the saved bits, identical on all ranks.
+    Spectral norm's power iteration advances at both forwards, and dropout / latent-noise keys are drawn in both.  SAM
+    holds no state between steps, so snapshots / resume= stay bit for bit.  The returned model carries the SharpnessAware
+    as `model._calm_sam`.  Refused: graph=True, accumulate > 1, teacher=, unknown keys, rho <= 0, a torch optimizer or a
+    FusedClipAdamW without the window."""
     from functools import partial
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
     args = _check_train_args(initializer, optimizer, use_gpu, num_classes, device_collate, crop, graph, device_metrics,
                           device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path,
                           snapshot_every, accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task,
-                          teacher, distill, param_groups, scheduler_step, monitor, random_erasing, label_smoothing, rand_augment)
+                          teacher, distill, param_groups, scheduler_step, monitor, random_erasing, label_smoothing, rand_augment,
+                          sam)
     accumulate, per_step, teacher_mod = args.accumulate, args.per_step, args.teacher_mod
     rank, local_rank, world = init_distributed(use_gpu)
     main = rank == 0 and local_rank == 0                    # the one process that prints and writes
@@ -3987,7 +4301,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             torch.cuda.empty_cache()
     model = initializer.to(device)
     if isinstance(optimizer, str) and optimizer == "fused":
-        optimizer = _fused_optimizer(model, param_groups, accumulate, verbose=main)
+        optimizer = _fused_optimizer(model, param_groups, accumulate, verbose=main, window=args.sam_kw is not None)
     if (scheduler is None or scheduler is True) and not per_step:
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=epochs, eta_min=1e-6)      # cls:52
     elif scheduler is False:
@@ -4006,7 +4320,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         sync_module_states(teacher_mod)
         dmetrics = DistillMetrics(device) if _backend.get_loss_kernels() else None
     ema_obj = ModelEMA(model, **args.ema_kw) if ema is not None else None
-    reducer = (HeldGradReducer(model) if accumulate > 1 else BucketedGradReducer(model)) if world > 1 else None
+    held = accumulate > 1 or args.sam_kw is not None        # (SamTrainStep exchanges a window of one: reduce_held)
+    reducer = (HeldGradReducer(model) if held else BucketedGradReducer(model)) if world > 1 else None
     if world > 1:
         sampler = DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=True, seed=2006)       # cls:56
     else:
@@ -4026,7 +4341,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     job = _RegTask(kl_weight) if args.reg else _ClsTask(metrics, val_topk)
     step = _make_step(job, model, optimizer, reducer, accumulate, teacher, {**args.distill_kw, "distill_metrics": dmetrics},
                       max_norm=1.0, scaler=scaler if use_gpu else None, autocast_dtype=torch.bfloat16 if use_gpu else None,
-                      ema=ema_obj)
+                      ema=ema_obj, sam_kw=args.sam_kw)
     model.train()
     n_steps = 0
     gstep = None
@@ -4124,6 +4439,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     if mon is not None:
         mon.detach()
         model._calm_monitor = mon
+    if args.sam_kw is not None:
+        model._calm_sam = step.sam
     if destroy_process_group and dist.is_initialized():
         dist.destroy_process_group()
     return model

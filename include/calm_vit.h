@@ -645,6 +645,54 @@ int calm_grad_stats(const calm_optim_tensor* tensors_dev, int32_t n_tensors, con
                     calm_grad_stat* out_dev, int32_t* summary_dev, float* scratch, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Sharpness-aware minimisation (additions to ABI v7): between the first backward of a step and its second forward,
+ * calm_sam_perturb moves every parameter of calm_optim_step's table (tensors_dev / chunk_tensor_dev exactly as handed to
+ * it, gradient pointers of the FIRST pass) by rho along the normalised TRUE gradient — corrected for the deferred
+ * spectral-norm layers and unscaled, as calm_grad_stats documents it — IN PLACE, after saving its bits; behind the second
+ * backward calm_sam_restore moves the saved bits back.  exp_avg and exp_avg_sq are not read.  All in fp32:
+ *   inv = grad_scale ? 1.0f / grad_scale[0] : 1.0f
+ *   plain tensor:               g' = G[i] * inv
+ *   tensor with sn_sigma != 0:  c = (sum over chunks of <G, W_orig>) / sigma, the per-chunk partials summed in the
+ *                               thread / block order of calm_optim_step's first pass and then in chunk order (the bits
+ *                               calm_optim_step, calm_grad_accum and calm_grad_stats give c);
+ *                               g' = ((G[i] - c * u[r] * v[col]) * (1.0f / sigma)) * inv
+ *   s:                          adaptive == 0: s = g'.   adaptive == 1 (ASAM): t = fabsf(w[i]) + eta, s = t * g'
+ *   norm = sqrtf(total):        per tensor, s^2 summed by a thread's serial sum over its (at most 64) elements of a chunk,
+ *                               the block sum (six shuffle levels, three adds of the wave sums), then the tensor's chunks in
+ *                               chunk order; then the tensors: 256 running sums, sum k adding tensors k, k + 256, k + 512,
+ *                               ... in rising order, and the block sum over the 256
+ *   found_inf:                  1 when any RAW G[i] has !(fabsf(G[i]) <= FLT_MAX), or when !(fabsf(norm) <= FLT_MAX); else 0
+ *   scale:                      found_inf ? 0 : rho / (norm + eps)
+ *   stats_out[3]                = {norm, found_inf, scale}
+ *   apply:                      backup[t][i] = w[i] (the bits, always).  found_inf == 0: adaptive == 0:
+ *                               w[i] = w[i] + scale * s;  adaptive == 1: w[i] = w[i] + (scale * t) * s, i.e. a step of
+ *                               scale * t^2 * g'.  found_inf != 0: no parameter is written (and G is not read again)
+ *   calm_sam_restore:           w[i] = backup[t][i], 32-bit words moved, no arithmetic: whatever the perturbed weights
+ *                               were (they differ between data-parallel ranks whose first-pass gradients were not
+ *                               exchanged), the restored ones are the saved bits
+ * A chunk whose operand addresses are all 16-byte aligned (the gradient; the weights where they are read or written; the
+ * backup in the apply pass and in the restore) is moved as 16-byte vectors, any other as single words; the thread that
+ * owns an element differs between the two, the summation depth does not.
+ * backup_dev: device array of n_tensors pointers (fp32 storage of numel elements each, 4-byte aligned, overlapping
+ * nothing else of the call).  scratch: calm_sam_scratch_floats(n_tensors, n_chunks) floats (host-only query), written by
+ * calm_sam_perturb and needed by nothing afterwards.  calm_sam_perturb writes param, the backups, scratch and stats_out;
+ * calm_sam_restore writes param; neither writes anything else.  calm_sam_restore reads param / numel / chunk0 of the
+ * table only: stale gradient pointers in it do not matter.
+ * calm_sam_perturb: four launches, calm_sam_restore: one.  No atomics, no result depends on the grid; neither allocates
+ * or synchronises (capturable).
+ * CALM_E_INVAL, before any launch: a null tensors_dev / chunk_tensor_dev / hparams / backup_dev / scratch / stats_out
+ * (calm_sam_restore: tensors_dev / chunk_tensor_dev / backup_dev), n_tensors <= 0, n_chunks <= 0, rho < 0 or NaN,
+ * eps <= 0 or NaN, adaptive other than 0 or 1, and with adaptive == 1 eta < 0 or NaN.
+ * ------------------------------------------------------------------------------------- */
+typedef struct calm_sam_hparams { float rho, eps, eta; int32_t adaptive; } calm_sam_hparams;   /* 16 bytes */
+int64_t calm_sam_scratch_floats(int32_t n_tensors, int32_t n_chunks);
+int calm_sam_perturb(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev,
+                     int32_t n_chunks, const calm_sam_hparams* hparams, const float* grad_scale /* device scalar or NULL */,
+                     float* const* backup_dev, float* scratch, float* stats_out /* [3] */, void* stream);
+int calm_sam_restore(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev,
+                     int32_t n_chunks, const float* const* backup_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Exponential moving average of ALL parameters (additions to ABI v7), a launch of its own behind calm_optim_step — the
  * weight EMA every ImageNet ViT recipe evaluates and checkpoints with (timm's ModelEmaV2 / torch's AveragedModel):
  *   ema += w * (src - ema),  w = 1 - d,  d = decay (CALM_EMA_CONSTANT) | min(decay, (1 + n) / (10 + n)) (CALM_EMA_WARMUP)
