@@ -95,6 +95,11 @@ class OptimHparams(C.Structure):
                 ("max_norm", _f32), ("step", _i32)]
 
 
+class LambHparams(C.Structure):
+    """struct calm_lamb_hparams (8 bytes)."""
+    _fields_ = [("trust_clip", _f32), ("always_adapt", _i32)]
+
+
 class GradStat(C.Structure):
     """struct calm_grad_stat (32 bytes, one per tensor of calm_grad_stats; np.dtype(GradStat) is the numpy record)."""
     _fields_ = [("grad_sq", _f32), ("grad_absmax", _f32), ("param_sq", _f32), ("param_absmax", _f32), ("dir_sq", _f32),
@@ -233,6 +238,9 @@ SIGNATURES = {
     "calm_optim_chunk_elems": (_i32, []),
     "calm_optim_step": (_i32, [_p, _i32, _p, _i32, _p, C.POINTER(OptimHparams), _p, _p, _p, _p, _p]),
     "calm_optim_step_groups": (_i32, [_p, _i32, _p, _i32, _p, C.POINTER(OptimHparams), _p, _i32, _p, _p, _p, _p]),
+    "calm_optim_lamb_scratch_floats": (_i64, [_i32, _i32]),
+    "calm_optim_step_lamb": (_i32, [_p, _i32, _p, _i32, _p, C.POINTER(OptimHparams), C.POINTER(LambHparams), _p, _i32, _p, _p,
+                                    _p, _p, _p, _p]),
     "calm_grad_accum": (_i32, [_p, _i32, _p, _i32, _p, _p, _i32, _p]),
     "calm_grad_stats_scratch_floats": (_i64, [_i32, _i32]),
     "calm_grad_stats": (_i32, [_p, _i32, _p, _i32, C.POINTER(OptimHparams), _p, _p, _p, _p, _p, _p]),

@@ -344,6 +344,7 @@ class OptimPlan(ChunkPlan):
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)      # advanced by the device, not on skipped steps
         self.param_ptrs = rec["param"].copy()
         self.n_groups, self._groups = int(n_groups), None
+        self._lamb = None                       # (scratch, trust table) of calm_optim_step_lamb, made at its first use
 
     @property
     def groups(self):
@@ -357,6 +358,21 @@ class OptimPlan(ChunkPlan):
         if table.n != self.n_groups:
             raise ValueError(f"the plan has {self.n_groups} parameter groups, the table {table.n}")
         self._groups = table
+
+    def lamb_buffers(self, be):
+        """(scratch, trust table) of calm_optim_step_lamb, made once — outside a capture they would be ordinary
+        allocations, inside one they live in the graph's pool, and either way every later call finds the same addresses.
+        The trust table starts at (0, 0, 1): what a tensor shows until an applied step writes it."""
+        if self._lamb is None:
+            dev = self.table_dev.device
+            trust = torch.zeros(self.n, 3, dtype=torch.float32, device=dev)
+            trust[:, 2] = 1.0
+            self._lamb = (torch.empty(be.lamb_scratch_floats(self), dtype=torch.float32, device=dev), trust)
+        return self._lamb
+
+    @property
+    def lamb_trust(self):
+        return None if self._lamb is None else self._lamb[1]
 
     def upload(self, grad_ptrs):
         """Stage this step's gradient pointers (numpy uint64 array) and enqueue their copy on the current stream."""
@@ -940,6 +956,38 @@ class HipBackend:
                                                    plan.groups.dev.data_ptr(), plan.groups.n, _ptr(grad_scale, True),
                                                    _ptr(stats_out), plan.step_dev.data_ptr(), _stream()),
                    "calm_optim_step_groups")
+
+    def lamb_scratch_floats(self, plan):
+        """calm_optim_lamb_scratch_floats for the table of `plan` (host only)."""
+        return int(self.lib.calm_optim_lamb_scratch_floats(plan.n, plan.n_chunks))
+
+    def optim_step_lamb(self, plan, grads, hp, lamb_hp, grad_scale, stats_out, group_hp=None, lr_dev=None, scratch=None,
+                        trust_out=None):
+        """calm_optim_step_lamb: optim_step (group_hp None) or optim_step_groups (group_hp: one (lr, weight_decay) per
+        group of the plan, uploaded as optim_step_groups uploads them — the same CAUTION about captures holds) with the
+        update of every tensor scaled by its trust ratio.  lamb_hp = (trust_clip or None / 0 for no limit, always_adapt).
+        The scratch and the table (wn, un, trust) per tensor, `plan.lamb_trust` (float32 [n, 3]), are allocated at the
+        plan's first LAMB step and kept for its lifetime: a captured step bakes their addresses in.  scratch / trust_out:
+        the caller's own buffers instead (lamb_scratch_floats(plan) floats; float32 [n, 3])."""
+        plan.upload(np.asarray([_ptr(g) for g in grads], dtype=np.uint64))
+        if group_hp is not None:
+            plan.groups.set(group_hp)
+        if scratch is None or trust_out is None:
+            own = plan.lamb_buffers(self)
+            scratch, trust_out = own[0] if scratch is None else scratch, own[1] if trust_out is None else trust_out
+        if scratch.dtype != torch.float32 or scratch.numel() < self.lamb_scratch_floats(plan):
+            raise ValueError("optim_step_lamb: scratch smaller than calm_optim_lamb_scratch_floats answers")
+        if trust_out.dtype != torch.float32 or trust_out.numel() != 3 * plan.n or not trust_out.is_contiguous():
+            raise ValueError("optim_step_lamb expects three contiguous float32 per tensor of the plan as trust_out")
+        clip, always = lamb_hp
+        h, lh = _lib.OptimHparams(*hp), _lib.LambHparams(float(clip or 0.0), int(bool(always)))
+        grouped = group_hp is not None
+        _lib.check(self.lib.calm_optim_step_lamb(plan.table_dev.data_ptr(), plan.n, plan.chunk_dev.data_ptr(), plan.n_chunks,
+                                                 _ptr(scratch), C.byref(h), C.byref(lh),
+                                                 plan.groups.dev.data_ptr() if grouped else None,
+                                                 plan.groups.n if grouped else 0, _ptr(grad_scale, True), _ptr(stats_out),
+                                                 _ptr(trust_out), plan.step_dev.data_ptr(),
+                                                 None if grouped else _ptr(lr_dev, True), _stream()), "calm_optim_step_lamb")
 
     def grad_accum(self, plan, grads, acc_ptrs_dev, first):
         """calm_grad_accum over the table of `plan` (the optimizer's deferred plan, this micro-batch's gradient pointers

@@ -16,6 +16,24 @@
 //                           p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps);   skipped entirely if found_inf
 //           optim_update_groups  the same update with lr and wd of the tensor's parameter group (calm_optim_step_groups)
 // Work item = chunk of CHUNK consecutive elements of one tensor (table built by the host).
+//
+// calm_optim_step_lamb: LAMB (You et al. 2020, as timm's `Lamb` decides which tensors adapt) over the same table in four
+// launches.  lr_t, wd_t = the tensor's group's with a group table, hparams' (lr_dev) otherwise; all in fp32:
+//   pass 1, 2  optim_stats, optim_finalize: the kernels above on the scratch layout above — the norm, the clip coefficient,
+//                           found_inf and the step counter have calm_optim_step's bits
+//   pass 3  lamb_moments    g' as pass 3 above; m = m + (g' - m)(1 - b1); v = v b2 + g'^2 (1 - b2), both stored;
+//                           r = (m / (sqrt(v) * (1 / sqrt(1 - b2^t)) + eps)) / (1 - b1^t);  u = r + wd_t * w  (lamb_u: its
+//                           three roundings are never contracted, so pass 4 forms the same bits); per chunk sum w^2 and
+//                           sum u^2 — a thread adds its elements serially, then block_sum_256; w is not written
+//   pass 4  lamb_apply      thread 0 of every workgroup adds its tensor's partials in chunk order (tensor_sn_c's scheme: no
+//                           fifth launch, chunks^2 eight-byte loads per tensor); wn = sqrt(W2), un = sqrt(U2);
+//                           trust = (adapt_t && wn > 0 && un > 0) ? wn / un : 1, adapt_t = always_adapt || wd_t != 0;
+//                           trust_clip > 0: trust = min(trust, trust_clip); the tensor's first chunk stores (wn, un, trust);
+//                           lr_t != 0: u = lamb_u(stored m, stored v, w), w = w - (lr_t * trust) * u
+//   found_inf: passes 3 and 4 return at once — nothing is written, trust_out included.
+// A chunk whose operand addresses (pass 3: grad, param, exp_avg, exp_avg_sq + i0; pass 4: the last three) are all 16-byte
+// aligned moves as 16-byte vectors with a single-word tail (a thread's serial sums then run over its vectors' elements in
+// address order), any other chunk as single words.  No atomics; every sum has a fixed order; no result depends on the grid.
 #include "chunk_table.h"
 
 namespace {
@@ -165,6 +183,175 @@ __global__ __launch_bounds__(NT) void optim_update_groups(const calm_optim_tenso
     update_chunk(e, t, blockIdx.x, stats, G, hp, gr.lr, gr.weight_decay);
 }
 
+// ---- LAMB ---------------------------------------------------------------------------------------------------------------
+constexpr int LP = 2;                        // per-chunk partials behind calm_optim_step's scratch: sum w^2, sum u^2
+constexpr int LU3 = 2, LU4 = 4;              // 16-byte vectors a thread has in flight per operand (pass 3: four operands)
+
+struct LambCoef { float b1c, b2, b2c, inv_sqrt_bc2, eps, bc1, wd; };
+
+__device__ __forceinline__ LambCoef lamb_coef(float beta1, float beta2, float eps, int step, float wd) {
+    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);   // update_chunk's
+    return {1.0f - beta1, beta2, 1.0f - beta2, 1.0f / sqrtf(bc2), eps, bc1, wd};
+}
+
+// u of one element from the NEW moments and the OLD weight; passes 3 and 4 must agree to the bit: no contraction
+__device__ __forceinline__ float lamb_u(const LambCoef& k, float m, float v, float w) {
+#pragma clang fp contract(off)
+    const float r = (m / (sqrtf(v) * k.inv_sqrt_bc2 + k.eps)) / k.bc1;
+    const float d = k.wd * w;
+    return r + d;
+}
+
+struct LambSums { float w2 = 0.f, u2 = 0.f; };
+
+// pass 3 over one chunk [i0, i1) of tensor e
+template <bool SN>
+__device__ __forceinline__ LambSums lamb_moments_span(const calm_optim_tensor& e, long i0, long i1, const LambCoef& k, float c,
+                                                      float inv_sg, float mul) {
+    const gf32* g = (const gf32*)e.grad;
+    const gf32* p = (const gf32*)e.param;
+    gf32* ma = (gf32*)e.exp_avg;
+    gf32* va = (gf32*)e.exp_avg_sq;
+    const gf32* su = (const gf32*)e.sn_u;
+    const gf32* sv = (const gf32*)e.sn_v;
+    const unsigned cols = (unsigned)e.cols;
+    LambSums a;
+    const auto element = [&](float gi, float wi, float& mi, float& vi, unsigned r, unsigned cc) __attribute__((always_inline)) {
+        if (SN) gi = (gi - c * su[r] * sv[cc]) * inv_sg;
+        gi *= mul;
+        mi = mi + (gi - mi) * k.b1c;                             // lerp_
+        vi = vi * k.b2 + gi * gi * k.b2c;
+        const float u = lamb_u(k, mi, vi, wi);
+        a.w2 += wi * wi;
+        a.u2 += u * u;
+    };
+    // the 32-bit row / column split of optim_update (rows * cols < 2^31, checked by the host)
+    const auto scalar = [&](long b, long end) __attribute__((always_inline)) {
+        for (long i = b + threadIdx.x; i < end; i += NT) {
+            unsigned r = 0, cc = 0;
+            if (SN) { r = (unsigned)i / cols; cc = (unsigned)i - r * cols; }
+            float mi = ma[i], vi = va[i];
+            element(g[i], p[i], mi, vi, r, cc);
+            ma[i] = mi; va[i] = vi;
+        }
+    };
+    if (dev_aligned16(g + i0) && dev_aligned16(p + i0) && dev_aligned16(ma + i0) && dev_aligned16(va + i0)) {
+        const long v1 = i0 + ((i1 - i0) & ~3L);
+        struct Quad { f32x4 g, w, m, v; };
+        const auto load = [&](long i) __attribute__((always_inline)) {
+            Quad q;
+            q.g = *(const gf32x4*)(g + i); q.w = *(const gf32x4*)(p + i);
+            q.m = *(const gf32x4*)(ma + i); q.v = *(const gf32x4*)(va + i);
+            return q;
+        };
+        const auto store = [&](long i, const Quad& q) __attribute__((always_inline)) {
+            unsigned r = 0, cc = 0;
+            if (SN) { r = (unsigned)i / cols; cc = (unsigned)i - r * cols; }
+            f32x4 m4 = q.m, v4 = q.v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float mi = m4[j], vi = v4[j];
+                element(q.g[j], q.w[j], mi, vi, r, cc);
+                m4[j] = mi; v4[j] = vi;
+                if (SN && ++cc == cols) { cc = 0; ++r; }         // (cols = 1: every element starts a row)
+            }
+            *(gf32x4*)(ma + i) = m4;
+            *(gf32x4*)(va + i) = v4;
+        };
+        loads_ahead_of_stores<LU3, 4, NT>(i0, v1, load, store);
+        scalar(v1, i1);
+    } else {
+        scalar(i0, i1);
+    }
+    return a;
+}
+
+__global__ __launch_bounds__(NT) void lamb_moments(const calm_optim_tensor* __restrict__ T, const int* __restrict__ chunk_tensor,
+                                                   const float* __restrict__ stats, const Globals* __restrict__ G,
+                                                   const calm_optim_hparams hp, const int* __restrict__ step_dev,
+                                                   const calm_optim_group* __restrict__ groups, float* __restrict__ lamb_part) {
+    __shared__ float red[4];
+    if (G->found_inf != 0.f) return;          // a skipped step writes nothing: not the moments, not the partials
+    const int step = step_dev ? step_dev[0] : hp.step;     // already advanced by optim_finalize for this (un-skipped) step
+    const int t = chunk_tensor[blockIdx.x];
+    const calm_optim_tensor e = T[t];
+    const auto [i0, i1] = chunk_span(blockIdx.x, CHUNK, e.chunk0, e.numel);
+    const LambCoef k = lamb_coef(hp.beta1, hp.beta2, hp.eps, step, groups ? groups[e.group].weight_decay : hp.weight_decay);
+    const float mul = G->clip;
+    LambSums a;
+    if (e.sn_sigma) {                         // (uniform over the workgroup)
+        a = lamb_moments_span<true>(e, i0, i1, k, stats[ST * t + 5], 1.0f / e.sn_sigma[0], mul);
+    } else {
+        a = lamb_moments_span<false>(e, i0, i1, k, 0.f, 1.f, mul);
+    }
+    const float w2 = block_sum_256(a.w2, red);
+    const float u2 = block_sum_256(a.u2, red);
+    if (threadIdx.x == 0) { lamb_part[LP * blockIdx.x] = w2; lamb_part[LP * blockIdx.x + 1] = u2; }
+}
+
+__global__ __launch_bounds__(NT) void lamb_apply(const calm_optim_tensor* __restrict__ T, const int* __restrict__ chunk_tensor,
+                                                 const Globals* __restrict__ G, const calm_optim_hparams hp,
+                                                 const calm_lamb_hparams lhp,
+                                                 const int* __restrict__ step_dev, const float* __restrict__ lr_dev,
+                                                 const calm_optim_group* __restrict__ groups,
+                                                 const float* __restrict__ lamb_part, float* __restrict__ trust_out) {
+    __shared__ float trust_lds;
+    if (G->found_inf != 0.f) return;
+    const int step_no = step_dev ? step_dev[0] : hp.step;
+    const int t = chunk_tensor[blockIdx.x];
+    const calm_optim_tensor e = T[t];
+    const auto [i0, i1] = chunk_span(blockIdx.x, CHUNK, e.chunk0, e.numel);
+    float lr = hp.lr, wd = hp.weight_decay;
+    if (lr_dev) lr = lr_dev[0];               // a captured step follows the LR schedule through this device scalar
+    if (groups) { const calm_optim_group gr = groups[e.group]; lr = gr.lr; wd = gr.weight_decay; }
+    const LambCoef k = lamb_coef(hp.beta1, hp.beta2, hp.eps, step_no, wd);
+    if (threadIdx.x == 0) {
+        const int nch = chunk_count(CHUNK, e.numel);
+        float W2 = 0.f, U2 = 0.f;
+        for (int c = 0; c < nch; ++c) {                          // fixed order: chunk 0, 1, 2, ...
+            W2 += lamb_part[LP * (e.chunk0 + c)];
+            U2 += lamb_part[LP * (e.chunk0 + c) + 1];
+        }
+        const float wn = sqrtf(W2), un = sqrtf(U2);
+        const bool adapt = lhp.always_adapt != 0 || wd != 0.f;
+        float trust = (adapt && wn > 0.f && un > 0.f) ? wn / un : 1.0f;
+        if (lhp.trust_clip > 0.f) trust = fminf(trust, lhp.trust_clip);
+        if (trust_out && i0 == 0) { trust_out[3 * t] = wn; trust_out[3 * t + 1] = un; trust_out[3 * t + 2] = trust; }
+        trust_lds = trust;
+    }
+    __syncthreads();
+    if (lr == 0.f) return;                    // a frozen tensor keeps its bits (its moments moved in pass 3)
+    const float step = lr * trust_lds;
+    gf32* p = (gf32*)e.param;
+    const gf32* ma = (const gf32*)e.exp_avg;
+    const gf32* va = (const gf32*)e.exp_avg_sq;
+    const auto scalar = [&](long b, long end) __attribute__((always_inline)) {
+        for (long i = b + threadIdx.x; i < end; i += NT) {
+            const float wi = p[i];
+            p[i] = wi - step * lamb_u(k, ma[i], va[i], wi);
+        }
+    };
+    if (dev_aligned16(p + i0) && dev_aligned16(ma + i0) && dev_aligned16(va + i0)) {
+        const long v1 = i0 + ((i1 - i0) & ~3L);
+        struct Triple { f32x4 w, m, v; };
+        const auto load = [&](long i) __attribute__((always_inline)) {
+            Triple q;
+            q.w = *(const gf32x4*)(p + i); q.m = *(const gf32x4*)(ma + i); q.v = *(const gf32x4*)(va + i);
+            return q;
+        };
+        const auto store = [&](long i, const Triple& q) __attribute__((always_inline)) {
+            f32x4 out;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) out[j] = q.w[j] - step * lamb_u(k, q.m[j], q.v[j], q.w[j]);
+            *(gf32x4*)(p + i) = out;
+        };
+        loads_ahead_of_stores<LU4, 4, NT>(i0, v1, load, store);
+        scalar(v1, i1);
+    } else {
+        scalar(i0, i1);
+    }
+}
+
 // passes 1 and 2 of both entry points: scratch cleared, per-chunk partials, the norm / clip / found_inf / step count
 int stats_and_finalize(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev, int32_t n_chunks,
                        float* scratch, float max_norm, const float* grad_scale, float* stats_out, int32_t* step_dev, void* stream) {
@@ -214,6 +401,31 @@ int calm_optim_step_groups(const calm_optim_tensor* tensors_dev, int32_t n_tenso
     const Globals* G = reinterpret_cast<const Globals*>(scratch + ST * (size_t)n_tensors);
     return calm_launch(optim_update_groups, n_chunks, NT, 0, stream, tensors_dev, chunk_tensor_dev, scratch, G, *hp, step_dev,
                        groups_dev);
+}
+
+int64_t calm_optim_lamb_scratch_floats(int32_t n_tensors, int32_t n_chunks) {
+    if (n_tensors <= 0 || n_chunks <= 0) return CALM_E_INVAL;
+    return ST * (int64_t)n_tensors + (int64_t)(sizeof(Globals) / sizeof(float)) + (CP + LP) * (int64_t)n_chunks;
+}
+
+int calm_optim_step_lamb(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev,
+                         int32_t n_chunks, float* scratch, const calm_optim_hparams* hp, const calm_lamb_hparams* lhp,
+                         const calm_optim_group* groups_dev, int32_t n_groups, const float* grad_scale, float* stats_out,
+                         float* trust_out, int32_t* step_dev, const float* lr_dev, void* stream) {
+    if (bad_step_args(tensors_dev, n_tensors, chunk_tensor_dev, n_chunks, scratch, hp, stats_out, step_dev) || !lhp)
+        return CALM_E_INVAL;
+    if (groups_dev ? n_groups <= 0 : hp->lr < 0.f) return CALM_E_INVAL;
+    if (!(lhp->trust_clip >= 0.f) || (lhp->always_adapt != 0 && lhp->always_adapt != 1)) return CALM_E_INVAL;   // (NaN too)
+    if (int e = stats_and_finalize(tensors_dev, n_tensors, chunk_tensor_dev, n_chunks, scratch, hp->max_norm, grad_scale,
+                                   stats_out, step_dev, stream))
+        return e;
+    const Globals* G = reinterpret_cast<const Globals*>(scratch + ST * (size_t)n_tensors);
+    float* lamb_part = scratch + ST * (size_t)n_tensors + sizeof(Globals) / sizeof(float) + CP * (size_t)n_chunks;
+    if (int e = calm_launch(lamb_moments, n_chunks, NT, 0, stream, tensors_dev, chunk_tensor_dev, scratch, G, *hp, step_dev,
+                            groups_dev, lamb_part))
+        return e;
+    return calm_launch(lamb_apply, n_chunks, NT, 0, stream, tensors_dev, chunk_tensor_dev, G, *hp, *lhp, step_dev,
+                       groups_dev ? nullptr : lr_dev, groups_dev, lamb_part, trust_out);
 }
 
 }  // extern "C"

@@ -31,6 +31,9 @@ as set by torchrun):
         sharpness-aware minimisation: calm_sam_perturb behind a first backward (in place, along the true gradient, the
         bits saved), a second pass at the perturbed weights whose gradients calm_grad_accum finishes there,
         calm_sam_restore, then the unchanged optimizer-side step.
+  * `FusedClipAdamW(lamb=)` / `lamb_step_torch` / `train(lamb=)`   (no counterpart: the reference has no large-batch optimizer)
+        LAMB inside the fused optimizer-side step (calm_optim_step_lamb): AdamW's moments, clip and inf check, every
+        tensor's update rescaled by its trust ratio ||w|| / ||update||.
 
 The model also works under stock `torch.nn.parallel.DistributedDataParallel` (that is what the
 reference's train() does with it); the reducer here is the MI355X-tuned equivalent.  Under DDP the step
@@ -1977,19 +1980,29 @@ class FusedClipAdamW(torch.optim.Optimizer):
 
     `perturbed_by`: None, or the `SharpnessAware` whose perturbation the parameters carry right now: until its restore()
     it stands in front of step() and refuses it (an attribute of the INSTANCE that perturb() sets and restore() removes,
-    so step() itself has no branch for it)."""
+    so step() itself has no branch for it).
+
+    lamb=None | True | {"trust_clip": None, "always_adapt": False}: the step is LAMB (calm_optim_step_lamb, four launches):
+    the same unscale / inf check / clip / moments, and every tensor's update u = Adam direction + weight_decay * w applied
+    as w -= lr * trust * u with trust = ||w|| / ||u|| per tensor — 1 for a tensor without weight decay unless always_adapt
+    (timm's rule), 1 where either norm is 0, at most trust_clip.  One entry point serves one and several param groups.  The
+    state is AdamW's (`exp_avg`, `exp_avg_sq`, the step count), so snapshots and the accumulation window are unchanged;
+    `trust_ratios()` reads what the last applied step used.  `lamb` holds the normalised settings, or None."""
 
     monitor = None
     perturbed_by = None
 
     def __init__(self, model, lr=3.1e-3, weight_decay=0.02, betas=(0.9, 0.98), eps=1e-8, max_norm=1.0, defer_sn=True,
-                 groups=None):
+                 groups=None, lamb=None):
         from . import ops
         from .backend import get_backend
         from .spectral_norm import SpectralWeight
         self.be = get_backend()
         self.max_norm = max_norm
+        self.lamb = _lamb_settings("FusedClipAdamW", lamb)
         params = [p for p in model.parameters() if p.requires_grad]
+        names = {id(p): n for n, p in model.named_parameters()}
+        self.param_names = [names[id(p)] for p in params]
         group_of = [0] * len(params)
         if groups is None:
             super().__init__(params, dict(lr=lr, weight_decay=weight_decay, betas=tuple(betas), eps=eps))
@@ -2036,6 +2049,16 @@ class FusedClipAdamW(torch.optim.Optimizer):
         self.lr_on_device = False
         self._lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=self.params[0].device)
         self._lr_dev_value = float(lr)
+        # LAMB without the entry point (CPU parameters): the (wn, un, trust) table lamb_step_torch writes
+        self._trust_host = None
+        if self.lamb is not None and not hasattr(self.be, "optim_step_lamb"):
+            self._trust_host = torch.zeros(len(self.params), 3, dtype=torch.float32)
+            self._trust_host[:, 2] = 1.0
+        if self.lamb is not None:
+            # (through a weak reference: a bound method stored on its own instance would be a cycle, and the finalizer
+            # above is to run when the last outside reference goes)
+            me = weakref.ref(self)
+            self._launch = lambda *a, **kw: FusedClipAdamW._launch_lamb(me(), *a, **kw)
 
     @property
     def grouped(self):
@@ -2137,6 +2160,28 @@ class FusedClipAdamW(torch.optim.Optimizer):
             p.grad = None
         return self.stats
 
+    def _launch_lamb(self, plan, grads, divisor, records=None):
+        """_launch of an optimizer built with lamb=: calm_optim_step_lamb, one entry point for one and for several param
+        groups.  __init__ puts it in front of `_launch` as an attribute of the INSTANCE, so `_launch` has no branch for it
+        and FusedClipAdamWindow, whose window steps through `self._launch`, steps with LAMB too."""
+        hp = self._hparams()
+        if self.monitor is not None:            # a GradMonitor: this step's gradients, in front of the step
+            self.monitor.observe(plan, grads, divisor, self._records if records is None else records)
+        group_hp = self.group_hparams() if self.grouped else None
+        lamb_hp = (self.lamb["trust_clip"], self.lamb["always_adapt"])
+        if self._trust_host is None:
+            on_dev = self.lr_on_device and not self.grouped
+            if on_dev and not torch.cuda.is_current_stream_capturing():
+                self.sync_lr_to_device()
+            self.be.optim_step_lamb(plan, grads, hp, lamb_hp, divisor, self.stats, group_hp=group_hp,
+                                    lr_dev=self._lr_dev if on_dev else None)
+        else:                                   # a backend without the entry point (CPU parameters)
+            lamb_step_torch(self._records if records is None else records, plan.step_dev, grads, hp, lamb_hp, group_hp,
+                            divisor, self.stats, self._trust_host)
+        for p in self.params:
+            p.grad = None
+        return self.stats
+
     @torch.no_grad()
     def step(self, closure=None, grad_scale=None):
         """One optimizer-side step on the current `.grad`s; grads are released (set to None) afterwards.
@@ -2154,10 +2199,15 @@ class FusedClipAdamW(torch.optim.Optimizer):
         hparams = dict(lr=self.lr, weight_decay=self.weight_decay, betas=self.betas, eps=self.eps, max_norm=self.max_norm)
         if self.grouped:
             hparams["groups"] = [list(pair) for pair in self.group_hparams()]
+        if self.lamb is not None:
+            hparams["lamb"] = dict(self.lamb)
         return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "hparams": hparams}
 
     def load_state_dict(self, sd):
         if "hparams" in sd:
+            if (sd["hparams"].get("lamb") is not None) != (self.lamb is not None):
+                raise ValueError(f"FusedClipAdamW.load_state_dict: the state was written with{'' if sd['hparams'].get('lamb') else 'out'} "
+                                 f"LAMB, this optimizer steps with{'' if self.lamb else 'out'} it")
             saved = sd["hparams"].get("groups")
             if (len(saved) if saved is not None else 1) != len(self.param_groups):
                 raise ValueError(f"FusedClipAdamW.load_state_dict: the state holds {len(saved) if saved is not None else 1} "
@@ -2171,6 +2221,79 @@ class FusedClipAdamW(torch.optim.Optimizer):
             dst.copy_(src)
         for dst, src in zip(self.exp_avg_sq, sd["exp_avg_sq"]):
             dst.copy_(src)
+
+    def trust_ratios(self):
+        """{parameter name: (w_norm, update_norm, trust)} of the last applied LAMB step, from one read of the table (it
+        synchronises); (0, 0, 1) for every tensor before the first one.  A skipped step leaves the table as it was."""
+        if self.lamb is None:
+            raise RuntimeError("FusedClipAdamW.trust_ratios: the optimizer was built without lamb=")
+        table = self._trust_host if self._trust_host is not None else self._plan.lamb_buffers(self.be)[1]
+        rows = table.detach().cpu().tolist()
+        return {n: (r[0], r[1], r[2]) for n, r in zip(self.param_names, rows)}
+
+
+def _lamb_settings(who, lamb):
+    """lamb= of FusedClipAdamW / train() -> None, or {"trust_clip": None | float > 0, "always_adapt": bool}."""
+    if lamb is None or lamb is False:
+        return None
+    if lamb is True:
+        lamb = {}
+    if not isinstance(lamb, dict):
+        raise ValueError(f'{who}: lamb is None, True or a dict with "trust_clip" / "always_adapt", got {lamb!r}')
+    if not set(lamb) <= {"trust_clip", "always_adapt"}:
+        raise ValueError(f'{who}: lamb takes the keys "trust_clip", "always_adapt", got {sorted(lamb)}')
+    clip, always = lamb.get("trust_clip"), lamb.get("always_adapt", False)
+    if clip is not None and (isinstance(clip, bool) or not isinstance(clip, (int, float)) or not (clip > 0.0 and math.isfinite(clip))):
+        raise ValueError(f'{who}: lamb["trust_clip"] is None or a positive finite limit, got {clip!r}')
+    if not isinstance(always, (bool, int)) or always not in (0, 1):
+        raise ValueError(f'{who}: lamb["always_adapt"] is a flag, got {always!r}')
+    return {"trust_clip": None if clip is None else float(clip), "always_adapt": bool(always)}
+
+
+def lamb_step_torch(records, step_dev, grads, hp, lamb_hp, group_hp, grad_scale, stats_out, trust_out=None):
+    """calm_optim_step_lamb in torch, for a backend without `optim_step_lamb` (CPU parameters), in the header's fp32 order:
+    the correction, the norm / clip / inf check and the step count of optim_step_groups_torch; then per record, with
+    (lr_t, wd_t) = group_hp[record["group"]] (group_hp None: hp's), m = m + (g' - m)(1 - b1), v = v b2 + g'^2 (1 - b2),
+    r = (m / (sqrt(v) / sqrt(bc2) + eps)) / bc1, u = r + wd_t w, trust = ||w|| / ||u|| where the tensor adapts and both norms
+    are positive, else 1, at most trust_clip, and w -= (lr_t trust) u unless lr_t == 0.  lamb_hp = (trust_clip or None,
+    always_adapt); trust_out: None or float32 [n, 3] <- (wn, un, trust).  A skipped step writes nothing."""
+    f32 = lambda x: float(torch.tensor(float(x), dtype=torch.float32))        # the ABI's hyper-parameters are fp32  # noqa: E731
+    lr0, b1, b2, eps, wd0, max_norm, _ = (f32(x) for x in hp)
+    clip, always = f32(lamb_hp[0] or 0.0), bool(lamb_hp[1])
+    group_hp = None if group_hp is None else [(f32(lr), f32(wd)) for lr, wd in group_hp]
+    fixed = []
+    for r, g in zip(records, grads):
+        if r["sn"] is not None:
+            u, v, sigma, rows, cols = r["sn"]
+            G = g.reshape(rows, cols)
+            c = (G * r["param"].reshape(rows, cols)).sum() / sigma
+            g = ((G - (c * u)[:, None] * v[None, :]) * (1.0 / sigma)).reshape(g.shape)
+        fixed.append(g)
+    inv = 1.0 / float(grad_scale) if grad_scale is not None else 1.0
+    norm = torch.sqrt(sum((g.double() ** 2).sum() for g in fixed)).float() * inv
+    bad = not bool(torch.isfinite(norm))
+    stats_out[0], stats_out[1] = norm, float(bad)
+    if bad:
+        return
+    step_dev += 1
+    step = int(step_dev)
+    mul = (min(1.0, max_norm / (float(norm) + 1e-6)) if max_norm > 0 else 1.0) * inv
+    bc1, isb2 = 1 - b1 ** step, 1.0 / math.sqrt(1 - b2 ** step)
+    for k, (r, g) in enumerate(zip(records, fixed)):
+        lr, wd = (lr0, wd0) if group_hp is None else group_hp[r.get("group", 0)]
+        g = g * mul
+        p, m, v = r["param"], r["exp_avg"], r["exp_avg_sq"]
+        m.copy_(m + (g - m) * (1 - b1))
+        v.copy_(v * b2 + g * g * (1 - b2))
+        u = (m / (v.sqrt() * isb2 + eps)) / bc1 + wd * p
+        wn, un = (p * p).sum().sqrt(), (u * u).sum().sqrt()
+        trust = wn / un if (always or wd != 0.0) and bool(wn > 0) and bool(un > 0) else torch.ones(())
+        if clip > 0:
+            trust = trust.clamp(max=clip)
+        if trust_out is not None:
+            trust_out[k, 0], trust_out[k, 1], trust_out[k, 2] = wn, un, trust
+        if lr != 0.0:
+            p.sub_((torch.tensor(lr, dtype=torch.float32) * trust) * u)
 
 
 def optim_step_groups_torch(records, step_dev, grads, hp, group_hp, grad_scale, stats_out):
@@ -2265,6 +2388,8 @@ class FusedClipAdamWindow(FusedClipAdamW):
         plan.step_dev = self._plan.step_dev     # one counter: snapshots and step_count see every step
         if self.grouped and hasattr(self.be, "optim_step_groups"):
             plan.groups = self._plan.groups     # one (lr, weight_decay) table: both plans step the same groups
+        if self.lamb is not None and self._trust_host is None:
+            plan._lamb = self._plan.lamb_buffers(self.be)       # one scratch, one trust table: trust_ratios() reads either
         self._acc, self._acc_plan = accs, plan
         self._acc_ptrs = np.asarray([a.data_ptr() for a in accs], dtype=np.uint64)
         self._acc_ptrs_dev = torch.from_numpy(self._acc_ptrs.view(np.int64).copy()).to(self.params[0].device)
@@ -3109,6 +3234,8 @@ class TrainState:
              "generators": {n: g.bit_generator.state for n, g in self.generators.items()}}
         if self.fused and len(self.opt.param_groups) > 1:     # (a torch optimizer's groups travel in its own state dict)
             h["lrs"] = [g["lr"] for g in self.opt.param_groups]
+        if self.fused and self.opt.lamb is not None:          # the state is AdamW's; the key alone tells the two rules apart
+            h["lamb"] = dict(self.opt.lamb)
         if not self.fused and self.payload:
             h["optimizer"] = self._optim_desc
             if self.scaler is not None:            # torch's own GradScaler policy: its growth count (reading it synchronises)
@@ -3274,6 +3401,9 @@ class TrainState:
         if self.fused and n_groups != len(self.opt.param_groups):
             raise ValueError(f"{path}: written with {n_groups} parameter group(s), this optimizer has "
                              f"{len(self.opt.param_groups)}")
+        if self.fused and ("lamb" in host) != (self.opt.lamb is not None):
+            raise ValueError(f"{path}: written with{'' if 'lamb' in host else 'out'} LAMB, this optimizer steps "
+                             f"with{'' if self.opt.lamb is not None else 'out'} it")
         # the entries: everything but a torch optimizer's state must be the live set, name by name
         head, optim, tail = self._fixed_entries()
         live = head + optim + tail
@@ -3653,14 +3783,15 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
                       device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path, snapshot_every,
                       accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task, teacher, distill,
                       param_groups, scheduler_step, monitor=None, random_erasing=None, label_smoothing=0.0, rand_augment=None,
-                      sam=None):
+                      sam=None, lamb=None):
     """Every refusal train() makes from its arguments alone: it touches no device and no process group, so a bad call
     fails before either exists.  Returns the normalised values the job is assembled from: accumulate (int), ema_kw
     (None without ema), distill_kw (DistillTrainStep's keywords, {} without a teacher), teacher_mod, resize (the
     DeviceResize or None), window (the DeviceResizedCrop.window or None), reg, per_step, monitor_kw (None without
     monitor=; "every" None: log_every), erase (None, a DeviceErase, or the dict of arguments one is built from),
     label_smoothing (float), rand_augment (None, a DeviceRandAugment, or the dict of arguments one is built from), sam_kw
-    (None without sam=; SharpnessAware's keywords and "sync")."""
+    (None without sam=; SharpnessAware's keywords and "sync"), lamb (None, or the normalised settings of
+    FusedClipAdamW(lamb=) — the argument's, or those of the optimizer object handed in)."""
     from . import backend as _backend
     from types import SimpleNamespace
     if scheduler_step not in ("epoch", "step"):
@@ -3711,6 +3842,16 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
             raise ValueError("train: sam= excludes accumulate > 1 (SAM under an accumulation window is not supported)")
         if teacher is not None:
             raise ValueError("train: sam= excludes teacher= (SAM under distillation is not supported)")
+    lamb_kw = _lamb_settings("train", lamb)
+    if lamb_kw is not None:
+        if not (isinstance(optimizer, FusedClipAdamW) or (isinstance(optimizer, str) and optimizer == "fused")):
+            raise ValueError('train: lamb= needs optimizer="fused" or a FusedClipAdamW built with lamb= (the trust ratios are '
+                             "taken inside the fused optimizer-side step; a torch optimizer is not given them)")
+        if isinstance(optimizer, FusedClipAdamW) and optimizer.lamb != lamb_kw:
+            raise ValueError(f"train: lamb={lamb_kw} contradicts the optimizer handed in, which was built with "
+                             f"lamb={optimizer.lamb}")
+    elif isinstance(optimizer, FusedClipAdamW):
+        lamb_kw = optimizer.lamb
     if task not in ("cls", "reg"):
         raise ValueError(f'train: task is "cls" or "reg", got {task!r}')
     reg = task == "reg"
@@ -3834,7 +3975,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
             EvalMetrics(num_classes, topk=val_topk)         # (refuses a malformed val_topk here, not after the first epoch)
     return SimpleNamespace(accumulate=accumulate, ema_kw=ema_kw, distill_kw=distill_kw, teacher_mod=teacher_mod, resize=resize,
                            window=window, reg=reg, per_step=scheduler_step == "step", monitor_kw=monitor_kw, erase=erase,
-                           label_smoothing=float(label_smoothing), rand_augment=randaug, sam_kw=sam_kw)
+                           label_smoothing=float(label_smoothing), rand_augment=randaug, sam_kw=sam_kw, lamb=lamb_kw)
 
 
 class _TrainInput:
@@ -3937,17 +4078,17 @@ class _TrainInput:
         return x, y
 
 
-def _fused_optimizer(model, param_groups, accumulate, verbose, window=False):
+def _fused_optimizer(model, param_groups, accumulate, verbose, window=False, lamb=None):
     """train(optimizer="fused"): FusedClipAdamW (FusedClipAdamWindow for an accumulation window, or with `window`: sam=
     finishes its second pass's gradients in a window of one) over the model on its
     device, with the groups of param_groups=; the frozen parameters lose requires_grad here, before the reducer and the EMA
-    are built.  verbose: print one line per group."""
-    group_kw = {}
+    are built.  lamb: FusedClipAdamW's.  verbose: print one line per group."""
+    group_kw = {} if lamb is None else {"lamb": lamb}
     if param_groups is not None:
         groups, frozen = _build_param_groups(model, param_groups)
         for p in frozen:                    # before the reducer, the optimizer and the EMA: all three filter on it
             p.requires_grad_(False)
-        group_kw = {"groups": groups}
+        group_kw["groups"] = groups
     optimizer = FusedClipAdamWindow(model, **group_kw) if accumulate > 1 or window else FusedClipAdamW(model, **group_kw)
     if param_groups is not None and verbose:
         for k, g in enumerate(optimizer.param_groups):
@@ -4043,6 +4184,15 @@ class _MonitorLog:
                    top_update_ratio=top("update_ratio"),
                    nonfinite=[{"name": n, "bad_calls": tensors[n]["bad_calls"], "first_bad_call": tensors[n]["first_bad_call"]}
                               for n in grew])
+        trust = None
+        if getattr(self.monitor.optimizer, "lamb", None) is not None:      # one read of the optimizer's trust table
+            ratios = self.monitor.optimizer.trust_ratios()
+            by_trust = sorted(ratios, key=lambda n: ratios[n][2])
+            vals = [ratios[n][2] for n in by_trust]
+            trust = dict(min=vals[0], median=vals[len(vals) // 2], max=vals[-1])
+            out["trust"] = trust
+            out["top_small_trust"] = [{"name": n, "trust": ratios[n][2], "weight_norm": ratios[n][0], "update_norm": ratios[n][1]}
+                                      for n in by_trust[:self.top]]
         if per_tensor:
             out["tensors"] = tensors
         if self.path:
@@ -4054,6 +4204,8 @@ class _MonitorLog:
         worst = out["top_update_ratio"][:1]
         if worst:
             text += f", Largest update ratio: {worst[0]['update_ratio']:.3g} ({worst[0]['name']})"
+        if trust is not None:
+            text += f", Trust ratio min / median / max: {trust['min']:.3g} / {trust['median']:.3g} / {trust['max']:.3g}"
         if rep["skipped"] > self.skipped:
             text += f", Non-finite gradient in: {', '.join(grew)}"
         print(text)
@@ -4069,7 +4221,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
           val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
           teacher=None, distill=None, param_groups=None, scheduler_step="epoch", monitor=None, random_erasing=None,
-          label_smoothing=0.0, rand_augment=None, sam=None):
+          label_smoothing=0.0, rand_augment=None, sam=None, lamb=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -4276,7 +4428,20 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     Spectral norm's power iteration advances at both forwards, and dropout / latent-noise keys are drawn in both.  SAM
     holds no state between steps, so snapshots / resume= stay bit for bit.  The returned model carries the SharpnessAware
     as `model._calm_sam`.  Refused: graph=True, accumulate > 1, teacher=, unknown keys, rho <= 0, a torch optimizer or a
-    FusedClipAdamW without the window."""
+    FusedClipAdamW without the window.
+
+    lamb=True | {"trust_clip": None, "always_adapt": False} (the large-batch optimizer of DeiT III / timm's `lamb`; needs
+    optimizer="fused", which is then built with it, or a FusedClipAdamW / FusedClipAdamWindow built with the same lamb=): the
+    optimizer-side step is calm_optim_step_lamb — AdamW's moments, clip and inf check, and per tensor
+    w -= lr trust (Adam direction + weight_decay w) with trust = ||w|| / ||update||, 1 for tensors without weight decay
+    unless always_adapt, at most trust_clip.  It is the optimizer's step, so graph=True, accumulate, sam=, ema,
+    param_groups / scheduler_step, teacher=, task="reg", monitor= and snapshots / resume= work as before; the optimizer
+    state is AdamW's, and a snapshot written with lamb= is refused by a run without it (and the other way round).  With
+    monitor= each line also carries the minimum, median and maximum trust ratio and the `top` tensors by smallest trust; the
+    update-ratio fields keep their meaning (the AdamW direction at the group's rate) — under LAMB the APPLIED ratio
+    ||dw|| / ||w|| of an adapted, unclipped tensor is its lr by construction.  Rank 0 prints one line with the settings, and
+    the returned model carries the optimizer as `model._calm_lamb` (`trust_ratios()`).  Refused: unknown keys,
+    trust_clip <= 0, a torch optimizer, an optimizer object whose lamb setting differs from the argument."""
     from functools import partial
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
@@ -4284,7 +4449,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                           device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path,
                           snapshot_every, accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task,
                           teacher, distill, param_groups, scheduler_step, monitor, random_erasing, label_smoothing, rand_augment,
-                          sam)
+                          sam, lamb)
     accumulate, per_step, teacher_mod = args.accumulate, args.per_step, args.teacher_mod
     rank, local_rank, world = init_distributed(use_gpu)
     main = rank == 0 and local_rank == 0                    # the one process that prints and writes
@@ -4301,7 +4466,10 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             torch.cuda.empty_cache()
     model = initializer.to(device)
     if isinstance(optimizer, str) and optimizer == "fused":
-        optimizer = _fused_optimizer(model, param_groups, accumulate, verbose=main, window=args.sam_kw is not None)
+        optimizer = _fused_optimizer(model, param_groups, accumulate, verbose=main, window=args.sam_kw is not None,
+                                     lamb=args.lamb)
+    if args.lamb is not None and main:
+        print(f"LAMB: per-tensor trust ratios on, trust_clip {args.lamb['trust_clip']}, always_adapt {args.lamb['always_adapt']}")
     if (scheduler is None or scheduler is True) and not per_step:
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=epochs, eta_min=1e-6)      # cls:52
     elif scheduler is False:
@@ -4441,6 +4609,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         model._calm_monitor = mon
     if args.sam_kw is not None:
         model._calm_sam = step.sam
+    if args.lamb is not None:
+        model._calm_lamb = optimizer
     if destroy_process_group and dist.is_initialized():
         dist.destroy_process_group()
     return model

@@ -573,6 +573,45 @@ int calm_optim_step_groups(const calm_optim_tensor* tensors_dev, int32_t n_tenso
                            void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * LAMB over calm_optim_step's table (addition to ABI v7): Adam's direction plus decoupled weight decay, rescaled per TENSOR
+ * by the trust ratio ||w|| / ||update|| (You et al. 2020; which tensors adapt is timm's rule).  Four launches.  Tensor t
+ * uses lr_t, wd_t = those of groups_dev[tensors_dev[t].group] when groups_dev != NULL (lr_dev is then ignored), else
+ * hparams->lr (lr_dev[0] when lr_dev != NULL) and hparams->weight_decay.  All arithmetic in fp32, in this order:
+ *   passes 1, 2  calm_optim_step's own kernels on its scratch layout (the first 6*n_tensors + 4 + 3*n_chunks floats): the
+ *                gradient norm, the clip coefficient, found_inf and step_dev have the bits calm_optim_step gives them
+ *   pass 3       g' = ((G - c u_i v_j) * (1/sigma)) * (clip / grad_scale)    (the first factor only with sn_sigma)
+ *                m = m + (g' - m) * (1 - b1);   v = v * b2 + g'^2 * (1 - b2);   both stored
+ *                r = (m / (sqrt(v) * (1 / sqrt(1 - b2^t)) + eps)) / (1 - b1^t)
+ *                u = r + wd_t * w                                 (three roundings, never contracted into an fma)
+ *                per chunk: sum w^2 and sum u^2, a thread's elements added serially, then the workgroup's tree; w is read only
+ *   pass 4       W2, U2 = the tensor's chunk sums added in chunk order;  wn = sqrt(W2), un = sqrt(U2)
+ *                trust = (adapt_t && wn > 0 && un > 0) ? wn / un : 1,   adapt_t = always_adapt || wd_t != 0
+ *                trust_clip > 0:  trust = min(trust, trust_clip)
+ *                lr_t != 0:  u recomputed from the stored m, v and the untouched w (the same bits as in pass 3),
+ *                            w = w - (lr_t * trust) * u;    lr_t == 0: w keeps its bits, its moments have moved
+ * found_inf: nothing is written — not w, m, v, not trust_out — and step_dev does not advance.
+ * scratch: calm_optim_lamb_scratch_floats(n_tensors, n_chunks) floats (calm_optim_step's plus 2 per chunk).
+ * trust_out (nullable, device): 3*n_tensors floats, (wn, un, trust) of every tensor on an applied step.
+ * hparams->beta1, beta2, eps, max_norm, step / step_dev and stats_out mean what they mean to calm_optim_step.  As for
+ * calm_optim_step_groups the caller guarantees 0 <= group < n_groups and lr >= 0 for every group.
+ * No atomics, every sum in a fixed order, no result depends on the grid; does not allocate or synchronise; captures into a
+ * hipGraph.  CALM_E_INVAL, before any launch: everything calm_optim_step (without groups_dev) / calm_optim_step_groups (with
+ * it) refuse, a null lamb_hparams, a trust_clip that is NaN or negative, always_adapt outside {0, 1}, groups_dev with
+ * n_groups <= 0.
+ * ------------------------------------------------------------------------------------- */
+typedef struct calm_lamb_hparams {
+    float trust_clip;         /* 0: no upper limit on the trust ratio */
+    int32_t always_adapt;     /* 1: tensors with wd_t == 0 get a trust ratio too */
+} calm_lamb_hparams;
+int64_t calm_optim_lamb_scratch_floats(int32_t n_tensors, int32_t n_chunks);   /* CALM_E_INVAL for a count <= 0 */
+int calm_optim_step_lamb(const calm_optim_tensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev,
+                         int32_t n_chunks, float* scratch, const calm_optim_hparams* hparams,
+                         const calm_lamb_hparams* lamb_hparams, const calm_optim_group* groups_dev /* nullable */,
+                         int32_t n_groups, const float* grad_scale /* device scalar or NULL */, float* stats_out,
+                         float* trust_out /* nullable */, int32_t* step_dev,
+                         const float* lr_dev /* nullable, ignored with groups_dev */, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gradient accumulation over micro-batches (addition to ABI v7), between a backward and calm_optim_step:
  *   acc[t][i] = first ? g'[i] : acc[t][i] + g'[i]
  * for every tensor t of calm_optim_step's table (tensors_dev / chunk_tensor_dev exactly as handed to it, gradient
