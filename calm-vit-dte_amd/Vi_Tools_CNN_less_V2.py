@@ -141,6 +141,10 @@ class GELU(torch.nn.Module):
 class VMLA_Block(torch.nn.Module):
     """Multi-head latent-distribution attention block (Vi_Tools:98-315)."""
 
+    # stochastic-depth rate of the block's two residual joins (set_drop_path; no counterpart in the reference, whose
+    # constructor signature stays).  Read at call time, in training mode only, as the dropout modules' `.p` is.
+    drop_path = 0.0
+
     def __init__(
         self,
         heads: int,
@@ -321,7 +325,15 @@ class VMLA_Block(torch.nn.Module):
         # the two nn.Dropout modules only carry p (read at call time, so setting `.p` on them works); the dropout itself is
         # ops.DropoutAddFn / inside ops.MlpFn.  Keys in the reference's call order: attention site (301), then the MLP (203)
         p_att = self.dropout.p if self.training else 0.0
-        if p_att > 0:
+        # stochastic depth (no counterpart in the reference): each residual join is skip + drop_path(dropout(ls * branch)),
+        # as timm composes them, with one key per site — attention dropout, attention drop-path, MLP dropout, MLP drop-path
+        p_path = self.drop_path if self.training else 0.0
+        if p_path > 0:
+            x = self.out_proj(x, ls=self.ls_att)                         # 300
+            if p_att > 0:
+                x = ops.DropoutAddFn.apply(x, None, p_att, ops.draw_dropout_key(x.device))   # 301, in place
+            x = ops.DropPathAddFn.apply(x, residual, p_path, ops.draw_dropout_key(x.device))   # 309
+        elif p_att > 0:
             x = self.out_proj(x, ls=self.ls_att)                         # 300
             x = ops.DropoutAddFn.apply(x, residual, p_att, ops.draw_dropout_key(x.device))   # 301, 309
         else:
@@ -330,12 +342,37 @@ class VMLA_Block(torch.nn.Module):
             return self.ln_2(x)                                          # block output: stays fp32
         y, x = self.ln_2.with_skip(x)
         l0, l3 = self.mlp[0], self.mlp[3]
-        mlp_args = (y, l0.weight_orig, None, l3.weight_orig, None, self.ls_mlp, x,
+        mlp_args = (y, l0.weight_orig, None, l3.weight_orig, None, self.ls_mlp, None if p_path > 0 else x,
                     l0.weight_u, l0.weight_v, l0.sigma(), l3.weight_u, l3.weight_v, l3.sigma())
         p_mlp = self.mlp[2].p if self.training else 0.0
         if p_mlp > 0:
-            return ops.MlpFn.apply(*mlp_args, p_mlp, ops.draw_dropout_key(y.device))
-        return ops.MlpFn.apply(*mlp_args, 0.0, None, lean_forward())
+            out = ops.MlpFn.apply(*mlp_args, p_mlp, ops.draw_dropout_key(y.device))
+        else:
+            out = ops.MlpFn.apply(*mlp_args, 0.0, None, lean_forward())
+        if p_path > 0:
+            out = ops.DropPathAddFn.apply(out, x, p_path, ops.draw_dropout_key(out.device))
+        return out
+
+
+def drop_path_rates(module):
+    """[(name, rate)] of every VMLA_Block under `module`, in forward order (the modules' registration order: encoder_blocks,
+    the two bottlenecks, decoder_blocks, and inside each Block encoder, decoder, cross)."""
+    return [(name, float(m.drop_path)) for name, m in module.named_modules() if isinstance(m, VMLA_Block)]
+
+
+def set_drop_path(module, rate, schedule="linear"):
+    """Stochastic depth for every VMLA_Block under `module` (timm's drop_path_rate): block i of n, in forward order, drops
+    each of its two residual branches per sample with probability rate * i / (n - 1) ("linear", timm's rule; a single
+    block gets `rate`) or `rate` ("uniform").  rate=0 switches it off.  Returns the (name, rate) list."""
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= rate < 1.0:
+        raise ValueError(f"set_drop_path: rate must be in the range 0 <= rate < 1, got {rate!r}")
+    if schedule not in ("linear", "uniform"):
+        raise ValueError(f'set_drop_path: schedule is "linear" or "uniform", got {schedule!r}')
+    blocks = [m for m in module.modules() if isinstance(m, VMLA_Block)]
+    n = len(blocks)
+    for i, blk in enumerate(blocks):
+        blk.drop_path = float(rate) if schedule == "uniform" or n == 1 else float(rate) * i / (n - 1)
+    return drop_path_rates(module)
 
 
 class CnnResidual(torch.nn.Sequential):

@@ -290,6 +290,7 @@ SIGNATURES = {
     "calm_distill_fwd": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i64, _f32, _f32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p]),
     "calm_distill_bwd": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i64, _f32, _f32, _i32, _p, _p, _p, _i32, _i32, _p]),
     "calm_dropout": (_i32, [_p, _p, _p, _i64, _i64, _f32, _p, _i32, _i32, _i32, _p]),
+    "calm_drop_path": (_i32, [_p, _p, _p, _i64, _i64, _i64, _f32, _p, _i32, _i32, _i32, _p]),
 }
 
 _lib = None

@@ -1497,6 +1497,17 @@ class HipBackend:
                                          n, e0, float(p), key.data_ptr(), _st(x), _st(residual), _st(y), _stream()),
                    "calm_dropout")
 
+    def drop_path(self, x, residual, y, B, L, p, key, sample0=0):
+        """y[b, j] = x[b, j] * mask(sample0 + b) / (1 - p) + residual[b, j] over B rows of L elements: stochastic depth with
+        ONE decision per row, the dropout mask's decision for element index sample0 + b under `key` (device int64 [2] = seed,
+        offset, read by the kernel); x / residual / y fp32 or bf16 independently, residual may be None, y may be x."""
+        if key is None or not key.is_cuda or key.dtype != torch.int64 or key.numel() != 2 or not key.is_contiguous():
+            raise TypeError("drop_path expects its key as a contiguous int64 CUDA tensor of two elements (seed, offset)")
+        _lib.check(self.lib.calm_drop_path(_ptr(x, bf16_ok=True), _ptr(residual, True, bf16_ok=True), _ptr(y, bf16_ok=True),
+                                           B, L, sample0, float(p), key.data_ptr(), _st(x), _st(residual), _st(y),
+                                           _stream()),
+                   "calm_drop_path")
+
     # ---- helpers ----------------------------------------------------------------------
     def add(self, a, b, out, n):
         _lib.check(self.lib.calm_add(_ptr(a), _ptr(b), _ptr(out), n, _stream()), "calm_add")

@@ -14,6 +14,10 @@
 // into an fma), bf16 inputs widen exactly and a bf16 output is one round-to-nearest-even of the fp32
 // result.  It is a multiply, not a select: a dropped NaN / inf yields NaN.  y may alias x (each element is read by the
 // thread that writes it, before it writes it).  No LDS, no atomics.
+//
+// Stochastic depth (calm_drop_path) is the per-sample sibling: row b of a [B, L] tensor is multiplied by ONE factor, decided
+// by word(sample0 + b) of the same generator, under the same arithmetic contract and with the same vector / element-wise
+// split.
 #include "common.h"
 #include "philox.h"
 
@@ -66,52 +70,65 @@ __device__ __forceinline__ void drop_elements(const void* x, const void* res, vo
     }
 }
 
-// EPT elements per thread and pass: 8 when a tensor is bf16 (its 16-byte vector), else 4.  R: 0 = no residual, 1 = fp32,
-// 2 = bf16.  The tensors carry no __restrict__: y may be x.
+// One unit of EPT elements — 8 when a tensor is bf16 (its 16-byte vector), else 4 — as EPT / 4 fp32 quads: a bf16 tensor
+// moves as one 16-byte vector, an fp32 tensor as EPT / 4 of them.  R: 0 = no residual, 1 = fp32, 2 = bf16.
+template <bool X16, int R, bool Y16>
+constexpr int unit_elems() { return (X16 || Y16 || R == 2) ? 8 : 4; }
+
+template <bool T16, int EPT>
+__device__ __forceinline__ void load_unit(const void* p, long u, f32x4 (&v)[EPT / 4]) {
+    if constexpr (T16) {                                       // one 16-byte load of eight bf16 (T16 implies EPT == 8)
+        const bf16x8 t = reinterpret_cast<const bf16x8*>(p)[u];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i / 4][i % 4] = (float)t[i];
+    } else {
+#pragma unroll
+        for (int h = 0; h < EPT / 4; ++h) v[h] = reinterpret_cast<const f32x4*>(p)[u * (EPT / 4) + h];
+    }
+}
+template <int R, int EPT>
+__device__ __forceinline__ void add_unit(const void* res, long u, f32x4 (&v)[EPT / 4]) {
+    if constexpr (R != 0) {
+        f32x4 t[EPT / 4];
+        load_unit<R == 2, EPT>(res, u, t);
+#pragma unroll
+        for (int h = 0; h < EPT / 4; ++h)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[h][i] = add_rn(v[h][i], t[h][i]);
+    }
+}
+template <bool T16, int EPT>
+__device__ __forceinline__ void store_unit(void* p, long u, const f32x4 (&v)[EPT / 4]) {
+    if constexpr (T16) {
+        bf16x8 o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = (__bf16)v[i / 4][i % 4];
+        reinterpret_cast<bf16x8*>(p)[u] = o;
+    } else {
+#pragma unroll
+        for (int h = 0; h < EPT / 4; ++h) reinterpret_cast<f32x4*>(p)[u * (EPT / 4) + h] = v[h];
+    }
+}
+
+// The tensors carry no __restrict__: y may be x.
 template <bool X16, int R, bool Y16>
 __global__ __launch_bounds__(NT) void dropout_vec_kernel(const void* x, const void* res, void* y, long n,
                                                          uint64_t g0, uint32_t thr, float scale,
                                                          const uint64_t* __restrict__ key) {
-    constexpr int EPT = (X16 || Y16 || R == 2) ? 8 : 4;
+    constexpr int EPT = unit_elems<X16, R, Y16>();
     const DropKey k = drop_key(key);
     const long stride = (long)gridDim.x * NT, units = n / EPT;
     for (long u = (long)blockIdx.x * NT + threadIdx.x; u < units; u += stride) {
         f32x4 v[EPT / 4];
-        if constexpr (X16 && EPT == 8) {                       // one 16-byte load of eight bf16
-            const bf16x8 t = reinterpret_cast<const bf16x8*>(x)[u];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i / 4][i % 4] = (float)t[i];
-        } else {
-#pragma unroll
-            for (int h = 0; h < EPT / 4; ++h) v[h] = reinterpret_cast<const f32x4*>(x)[u * (EPT / 4) + h];
-        }
+        load_unit<X16, EPT>(x, u, v);
 #pragma unroll
         for (int h = 0; h < EPT / 4; ++h) {
             const u32x4 w = philox4x32_10(g0 + (uint64_t)u * (EPT / 4) + h, k);
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[h][i] = drop_one(v[h][i], w[i], thr, scale);
         }
-        if constexpr (R == 2) {
-            const bf16x8 t = reinterpret_cast<const bf16x8*>(res)[u];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i / 4][i % 4] = add_rn(v[i / 4][i % 4], (float)t[i]);
-        } else if constexpr (R == 1) {
-#pragma unroll
-            for (int h = 0; h < EPT / 4; ++h) {
-                const f32x4 t = reinterpret_cast<const f32x4*>(res)[u * (EPT / 4) + h];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[h][i] = add_rn(v[h][i], t[i]);
-            }
-        }
-        if constexpr (Y16) {
-            bf16x8 o;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o[i] = (__bf16)v[i / 4][i % 4];
-            reinterpret_cast<bf16x8*>(y)[u] = o;
-        } else {
-#pragma unroll
-            for (int h = 0; h < EPT / 4; ++h) reinterpret_cast<f32x4*>(y)[u * (EPT / 4) + h] = v[h];
-        }
+        add_unit<R, EPT>(res, u, v);
+        store_unit<Y16, EPT>(y, u, v);
     }
     drop_elements(x, R ? res : nullptr, y, units * EPT, n, g0, thr, scale, k, X16 ? CALM_ST_BF16 : CALM_ST_F32,
                   R == 2 ? CALM_ST_BF16 : CALM_ST_F32, Y16 ? CALM_ST_BF16 : CALM_ST_F32);       // the n % EPT last elements
@@ -122,6 +139,83 @@ __global__ __launch_bounds__(NT) void dropout_elem_kernel(const void* x, const v
                                                           uint32_t thr, float scale, const uint64_t* __restrict__ key,
                                                           int x_type, int r_type, int y_type) {
     drop_elements(x, res, y, 0, n, g0, thr, scale, drop_key(key), x_type, r_type, y_type);
+}
+
+// ---- stochastic depth: one decision per sample (row), the word calm_dropout defines for element index sample0 + b ------
+// A workgroup walks (sample, chunk-of-row) pairs, pair = blockIdx.x + i * gridDim.x = b * cpr + c with cpr chunks of NT
+// units (vector kernel) or NT elements (element-wise kernel) per row.  (b, c) advance by (gridDim.x / cpr, gridDim.x % cpr)
+// with a carry — both computed on the host — so the walk holds no division; the first pair's division is a 32-bit one
+// (blockIdx.x < MAX_BLOCKS, and cpr32 = min(cpr, 2^31 - 1) divides like cpr below that).
+struct PathWalk {
+    long B, cpr, db, dc;
+    uint32_t cpr32;
+};
+
+// f_b: the sample index, its Philox call and the factor are uniform over the workgroup — once per pair
+__device__ __forceinline__ float path_factor(uint64_t s, uint32_t thr, float scale, const DropKey& k) {
+    const u32x4 w = philox4x32_10(s >> 2, k);
+    const int q = (int)(s & 3);
+    const uint32_t word = q == 0 ? w[0] : q == 1 ? w[1] : q == 2 ? w[2] : w[3];
+    return word >= thr ? scale : 0.0f;
+}
+
+// body(b, c, f) for every pair of this workgroup
+template <class Body>
+__device__ __forceinline__ void path_walk(const PathWalk& w, uint64_t sample0, uint32_t thr, float scale,
+                                          const uint64_t* __restrict__ key, Body&& body) {
+    const DropKey k = drop_key(key);
+    long b = blockIdx.x / w.cpr32, c = blockIdx.x % w.cpr32;
+    while (b < w.B) {
+        body(b, c, path_factor(sample0 + (uint64_t)b, thr, scale, k));
+        b += w.db;
+        c += w.dc;
+        if (c >= w.cpr) {
+            c -= w.cpr;
+            ++b;
+        }
+    }
+}
+
+// rows of UL units of EPT elements each (L == UL * EPT, every base 16-byte aligned: every row starts on a vector)
+template <bool X16, int R, bool Y16>
+__global__ __launch_bounds__(NT) void drop_path_vec_kernel(const void* x, const void* res, void* y, long UL, PathWalk w,
+                                                           uint64_t sample0, uint32_t thr, float scale,
+                                                           const uint64_t* __restrict__ key) {
+    constexpr int EPT = unit_elems<X16, R, Y16>();
+    path_walk(w, sample0, thr, scale, key, [&](long b, long c, float f) {
+        const long ur = c * NT + threadIdx.x;                  // unit within the row
+        if (ur >= UL) return;
+        const long u = b * UL + ur;
+        f32x4 v[EPT / 4];
+        load_unit<X16, EPT>(x, u, v);
+#pragma unroll
+        for (int h = 0; h < EPT / 4; ++h) v[h] = v[h] * f;     // a multiply, not a select
+        add_unit<R, EPT>(res, u, v);
+        store_unit<Y16, EPT>(y, u, v);
+    });
+}
+
+// any L and any alignment; storage types are run-time values here
+__global__ __launch_bounds__(NT) void drop_path_elem_kernel(const void* x, const void* res, void* y, long L, PathWalk w,
+                                                            uint64_t sample0, uint32_t thr, float scale,
+                                                            const uint64_t* __restrict__ key, int x_type, int r_type,
+                                                            int y_type) {
+    path_walk(w, sample0, thr, scale, key, [&](long b, long c, float f) {
+        const long jr = c * NT + threadIdx.x;
+        if (jr >= L) return;
+        const long j = b * L + jr;
+        float v = ld1(x, j, x_type) * f;
+        if (res) v = add_rn(v, ld1(res, j, r_type));
+        if (y_type == CALM_ST_BF16) reinterpret_cast<__bf16*>(y)[j] = (__bf16)v;
+        else reinterpret_cast<float*>(y)[j] = v;
+    });
+}
+
+// the walk of B rows of `per_row` work items (units or elements) and its grid
+inline PathWalk path_walk_for(int64_t B, int64_t per_row, int* grid) {
+    const int64_t cpr = (per_row + NT - 1) / NT;
+    *grid = (int)(B <= MAX_BLOCKS / cpr ? B * cpr : MAX_BLOCKS);       // min(B * cpr, MAX_BLOCKS) without the overflow
+    return {B, cpr, *grid / cpr, *grid % cpr, (uint32_t)(cpr < 0x7fffffff ? cpr : 0x7fffffff)};
 }
 
 }  // namespace
@@ -147,6 +241,33 @@ int calm_dropout(const void* x, const void* residual, void* y, int64_t n, int64_
             return with_bool(y16, [&](auto yb) {
                 return calm_launch(dropout_vec_kernel<decltype(xb)::value, decltype(rv)::value, decltype(yb)::value>,
                                    grid_for(n / ept, NT), NT, 0, stream, x, residual, y, n, g0, thr, scale, key);
+            });
+        });
+    });
+}
+
+int calm_drop_path(const void* x, const void* residual, void* y, int64_t B, int64_t L, int64_t sample0, float p,
+                   const uint64_t* key, int32_t x_type, int32_t r_type, int32_t y_type, void* stream) {
+    if (!x || !y || !key || B < 0 || L < 0 || sample0 < 0 || !(p >= 0.0f && p < 1.0f)) return CALM_E_INVAL;
+    if (!st_ok(x_type) || !st_ok(r_type) || !st_ok(y_type)) return CALM_E_INVAL;
+    if (B == 0 || L == 0) return 0;
+    const uint32_t thr = (uint32_t)((double)p * 4294967296.0);
+    const float scale = 1.0f / (1.0f - p);
+    const bool x16 = x_type == CALM_ST_BF16, y16 = y_type == CALM_ST_BF16, r16 = r_type == CALM_ST_BF16;
+    const int ept = (x16 || y16 || (residual && r16)) ? 8 : 4;
+    int grid;
+    if (!(aligned16(x) && aligned16(y) && aligned16(residual)) || L % ept) {
+        const PathWalk w = path_walk_for(B, L, &grid);
+        return calm_launch(drop_path_elem_kernel, grid, NT, 0, stream, x, residual, y, L, w, (uint64_t)sample0, thr, scale,
+                           key, x_type, r_type, y_type);
+    }
+    const PathWalk w = path_walk_for(B, L / ept, &grid);
+    const int r = !residual ? 0 : r16 ? 2 : 1;
+    return with_bool(x16, [&](auto xb) {
+        return with_int<0, 1, 2>(r, [&](auto rv) {
+            return with_bool(y16, [&](auto yb) {
+                return calm_launch(drop_path_vec_kernel<decltype(xb)::value, decltype(rv)::value, decltype(yb)::value>,
+                                   grid, NT, 0, stream, x, residual, y, L / ept, w, (uint64_t)sample0, thr, scale, key);
             });
         });
     });

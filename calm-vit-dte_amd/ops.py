@@ -1269,18 +1269,27 @@ class AddFn(Function):
 class DropoutAddFn(Function):
     """y = dropout(x) + residual (Vi_Tools:301,309: the attention branch behind out_proj * ls_att joins the skip path).
     apply(x, residual, p, key); key from draw_dropout_key.  Only the 16-byte key is kept for the backward, which
-    regenerates the mask: dx = dropout(dy), dresidual = dy."""
+    regenerates the mask: dx = dropout(dy), dresidual = dy.  residual=None: x is dropped IN PLACE and returned (the site
+    in front of a drop-path join, which adds the skip path itself); x is then a contiguous result nothing else has saved."""
 
     @staticmethod
     @_amp_fwd
     def forward(ctx, x, residual, p, key):
         be = get_backend()
+        if residual is None:
+            if not x.is_contiguous():
+                raise ValueError("DropoutAddFn: the in-place form needs a contiguous x")
+            ctx.mark_dirty(x)
+            be.dropout(x, None, x, x.numel(), p, key)
+            ctx.p, ctx.has_res = float(p), False
+            ctx.save_for_backward(key)
+            return x
         x, residual = _c(x), _c(residual)
         if x.shape != residual.shape:
             raise ValueError("DropoutAddFn: x and residual must have one shape")
         y = torch.empty_like(x)
         be.dropout(x, residual, y, x.numel(), p, key)
-        ctx.p = float(p)
+        ctx.p, ctx.has_res = float(p), True
         ctx.save_for_backward(key)
         return y
 
@@ -1294,6 +1303,40 @@ class DropoutAddFn(Function):
             dy_c = _c(dy)
             dx = torch.empty_like(dy_c)
             get_backend().dropout(dy_c, None, dx, dy_c.numel(), ctx.p, key)
+        return dx, dy if ctx.has_res else None, None, None
+
+
+class DropPathAddFn(Function):
+    """y = drop_path(x) + residual: stochastic depth at a residual join, one keep decision per sample (timm's drop_path,
+    torchvision's StochasticDepth(mode="row")).  apply(x, residual, p, key); x [B, ...] contiguous, one row per leading
+    index; key from draw_dropout_key.  Only the 16-byte key is kept for the backward, which regenerates the mask:
+    dx = drop_path(dy), dresidual = dy."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, x, residual, p, key):
+        be = get_backend()
+        x, residual = _c(x), _c(residual)
+        if x.shape != residual.shape or x.dim() < 1:
+            raise ValueError("DropPathAddFn: x and residual must have one shape [B, ...]")
+        y = torch.empty_like(x)
+        B = x.shape[0]
+        be.drop_path(x, residual, y, B, x.numel() // max(B, 1), p, key)
+        ctx.p = float(p)
+        ctx.save_for_backward(key)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    @_amp_bwd
+    def backward(ctx, dy):
+        key, = ctx.saved_tensors
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dy_c = _c(dy)
+            dx = torch.empty_like(dy_c)
+            B = dy_c.shape[0]
+            get_backend().drop_path(dy_c, None, dx, B, dy_c.numel() // max(B, 1), ctx.p, key)
         return dx, dy, None, None
 
 

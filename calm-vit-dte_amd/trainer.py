@@ -34,6 +34,9 @@ as set by torchrun):
   * `FusedClipAdamW(lamb=)` / `lamb_step_torch` / `train(lamb=)`   (no counterpart: the reference has no large-batch optimizer)
         LAMB inside the fused optimizer-side step (calm_optim_step_lamb): AdamW's moments, clip and inf check, every
         tensor's update rescaled by its trust ratio ||w|| / ||update||.
+  * `train(drop_path=)`   (no counterpart: the reference has no stochastic depth)
+        Vi_Tools_CNN_less_V2.set_drop_path on the model before the step is built: per-sample drops of both residual
+        branches of every VMLA_Block (calm_drop_path), the per-block rates recorded in the snapshot header.
 
 The model also works under stock `torch.nn.parallel.DistributedDataParallel` (that is what the
 reference's train() does with it); the reducer here is the MI355X-tuned equivalent.  Under DDP the step
@@ -3236,11 +3239,20 @@ class TrainState:
             h["lrs"] = [g["lr"] for g in self.opt.param_groups]
         if self.fused and self.opt.lamb is not None:          # the state is AdamW's; the key alone tells the two rules apart
             h["lamb"] = dict(self.opt.lamb)
+        rates = self._drop_path_rates()
+        if rates is not None:                                 # stochastic depth changes what a step computes, not its state
+            h["drop_path"] = rates
         if not self.fused and self.payload:
             h["optimizer"] = self._optim_desc
             if self.scaler is not None:            # torch's own GradScaler policy: its growth count (reading it synchronises)
                 h["scaler"] = {"growth_tracker": int(self.scaler.state_dict()["_growth_tracker"])}
         return h
+
+    def _drop_path_rates(self):
+        """The per-block stochastic-depth rates of the model in forward order, or None when every rate is 0."""
+        from .Vi_Tools_CNN_less_V2 import drop_path_rates
+        rates = [r for _, r in drop_path_rates(self.model)]
+        return rates if any(r > 0 for r in rates) else None
 
     def _set_rng(self, h):
         torch.set_rng_state(_unb64(h["rng"]["torch_cpu"]))
@@ -3404,6 +3416,10 @@ class TrainState:
         if self.fused and ("lamb" in host) != (self.opt.lamb is not None):
             raise ValueError(f"{path}: written with{'' if 'lamb' in host else 'out'} LAMB, this optimizer steps "
                              f"with{'' if self.opt.lamb is not None else 'out'} it")
+        rates = self._drop_path_rates()
+        if host.get("drop_path") != rates:
+            said = lambda r: "without drop_path" if r is None else f"with drop_path rates {min(r):.4g} .. {max(r):.4g}"  # noqa: E731
+            raise ValueError(f"{path}: written {said(host.get('drop_path'))}, this model runs {said(rates)}")
         # the entries: everything but a torch optimizer's state must be the live set, name by name
         head, optim, tail = self._fixed_entries()
         live = head + optim + tail
@@ -3783,7 +3799,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
                       device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path, snapshot_every,
                       accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task, teacher, distill,
                       param_groups, scheduler_step, monitor=None, random_erasing=None, label_smoothing=0.0, rand_augment=None,
-                      sam=None, lamb=None):
+                      sam=None, lamb=None, drop_path=None):
     """Every refusal train() makes from its arguments alone: it touches no device and no process group, so a bad call
     fails before either exists.  Returns the normalised values the job is assembled from: accumulate (int), ema_kw
     (None without ema), distill_kw (DistillTrainStep's keywords, {} without a teacher), teacher_mod, resize (the
@@ -3791,9 +3807,11 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
     monitor=; "every" None: log_every), erase (None, a DeviceErase, or the dict of arguments one is built from),
     label_smoothing (float), rand_augment (None, a DeviceRandAugment, or the dict of arguments one is built from), sam_kw
     (None without sam=; SharpnessAware's keywords and "sync"), lamb (None, or the normalised settings of
-    FusedClipAdamW(lamb=) — the argument's, or those of the optimizer object handed in)."""
+    FusedClipAdamW(lamb=) — the argument's, or those of the optimizer object handed in), drop_path (None, or
+    {"rate", "schedule"} for set_drop_path)."""
     from . import backend as _backend
     from types import SimpleNamespace
+    drop_kw = _drop_path_settings(drop_path)
     if scheduler_step not in ("epoch", "step"):
         raise ValueError(f'train: scheduler_step is "epoch" or "step", got {scheduler_step!r}')
     if param_groups is not None and not (isinstance(optimizer, str) and optimizer == "fused"):
@@ -3975,7 +3993,28 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
             EvalMetrics(num_classes, topk=val_topk)         # (refuses a malformed val_topk here, not after the first epoch)
     return SimpleNamespace(accumulate=accumulate, ema_kw=ema_kw, distill_kw=distill_kw, teacher_mod=teacher_mod, resize=resize,
                            window=window, reg=reg, per_step=scheduler_step == "step", monitor_kw=monitor_kw, erase=erase,
-                           label_smoothing=float(label_smoothing), rand_augment=randaug, sam_kw=sam_kw, lamb=lamb_kw)
+                           label_smoothing=float(label_smoothing), rand_augment=randaug, sam_kw=sam_kw, lamb=lamb_kw,
+                           drop_path=drop_kw)
+
+
+def _drop_path_settings(drop_path):
+    """drop_path= of train() -> None, or {"rate": in [0, 1), "schedule": "linear" | "uniform"}."""
+    if drop_path is None or drop_path is False:
+        return None
+    if isinstance(drop_path, dict):
+        if not set(drop_path) <= {"rate", "schedule"} or "rate" not in drop_path:
+            raise ValueError(f'train: drop_path takes the keys "rate" (needed) and "schedule", got {sorted(drop_path)}')
+        kw = {"schedule": "linear", **drop_path}
+    elif not isinstance(drop_path, bool) and isinstance(drop_path, (int, float)):
+        kw = {"rate": drop_path, "schedule": "linear"}
+    else:
+        raise ValueError(f'train: drop_path is None, a rate or a dict with "rate" / "schedule", got {drop_path!r}')
+    rate = kw["rate"]
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= rate < 1.0:
+        raise ValueError(f'train: drop_path["rate"] is a probability in [0, 1), got {rate!r}')
+    if kw["schedule"] not in ("linear", "uniform"):
+        raise ValueError(f'train: drop_path["schedule"] is "linear" or "uniform", got {kw["schedule"]!r}')
+    return {"rate": float(rate), "schedule": kw["schedule"]}
 
 
 class _TrainInput:
@@ -4221,7 +4260,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
           val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
           teacher=None, distill=None, param_groups=None, scheduler_step="epoch", monitor=None, random_erasing=None,
-          label_smoothing=0.0, rand_augment=None, sam=None, lamb=None):
+          label_smoothing=0.0, rand_augment=None, sam=None, lamb=None, drop_path=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -4441,7 +4480,20 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     update-ratio fields keep their meaning (the AdamW direction at the group's rate) — under LAMB the APPLIED ratio
     ||dw|| / ||w|| of an adapted, unclipped tensor is its lr by construction.  Rank 0 prints one line with the settings, and
     the returned model carries the optimizer as `model._calm_lamb` (`trust_ratios()`).  Refused: unknown keys,
-    trust_clip <= 0, a torch optimizer, an optimizer object whose lamb setting differs from the argument."""
+    trust_clip <= 0, a torch optimizer, an optimizer object whose lamb setting differs from the argument.
+
+    drop_path=rate | {"rate": r, "schedule": "linear" | "uniform"} (stochastic depth: timm's `drop_path_rate`, the
+    regulariser of the DeiT / DeiT III recipes; no counterpart in the reference): `set_drop_path(model, rate, schedule)`
+    before the step is built, so VMLA_Block i of n drops each of its two residual branches per sample with probability
+    rate i / (n - 1) ("linear") or rate ("uniform") — skip + drop_path(dropout(ls branch)) through calm_drop_path, the mask
+    regenerated in the backward from a 16-byte key drawn on the device.  It needs no particular optimizer and works with
+    graph=True (every replay draws new masks), accumulate, sam= (the two passes draw DIFFERENT masks, as they do for
+    dropout: the perturbation is taken on one sub-network and the step on another), lamb=, ema, teacher= (the teacher runs
+    in eval mode and is not dropped), task="reg", monitor=, device_collate and its companions.  Validation and eval run the
+    full network.  The keys come from torch's device generator, whose state a snapshot holds: resume= continues bit for
+    bit; the snapshot's header records the per-block rates, and a snapshot written with rates is refused by a run with
+    other rates or none (and the other way round).  Rank 0 prints one line with the schedule and the lowest / highest
+    rate, and the returned model keeps its rates.  Refused: unknown keys, a rate outside [0, 1), an unknown schedule."""
     from functools import partial
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
@@ -4449,7 +4501,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                           device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path,
                           snapshot_every, accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task,
                           teacher, distill, param_groups, scheduler_step, monitor, random_erasing, label_smoothing, rand_augment,
-                          sam, lamb)
+                          sam, lamb, drop_path)
     accumulate, per_step, teacher_mod = args.accumulate, args.per_step, args.teacher_mod
     rank, local_rank, world = init_distributed(use_gpu)
     main = rank == 0 and local_rank == 0                    # the one process that prints and writes
@@ -4465,6 +4517,12 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
             be._selfcheck_done = True
             torch.cuda.empty_cache()
     model = initializer.to(device)
+    if args.drop_path is not None:
+        from .Vi_Tools_CNN_less_V2 import set_drop_path
+        rates = [r for _, r in set_drop_path(model, args.drop_path["rate"], args.drop_path["schedule"])]
+        if main:
+            print(f"drop_path: {args.drop_path['schedule']} over {len(rates)} blocks, rates {min(rates, default=0.0):.4f} .. "
+                  f"{max(rates, default=0.0):.4f}")
     if isinstance(optimizer, str) and optimizer == "fused":
         optimizer = _fused_optimizer(model, param_groups, accumulate, verbose=main, window=args.sam_kw is not None,
                                      lamb=args.lamb)

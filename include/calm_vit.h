@@ -1135,6 +1135,28 @@ int calm_dropout(const void* x, const void* residual /* nullable */, void* y, in
                  void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Stochastic depth with the mask of calm_dropout, one decision per sample (an addition to ABI v7; timm's drop_path,
+ * torchvision's StochasticDepth(mode="row"); no counterpart in the reference).  x, residual, y: [B, L], rows contiguous.
+ *     y[b, j] = x[b, j] * f_b + (residual ? residual[b, j] : 0),      f_b = word(sample0 + b) >= thr ? scale : 0
+ * word(s), thr and scale are calm_dropout's (word(s) is what that entry point uses for element index s), so the keep
+ * decisions of a call are those of elements sample0 .. sample0 + B - 1 of a calm_dropout mask under the same key and p:
+ * a function of (seed, offset, sample0 + b) only — not of L, the grid, the vector width, the storage types or of how a
+ * batch is split into calls.  sample0 >= 0 is ANY value (no multiple of 4 is asked for).
+ * key: DEVICE uint64[2] = (seed, offset), read by the kernel — no host synchronisation, valid inside a captured graph.  The
+ * backward is the same entry point: dx = calm_drop_path(dy, NULL, ...) with the forward's key, dresidual = dy.
+ * One fp32 multiply and one fp32 add, each rounded on its own (the add is skipped without a residual); bf16 inputs widen
+ * exactly, a bf16 output is one round-to-nearest-even of the fp32 result.  A multiply, not a select: a NaN / inf in a
+ * dropped sample yields NaN (timm's x * mask does the same).  y may alias x.  Rows move as 16-byte vectors when every base
+ * is 16-byte aligned and L is a multiple of the unit (4 elements with all tensors fp32, 8 with any bf16), else element by
+ * element.  No LDS, no atomics.  x_type / r_type / y_type: CALM_ST_F32 or CALM_ST_BF16.
+ * CALM_E_INVAL: null x / y / key, B < 0, L < 0, sample0 < 0, p outside [0, 1), another storage type.  B == 0 or L == 0
+ * returns 0 without a launch.
+ * ------------------------------------------------------------------------------------- */
+int calm_drop_path(const void* x, const void* residual /* nullable */, void* y, int64_t B, int64_t L, int64_t sample0,
+                   float p, const uint64_t* key /* device, [2] = seed, offset */, int32_t x_type, int32_t r_type,
+                   int32_t y_type, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * The loss end of the step (additions to ABI v7 — no existing signature or struct changes, so the version number
  * stays): logits -> loss and loss -> dL/dlogits as entry points, so that a host driving this boundary without torch can
  * train (forward, one of these, backward, calm_optim_step).  Logits are fp32 (module outputs stay fp32 in every
