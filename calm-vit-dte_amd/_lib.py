@@ -190,6 +190,10 @@ SIGNATURES = {
     "calm_gemm_workspace_bytes": (_i64, [C.POINTER(GemmArgs)]),
     "calm_gemm_set_option": (C.c_int, [_i32, _i32]),
     "calm_gemm_describe": (_i32, [C.POINTER(GemmArgs), C.POINTER(GemmPlan)]),
+    "calm_gemm_lane": (_i32, [C.POINTER(GemmArgs), _p]),
+    "calm_gemm_lane_fork": (_i32, [_p]),
+    "calm_gemm_lane_join": (_i32, [_p]),
+    "calm_gemm_lane_stats": (_i32, [C.POINTER(_i64 * 4)]),
     "calm_reduce_scratch_floats": (_i64, [_i32, _i64, _i32]),
     "calm_reduce_batch_max": (_i32, []),
     "calm_reduce_partials_batch": (_i32, [C.POINTER(ReduceEntry), _i32, _p]),

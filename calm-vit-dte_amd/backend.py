@@ -111,6 +111,32 @@ def get_loss_kernels():
     return _loss_kernels
 
 
+# Weight-gradient GEMMs of a backward on the library's side lane (calm_gemm_lane; ops._lin_wgrad): on by default (Small-224
+# fp32: -1.8 ms of a 128.8 ms step, DESIGN.md section 7, "Weight-gradient lane").  CALM_WGRAD_LANE=0 is the A/B switch,
+# read once, at import.
+_wgrad_lane = os.environ.get("CALM_WGRAD_LANE", "1") != "0"
+
+
+def set_wgrad_lane(on):
+    """True: while the gradient tail is armed (the trainer's step classes), the weight-gradient GEMMs whose first reader
+    is the optimizer-side step are issued on a second, lowest-priority stream the library owns and joined before the
+    backward ends.  Same plans, same kernels: with CALM_GEMM_OPT_DETERMINISTIC the step is bit for bit the step without
+    the lane.  Inside a graph capture the lane is off whatever the switch says.  False: one stream."""
+    global _wgrad_lane
+    _wgrad_lane = bool(on)
+    if isinstance(_backend, HipBackend):
+        _backend.gemm_set_option(HipBackend.GEMM_OPT_LANE, int(_wgrad_lane))
+
+
+def get_wgrad_lane():
+    return _wgrad_lane
+
+
+def wgrad_lane():
+    """Whether ops._lin_wgrad may use the side lane now."""
+    return _wgrad_lane
+
+
 def loss_kernels_take(t):
     """Whether the loss kernels serve tensor `t` now: the switch is on and `t` is an fp32 tensor the installed backend
     can address (HipBackend: CUDA tensors only)."""
@@ -545,6 +571,9 @@ class HipBackend:
         self._scratch_need = {}
         self.plan_epoch = 0
         self.upcast_launches = 0        # calm_gemm launches re-run on fp32 copies (CALM_E_LAYOUT with bf16 tensors)
+        self._lane_ws = []              # workspaces of launches on the side lane, kept until gemm_lane_join
+        if _wgrad_lane:
+            self.gemm_set_option(self.GEMM_OPT_LANE, 1)
 
     def _partials(self, op, rows, cols, device):
         """Device scratch for the fixed-order cross-workgroup reduction of one call (calm_reduce_scratch_floats).  One
@@ -590,11 +619,12 @@ class HipBackend:
         _lib.check(self.lib.calm_reduce_partials_batch(ent, len(items), _stream()), "calm_reduce_partials_batch")
 
     # ---- GEMM -------------------------------------------------------------------------
-    GEMM_OPT_PIPE, GEMM_OPT_PIPE32, GEMM_OPT_DETERMINISTIC = 0, 1, 2
+    GEMM_OPT_PIPE, GEMM_OPT_PIPE32, GEMM_OPT_DETERMINISTIC, GEMM_OPT_LANE = 0, 1, 2, 3
 
     def gemm_set_option(self, option, value):
         """calm_gemm_set_option (ABI v6; v7: GEMM_OPT_DETERMINISTIC = k-split launches through the workspace and a
-        fixed-order reduction instead of fp32 atomics); returns the previous value."""
+        fixed-order reduction instead of fp32 atomics; GEMM_OPT_LANE = gemm(lane=True) launches go to the side lane,
+        see set_wgrad_lane); returns the previous value."""
         prev = self.lib.calm_gemm_set_option(int(option), int(value))
         if prev < 0:
             raise ValueError(f"calm_gemm_set_option({option}, {value}) -> {prev}")
@@ -692,8 +722,11 @@ class HipBackend:
 
     def gemm(self, A, B, Cout, M, N, K, a, b, c, batch=(1, 1), alpha=1.0, inv_scale=None, bias=None,
              col_scale=None, residual=None, r=(0, 0, 0), C_pre=None, aux=None, act=ACT_NONE,
-             accumulate=False, reduce_batch=False, split_k=0, a_dq=None, b_dq=None):
-        """a_dq / b_dq: device dequantisation factors of fp8 operands (quantize_fp8's state[1:2])."""
+             accumulate=False, reduce_batch=False, split_k=0, a_dq=None, b_dq=None, lane=False):
+        """a_dq / b_dq: device dequantisation factors of fp8 operands (quantize_fp8's state[1:2]).
+        lane=True: calm_gemm_lane_fork on the current stream, then the launch through calm_gemm_lane — on the library's
+        side lane while GEMM_OPT_LANE is on and the stream is not capturing, else on the current stream.  The caller
+        keeps A, B and Cout referenced until gemm_lane_join(); the backend keeps the launch's workspace until then."""
         g, (A, B, Cout) = self._gemm_args(A, B, Cout, M, N, K, a, b, c, batch, alpha, inv_scale, bias, col_scale, residual,
                                           r, C_pre, aux, act, accumulate, reduce_batch, split_k, a_dq, b_dq)
         ws = None
@@ -704,7 +737,12 @@ class HipBackend:
             if need > 0:
                 ws = torch.empty(need // 4, dtype=torch.float32, device=Cout.device)
                 g.workspace, g.workspace_bytes = ws.data_ptr(), need
-        rc = self.lib.calm_gemm(C.byref(g), _stream())
+        if lane:
+            # (the fork follows the workspace allocation: whatever the allocator did to hand it out is ordered before it)
+            _lib.check(self.lib.calm_gemm_lane_fork(_stream()), "calm_gemm_lane_fork")
+            rc = self.lib.calm_gemm_lane(C.byref(g), _stream())
+        else:
+            rc = self.lib.calm_gemm(C.byref(g), _stream())
         fp8_operand = g.a_type >= _lib.ST_FP8_E4M3 or g.b_type >= _lib.ST_FP8_E4M3     # fp8 tensors have no fp32 re-run: report
         if rc == _lib.E_LAYOUT and not fp8_operand and (g.a_type or g.b_type or g.c_type or g.aux_type or g.r_type):
             # a bf16 tensor in a launch whose sizes / strides rule out 16-byte staging (the 10-class head of the fixture
@@ -712,6 +750,19 @@ class HipBackend:
             return self._gemm_upcast(A, B, Cout, M, N, K, a, b, c, batch, alpha, inv_scale, bias, col_scale, residual,
                                      r, C_pre, aux, act, accumulate, reduce_batch, split_k, g)
         _lib.check(rc, "calm_gemm")
+        if lane and ws is not None:
+            self._lane_ws.append(ws)    # (the caching allocator knows the block as the current stream's, not the lane's)
+
+    def gemm_lane_join(self):
+        """calm_gemm_lane_join on the current stream: what it is given next follows every lane launch so far."""
+        _lib.check(self.lib.calm_gemm_lane_join(_stream()), "calm_gemm_lane_join")
+        self._lane_ws.clear()
+
+    def gemm_lane_stats(self):
+        """calm_gemm_lane_stats: {"forks", "launches", "joins", "events"} since the library was loaded."""
+        out = (C.c_int64 * 4)()
+        _lib.check(self.lib.calm_gemm_lane_stats(C.byref(out)), "calm_gemm_lane_stats")
+        return dict(zip(("forks", "launches", "joins", "events"), out))
 
     def _gemm_args(self, A, B, Cout, M, N, K, a, b, c, batch=(1, 1), alpha=1.0, inv_scale=None, bias=None,
                    col_scale=None, residual=None, r=(0, 0, 0), C_pre=None, aux=None, act=ACT_NONE,

@@ -7,6 +7,7 @@
 // no side effects; calm_gemm_workspace_bytes, calm_gemm_describe and calm_gemm report or launch that one decision.
 #include <atomic>
 #include "gemm_common.h"
+#include "gemm_lane.h"
 #include <stdlib.h>
 
 using namespace calm_gemm_detail;
@@ -113,14 +114,16 @@ struct Decomp {
 constexpr int PIPE_DECLINED = -1000;
 
 std::atomic<int>& pipe_option(int which) {
-    static std::atomic<int> opt[3] = {
+    static std::atomic<int> opt[4] = {
         [] { const char* e = getenv("CALM_GEMM_PIPE"); return (e && e[0] == '0') ? 0 : 1; }(),
         [] { const char* e = getenv("CALM_GEMM_PIPE32"); return e ? atoi(e) : 0; }(),
-        [] { const char* e = getenv("CALM_GEMM_DETERMINISTIC"); return (e && e[0] == '1') ? 1 : 0; }()};
+        [] { const char* e = getenv("CALM_GEMM_DETERMINISTIC"); return (e && e[0] == '1') ? 1 : 0; }(),
+        0};                                  // CALM_GEMM_OPT_LANE: the caller switches the side lane on (backend.set_wgrad_lane)
     return opt[which];
 }
 // every k-split / batch-reduced launch through the workspace + fixed-order reduction (no fp32 atomics)
 bool deterministic() { return pipe_option(CALM_GEMM_OPT_DETERMINISTIC).load(std::memory_order_relaxed) != 0; }
+bool lane_enabled() { return pipe_option(CALM_GEMM_OPT_LANE).load(std::memory_order_relaxed) != 0; }
 bool pipe_enabled() { return pipe_option(CALM_GEMM_OPT_PIPE).load(std::memory_order_relaxed) != 0; }
 // fp32 instantiation: 0 off (default), 1 every eligible launch, 2 k-contiguous operand pairs only
 int pipe32_mode() { return pipe_enabled() ? pipe_option(CALM_GEMM_OPT_PIPE32).load(std::memory_order_relaxed) : 0; }
@@ -584,14 +587,44 @@ int launch_main(const GemmP& p, const Decomp& d, hipStream_t s) {
     }
 }
 
-}  // namespace
+// ---- the side lane (gemm_lane.h) -----------------------------------------------------------------------------------------
+struct HipLaneRt {
+    using Stream = hipStream_t;
+    using Event = hipEvent_t;
+    static int device(int* d) { return (int)hipGetDevice(d); }
+    static int capturing(Stream s, bool* c) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        const hipError_t e = hipStreamIsCapturing(s, &st);
+        *c = st != hipStreamCaptureStatusNone;
+        return (int)e;
+    }
+    static int stream_create(Stream* s) {       // non-blocking, the lowest priority the device offers
+        int least = 0, greatest = 0;
+        const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+        if (e != hipSuccess) return (int)e;
+        return (int)hipStreamCreateWithPriority(s, hipStreamNonBlocking, least);
+    }
+    static int event_create(Event* e) { return (int)hipEventCreateWithFlags(e, hipEventDisableTiming); }
+    static int record(Event e, Stream s) { return (int)hipEventRecord(e, s); }
+    static int wait(Stream s, Event e) { return (int)hipStreamWaitEvent(s, e, 0); }
+};
 
-extern "C" int calm_gemm(const calm_gemm_args* a, void* stream) {
+calm_lane::Book<HipLaneRt>& lane_book() {
+    static calm_lane::Book<HipLaneRt> book;
+    return book;
+}
+
+// One planned launch on stream `s`, or — `lane` — on the side lane of the current device (on `s` itself while the lane is
+// off or `s` is capturing).  Plan, kernels, split and combine do not depend on the stream.
+int gemm_launch(const calm_gemm_args* a, hipStream_t s, bool lane) {
     GemmP p{};
     Decomp d;
     int rc = plan_gemm(a, p, d);
     if (rc) return rc;
-    hipStream_t s = as_stream(stream);
+    if (lane) {
+        rc = lane_book().launch_stream(lane_enabled(), s, &s);
+        if (rc) return rc;
+    }
     const bool use_ws = uses_workspace(a, d);
     if (use_ws) {
         p.ws = (float*)a->workspace;
@@ -621,8 +654,28 @@ extern "C" int calm_gemm(const calm_gemm_args* a, void* stream) {
     return 0;
 }
 
+}  // namespace
+
+extern "C" int calm_gemm(const calm_gemm_args* a, void* stream) { return gemm_launch(a, as_stream(stream), false); }
+
+extern "C" int calm_gemm_lane(const calm_gemm_args* a, void* main_stream) {
+    return gemm_launch(a, as_stream(main_stream), true);
+}
+
+extern "C" int calm_gemm_lane_fork(void* main_stream) { return lane_book().fork(lane_enabled(), as_stream(main_stream)); }
+
+extern "C" int calm_gemm_lane_join(void* main_stream) { return lane_book().join(as_stream(main_stream)); }
+
+extern "C" int calm_gemm_lane_stats(int64_t out[4]) {
+    if (!out) return CALM_E_INVAL;
+    const calm_lane::Stats st = lane_book().stats();
+    out[0] = st.forks; out[1] = st.launches; out[2] = st.joins; out[3] = st.events;
+    return 0;
+}
+
 extern "C" int calm_gemm_set_option(int32_t option, int32_t value) {
-    if (option != CALM_GEMM_OPT_PIPE && option != CALM_GEMM_OPT_PIPE32 && option != CALM_GEMM_OPT_DETERMINISTIC)
+    if (option != CALM_GEMM_OPT_PIPE && option != CALM_GEMM_OPT_PIPE32 && option != CALM_GEMM_OPT_DETERMINISTIC &&
+        option != CALM_GEMM_OPT_LANE)
         return CALM_E_INVAL;
     if (value < 0 || value > (option == CALM_GEMM_OPT_PIPE32 ? 2 : 1)) return CALM_E_INVAL;
     return pipe_option(option).exchange(value);

@@ -16,7 +16,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .backend import (ACT_GELU, ACT_GELU_BWD, ACT_NONE, act_dtype, bf16_pipeline, effective_precision, fp8_linears,
-                      get_attention_storage, get_backend)
+                      get_attention_storage, get_backend, wgrad_lane)
 from .spectral_norm import W16_ATTR, W16_GEN_ATTR
 
 # The reference calls the model under autocast(bfloat16) (distributed_trainer_cls.py:84): custom_fwd records the
@@ -165,6 +165,7 @@ class _GradTail:
         self.lock = threading.RLock()       # (backward nodes run on the autograd engine's device thread)
         self.armed = False
         self.reduce, self.sn, self.pending = [], [], set()
+        self.lane = []                      # tensors of weight-gradient GEMMs on the side lane, held until the join
         self.callback_queued = False
         self.flushes = 0                    # flushes that launched something
 
@@ -207,6 +208,26 @@ class _GradTail:
     def add_sn(self, G, w, u, v, sigma, ls, dW, d_ls, rows, cols):
         self._enqueue(self.sn, lambda o: (G, w, u, v, sigma, ls, o[0], o[1], rows, cols), [dW, d_ls], (w, ls))
 
+    def add_lane(self, keep, params):
+        """A weight-gradient GEMM went to the library's side lane (backend.gemm(lane=True)): `keep` — its operands and
+        its output — stays referenced until the join, so that the caching allocator, which knows these
+        blocks as the main stream's, hands none of them to main-stream work while the lane reads or writes it."""
+        from torch.autograd import Variable
+        with self.lock:
+            self.lane.append(keep)
+            self.pending.update(id(p) for p in params)
+            if not self.callback_queued:
+                self.callback_queued = True
+                Variable._execution_engine.queue_callback(self._backward_end)
+
+    def _join_lane(self):
+        """Order everything on the side lane before what the current stream is given next; release what it held."""
+        with self.lock:
+            held, self.lane = self.lane, []
+        if held:
+            get_backend().gemm_lane_join()
+        del held
+
     def _backward_end(self):
         self.callback_queued = False
         self.flush()
@@ -217,6 +238,7 @@ class _GradTail:
         with self.lock:
             red, sn = self.reduce, self.sn
             self.reduce, self.sn, self.pending = [], [], set()
+        self._join_lane()                   # first: sn_weight_bwd_batch and every later reader of a gradient follow it
         if not red and not sn:
             return
         be = get_backend()
@@ -239,6 +261,7 @@ class _GradTail:
         with self.lock:
             self.reduce, self.sn, self.pending = [], [], set()
             self.callback_queued = False
+        self._join_lane()                   # (before the references go: the lane may still be running)
 
 
 _tail = _GradTail()
@@ -315,12 +338,27 @@ def _lin_dgrad(be, dy2, w, sigma, dx, act=ACT_NONE, aux=None, residual=None, acc
             residual=residual, r=(K, 0, 0), accumulate=accumulate, split_k=1)
 
 
-def _lin_wgrad(be, dy2, x2, G):
+def _wgrad_on_lane(be, *ws):
+    """Whether the weight-gradient GEMM(s) of the parameters `ws` may run on the library's side lane (calm_gemm_lane): the
+    switch is on, the gradient tail is armed — its flush joins the lane before the backward ends — and each `w` is a
+    leaf whose gradient nothing reads or adds to before that flush (_GradTail.takes).  Callers pass only weights whose
+    spectral-norm correction is deferred to the optimizer-side step: G goes to autograd untouched."""
+    return wgrad_lane() and _tail.armed and hasattr(be, "gemm_lane_join") and _tail.takes(be, *ws)
+
+
+def _lin_wgrad(be, dy2, x2, G, w=None):
     """split_k=0: the library may slice the long token reduction and combine with fp32 atomics (the
-    only non-bitwise-reproducible launches of the path; forward and dgrad GEMMs never split)."""
+    only non-bitwise-reproducible launches of the path; forward and dgrad GEMMs never split).
+    w: the weight parameter when the first reader of G is the optimizer-side step (a deferred spectral-norm correction);
+    the launch may then go to the side lane."""
     M, N = dy2.shape
     K = x2.shape[1]
-    be.gemm(dy2, x2, G, N, K, M, (1, N, 0, 0), (1, K, 0, 0), (K, 0, 0), accumulate=True)     # G comes zeroed (_zeros_big)
+    args = (dy2, x2, G, N, K, M, (1, N, 0, 0), (1, K, 0, 0), (K, 0, 0))
+    if w is not None and _wgrad_on_lane(be, w):
+        be.gemm(*args, accumulate=True, lane=True)
+        _tail.add_lane((dy2, x2, G), (w,))
+    else:
+        be.gemm(*args, accumulate=True)                                                      # G comes zeroed (_zeros_big)
 
 
 # Attribute set (by trainer.FusedClipAdamW) on the weight_orig PARAMETER of a spectral-normed layer whose weight-gradient
@@ -541,7 +579,7 @@ class SNLinearFn(Function):
             dz = dy2
         dzg = _gop(be, dz) if ctx.needs_input_grad[0] else dz
         G = _zeros_big(w.shape, w)
-        _lin_wgrad(be, dzg, x2, G)
+        _lin_wgrad(be, dzg, x2, G, w if ctx.defer else None)
         dW, d_ls = _sn_wbwd(be, G, w, u, v, sigma, ls, defer=ctx.defer)
         dx = None
         if ctx.needs_input_grad[0]:
@@ -609,7 +647,12 @@ class SNLinearGroupFn(Function):
             dy2 = [_gop(be, d) for d in dy2]             # each is read by the weight-gradient and the input-gradient launch
         # weight gradients G_g = dy_g^T x: one grouped launch, every group split over its own k-slices
         Gs = [_zeros_big(w.shape, w) for w in ws]
-        be.gemm(dy2, x2, Gs, N, K, M, (1, N, 0, 0), (1, K, 0, 0), (K, 0, 0), batch=(n, 1), accumulate=True)
+        args = (dy2, x2, Gs, N, K, M, (1, N, 0, 0), (1, K, 0, 0), (K, 0, 0))
+        if all(ctx.defer) and _wgrad_on_lane(be, *ws):
+            be.gemm(*args, batch=(n, 1), accumulate=True, lane=True)
+            _tail.add_lane((dy2, x2, Gs), ws)
+        else:
+            be.gemm(*args, batch=(n, 1), accumulate=True)
         grads = []
         for g in range(n):
             grads += [_sn_wbwd(be, Gs[g], ws[g], us[g], vs[g], sigmas[g], defer=ctx.defer[g])[0], None, None, None]
@@ -680,7 +723,7 @@ class MlpFn(Function):
         do2 = _c(dout).reshape(-1, N)
         do2g = _gop(be, do2)
         G2 = _zeros_big(w2.shape, w2)
-        _lin_wgrad(be, do2g, hg, G2)
+        _lin_wgrad(be, do2g, hg, G2, w2 if ctx.defer[1] else None)
         dW2, d_ls = _sn_wbwd(be, G2, w2, u2, v2, s2, ls, defer=ctx.defer[1])
         db2 = _colsum(be, do2, ctx.biases[1]) if ctx.has_b2 else None
         wop1, wop2 = ctx.wops
@@ -697,7 +740,7 @@ class MlpFn(Function):
         if ctx.p > 0:                    # the mask and gelu' are both element-wise factors: either order gives d(pre-activation)
             be.dropout(dhp, None, dhp, dhp.numel(), ctx.p, key)
         G1 = _zeros_big(w1.shape, w1)
-        _lin_wgrad(be, dhp, x2, G1)
+        _lin_wgrad(be, dhp, x2, G1, w1 if ctx.defer[0] else None)
         dW1, _ = _sn_wbwd(be, G1, w1, u1, v1, s1, defer=ctx.defer[0])
         db1 = _colsum(be, dhp, ctx.biases[0]) if ctx.has_b1 else None
         dx = None
@@ -811,14 +854,14 @@ def _attn_mask_bwd(be, defer, dM, q, k, dq, dk, R, hp, hg, w1, w2, u1, v1, s1, u
     Skv = k.shape[1]
     dev, dt = q.device, q.dtype
     G2 = _zeros_big(w2.shape, w2)
-    _lin_wgrad(be, dM, hg, G2)
+    _lin_wgrad(be, dM, hg, G2, w2 if defer[1] else None)
     dW2, _ = _sn_wbwd(be, G2, w2, u2, v2, s2, defer=defer[1])
     db2 = _colsum(be, dM, biases[1])
     dhp = torch.empty_like(hp)
     _lin_dgrad(be, dM, w2o, s2, dhp, act=ACT_GELU_BWD, aux=hp)
     R2 = R.view(B * Sq, Skv)
     G1 = _zeros_big(w1.shape, w1)
-    _lin_wgrad(be, dhp, R2, G1)
+    _lin_wgrad(be, dhp, R2, G1, w1 if defer[0] else None)
     dW1, _ = _sn_wbwd(be, G1, w1, u1, v1, s1, defer=defer[0])
     db1 = _colsum(be, dhp, biases[0])
     dR = torch.empty(B, Sq, Skv, dtype=dt, device=dev)

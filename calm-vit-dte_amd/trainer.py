@@ -45,6 +45,7 @@ classes leave the gradient tail (ops.grad_tail) off: DDP reads gradients during 
 import contextlib
 import math
 import os
+import time
 import weakref
 
 import torch
@@ -3562,6 +3563,13 @@ class GraphedTrainStep:
                 self.inner(self.x, self.y)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        if reducer is not None and getattr(reducer, "enabled", False) and getattr(reducer, "on_gpu", False):
+            # The warm-up's all-reduces left Work objects with ProcessGroupNCCL's watchdog thread, which drops a finished
+            # one only at its next sweep (every 100 ms) and finds out by hipEventQuery — a call the runtime refuses from
+            # any thread while a stream captures in global mode: the watchdog then throws and the process aborts.  All of
+            # them are finished here, so three sweep periods later its list is empty and it queries nothing during the
+            # capture (collectives issued while capturing are not handed to it).
+            time.sleep(0.3)
         if isinstance(optimizer, FusedClipAdamW):
             optimizer.sync_lr_to_device()          # nothing is written to the rates during the capture
         self.graph = torch.cuda.CUDAGraph()

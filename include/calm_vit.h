@@ -144,8 +144,30 @@ int64_t calm_gemm_workspace_bytes(const calm_gemm_args* args);
  *                         they are reproducible in either mode. */
 #define CALM_GEMM_OPT_PIPE   0
 #define CALM_GEMM_OPT_PIPE32 1
+/*   CALM_GEMM_OPT_LANE (an addition to ABI v7) 0 (default): 1 = calm_gemm_lane launches go to the side lane, see below. */
 #define CALM_GEMM_OPT_DETERMINISTIC 2
+#define CALM_GEMM_OPT_LANE 3
 int calm_gemm_set_option(int32_t option, int32_t value);
+
+/* The side lane (an addition to ABI v7): one non-blocking stream of the lowest priority per device, owned by the
+ * library, for launches whose result nothing reads soon — the weight-gradient GEMMs of a backward, which are MFMA-bound
+ * and can fill the CUs while the caller's stream runs kernels that leave the matrix pipe idle.
+ *   calm_gemm_lane_fork(main)   an event recorded on `main`, the lane waits for it.  Call it immediately before each
+ *                               lane launch: the lane then sees the launch's operands (and a zeroed C) finished.
+ *   calm_gemm_lane(args, main)  calm_gemm(args, .) on the lane: same plan, same kernels, same split and combine.  The
+ *                               caller keeps A, B, C and the workspace alive, and unused by other streams, until the
+ *                               join — the lane is not the stream their allocator knows.
+ *   calm_gemm_lane_join(main)   an event recorded on the lane, `main` waits for it: every lane launch so far is ordered
+ *                               before what `main` is given next.  Does nothing if no launch went to the lane since the
+ *                               last join.
+ * With CALM_GEMM_OPT_LANE = 0, and while `main` is capturing a graph, fork and join do nothing and calm_gemm_lane
+ * launches on `main`: it is then exactly calm_gemm, and a captured graph has the shape it has without the lane.
+ * calm_gemm_lane_stats: counts since the library was loaded — out[0] forks that recorded an event, out[1] launches that
+ * went to a lane, out[2] joins that recorded an event, out[3] events recorded. */
+int calm_gemm_lane(const calm_gemm_args* args, void* main_stream);
+int calm_gemm_lane_fork(void* main_stream);
+int calm_gemm_lane_join(void* main_stream);
+int calm_gemm_lane_stats(int64_t out[4]);
 
 /* ABI v7 — what calm_gemm would launch for `args` (nothing is enqueued): kernel family, tile, work decomposition.
  * Diagnostic surface: tests use it to map a wrong output element back to (tile, persistent workgroup, XCD, wave,
