@@ -813,14 +813,23 @@ struct RopePlan {
 };
 static_assert(ROPE_BWD_MAX_GRID <= ROPE_SCRATCH_ROWS && CALM_ROPE_BWD_GRID <= ROPE_SCRATCH_ROWS,
               "calm_reduce_scratch_floats sizes the RoPE backward for ROPE_SCRATCH_ROWS partial rows");
-// main_type: out / d_out; content_type counts only when there are content columns; the forward has no d_xr (pass xr's)
-RopePlan rope_plan(int B, int S, int H, int dc, int dr, int main_type, int content_type, int xr_type, int dxr_type) {
+struct RopeTensor { const void* p; int type; };   // a tensor the row-walking kernels access in groups of vw elements
+// main_type: out / d_out; content_type counts only when there are content columns; the forward has no d_xr (pass xr's).
+// vec_tensors: every tensor of the call that the kernels read or write as vectors (the table is fp32).  Row strides and
+// column offsets are multiples of vw by the choice below, so a tensor's accesses are aligned iff its base is: to
+// vw * 4 bytes for fp32, vw * 2 bytes for bf16 (a null pointer is).  vw halves until that holds for all of them.
+RopePlan rope_plan(int B, int S, int H, int dc, int dr, int main_type, int content_type, int xr_type, int dxr_type,
+                   std::initializer_list<RopeTensor> vec_tensors) {
     const int half = dr / 2;
     RopePlan p{(long)B * S * H, false, -1, 1, 0, 0};
     if (xr_type == main_type && dxr_type == main_type && (dc == 0 || content_type == main_type)) p.tt = main_type;
     p.fits = half <= ROPE_MAX_HALF && half <= NT && p.nrows * (dc + dr) < (1L << 31);
     if (!p.fits) return p;
     p.vw = ((dc & 3) == 0 && (half & 3) == 0 && CALM_ROPE_VW4) ? 4 : ((dc & 1) == 0 && (half & 1) == 0) ? 2 : 1;
+    for (const RopeTensor& t : vec_tensors) {
+        const uintptr_t bytes = t.type == CALM_ST_BF16 ? 2 : 4;
+        while (p.vw > 1 && (reinterpret_cast<uintptr_t>(t.p) & (p.vw * bytes - 1)) != 0) p.vw >>= 1;
+    }
     const int rpb = NT / (half / p.vw);                                    // rows per workgroup pass
     const long blocks = (p.nrows + rpb - 1) / rpb;
     p.grid = (int)(blocks < ROPE_VEC_MAX_GRID ? blocks : ROPE_VEC_MAX_GRID);
@@ -944,7 +953,8 @@ int calm_rope_fwd(const void* content, const void* xr, const float* inv_freq, fl
     if (!st_ok(content_type) || !st_ok(xr_type) || !st_ok(out_type)) return CALM_E_INVAL;
     const int half = dr / 2;
     if (int e = calm_launch(rope_table_kernel, (S * half + 255) / 256, 256, 0, stream, inv_freq, table, S, half)) return e;
-    const RopePlan p = rope_plan(B, S, H, dc, dr, out_type, content_type, xr_type, xr_type);
+    const RopePlan p = rope_plan(B, S, H, dc, dr, out_type, content_type, xr_type, xr_type,
+                                 {{content, content_type}, {xr, xr_type}, {out, out_type}, {table, CALM_ST_F32}});
     if (CALM_ROPE_VEC && p.fits)
         return with_rope(p, [&](auto vw, auto tt) {
             return calm_launch(rope_fwd_vec_kernel<decltype(vw)::value, decltype(tt)::value>, p.grid, NT, 0, stream, content,
@@ -964,7 +974,9 @@ static int rope_bwd_launch(const void* d_out, const void* xr, const float* table
     if (!st_ok(dout_type) || !st_ok(xr_type) || !st_ok(dcontent_type) || !st_ok(dxr_type)) return CALM_E_INVAL;
     // (the one-element-per-thread backward of round 1 combined its angle gradients with LDS atomics; the row-walking
     // kernel serves every shape of the path: dr/2 <= 256 rotation pairs, tensors below 2^31 elements)
-    const RopePlan p = rope_plan(B, S, H, dc, dr, dout_type, dcontent_type, xr_type, dxr_type);
+    const RopePlan p = rope_plan(B, S, H, dc, dr, dout_type, dcontent_type, xr_type, dxr_type,
+                                 {{d_out, dout_type}, {xr, xr_type}, {table, CALM_ST_F32}, {d_content, dcontent_type},
+                                  {d_xr, dxr_type}});
     if (!p.fits) return CALM_E_UNSUPP;
     *g_out = p.bwd_grid;
     return with_rope(p, [&](auto vw, auto tt) {
