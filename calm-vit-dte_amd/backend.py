@@ -1419,6 +1419,17 @@ class HipBackend:
                                              _ptr(row_stats), _ptr(dloss), _ptr(dlogits), B, C, _stream()),
                    "calm_soft_ce_bwd")
 
+    # binary cross-entropy with logits: logits / targets fp32 [B,C] with unit column stride (any row stride); flags: a sum
+    # of _lib.BCE_SUM_CLASSES / BCE_THRESHOLD; loss 0-dim, metrics [4] or None; dlogits contiguous [B,C]
+    def bce_fwd(self, logits, targets, flags, threshold, loss, metrics, B, C):
+        _lib.check(self.lib.calm_bce_fwd(_ptr(logits), logits.stride(0), _ptr(targets), targets.stride(0), int(flags),
+                                         float(threshold), _ptr(loss), _ptr(metrics, True), B, C,
+                                         self._partials(_lib.RED_BCE, B, C, logits.device), _stream()), "calm_bce_fwd")
+
+    def bce_bwd(self, logits, targets, flags, threshold, dloss, dlogits, B, C):
+        _lib.check(self.lib.calm_bce_bwd(_ptr(logits), logits.stride(0), _ptr(targets), targets.stride(0), int(flags),
+                                         float(threshold), _ptr(dloss), _ptr(dlogits), B, C, _stream()), "calm_bce_bwd")
+
     # knowledge distillation: logits / targets fp32 and teacher fp32 or bf16, all [B,C] with unit column stride (any row
     # stride); row_stats [B, DISTILL_ROW_STATS]; mode "soft" | "hard"; metrics / dmetrics [4] or None
     _DISTILL_MODES = {"soft": _lib.DISTILL_SOFT, "hard": _lib.DISTILL_HARD}

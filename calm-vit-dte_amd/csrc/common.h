@@ -193,6 +193,7 @@ constexpr int COLSUM_VEC_MAX_GRID = COLSUM_GRID;   // 16-byte form: few blocks, 
 constexpr int CNN_BWD_MAX_GRID = 256;
 constexpr int CNN_PART_STRIDE = 560;           // floats between the CNN tail's partial rows (cnn_fused.hip: CNN_PART_N of them used)
 constexpr int SOFT_CE_PART_ROWS = 2;           // soft-target CE: one workgroup per sample; B row losses, then B agreement flags
+constexpr int BCE_PART_ROWS = 2;               // calm_bce_fwd: one workgroup per sample; B row sums, then B agreement flags
 constexpr int DISTILL_PART_ROWS = 5;           // calm_distill_fwd: one workgroup per sample; B totals, CE, D, agreement with y, with t
 constexpr int HUBER_MAX_GRID = 2048;           // one block sum per workgroup
 constexpr int EVAL_REC_FLOATS = 4;             // calm_eval_metrics: one 16-byte record per row (no cross-workgroup sum in launch 1)

@@ -1,7 +1,8 @@
 // The loss end of the step: soft-target cross-entropy (distributed_trainer_cls.py:63,86), the token-layout Huber loss of
-// the generative trainer (distributed_trainer_reg.py:59,78-81) and the device-side step metrics (cls:98-102,
-// CALM_ViT_V2.py:228-239).  Every cross-workgroup sum goes through the caller's `partials` and ONE final workgroup that
-// adds them in a fixed order: no atomics, results repeat bit for bit.
+// the generative trainer (distributed_trainer_reg.py:59,78-81), binary cross-entropy with logits (the DeiT III / timm
+// recipe's loss on the same soft targets) and the device-side step metrics (cls:98-102, CALM_ViT_V2.py:228-239).  Every
+// cross-workgroup sum goes through the caller's `partials` and ONE final workgroup that adds them in a fixed order: no
+// atomics, results repeat bit for bit.
 #include <math.h>
 
 #include "common.h"
@@ -107,12 +108,13 @@ static __global__ __launch_bounds__(LOSS_NT) void soft_ce_fwd_kernel(const float
     }
 }
 
-// The final pass of both losses: ONE workgroup adds n partials in a fixed order (thread t takes t, t + 256, ... in
+// The final pass of the losses: ONE workgroup adds n partials in a fixed order (thread t takes t, t + 256, ... in
 // increasing index, then a fixed tree over the 256 running sums) and OVERWRITES the loss.  metrics (nullable) is the
-// caller's float[4]; it is updated by one thread with a plain read-modify-write, ordered by the stream.
+// caller's float[4]; it is updated by one thread with a plain read-modify-write, ordered by the stream.  mscale: what
+// turns the sum into B * loss for metrics[0] (1 for the cross-entropy, whose sum it is: s * 1.0f == s).
 static __global__ __launch_bounds__(LOSS_NT) void loss_final_kernel(const float* __restrict__ part, int n, float scale,
                                                                     float* __restrict__ loss, const float* __restrict__ agree,
-                                                                    float* __restrict__ metrics, int B) {
+                                                                    float* __restrict__ metrics, int B, float mscale) {
     __shared__ float red[8];
     float s = 0.f, a = 0.f;
     for (int g = threadIdx.x; g < n; g += LOSS_NT) s += part[g];
@@ -123,7 +125,7 @@ static __global__ __launch_bounds__(LOSS_NT) void loss_final_kernel(const float*
     if (threadIdx.x == 0) {
         loss[0] = s * scale;
         if (metrics) {
-            metrics[0] += s;
+            metrics[0] += s * mscale;
             metrics[1] += a;
             metrics[2] += (float)B;
             metrics[3] += 1.f;
@@ -160,6 +162,92 @@ static __global__ __launch_bounds__(LOSS_NT) void soft_ce_bwd_kernel(const float
         *reinterpret_cast<f32x4*>(dz + 4 * q) = o;
     }
     for (int c = 4 * c4 + tid; c < C; c += LOSS_NT) dz[c] = g * fmaf(__expf((z[c] - zm) - ls), ysum, -y[c]);
+}
+
+// ---- binary cross-entropy with logits ----------------------------------------------------------------------------------
+// Every class is its own two-way problem: l(z, t) = max(z, 0) - z t + log(1 + exp(-|z|)), evaluated as
+//   |z| * (z >= 0 ? 1 - t : t) + log1p(exp(-|z|))
+// — exp never sees a positive argument, and for t in [0, 1] both terms are non-negative, so nothing cancels
+// (max(z, 0) - z t does at z >> 0, t -> 1).  t is the target, or (y > threshold) with CALM_BCE_THRESHOLD.
+__device__ __forceinline__ float bce_target(float y, bool thresholded, float threshold) {
+    return thresholded ? (y > threshold ? 1.f : 0.f) : y;
+}
+__device__ __forceinline__ float bce_term(float z, float t) {
+    const float a = fabsf(z);
+    return fmaf(a, z >= 0.f ? 1.f - t : t, log1pf(__expf(-a)));
+}
+// sigmoid(z) - t with the two-branch sigmoid (one exponential of -|z|); z - z is 0 for a finite logit and NaN for an
+// infinite one, whose loss is not finite either: the gradient says so and the scaled optimizer step is skipped
+__device__ __forceinline__ float bce_slope(float z, float t) {
+    const float e = __expf(-fabsf(z));
+    const float s = (z >= 0.f ? 1.f : e) / (1.f + e);
+    return (s - t) + (z - z);
+}
+
+// One workgroup per row, ONE pass: the row's loss sum, the maxima of z and of the ORIGINAL y with their lowest indices,
+// the NaN flag.  c4 as in soft_ce_fwd_kernel.
+static __global__ __launch_bounds__(LOSS_NT) void bce_fwd_kernel(const float* __restrict__ logits, long ld,
+                                                                 const float* __restrict__ targets, long td,
+                                                                 int thresholded, float threshold,
+                                                                 float* __restrict__ partials, int B, int C, int c4) {
+    __shared__ float red[8];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* z = logits + (long)b * ld;
+    const float* y = targets + (long)b * td;
+    float zm = -INFINITY, ym = -INFINITY, acc = 0.f;
+    int zi = 0x7fffffff, yi = 0x7fffffff;
+    bool bad = false;
+    for (int q = tid; q < c4; q += LOSS_NT) {
+        const f32x4 zv = *reinterpret_cast<const f32x4*>(z + 4 * q);
+        const f32x4 yv = *reinterpret_cast<const f32x4*>(y + 4 * q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            bad |= (zv[k] != zv[k]) | (yv[k] != yv[k]);
+            if (zv[k] > zm) { zm = zv[k]; zi = 4 * q + k; }
+            if (yv[k] > ym) { ym = yv[k]; yi = 4 * q + k; }
+            acc += bce_term(zv[k], bce_target(yv[k], thresholded, threshold));
+        }
+    }
+    for (int c = 4 * c4 + tid; c < C; c += LOSS_NT) {
+        const float zc = z[c], yc = y[c];
+        bad |= (zc != zc) | (yc != yc);
+        if (zc > zm) { zm = zc; zi = c; }
+        if (yc > ym) { ym = yc; yi = c; }
+        acc += bce_term(zc, bce_target(yc, thresholded, threshold));
+    }
+    // (as soft_ce_fwd_kernel: a thread that saw only -inf, or nothing, must not win with index INT_MAX)
+    if (zm == -INFINITY && zi == 0x7fffffff && tid < C) zi = tid;
+    if (ym == -INFINITY && yi == 0x7fffffff && tid < C) yi = tid;
+    block_argmax_256(zm, zi, red);
+    block_argmax_256(ym, yi, red);
+    acc = block_sum_256(acc, red);
+    const float nbad = block_sum_256(bad ? 1.f : 0.f, red);
+    if (tid == 0) {
+        partials[b] = acc;
+        partials[B + b] = (nbad == 0.f && zi == yi) ? 1.f : 0.f;
+    }
+}
+
+// dlogits = dloss / denom * (sigmoid(z) - t), denom = B C or B: one workgroup per row, nothing saved, nothing summed
+static __global__ __launch_bounds__(LOSS_NT) void bce_bwd_kernel(const float* __restrict__ logits, long ld,
+                                                                 const float* __restrict__ targets, long td,
+                                                                 int thresholded, float threshold, float denom,
+                                                                 const float* __restrict__ dloss,
+                                                                 float* __restrict__ dlogits, int C, int c4) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* z = logits + (long)b * ld;
+    const float* y = targets + (long)b * td;
+    float* dz = dlogits + (long)b * C;
+    const float g = dloss[0] / denom;
+    for (int q = tid; q < c4; q += LOSS_NT) {
+        const f32x4 zv = *reinterpret_cast<const f32x4*>(z + 4 * q);
+        const f32x4 yv = *reinterpret_cast<const f32x4*>(y + 4 * q);
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = g * bce_slope(zv[k], bce_target(yv[k], thresholded, threshold));
+        *reinterpret_cast<f32x4*>(dz + 4 * q) = o;
+    }
+    for (int c = 4 * c4 + tid; c < C; c += LOSS_NT) dz[c] = g * bce_slope(z[c], bce_target(y[c], thresholded, threshold));
 }
 
 // ---- top-1 count against integer labels --------------------------------------------------------------------------------
@@ -790,7 +878,8 @@ int calm_soft_ce_fwd(const float* logits, int64_t ld, const float* targets, int6
     // one workgroup per sample: B row losses at partials, B agreement flags behind them (SOFT_CE_PART_ROWS * B floats)
     if (int e = calm_launch(soft_ce_fwd_kernel, B, LOSS_NT, 0, stream, logits, ld, targets, td, row_stats, partials, B, C, c4))
         return e;
-    return calm_launch(loss_final_kernel, 1, LOSS_NT, 0, stream, partials, B, 1.0f / (float)B, loss, partials + B, metrics, B);
+    return calm_launch(loss_final_kernel, 1, LOSS_NT, 0, stream, partials, B, 1.0f / (float)B, loss, partials + B, metrics, B,
+                       1.0f);
 }
 
 int calm_soft_ce_bwd(const float* logits, int64_t ld, const float* targets, int64_t td, const float* row_stats,
@@ -798,6 +887,41 @@ int calm_soft_ce_bwd(const float* logits, int64_t ld, const float* targets, int6
     if (!logits || !targets || !row_stats || !dloss || !dlogits || B <= 0 || C <= 0) return CALM_E_INVAL;
     const int c4 = (C & 3) == 0 && aligned16(dlogits) ? vec_groups(logits, (long)ld, targets, (long)td, C) : 0;
     return calm_launch(soft_ce_bwd_kernel, B, LOSS_NT, 0, stream, logits, ld, targets, td, row_stats, dloss, dlogits, B, C, c4);
+}
+
+// the checks both directions share, all before any launch
+static int bce_args(const float* logits, const float* targets, int32_t flags, float threshold, int32_t B, int32_t C) {
+    if (!logits || !targets || B <= 0 || C <= 0) return CALM_E_INVAL;
+    if (flags & ~(CALM_BCE_SUM_CLASSES | CALM_BCE_THRESHOLD)) return CALM_E_INVAL;
+    if ((flags & CALM_BCE_THRESHOLD) && !isfinite(threshold)) return CALM_E_INVAL;
+    if ((int64_t)B * C >= ((int64_t)1 << 31)) return CALM_E_UNSUPP;      // (the divisor B C and the flat dlogits index)
+    return 0;
+}
+
+int calm_bce_fwd(const float* logits, int64_t ld, const float* targets, int64_t td, int32_t flags, float threshold,
+                 float* loss, float* metrics, int32_t B, int32_t C, float* partials, void* stream) {
+    if (!loss || !partials) return CALM_E_INVAL;
+    if (int e = bce_args(logits, targets, flags, threshold, B, C)) return e;
+    const int c4 = vec_groups(logits, (long)ld, targets, (long)td, C);
+    const int thresholded = (flags & CALM_BCE_THRESHOLD) != 0;
+    const bool sum_classes = (flags & CALM_BCE_SUM_CLASSES) != 0;
+    // one workgroup per sample: B row sums at partials, B agreement flags behind them (BCE_PART_ROWS * B floats)
+    if (int e = calm_launch(bce_fwd_kernel, B, LOSS_NT, 0, stream, logits, ld, targets, td, thresholded, threshold, partials,
+                            B, C, c4))
+        return e;
+    const float scale = 1.0f / (sum_classes ? (float)B : (float)B * (float)C);
+    return calm_launch(loss_final_kernel, 1, LOSS_NT, 0, stream, partials, B, scale, loss, partials + B, metrics, B,
+                       sum_classes ? 1.0f : 1.0f / (float)C);
+}
+
+int calm_bce_bwd(const float* logits, int64_t ld, const float* targets, int64_t td, int32_t flags, float threshold,
+                 const float* dloss, float* dlogits, int32_t B, int32_t C, void* stream) {
+    if (!dloss || !dlogits) return CALM_E_INVAL;
+    if (int e = bce_args(logits, targets, flags, threshold, B, C)) return e;
+    const int c4 = (C & 3) == 0 && aligned16(dlogits) ? vec_groups(logits, (long)ld, targets, (long)td, C) : 0;
+    const float denom = (flags & CALM_BCE_SUM_CLASSES) ? (float)B : (float)B * (float)C;
+    return calm_launch(bce_bwd_kernel, B, LOSS_NT, 0, stream, logits, ld, targets, td,
+                       (int)((flags & CALM_BCE_THRESHOLD) != 0), threshold, denom, dloss, dlogits, C, c4);
 }
 
 int calm_top1_count(const float* logits, int64_t ld, const int64_t* labels, float* metrics, int32_t B, int32_t C,
@@ -847,7 +971,7 @@ int calm_huber_tokens_fwd(const float* tokens, const float* x, float delta, floa
                             partials, g))
         return e;
     return calm_launch(loss_final_kernel, 1, LOSS_NT, 0, stream, partials, grid, 1.0f / (3.0f * (float)g.rows * (float)S),
-                       loss, nullptr, nullptr, 0);
+                       loss, nullptr, nullptr, 0, 1.0f);
 }
 
 int calm_huber_tokens_bwd(const float* tokens, const float* x, float delta, const float* dloss, float* dtokens, int32_t B,

@@ -1199,6 +1199,41 @@ class SoftTargetCrossEntropyFn(Function):
         return dlogits, None, None
 
 
+class BinaryCrossEntropyFn(Function):
+    """nn.BCEWithLogitsLoss() on soft targets (calm_bce_fwd / _bwd, include/calm_vit.h): logits, targets [B,C] fp32 ->
+    0-dim fp32 loss, the mean over B * C elements, or with sum_classes the sum over the classes and the mean over the
+    batch (timm's BinaryCrossEntropy(sum_classes=True)).  target_threshold (None: off): the targets become
+    (targets > target_threshold).  metrics: the device float[4] of SoftTargetCrossEntropyFn, or None.  Saves logits and
+    targets only; the gradient goes to the logits alone."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, logits, targets, metrics=None, target_threshold=None, sum_classes=False):
+        be = get_backend()
+        logits, targets = _rows_unit_stride(logits), _rows_unit_stride(targets)
+        B, C = logits.shape
+        if targets.shape != logits.shape:
+            raise ValueError("binary cross-entropy expects targets of the logits' shape")
+        flags = (_lib.BCE_SUM_CLASSES if sum_classes else 0) | (_lib.BCE_THRESHOLD if target_threshold is not None else 0)
+        threshold = 0.0 if target_threshold is None else float(target_threshold)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        be.bce_fwd(logits, targets, flags, threshold, loss, metrics, B, C)
+        ctx.save_for_backward(logits, targets)
+        ctx.hyper = (flags, threshold)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    @_amp_bwd
+    def backward(ctx, g):
+        be = get_backend()
+        logits, targets = ctx.saved_tensors
+        B, C = logits.shape
+        dlogits = torch.empty(B, C, dtype=torch.float32, device=logits.device)
+        be.bce_bwd(logits, targets, *ctx.hyper, _dloss(g), dlogits, B, C)
+        return dlogits, None, None, None, None
+
+
 class DistillLossFn(Function):
     """Knowledge distillation against a frozen teacher's logits (calm_distill_fwd / _bwd, include/calm_vit.h):
     (1 - alpha) * CrossEntropy(logits, targets) + alpha * T^2 * KL(softmax(teacher / T) || softmax(logits / T)) in "soft"

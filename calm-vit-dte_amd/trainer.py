@@ -37,6 +37,9 @@ as set by torchrun):
   * `train(drop_path=)`   (no counterpart: the reference has no stochastic depth)
         Vi_Tools_CNN_less_V2.set_drop_path on the model before the step is built: per-sample drops of both residual
         branches of every VMLA_Block (calm_drop_path), the per-block rates recorded in the snapshot header.
+  * `soft_target_bce` / `TrainStep(loss=)` / `train(loss="bce")`   (no counterpart: the reference trains with softmax CE)
+        binary cross-entropy with logits on the CutMix / MixUp soft targets, the loss of the DeiT III / timm recipe
+        (calm_bce_fwd / _bwd with the loss kernels on; the StepMetrics buffer is fed as by the cross-entropy).
 
 The model also works under stock `torch.nn.parallel.DistributedDataParallel` (that is what the
 reference's train() does with it); the reducer here is the MI355X-tuned equivalent.  Under DDP the step
@@ -280,6 +283,65 @@ def soft_target_cross_entropy(logits, soft_targets, metrics=None):
         from .ops import SoftTargetCrossEntropyFn
         return SoftTargetCrossEntropyFn.apply(logits, soft_targets, None if metrics is None else metrics.buf)
     return torch.nn.functional.cross_entropy(logits, soft_targets)
+
+
+def soft_target_bce(logits, soft_targets, metrics=None, target_threshold=None, sum_classes=False):
+    """torch.nn.BCEWithLogitsLoss() on the CutMix / MixUp soft targets — the loss of the DeiT III recipe, timm's
+    `BinaryCrossEntropy`: every class is its own two-way problem.  The mean over all B * C elements, or with sum_classes
+    the sum over the classes and the mean over the batch; target_threshold (None: off) turns the targets into
+    (soft_targets > target_threshold) first.
+
+    Under the conditions of soft_target_cross_entropy — the loss kernels switched on, 2-D fp32 logits the installed backend
+    can address, fp32 targets of their shape — and with a backend that has bce_fwd, it goes through calm_bce_fwd / _bwd
+    (ops.BinaryCrossEntropyFn); `metrics` (a StepMetrics) then receives B * loss and the dominant-class agreement (against
+    the targets as they came, not the thresholded ones) on the device.  Everything else — the switch off, 1-D logits
+    (squeeze() at batch 1), CPU tensors, other dtypes — is F.binary_cross_entropy_with_logits."""
+    from . import backend
+    if (backend.get_loss_kernels() and logits.dim() == 2 and soft_targets.dtype == torch.float32
+            and soft_targets.shape == logits.shape and backend.loss_kernels_take(logits)
+            and hasattr(backend.get_backend(), "bce_fwd")):
+        from .ops import BinaryCrossEntropyFn
+        return BinaryCrossEntropyFn.apply(logits, soft_targets, None if metrics is None else metrics.buf,
+                                          target_threshold, bool(sum_classes))
+    if target_threshold is not None:
+        soft_targets = (soft_targets > target_threshold).to(soft_targets.dtype)
+    if sum_classes:
+        rows = logits.shape[0] if logits.dim() > 1 else 1
+        return torch.nn.functional.binary_cross_entropy_with_logits(logits, soft_targets, reduction="sum") / rows
+    return torch.nn.functional.binary_cross_entropy_with_logits(logits, soft_targets)
+
+
+def _loss_settings(who, loss):
+    """loss= of TrainStep / train() -> {"name": "ce"}, or {"name": "bce", "target_threshold": None | finite float,
+    "sum_classes": bool}."""
+    if loss is None or loss == "ce":
+        return {"name": "ce"}
+    if isinstance(loss, str):
+        loss = {"name": loss}
+    if not isinstance(loss, dict) or "name" not in loss:
+        raise ValueError(f'{who}: loss is None, "ce", "bce" or a dict with "name" / "target_threshold" / "sum_classes", '
+                         f"got {loss!r}")
+    name = loss["name"]
+    if name == "ce":
+        if set(loss) != {"name"}:
+            raise ValueError(f'{who}: loss "ce" takes no options, got {sorted(set(loss) - {"name"})}')
+        return {"name": "ce"}
+    if name != "bce":
+        raise ValueError(f'{who}: loss["name"] is "ce" or "bce", got {name!r}')
+    if not set(loss) <= {"name", "target_threshold", "sum_classes"}:
+        raise ValueError(f'{who}: loss takes the keys "name", "target_threshold", "sum_classes", got {sorted(loss)}')
+    thr, sum_classes = loss.get("target_threshold"), loss.get("sum_classes", False)
+    if thr is not None and (isinstance(thr, bool) or not isinstance(thr, (int, float)) or not math.isfinite(thr)):
+        raise ValueError(f'{who}: loss["target_threshold"] is None or a finite number, got {thr!r}')
+    if not isinstance(sum_classes, bool):
+        raise ValueError(f'{who}: loss["sum_classes"] is a bool, got {sum_classes!r}')
+    return {"name": "bce", "target_threshold": None if thr is None else float(thr), "sum_classes": sum_classes}
+
+
+def _cross_entropy_only(who, loss, why):
+    """The refusal of the steps whose loss is built on the cross-entropy (or is not a classification loss at all)."""
+    if _loss_settings(who, loss)["name"] != "ce":
+        raise ValueError(f"{who}: loss={loss!r} is refused: {why}")
 
 
 class StepMetrics:
@@ -559,11 +621,14 @@ class TrainStep:
     """One iteration of distributed_trainer_cls.py:79-96 (per rank)."""
 
     def __init__(self, model, optimizer, reducer=None, max_norm=1.0, scaler=None, autocast_dtype=None, metrics=None,
-                 ema=None):
+                 ema=None, loss=None):
         """metrics: a StepMetrics the loss kernel accumulates into (only with the loss kernels switched on).
         ema: a ModelEMA of `model`, updated right behind the optimizer step; a step skipped for inf/NaN gradients leaves
-        the average and its update count alone."""
+        the average and its update count alone.
+        loss: None / "ce" — soft_target_cross_entropy (cls:63,86) — or "bce" / {"name": "bce", "target_threshold": t,
+        "sum_classes": bool} — soft_target_bce, the DeiT III / timm recipe's loss on the same soft targets."""
         self.model, self.opt, self.reducer = model, optimizer, reducer
+        self.loss_settings = _loss_settings(type(self).__name__, loss)
         self.metrics = metrics
         self.ema = ema
         self.max_norm = max_norm
@@ -590,6 +655,9 @@ class TrainStep:
         return self._finish(loss, y_hat)
 
     def _loss(self, y_hat, y_soft):
+        if self.loss_settings["name"] == "bce":
+            return soft_target_bce(y_hat.squeeze(), y_soft, self.metrics, self.loss_settings["target_threshold"],
+                                   self.loss_settings["sum_classes"])
         return soft_target_cross_entropy(y_hat.squeeze(), y_soft, self.metrics)
 
     def _tail_enabled(self):
@@ -681,7 +749,9 @@ class RegTrainStep(TrainStep):
     (:81,87), then the same scale / clip(1.0) / optimizer step as the classification trainer."""
 
     def __init__(self, model, optimizer, reducer=None, max_norm=1.0, scaler=None, autocast_dtype=None, kl_weight=0.1,
-                 ema=None):
+                 ema=None, loss=None):
+        _cross_entropy_only(type(self).__name__, loss, "the generative job's loss is Huber + kl_weight * kl, it has no "
+                            "class targets")
         super().__init__(model, optimizer, reducer, max_norm=max_norm, scaler=scaler, autocast_dtype=autocast_dtype, ema=ema)
         self.kl_weight = kl_weight
 
@@ -801,7 +871,9 @@ class DistillTrainStep(TrainStep):
     student forward."""
 
     def __init__(self, model, optimizer, teacher, reducer=None, alpha=0.5, temperature=1.0, mode="soft", teacher_graph=False,
-                 distill_metrics=None, **kw):
+                 distill_metrics=None, loss=None, **kw):
+        _cross_entropy_only(type(self).__name__, loss, "the distillation loss is (1 - alpha) * cross-entropy + the teacher "
+                            "term (BCE distillation is not supported)")
         super().__init__(model, optimizer, reducer, **kw)
         _check_distill("DistillTrainStep: %s", mode, alpha, temperature)
         self.alpha, self.temperature, self.mode = float(alpha), float(temperature), mode
@@ -3529,8 +3601,9 @@ class GraphedTrainStep:
     capture, so that the first replay is step 1 of the run — the replayed trajectory then equals the eager one."""
 
     def __init__(self, model, optimizer, example_x, example_y, max_norm=1.0, warmup=3, scaler=None, autocast_dtype=None,
-                 reducer=None, restore_after_warmup=False, metrics=None, ema=None):
-        """ema: a ModelEMA of `model`; calm_ema_update is captured behind the optimizer step, and restore_after_warmup puts
+                 reducer=None, restore_after_warmup=False, metrics=None, ema=None, loss=None):
+        """loss: TrainStep's loss= (None / "ce" / "bce" / a dict), handed to the inner step.
+        ema: a ModelEMA of `model`; calm_ema_update is captured behind the optimizer step, and restore_after_warmup puts
         the averages and their device update count back with the rest, so the first replay is update 1.
         reducer: a BucketedGradReducer whose bucket copies and RCCL all-reduces are captured with the step (round 4:
         the collectives are issued in the capture-compatible form, see BucketedGradReducer._launch; exercised in a world
@@ -3541,7 +3614,7 @@ class GraphedTrainStep:
                                "to capture with it; with world_size > 1 pass reducer=... or use TrainStep")
         # metrics: the StepMetrics buffer's address is baked into the graph, so replays keep accumulating into it
         self.inner = TrainStep(model, optimizer, reducer, max_norm=max_norm, scaler=scaler, autocast_dtype=autocast_dtype,
-                               metrics=metrics, ema=ema)
+                               metrics=metrics, ema=ema, loss=loss)
         self.opt = optimizer
         if isinstance(optimizer, FusedClipAdamW):
             optimizer.lr_on_device = True          # replays read the learning rate from a device scalar
@@ -3692,8 +3765,8 @@ class _ClsTask:
     `evaluate`, its printed report and `best` = (report key, lower is better), the rule of the best checkpoints."""
     name, reg, best = "cls", False, ("top1", False)
 
-    def __init__(self, metrics, topk):
-        self.step_kw, self.topk = {"metrics": metrics}, topk
+    def __init__(self, metrics, topk, loss=None):
+        self.step_kw, self.topk = {"metrics": metrics, "loss": loss}, topk
         self.eval_kw = dict(report=True, topk=topk)
 
     def log_text(self, loss, y_hat, y):                    # (one host read of the accuracy: only on log_every batches)
@@ -3807,7 +3880,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
                       device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path, snapshot_every,
                       accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task, teacher, distill,
                       param_groups, scheduler_step, monitor=None, random_erasing=None, label_smoothing=0.0, rand_augment=None,
-                      sam=None, lamb=None, drop_path=None):
+                      sam=None, lamb=None, drop_path=None, loss=None):
     """Every refusal train() makes from its arguments alone: it touches no device and no process group, so a bad call
     fails before either exists.  Returns the normalised values the job is assembled from: accumulate (int), ema_kw
     (None without ema), distill_kw (DistillTrainStep's keywords, {} without a teacher), teacher_mod, resize (the
@@ -3816,10 +3889,11 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
     label_smoothing (float), rand_augment (None, a DeviceRandAugment, or the dict of arguments one is built from), sam_kw
     (None without sam=; SharpnessAware's keywords and "sync"), lamb (None, or the normalised settings of
     FusedClipAdamW(lamb=) — the argument's, or those of the optimizer object handed in), drop_path (None, or
-    {"rate", "schedule"} for set_drop_path)."""
+    {"rate", "schedule"} for set_drop_path), loss (the normalised loss= of TrainStep)."""
     from . import backend as _backend
     from types import SimpleNamespace
     drop_kw = _drop_path_settings(drop_path)
+    loss_kw = _loss_settings("train", loss)
     if scheduler_step not in ("epoch", "step"):
         raise ValueError(f'train: scheduler_step is "epoch" or "step", got {scheduler_step!r}')
     if param_groups is not None and not (isinstance(optimizer, str) and optimizer == "fused"):
@@ -3881,6 +3955,11 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
     if task not in ("cls", "reg"):
         raise ValueError(f'train: task is "cls" or "reg", got {task!r}')
     reg = task == "reg"
+    if reg and loss is not None:
+        raise ValueError('train: loss= excludes task="reg" (the generative job\'s loss is Huber + kl_weight * kl)')
+    if teacher is not None and loss_kw["name"] != "ce":
+        raise ValueError(f"train: teacher= excludes loss={loss!r} (the distillation loss is built on the cross-entropy; BCE "
+                         "distillation is not supported)")
     if reg and graph:
         raise ValueError('train: task="reg" excludes graph=True (GraphedTrainStep captures the classification step)')
     if reg and device_metrics:
@@ -4002,7 +4081,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
     return SimpleNamespace(accumulate=accumulate, ema_kw=ema_kw, distill_kw=distill_kw, teacher_mod=teacher_mod, resize=resize,
                            window=window, reg=reg, per_step=scheduler_step == "step", monitor_kw=monitor_kw, erase=erase,
                            label_smoothing=float(label_smoothing), rand_augment=randaug, sam_kw=sam_kw, lamb=lamb_kw,
-                           drop_path=drop_kw)
+                           drop_path=drop_kw, loss=loss_kw)
 
 
 def _drop_path_settings(drop_path):
@@ -4268,7 +4347,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
           val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
           teacher=None, distill=None, param_groups=None, scheduler_step="epoch", monitor=None, random_erasing=None,
-          label_smoothing=0.0, rand_augment=None, sam=None, lamb=None, drop_path=None):
+          label_smoothing=0.0, rand_augment=None, sam=None, lamb=None, drop_path=None, loss=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -4501,7 +4580,23 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     full network.  The keys come from torch's device generator, whose state a snapshot holds: resume= continues bit for
     bit; the snapshot's header records the per-block rates, and a snapshot written with rates is refused by a run with
     other rates or none (and the other way round).  Rank 0 prints one line with the schedule and the lowest / highest
-    rate, and the returned model keeps its rates.  Refused: unknown keys, a rate outside [0, 1), an unknown schedule."""
+    rate, and the returned model keeps its rates.  Refused: unknown keys, a rate outside [0, 1), an unknown schedule.
+
+    loss=None | "ce" | "bce" | {"name": "bce", "target_threshold": None, "sum_classes": False} (the training loss of the
+    classification job; None / "ce": the reference's soft-target cross-entropy): "bce" is the binary cross-entropy with
+    logits that DeiT III / timm's `BinaryCrossEntropy` train with on the same CutMix / MixUp soft targets —
+    `soft_target_bce`, the mean over all B * C elements (torch.nn.BCEWithLogitsLoss()), or with sum_classes the sum over
+    the classes and the mean over the batch; target_threshold=t trains against (y > t).  With the loss kernels switched on
+    the step runs calm_bce_fwd / _bwd, and device_metrics=True reads the same buffer: the epoch line's mean loss is the
+    mean of the printed BCE, its dominant-class accuracy is taken against the targets as they came.  label_smoothing stays
+    the one op in front of the step — y (1 - eps) + eps / num_classes is exactly what timm's BinaryCrossEntropy(smoothing=
+    eps) does to its targets.  The log_every line and its dominant-class accuracy are unchanged.  Validation
+    (evaluate(report=True)) keeps reporting the softmax cross-entropy of the logits, whatever the training loss.  It is the
+    step's loss, so graph=True, accumulate, sam=, lamb=, ema, param_groups, monitor=, drop_path=, device_collate and its
+    companions and snapshots work as before; the setting has no state and is not part of a snapshot: resume= needs the
+    same loss= handed in again, as it needs the same teacher=.  Rank 0 prints one line naming the loss and its options
+    when it is not the cross-entropy.  Refused: an unknown name or key, a threshold that is not finite, a sum_classes that
+    is not a bool, task="reg" (any loss=), teacher= with "bce" (the distillation loss is built on the cross-entropy)."""
     from functools import partial
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
@@ -4509,7 +4604,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                           device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path,
                           snapshot_every, accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task,
                           teacher, distill, param_groups, scheduler_step, monitor, random_erasing, label_smoothing, rand_augment,
-                          sam, lamb, drop_path)
+                          sam, lamb, drop_path, loss)
     accumulate, per_step, teacher_mod = args.accumulate, args.per_step, args.teacher_mod
     rank, local_rank, world = init_distributed(use_gpu)
     main = rank == 0 and local_rank == 0                    # the one process that prints and writes
@@ -4572,7 +4667,10 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=max(epochs * steps_per_epoch, 1), eta_min=1e-6)
     scaler = torch.amp.GradScaler("cuda", enabled=use_gpu)                                                 # cls:64
     metrics = StepMetrics(device) if device_metrics else None
-    job = _RegTask(kl_weight) if args.reg else _ClsTask(metrics, val_topk)
+    job = _RegTask(kl_weight) if args.reg else _ClsTask(metrics, val_topk, args.loss)
+    if args.loss["name"] != "ce" and main:
+        print(f"loss: binary cross-entropy with logits, target_threshold {args.loss['target_threshold']}, "
+              f"sum_classes {args.loss['sum_classes']}")
     step = _make_step(job, model, optimizer, reducer, accumulate, teacher, {**args.distill_kw, "distill_metrics": dmetrics},
                       max_norm=1.0, scaler=scaler if use_gpu else None, autocast_dtype=torch.bfloat16 if use_gpu else None,
                       ema=ema_obj, sam_kw=args.sam_kw)
@@ -4616,7 +4714,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                 x, y = inp(batch)
                 if graph and gstep is None:
                     gstep = _capture_step(step, st, model, optimizer, x, y, scaler=scaler, reducer=reducer, metrics=metrics,
-                                          ema=ema_obj)
+                                          ema=ema_obj, loss=args.loss)
                     if mon is not None:
                         mon.reset()                 # the capture's warm-up steps were undone: they are not counted
                 if gstep is not None and x.shape == gstep.x.shape and y.shape == gstep.y.shape:

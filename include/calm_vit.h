@@ -209,9 +209,11 @@ int calm_gemm_describe(const calm_gemm_args* args, calm_gemm_plan* plan);
  *   CALM_RED_EVAL             B                    C            (calm_eval_metrics: one 16-byte record per row)
  *   CALM_RED_RECON            B                    S            (calm_recon_metrics: one 32-byte record per workgroup)
  *   CALM_RED_DISTILL          B                    C            (calm_distill_fwd: five sums per row)
+ *   CALM_RED_BCE              B                    C            (calm_bce_fwd: 2 * B floats, row sums and agreement flags)
  * ------------------------------------------------------------------------------------- */
 enum { CALM_RED_LAYERNORM_BWD = 0, CALM_RED_ROPE_BWD = 1, CALM_RED_LATENT_FWD = 2, CALM_RED_COLSUM = 3, CALM_RED_CNN_BWD = 4,
-       CALM_RED_SOFT_CE = 5, CALM_RED_HUBER = 6, CALM_RED_EVAL = 7, CALM_RED_RECON = 8, CALM_RED_DISTILL = 9 };
+       CALM_RED_SOFT_CE = 5, CALM_RED_HUBER = 6, CALM_RED_EVAL = 7, CALM_RED_RECON = 8, CALM_RED_DISTILL = 9,
+       CALM_RED_BCE = 10 };
 int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols);
 
 /* ---------------------------------------------------------------------------------------
@@ -1341,6 +1343,41 @@ int calm_distill_bwd(const float* logits, int64_t ld, const void* teacher, int64
                      const float* targets, int64_t td, float temperature, float alpha, int32_t mode,
                      const float* row_stats, const float* dloss /* device scalar */, float* dlogits /* [B,C] contiguous */,
                      int32_t B, int32_t C, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Binary cross-entropy with logits (additions to ABI v7 — no existing signature or struct changes, so the version number
+ * stays): the loss the DeiT III / timm recipe trains with on the CutMix / MixUp soft targets, every class its own two-way
+ * problem.  z the logits (fp32, row stride ld), y the soft targets (fp32, row stride td); rows are read as 16-byte vectors
+ * where pointers and strides allow, element by element otherwise (and always for the last C % 4 classes).
+ *     t = y;  with CALM_BCE_THRESHOLD  t = (y > threshold) ? 1 : 0            (timm's target_threshold: strict >)
+ *     l(z, t) = max(z, 0) - z t + log(1 + exp(-|z|)),  evaluated as  |z| * (z >= 0 ? 1 - t : t) + log1p(exp(-|z|))
+ *     loss = sum_{b,c} l / (B C)                 (torch.nn.BCEWithLogitsLoss(), the DeiT III form)
+ *          = sum_{b,c} l / B                     with CALM_BCE_SUM_CLASSES (timm's sum_classes)
+ *     dlogits[b,c] = dloss (sigmoid(z) - t) / (B C),  / B with CALM_BCE_SUM_CLASSES
+ * The exponential never sees a positive argument, and for t in [0, 1] both terms of l are non-negative: nothing overflows
+ * and nothing cancels.  Targets outside [0, 1] are legal, the formula is used as it is.  The sigmoid is the two-branch form
+ * (1 / (1 + e) for z >= 0, e / (1 + e) otherwise, e = exp(-|z|)).  The backward needs nothing saved: it recomputes from
+ * z and y.  dloss is a DEVICE scalar: it carries GradScaler's scale.  A NaN or infinite logit makes the loss non-finite
+ * and its own dlogits element NaN (the other elements do not depend on it), so that the scaled optimizer step is skipped
+ * as with the cross-entropy.
+ * partials: calm_reduce_scratch_floats(CALM_RED_BCE, B, C) = 2 * B floats: one workgroup per row writes the row's sum and
+ *   its agreement flag; the final workgroup of calm_soft_ce_fwd adds them in its fixed order.  No atomics: results repeat
+ *   bit for bit.
+ * metrics (nullable): the float[4] of calm_soft_ce_fwd with its meaning —
+ *     [0] += B * loss (so that [0] / [2] is the mean of the printed loss under either reduction)
+ *     [1] += #{b : argmax_c z[b,:] == argmax_c y[b,:]} — over the ORIGINAL y, not the thresholded one; ties go to the
+ *            lowest index, a row holding a NaN in z or y counts as no agreement
+ *     [2] += B        [3] += 1
+ * CALM_E_INVAL: a null logits / targets / loss (dloss, dlogits) / partials, B <= 0, C <= 0, flag bits other than the two,
+ * a threshold that is not finite with CALM_BCE_THRESHOLD set;  CALM_E_UNSUPP: B * C >= 2^31.  All of them before any launch.
+ * ------------------------------------------------------------------------------------- */
+enum { CALM_BCE_SUM_CLASSES = 1, CALM_BCE_THRESHOLD = 2 };   /* flags */
+int calm_bce_fwd(const float* logits, int64_t ld, const float* targets, int64_t td, int32_t flags, float threshold,
+                 float* loss /* scalar, overwritten */, float* metrics /* nullable, [4] */,
+                 int32_t B, int32_t C, float* partials, void* stream);
+int calm_bce_bwd(const float* logits, int64_t ld, const float* targets, int64_t td, int32_t flags, float threshold,
+                 const float* dloss /* device scalar */, float* dlogits /* [B,C] contiguous */,
+                 int32_t B, int32_t C, void* stream);
 
 #ifdef __cplusplus
 }
