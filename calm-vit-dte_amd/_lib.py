@@ -56,6 +56,7 @@ RED_EVAL = 7                                       # calm_eval_metrics: one 16-b
 RED_RECON = 8                                      # calm_recon_metrics: one 32-byte record per workgroup
 RED_DISTILL = 9                                    # calm_distill_fwd: five sums per row
 RED_BCE = 10                                       # calm_bce_fwd: row sums and agreement flags
+RED_MIM = 11                                       # calm_mim_huber_fwd: one block sum per workgroup
 BCE_SUM_CLASSES, BCE_THRESHOLD = 1, 2              # calm_bce_*'s flags (CALM_BCE_*)
 DISTILL_SOFT, DISTILL_HARD = 0, 1                  # calm_distill_*'s mode (CALM_DISTILL_*)
 DISTILL_ROW_STATS = 8                              # CALM_DISTILL_ROW_STATS: floats per row of calm_distill_*'s row_stats
@@ -299,6 +300,10 @@ SIGNATURES = {
     "calm_bce_bwd": (_i32, [_p, _i64, _p, _i64, _i32, _f32, _p, _p, _i32, _i32, _p]),
     "calm_dropout": (_i32, [_p, _p, _p, _i64, _i64, _f32, _p, _i32, _i32, _i32, _p]),
     "calm_drop_path": (_i32, [_p, _p, _p, _i64, _i64, _i64, _f32, _p, _i32, _i32, _i32, _p]),
+    "calm_mim_draw": (_i32, [_p, _i64, _i32, _i32, _i64, _p, _p]),
+    "calm_mim_apply": (_i32, [_p, _p, _p, C.POINTER(_f32), _i32, _i32, _i32, _p]),
+    "calm_mim_huber_fwd": (_i32, [_p, _p, _p, _f32, _p, _i32, _i32, _i32, _i64, _p, _p]),
+    "calm_mim_huber_bwd": (_i32, [_p, _p, _p, _f32, _p, _p, _i32, _i32, _i32, _i64, _p]),
 }
 
 _lib = None

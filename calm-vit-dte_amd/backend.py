@@ -1570,6 +1570,39 @@ class HipBackend:
                                            _stream()),
                    "calm_drop_path")
 
+    # ---- masked image modelling (csrc/mim.hip) ------------------------------------------
+    @staticmethod
+    def _mim_mask(who, mask, B, P):
+        if mask is None or not mask.is_cuda or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != B * P:
+            raise TypeError(f"{who} expects its mask as a contiguous uint8 CUDA tensor [B, P] = [{B}, {P}]")
+        return mask.data_ptr()
+
+    def mim_draw(self, mask, B, G, k, key, sample0=0):
+        """mask [B, G * G] uint8: exactly k patches of every sample set, the k lowest-ranked words of the dropout generator
+        at element indices (sample0 + b) * 1024 + i under `key` (device int64 [2] = seed, offset, read by the kernel)."""
+        if key is None or not key.is_cuda or key.dtype != torch.int64 or key.numel() != 2 or not key.is_contiguous():
+            raise TypeError("mim_draw expects its key as a contiguous int64 CUDA tensor of two elements (seed, offset)")
+        _lib.check(self.lib.calm_mim_draw(self._mim_mask("mim_draw", mask, B, G * G), B, G, k, sample0, key.data_ptr(),
+                                          _stream()), "calm_mim_draw")
+
+    def mim_apply(self, x, y, mask, fill, B, S, p):
+        """y = mask ? fill[channel] : x over row tokens [B,S,3S] (contiguous fp32; y may be x); fill: three floats."""
+        f3 = (_lib.C.c_float * 3)(*[float(v) for v in fill])
+        _lib.check(self.lib.calm_mim_apply(_ptr(x), _ptr(y), self._mim_mask("mim_apply", mask, B, (S // p) ** 2), f3, B, S, p,
+                                           _stream()), "calm_mim_apply")
+
+    def mim_huber_fwd(self, tokens, target, mask, delta, loss, B, S, p, masked):
+        """Huber(delta) between two contiguous fp32 [B,S,3S] tensors, mean over the 3 p^2 `masked` masked elements; loss 0-dim."""
+        _lib.check(self.lib.calm_mim_huber_fwd(_ptr(tokens), _ptr(target), self._mim_mask("mim_huber_fwd", mask, B, (S // p) ** 2),
+                                               float(delta), _ptr(loss), B, S, p, int(masked),
+                                               self._partials(_lib.RED_MIM, B, S, tokens.device), _stream()),
+                   "calm_mim_huber_fwd")
+
+    def mim_huber_bwd(self, tokens, target, mask, delta, dloss, dtokens, B, S, p, masked):
+        _lib.check(self.lib.calm_mim_huber_bwd(_ptr(tokens), _ptr(target), self._mim_mask("mim_huber_bwd", mask, B, (S // p) ** 2),
+                                               float(delta), _ptr(dloss), _ptr(dtokens), B, S, p, int(masked), _stream()),
+                   "calm_mim_huber_bwd")
+
     # ---- helpers ----------------------------------------------------------------------
     def add(self, a, b, out, n):
         _lib.check(self.lib.calm_add(_ptr(a), _ptr(b), _ptr(out), n, _stream()), "calm_add")

@@ -196,6 +196,7 @@ constexpr int SOFT_CE_PART_ROWS = 2;           // soft-target CE: one workgroup 
 constexpr int BCE_PART_ROWS = 2;               // calm_bce_fwd: one workgroup per sample; B row sums, then B agreement flags
 constexpr int DISTILL_PART_ROWS = 5;           // calm_distill_fwd: one workgroup per sample; B totals, CE, D, agreement with y, with t
 constexpr int HUBER_MAX_GRID = 2048;           // one block sum per workgroup
+constexpr int MIM_MAX_GRID = 2048;             // calm_mim_huber_fwd (mim.hip): one block sum per workgroup
 constexpr int EVAL_REC_FLOATS = 4;             // calm_eval_metrics: one 16-byte record per row (no cross-workgroup sum in launch 1)
 // calm_recon_metrics (recon.hip): a workgroup owns RECON band rows x RECON_STRIP_OUT output columns of one image and writes
 // one record of RECON_REC_FLOATS floats; the band is 32 output rows at Base sizes (42 rows read for 32: the halo costs

@@ -1153,6 +1153,7 @@ int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols) {
         case CALM_RED_RECON: return (int64_t)RECON_REC_FLOATS * rows * recon_bands(cols) * recon_strips(cols);
         case CALM_RED_DISTILL: return DISTILL_PART_ROWS * rows;
         case CALM_RED_BCE: return BCE_PART_ROWS * rows;
+        case CALM_RED_MIM: return MIM_MAX_GRID;
         default: return 0;
     }
 }

@@ -6,16 +6,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "huber.h"                       // huber_value / huber_slope, huber_rows_final_kernel (shared with mim.hip)
 
-#define RECON_NT 256
-
-__device__ __forceinline__ float huber_value(float d, float delta) {
-    const float ad = fabsf(d);
-    return ad <= delta ? 0.5f * d * d : (ad != ad ? d : delta * (ad - 0.5f * delta));
-}
-__device__ __forceinline__ float huber_slope(float d, float delta) {
-    return d != d ? d : fminf(fmaxf(d, -delta), delta);              // (fminf / fmaxf drop a NaN: hand it on)
-}
+#define RECON_NT HUBER_NT
 
 // ---- Huber on one flat layout ------------------------------------------------------------------------------------------
 // n4 groups of four elements go as 16-byte vectors (0 when a base is not 16-byte aligned), the elements behind 4 * n4 one
@@ -53,17 +46,7 @@ static __global__ __launch_bounds__(RECON_NT) void huber_rows_kernel(const float
     }
 }
 
-// ONE workgroup adds the G block sums in a fixed order (thread t takes t, t + 256, ... in increasing index, then a fixed
-// tree over the 256 running sums) and overwrites the loss.
-static __global__ __launch_bounds__(RECON_NT) void huber_rows_final_kernel(const float* __restrict__ part, int G, float scale,
-                                                                           float* __restrict__ loss) {
-    __shared__ float red[8];
-    float s = 0.f;
-    for (int g = threadIdx.x; g < G; g += RECON_NT) s += part[g];
-    s = block_sum_256(s, red);
-    if (threadIdx.x == 0) loss[0] = s * scale;
-}
-
+// (the final pass, one workgroup over the block sums: huber_rows_final_kernel of huber.h)
 static inline int huber_rows_grid(long n) {
     const long g = (n / 4 + RECON_NT - 1) / RECON_NT + 1;           // ~one vector per thread and turn at the cap
     return g < HUBER_MAX_GRID ? (int)g : HUBER_MAX_GRID;

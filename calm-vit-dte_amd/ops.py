@@ -1327,6 +1327,41 @@ class HuberRowsFn(Function):
         return dtokens, None, None
 
 
+class MimHuberFn(Function):
+    """The masked-image-modelling loss: Huber(delta) between the model's tokens and the clean target, both [B,S,3S], over
+    the elements of the masked patches alone (calm_mim_huber_fwd / _bwd).  apply(tokens, target, mask, delta, masked);
+    mask: uint8 [B, P], P = (S / p)^2, which fixes the patch side; masked: the number of set mask bytes (B * k behind
+    mim_draw).  tokens, target and the byte-per-patch mask are saved; the backward is one launch that writes every element
+    of dtokens (exact zeros outside the mask)."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, tokens, target, mask, delta, masked):
+        be = get_backend()
+        tokens, target = _c(tokens), _c(target)
+        if tokens.shape != target.shape or tokens.dim() != 3 or tokens.shape[2] != 3 * tokens.shape[1]:
+            raise ValueError("MimHuberFn expects tokens and a target of one shape [B,S,3S]")
+        B, S, _ = tokens.shape
+        G = math.isqrt(mask.numel() // max(B, 1))
+        if mask.dim() != 2 or mask.shape[0] != B or G * G != mask.shape[1] or G < 1 or S % G:
+            raise ValueError(f"MimHuberFn expects a mask [B, P] with P = (S / p)^2, got {tuple(mask.shape)} for S = {S}")
+        loss = torch.empty((), dtype=torch.float32, device=tokens.device)
+        ctx.geom = (B, S, S // G, int(masked))
+        be.mim_huber_fwd(tokens, target, mask, delta, loss, *ctx.geom)
+        ctx.save_for_backward(tokens, target, mask)
+        ctx.delta = float(delta)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    @_amp_bwd
+    def backward(ctx, g):
+        tokens, target, mask = ctx.saved_tensors
+        dtokens = torch.empty_like(tokens)
+        get_backend().mim_huber_bwd(tokens, target, mask, ctx.delta, _dloss(g), dtokens, *ctx.geom)
+        return dtokens, None, None, None, None
+
+
 class AddFn(Function):
     """Residual / U-net skip adds (Vi_Tools:309,315,403,513-522) and the latent running sum (43-44)."""
 

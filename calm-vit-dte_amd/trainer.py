@@ -41,6 +41,12 @@ as set by torchrun):
         binary cross-entropy with logits on the CutMix / MixUp soft targets, the loss of the DeiT III / timm recipe
         (calm_bce_fwd / _bwd with the loss kernels on; the StepMetrics buffer is fed as by the cross-entropy).
 
+  * `MaskedImageModelling` / `RegTrainStep(mim=)` / `train(task="reg", mim=)` / `load_backbone`   (no counterpart)
+        masked image modelling, the pre-training form of the generative job: a per-sample patch mask with exactly k set
+        patches (calm_mim_draw), the masked tokens as the model's input (calm_mim_apply), the Huber loss over the masked
+        elements alone against the clean tokens (calm_mim_huber_fwd / _bwd), and the hand-over of the pre-trained
+        `autoencoder.*` tensors to a classifier.
+
 The model also works under stock `torch.nn.parallel.DistributedDataParallel` (that is what the
 reference's train() does with it); the reducer here is the MI355X-tuned equivalent.  Under DDP the step
 classes leave the gradient tail (ops.grad_tail) off: DDP reads gradients during the backward.
@@ -617,6 +623,105 @@ class ReconMetrics:
                 "psnr": v[6] / imgs, "ssim": v[7] / imgs if self.ssim else None}
 
 
+def mim_huber_torch(tokens, target, mask, patch, delta=1.0, masked=None):
+    """calm_mim_huber_fwd as a plain torch expression (autograd gives calm_mim_huber_bwd): Huber(delta) between two
+    [B,S,3S] tensors, mean over the 3 * patch^2 * masked elements of the masked patches; mask uint8 / bool [B, (S / patch)^2],
+    masked: the number of set entries (None: counted here).  The difference is SELECTED before anything is computed on
+    it, so unmasked positions contribute exact zeros to the loss and to the gradient, whatever they hold."""
+    B, S, _ = target.shape
+    G = S // patch
+    m = (mask.reshape(B, G, 1, G, 1) != 0).expand(B, G, patch, G, 3 * patch).reshape(B, S, 3 * S)
+    d = torch.where(m, tokens.reshape(B, S, 3 * S).float() - target.float(), torch.zeros((), device=target.device))
+    n = 3 * patch * patch * (mask.sum() if masked is None else masked)
+    return torch.nn.functional.huber_loss(d, torch.zeros_like(d), reduction="sum", delta=delta) / n
+
+
+class MaskedImageModelling:
+    """Masked image modelling for the generative job (SimMIM, Xie et al. 2022; MAE, He et al. 2022): per sample exactly k of
+    the P = (S / patch)^2 patches are replaced by `fill` in the model's input, and the loss is the Huber loss between the
+    model's tokens and the CLEAN tokens over the masked patches alone — the U-shaped encoder-decoder cannot pass those
+    through its skips.
+
+        k = min(P - 1, max(1, floor(ratio * P + 0.5)))          0 < ratio < 1
+
+    patch: the patch side in pixels (S % patch == 0, S / patch <= 32).  fill: a float or three floats (per channel) in
+    normalised space; 0 is the dataset mean.  `draw(B, S, device)` -> uint8 mask [B, P] (calm_mim_draw; the 16-byte key comes
+    from ops.draw_dropout_key: torch.manual_seed reproduces it, ops.set_dropout_key_override injects it, it is drawn on the
+    device); `apply(tokens, mask)` -> the masked copy of row tokens [B,S,3S] (calm_mim_apply); `loss(y_hat, target, mask)`
+    -> the scalar (ops.MimHuberFn when the loss kernels take the tensors, `mim_huber_torch` otherwise).  draw and apply
+    always go through the backend: there is no torch twin of the mask."""
+    delta = 1.0                                   # nn.HuberLoss() of the reference's generative trainer (reg:59)
+
+    def __init__(self, patch=32, ratio=0.6, fill=0.0):
+        if isinstance(patch, bool) or not isinstance(patch, int) or patch < 1:
+            raise ValueError(f"MaskedImageModelling: patch is a side in pixels (an int >= 1), got {patch!r}")
+        if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 < ratio < 1.0:
+            raise ValueError(f"MaskedImageModelling: ratio is a share of the patches in (0, 1), got {ratio!r}")
+        f3 = list(fill) if isinstance(fill, (tuple, list)) else [fill] * 3
+        if len(f3) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) for v in f3):
+            raise ValueError(f"MaskedImageModelling: fill is a finite float or three of them, got {fill!r}")
+        self.patch, self.ratio, self.fill = patch, float(ratio), [float(v) for v in f3]
+
+    def grid(self, S):
+        """(G, P, k) at image side S."""
+        G = S // self.patch
+        if S % self.patch or G < 1:
+            raise ValueError(f"MaskedImageModelling: the image side {S} is not a multiple of the patch side {self.patch}")
+        if G > 32:
+            raise ValueError(f"MaskedImageModelling: the image side {S} holds {G} patches of side {self.patch} per row, "
+                             "more than the 32 the mask kernel ranks")
+        P = G * G
+        return G, P, min(P - 1, max(1, math.floor(self.ratio * P + 0.5)))
+
+    def draw(self, B, S, device):
+        from . import backend, ops
+        G, P, k = self.grid(S)
+        mask = torch.empty(B, P, dtype=torch.uint8, device=device)
+        backend.get_backend().mim_draw(mask, B, G, k, ops.draw_dropout_key(device))
+        return mask
+
+    def apply(self, tokens, mask):
+        from . import backend
+        B, S, _ = tokens.shape
+        self.grid(S)
+        tokens = tokens if tokens.is_contiguous() else tokens.contiguous()
+        out = torch.empty_like(tokens)
+        backend.get_backend().mim_apply(tokens, out, mask, self.fill, B, S, self.patch)
+        return out
+
+    def loss(self, y_hat, target, mask):
+        from . import backend
+        B, S, _ = target.shape
+        masked = B * self.grid(S)[2]
+        y_hat = y_hat.reshape(target.shape)
+        if target.dtype == torch.float32 and backend.loss_kernels_take(y_hat):
+            from .ops import MimHuberFn
+            return MimHuberFn.apply(y_hat, target, mask, self.delta, masked)
+        return mim_huber_torch(y_hat, target, mask, self.patch, self.delta, masked)
+
+    def settings(self):
+        return {"patch": self.patch, "ratio": self.ratio, "fill": list(self.fill)}
+
+
+def _mim_settings(who, mim):
+    """mim= of RegTrainStep / train() -> None, or the settings() of the MaskedImageModelling it describes."""
+    if mim is None or mim is False:
+        return None
+    if isinstance(mim, MaskedImageModelling):
+        return mim.settings()
+    if mim is True:
+        kw = {}
+    elif isinstance(mim, dict):
+        if not set(mim) <= {"patch", "ratio", "fill"}:
+            raise ValueError(f'{who}: mim takes the keys "patch", "ratio", "fill", got {sorted(mim)}')
+        kw = dict(mim)
+    elif isinstance(mim, (int, float)):
+        kw = {"ratio": mim}
+    else:
+        raise ValueError(f'{who}: mim is None, True, a ratio or a dict with "patch" / "ratio" / "fill", got {mim!r}')
+    return MaskedImageModelling(**kw).settings()          # (refuses a ratio outside (0, 1), a malformed patch or fill)
+
+
 class TrainStep:
     """One iteration of distributed_trainer_cls.py:79-96 (per rank)."""
 
@@ -746,24 +851,41 @@ class TrainStep:
 class RegTrainStep(TrainStep):
     """One iteration of the generative trainer (distributed_trainer_reg.py:71-95): the `generate=True` model returns
     tokens [B,S,3S]; they are viewed as the image [B,3,S,S] (:78-79), loss = HuberLoss(img, x) + 0.1 * kl_loss
-    (:81,87), then the same scale / clip(1.0) / optimizer step as the classification trainer."""
+    (:81,87), then the same scale / clip(1.0) / optimizer step as the classification trainer.
+
+    mim: a `MaskedImageModelling` or its settings dict (None: the job as above).  The step then draws a mask, feeds the
+    model the MASKED row tokens and takes `mim.loss(tokens, clean tokens, mask)` + kl_weight * kl: the Huber term looks only
+    where the input was replaced.  An image batch [B,3,S,S] is brought to row tokens once (ops.ImageToRowsFn; the first
+    Block takes either).  Every forward draws its own mask, so under SamRegTrainStep the two passes see DIFFERENT masks, as
+    they see different dropout keys; under AccumRegTrainStep every micro-batch draws one."""
 
     def __init__(self, model, optimizer, reducer=None, max_norm=1.0, scaler=None, autocast_dtype=None, kl_weight=0.1,
-                 ema=None, loss=None):
+                 ema=None, loss=None, mim=None):
         _cross_entropy_only(type(self).__name__, loss, "the generative job's loss is Huber + kl_weight * kl, it has no "
                             "class targets")
         super().__init__(model, optimizer, reducer, max_norm=max_norm, scaler=scaler, autocast_dtype=autocast_dtype, ema=ema)
         self.kl_weight = kl_weight
+        settings = _mim_settings(type(self).__name__, mim)
+        self.mim = mim if isinstance(mim, MaskedImageModelling) else \
+            None if settings is None else MaskedImageModelling(**settings)
 
     def __call__(self, x, _y=None):
         """x: the image [B,3,S,S], or the row tokens [B,S,3S] of the device collate — the channels-last image
         (Vi_Tools:389-391), which is then the Huber target in the layout of the model's output."""
         S = x.shape[1] if x.dim() == 3 else x.shape[-1]
+        mask, x_in = None, x
+        if self.mim is not None:
+            if x.dim() == 4:
+                from .ops import ImageToRowsFn
+                x = ImageToRowsFn.apply(x)                                 # the clean tokens: the target
+            mask = self.mim.draw(x.shape[0], S, x.device)
+            x_in = self.mim.apply(x, mask)
         with torch.autocast(device_type="cuda", dtype=self.autocast_dtype or torch.bfloat16,
                             enabled=self.autocast_dtype is not None and x.is_cuda):        # reg:76
-            y_hat, kl = self.model(x)                                      # reg:77
+            y_hat, kl = self.model(x_in)                                   # reg:77
             img = y_hat.reshape(-1, S, S, 3).permute(0, 3, 1, 2)           # reg:78-79 (a view)
-            loss = self._huber(y_hat, img, x) + kl * self.kl_weight        # reg:81,87
+            huber = self._huber(y_hat, img, x) if mask is None else self.mim.loss(y_hat, x, mask)
+            loss = huber + kl * self.kl_weight                             # reg:81,87
         return self._finish(loss, img)
 
     @staticmethod
@@ -3315,6 +3437,8 @@ class TrainState:
         rates = self._drop_path_rates()
         if rates is not None:                                 # stochastic depth changes what a step computes, not its state
             h["drop_path"] = rates
+        if self._mim_settings() is not None:                  # so does masked image modelling
+            h["mim"] = self._mim_settings()
         if not self.fused and self.payload:
             h["optimizer"] = self._optim_desc
             if self.scaler is not None:            # torch's own GradScaler policy: its growth count (reading it synchronises)
@@ -3326,6 +3450,11 @@ class TrainState:
         from .Vi_Tools_CNN_less_V2 import drop_path_rates
         rates = [r for _, r in drop_path_rates(self.model)]
         return rates if any(r > 0 for r in rates) else None
+
+    def _mim_settings(self):
+        """settings() of the bound step's MaskedImageModelling, or None."""
+        mim = getattr(self.step, "mim", None)
+        return None if mim is None else mim.settings()
 
     def _set_rng(self, h):
         torch.set_rng_state(_unb64(h["rng"]["torch_cpu"]))
@@ -3493,6 +3622,9 @@ class TrainState:
         if host.get("drop_path") != rates:
             said = lambda r: "without drop_path" if r is None else f"with drop_path rates {min(r):.4g} .. {max(r):.4g}"  # noqa: E731
             raise ValueError(f"{path}: written {said(host.get('drop_path'))}, this model runs {said(rates)}")
+        if host.get("mim") != self._mim_settings():
+            said = lambda m: "without mim" if m is None else f"with mim patch {m['patch']}, ratio {m['ratio']:.4g}, fill {m['fill']}"  # noqa: E731
+            raise ValueError(f"{path}: written {said(host.get('mim'))}, this step trains {said(self._mim_settings())}")
         # the entries: everything but a torch optimizer's state must be the live set, name by name
         head, optim, tail = self._fixed_entries()
         live = head + optim + tail
@@ -3736,6 +3868,32 @@ class SoftMixCollate:
         return self.mix(x, labels, mode, lam, box)
 
 
+def load_backbone(model, source, prefix="autoencoder."):
+    """Copy every tensor of `source` whose key starts with `prefix` into `model`, in place: the hand-over from a
+    `generate=True` model pre-trained with train(task="reg", mim=) to a classifier, which share the backbone
+    `ViT.autoencoder` key for key (parameters, spectral-norm `weight_orig` / `weight_u` / `weight_v` and every other buffer).
+    source: a state dict, or the path of a checkpoint train() wrote (the `_ema` / `_best` files as well).  The key sets
+    under the prefix and all shapes must agree; otherwise ValueError names the first three offenders and nothing is
+    copied.  Everything else in `model` (head, pool, proj) is left alone.  Returns {"loaded": keys copied, "ignored": keys
+    of the source outside the prefix}."""
+    sd = torch.load(source, map_location="cpu") if isinstance(source, (str, os.PathLike)) else source
+    if not isinstance(sd, dict) or not all(isinstance(v, torch.Tensor) for v in sd.values()):
+        raise ValueError("load_backbone: source is a state dict or the path of one")
+    own = model.state_dict()
+    mine, theirs = [k for k in own if k.startswith(prefix)], [k for k in sd if k.startswith(prefix)]
+    bad = [f"{k} (missing in the source)" for k in mine if k not in sd]
+    bad += [f"{k} (not in the model)" for k in theirs if k not in own]
+    bad += [f"{k} ({tuple(sd[k].shape)} in the source, {tuple(own[k].shape)} in the model)"
+            for k in mine if k in sd and sd[k].shape != own[k].shape]
+    if not mine or bad:
+        bad = bad or [f"no key of the model starts with {prefix!r}"]
+        raise ValueError(f"load_backbone: {len(bad)} mismatch(es) under {prefix!r}: " + "; ".join(bad[:3]))
+    with torch.no_grad():
+        for k in mine:
+            own[k].copy_(sd[k])
+    return {"loaded": mine, "ignored": [k for k in sd if not k.startswith(prefix)]}
+
+
 def _improves(best, name, value, lower):
     """The selection rule of the best checkpoints: True, and best[name] = value, when value strictly beats best[name] —
     lies below it with lower=True, above it otherwise."""
@@ -3785,8 +3943,8 @@ class _RegTask:
     name, reg, best = "reg", True, ("huber", True)
     eval_kw = dict(recon=True)
 
-    def __init__(self, kl_weight):
-        self.step_kw = {"kl_weight": kl_weight}
+    def __init__(self, kl_weight, mim=None):
+        self.step_kw = {"kl_weight": kl_weight, "mim": mim}
 
     def log_text(self, loss, y_hat, y):
         return f"Loss: {float(loss)}"
@@ -3880,7 +4038,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
                       device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path, snapshot_every,
                       accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task, teacher, distill,
                       param_groups, scheduler_step, monitor=None, random_erasing=None, label_smoothing=0.0, rand_augment=None,
-                      sam=None, lamb=None, drop_path=None, loss=None):
+                      sam=None, lamb=None, drop_path=None, loss=None, mim=None):
     """Every refusal train() makes from its arguments alone: it touches no device and no process group, so a bad call
     fails before either exists.  Returns the normalised values the job is assembled from: accumulate (int), ema_kw
     (None without ema), distill_kw (DistillTrainStep's keywords, {} without a teacher), teacher_mod, resize (the
@@ -3889,11 +4047,13 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
     label_smoothing (float), rand_augment (None, a DeviceRandAugment, or the dict of arguments one is built from), sam_kw
     (None without sam=; SharpnessAware's keywords and "sync"), lamb (None, or the normalised settings of
     FusedClipAdamW(lamb=) — the argument's, or those of the optimizer object handed in), drop_path (None, or
-    {"rate", "schedule"} for set_drop_path), loss (the normalised loss= of TrainStep)."""
+    {"rate", "schedule"} for set_drop_path), loss (the normalised loss= of TrainStep), mim (None, or the settings of the
+    MaskedImageModelling the step is built with)."""
     from . import backend as _backend
     from types import SimpleNamespace
     drop_kw = _drop_path_settings(drop_path)
     loss_kw = _loss_settings("train", loss)
+    mim_kw = _mim_settings("train", mim)
     if scheduler_step not in ("epoch", "step"):
         raise ValueError(f'train: scheduler_step is "epoch" or "step", got {scheduler_step!r}')
     if param_groups is not None and not (isinstance(optimizer, str) and optimizer == "fused"):
@@ -3960,6 +4120,9 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
     if teacher is not None and loss_kw["name"] != "ce":
         raise ValueError(f"train: teacher= excludes loss={loss!r} (the distillation loss is built on the cross-entropy; BCE "
                          "distillation is not supported)")
+    if mim_kw is not None and not reg:
+        raise ValueError('train: mim= needs task="reg" (masked image modelling is the generative job\'s pre-training; the '
+                         "classifier has no reconstruction target)")
     if reg and graph:
         raise ValueError('train: task="reg" excludes graph=True (GraphedTrainStep captures the classification step)')
     if reg and device_metrics:
@@ -4081,7 +4244,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
     return SimpleNamespace(accumulate=accumulate, ema_kw=ema_kw, distill_kw=distill_kw, teacher_mod=teacher_mod, resize=resize,
                            window=window, reg=reg, per_step=scheduler_step == "step", monitor_kw=monitor_kw, erase=erase,
                            label_smoothing=float(label_smoothing), rand_augment=randaug, sam_kw=sam_kw, lamb=lamb_kw,
-                           drop_path=drop_kw, loss=loss_kw)
+                           drop_path=drop_kw, loss=loss_kw, mim=mim_kw)
 
 
 def _drop_path_settings(drop_path):
@@ -4347,7 +4510,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
           val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
           teacher=None, distill=None, param_groups=None, scheduler_step="epoch", monitor=None, random_erasing=None,
-          label_smoothing=0.0, rand_augment=None, sam=None, lamb=None, drop_path=None, loss=None):
+          label_smoothing=0.0, rand_augment=None, sam=None, lamb=None, drop_path=None, loss=None, mim=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -4596,7 +4759,24 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     companions and snapshots work as before; the setting has no state and is not part of a snapshot: resume= needs the
     same loss= handed in again, as it needs the same teacher=.  Rank 0 prints one line naming the loss and its options
     when it is not the cross-entropy.  Refused: an unknown name or key, a threshold that is not finite, a sum_classes that
-    is not a bool, task="reg" (any loss=), teacher= with "bce" (the distillation loss is built on the cross-entropy)."""
+    is not a bool, task="reg" (any loss=), teacher= with "bce" (the distillation loss is built on the cross-entropy).
+
+    mim=True | ratio | {"patch": 32, "ratio": 0.6, "fill": 0.0} | a `MaskedImageModelling` (masked image modelling, SimMIM /
+    MAE style; needs task="reg"; no counterpart in the reference): the step is built with `RegTrainStep(mim=)` — per batch a
+    mask with exactly k = round(ratio * P) of the P = (S / patch)^2 patches of every sample (calm_mim_draw, from a 16-byte
+    key drawn on the device), the masked row tokens as the model's input (calm_mim_apply; `fill` in normalised space, a
+    float or one per channel), and Huber(tokens, CLEAN tokens) over the masked patches alone + kl_weight * kl
+    (calm_mim_huber_fwd / _bwd with the loss kernels on).  Reconstructing what the skips of the encoder-decoder hand
+    through teaches the backbone little; predicting what was removed does.  An image batch is brought to row tokens once;
+    device_collate and its companions, accumulate (a mask per micro-batch), sam= (a mask per pass), lamb=, ema,
+    param_groups, monitor=, drop_path= and snapshots work as before.  The key comes from torch's device generator, whose
+    state a snapshot holds, so resume= continues bit for bit; the snapshot's header records the settings only when mim is
+    on, and a snapshot written with settings is refused by a run with others or none (and the other way round).
+    Validation keeps reporting `ReconMetrics` on the UNMASKED input.  The log line is unchanged (its loss is the masked
+    one); rank 0 prints one line with the settings.  `load_backbone(classifier, checkpoint)` then hands the pre-trained
+    `autoencoder.*` tensors to a classifier for fine-tuning.  Refused: task="cls", unknown keys, a ratio outside (0, 1), a
+    patch that is not a positive int; an image side that is no multiple of the patch, or more than 32 patches per row, at
+    the first batch."""
     from functools import partial
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
@@ -4604,7 +4784,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                           device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path,
                           snapshot_every, accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task,
                           teacher, distill, param_groups, scheduler_step, monitor, random_erasing, label_smoothing, rand_augment,
-                          sam, lamb, drop_path, loss)
+                          sam, lamb, drop_path, loss, mim)
     accumulate, per_step, teacher_mod = args.accumulate, args.per_step, args.teacher_mod
     rank, local_rank, world = init_distributed(use_gpu)
     main = rank == 0 and local_rank == 0                    # the one process that prints and writes
@@ -4626,6 +4806,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         if main:
             print(f"drop_path: {args.drop_path['schedule']} over {len(rates)} blocks, rates {min(rates, default=0.0):.4f} .. "
                   f"{max(rates, default=0.0):.4f}")
+    if args.mim is not None and main:
+        print(f"mim: patch {args.mim['patch']}, ratio {args.mim['ratio']:.4f}, fill {args.mim['fill']}")
     if isinstance(optimizer, str) and optimizer == "fused":
         optimizer = _fused_optimizer(model, param_groups, accumulate, verbose=main, window=args.sam_kw is not None,
                                      lamb=args.lamb)
@@ -4667,7 +4849,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=max(epochs * steps_per_epoch, 1), eta_min=1e-6)
     scaler = torch.amp.GradScaler("cuda", enabled=use_gpu)                                                 # cls:64
     metrics = StepMetrics(device) if device_metrics else None
-    job = _RegTask(kl_weight) if args.reg else _ClsTask(metrics, val_topk, args.loss)
+    job = _RegTask(kl_weight, args.mim) if args.reg else _ClsTask(metrics, val_topk, args.loss)
     if args.loss["name"] != "ce" and main:
         print(f"loss: binary cross-entropy with logits, target_threshold {args.loss['target_threshold']}, "
               f"sum_classes {args.loss['sum_classes']}")

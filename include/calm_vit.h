@@ -210,10 +210,11 @@ int calm_gemm_describe(const calm_gemm_args* args, calm_gemm_plan* plan);
  *   CALM_RED_RECON            B                    S            (calm_recon_metrics: one 32-byte record per workgroup)
  *   CALM_RED_DISTILL          B                    C            (calm_distill_fwd: five sums per row)
  *   CALM_RED_BCE              B                    C            (calm_bce_fwd: 2 * B floats, row sums and agreement flags)
+ *   CALM_RED_MIM              B                    S            (calm_mim_huber_fwd: one block sum per workgroup)
  * ------------------------------------------------------------------------------------- */
 enum { CALM_RED_LAYERNORM_BWD = 0, CALM_RED_ROPE_BWD = 1, CALM_RED_LATENT_FWD = 2, CALM_RED_COLSUM = 3, CALM_RED_CNN_BWD = 4,
        CALM_RED_SOFT_CE = 5, CALM_RED_HUBER = 6, CALM_RED_EVAL = 7, CALM_RED_RECON = 8, CALM_RED_DISTILL = 9,
-       CALM_RED_BCE = 10 };
+       CALM_RED_BCE = 10, CALM_RED_MIM = 11 };
 int64_t calm_reduce_scratch_floats(int32_t op, int64_t rows, int32_t cols);
 
 /* ---------------------------------------------------------------------------------------
@@ -1378,6 +1379,58 @@ int calm_bce_fwd(const float* logits, int64_t ld, const float* targets, int64_t 
 int calm_bce_bwd(const float* logits, int64_t ld, const float* targets, int64_t td, int32_t flags, float threshold,
                  const float* dloss /* device scalar */, float* dlogits /* [B,C] contiguous */,
                  int32_t B, int32_t C, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Masked image modelling on row tokens (additions to ABI v7 — no existing signature or struct changes, so the version
+ * number stays; csrc/mim.hip; SimMIM / MAE style pre-training of the generative job, no counterpart in the reference):
+ * a per-sample patch mask with EXACTLY k set patches, the masked copy of a batch, and the Huber loss over the masked
+ * elements alone.  Tokens are [B,S,3S] fp32, tokens[b, r, 3x + c] (the channels-last image).  Patch side p, S % p == 0,
+ * G = S / p, P = G * G <= 1024; the patch of pixel (r, x) is i = (r / p) * G + x / p; mask is uint8 [B,P], 0 or 1.
+ *
+ * calm_mim_draw: mask[b, i] = rank(b, i) < k ? 1 : 0 with
+ *     w(b, i)    = calm_dropout's word(e), e = (sample0 + b) * 1024 + i          (same generator, same key layout)
+ *     rank(b, i) = #{ j < P : w(b, j) < w(b, i), or w(b, j) == w(b, i) and j < i }     (a permutation of 0 .. P - 1)
+ *   so exactly k patches of every sample are set; k == 0 writes zeros, k == P ones.  The slot stride is 1024 whatever P is:
+ *   the mask of a sample is a function of (seed, offset, sample0 + b, P, k) only — not of B, the grid, or of how a batch is
+ *   split into calls.  key: DEVICE uint64[2] = (seed, offset), read by the kernel — no host synchronisation, valid inside a
+ *   captured graph.  One workgroup per sample: the P words go to LDS, every thread ranks its patches against all of them
+ *   (at most 2^20 compares per sample); no sort, no atomics.
+ *   CALM_E_INVAL: null mask / key, B < 0, G < 1, k < 0, k > P, sample0 < 0, sample0 + B > 2^53;  CALM_E_UNSUPP: G > 32.
+ *   B == 0 returns 0 without a launch.
+ *
+ * calm_mim_apply: y[b, r, 3x + c] = mask[b, i] ? fill[c] : x[b, r, 3x + c].  fill: HOST array of three floats (normalised
+ *   space), read before the call returns.  A select: a NaN in a masked pixel of x does not reach y.  y may alias x (in
+ *   place, unmasked elements are not touched).
+ *   CALM_E_INVAL: null x / y / mask / fill, B < 0, S <= 0, p <= 0, S % p != 0;  CALM_E_UNSUPP: G > 32,
+ *   3 * B * S * S >= 2^31;  CALM_E_LAYOUT: x or y not 4-byte aligned.  B == 0 returns 0 without a launch.
+ *
+ * calm_mim_huber_fwd / _bwd: with n = 3 * p * p * masked,
+ *     loss       = 1/n * sum over the elements e with mask set of huber_delta(tokens[e] - target[e])
+ *     dtokens[e] = mask ? dloss / n * clamp(tokens[e] - target[e], -delta, delta) : +0.0f       (EVERY element is written)
+ *   masked: the number of set mask bytes in the batch — B * k behind calm_mim_draw, the caller's own count for a mask it
+ *   made itself (the kernels do not count).  dloss is a DEVICE scalar (it carries GradScaler's scale).  Both select and
+ *   never multiply: a NaN / inf at an unmasked position of tokens or target reaches neither the loss nor dtokens (a
+ *   16-byte vector without a masked element is not even loaded); a non-finite value at a masked position propagates.
+ *   partials: calm_reduce_scratch_floats(CALM_RED_MIM, B, S) floats, 16-byte aligned: one block sum per workgroup, added
+ *   by one final workgroup in a fixed order.  No atomics: results repeat bit for bit.
+ *   CALM_E_INVAL: a null pointer, B <= 0, S <= 0, p <= 0, S % p != 0, delta <= 0 or not finite, masked <= 0,
+ *   masked > B * P;  CALM_E_UNSUPP: G > 32, 3 * B * S * S >= 2^31;  CALM_E_LAYOUT: partials not 16-byte aligned, a
+ *   tensor not 4-byte aligned.
+ *
+ * The three streaming entry points move 16-byte vectors when every tensor base of the call is 16-byte aligned, single
+ * elements otherwise (and always for the last 3 B S^2 % 4 elements).  The mask decision is per element either way: with
+ * 3p % 4 != 0 a vector straddles a patch edge, with 3S % 4 != 0 a row end.  All refusals come before any launch.
+ * ------------------------------------------------------------------------------------- */
+int calm_mim_draw(uint8_t* mask /* [B,P] */, int64_t B, int32_t G, int32_t k, int64_t sample0,
+                  const uint64_t* key /* device, [2] = seed, offset */, void* stream);
+int calm_mim_apply(const float* x, float* y, const uint8_t* mask, const float* fill /* host [3] */, int32_t B, int32_t S,
+                   int32_t p, void* stream);
+int calm_mim_huber_fwd(const float* tokens, const float* target, const uint8_t* mask, float delta,
+                       float* loss /* scalar, overwritten */, int32_t B, int32_t S, int32_t p, int64_t masked,
+                       float* partials, void* stream);
+int calm_mim_huber_bwd(const float* tokens, const float* target, const uint8_t* mask, float delta,
+                       const float* dloss /* device scalar */, float* dtokens, int32_t B, int32_t S, int32_t p,
+                       int64_t masked, void* stream);
 
 #ifdef __cplusplus
 }
