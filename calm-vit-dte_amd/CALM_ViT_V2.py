@@ -53,6 +53,12 @@ class ViT(torch.nn.Module):
         else:                                                             # 60-67
             self.proj = vt.CnnResidual(32)
 
+    def features(self, q):
+        """The backbone's sequence-pooled output [B, in_features]: what the classification head reads, and the frozen
+        feature of a k-NN probe; the same for a generate=True model, which has no `pool` module of its own."""
+        with sn_scope(self):
+            return ops.mean_seq(self.autoencoder(q)[0])
+
     def forward(self, q):
         with sn_scope(self):
             x, kl_loss = self.autoencoder(q)

@@ -304,6 +304,9 @@ SIGNATURES = {
     "calm_mim_apply": (_i32, [_p, _p, _p, C.POINTER(_f32), _i32, _i32, _i32, _p]),
     "calm_mim_huber_fwd": (_i32, [_p, _p, _p, _f32, _p, _i32, _i32, _i32, _i64, _p, _p]),
     "calm_mim_huber_bwd": (_i32, [_p, _p, _p, _f32, _p, _p, _i32, _i32, _i32, _i64, _p]),
+    "calm_knn_normalize": (_i32, [_p, _i64, _i32, _p, _p, _i64, _i32, _p]),
+    "calm_knn_merge": (_i32, [_p, _i64, _i64, _p, _p, _i64, _i32, _i32, _p]),
+    "calm_knn_vote": (_i32, [_p, _p, _p, _i64, _f32, _p, _i64, _i64, _i32, _i32, _p]),
 }
 
 _lib = None

@@ -149,6 +149,25 @@ def eval_kernels_take(t):
             and (t.is_cuda or not isinstance(get_backend(), HipBackend)))
 
 
+def knn_kernels_take(t):
+    """Whether the calm_knn kernels serve features `t` (trainer.KnnProbe): fp32 or bf16, on a device the installed backend
+    can address (HipBackend: CUDA tensors only).  Anything else goes to the torch twins."""
+    return t.dtype in (torch.float32, torch.bfloat16) and (t.is_cuda or not isinstance(get_backend(), HipBackend))
+
+
+@contextlib.contextmanager
+def fp32_matmul():
+    """GEMMs issued inside run on the exact fp32 pipe whatever set_matmul_precision / an enclosing autocast say (the k-NN
+    probe's similarities: ties are decided on their bits)."""
+    global _precision
+    old, _precision = _precision, "fp32"
+    try:
+        with torch.autocast("cuda", enabled=False):
+            yield
+    finally:
+        _precision = old
+
+
 def recon_kernels_take(tokens, target):
     """Whether calm_recon_metrics serves this pair now (trainer.ReconMetrics): the switch is on, the generated tokens are
     fp32 or bf16, the target is fp32, and the installed backend can address both."""
@@ -1602,6 +1621,45 @@ class HipBackend:
         _lib.check(self.lib.calm_mim_huber_bwd(_ptr(tokens), _ptr(target), self._mim_mask("mim_huber_bwd", mask, B, (S // p) ** 2),
                                                float(delta), _ptr(dloss), _ptr(dtokens), B, S, p, int(masked), _stream()),
                    "calm_mim_huber_bwd")
+
+    # ---- k-NN probe (csrc/knn.hip) --------------------------------------------------------
+    @staticmethod
+    def _knn_state(who, best_sim, best_idx, Nq, k):
+        for name, t, dt in (("best_sim", best_sim, torch.float32), ("best_idx", best_idx, torch.int64)):
+            if t is None or not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != (Nq, k):
+                raise TypeError(f"{who} expects {name} as a contiguous {dt} CUDA tensor [Nq, k] = [{Nq}, {k}]")
+
+    def knn_normalize(self, x, out, bad, N, D):
+        """out[i] = x[i] / ||x[i]|| for x [N, D] fp32 or bf16 with unit column stride (any row stride), out fp32 [N, D]
+        contiguous; a row with a non-finite element or a zero norm becomes +0.0 and bad (int64 CUDA [1]) gains 1."""
+        if x.dim() != 2 or tuple(x.shape) != (N, D) or x.stride(1) != 1 or tuple(out.shape) != (N, D) or not out.is_contiguous():
+            raise ValueError(f"knn_normalize: x [N, D] = [{N}, {D}] with unit column stride and a contiguous out [N, D] expected")
+        if not bad.is_cuda or bad.dtype != torch.int64 or bad.numel() < 1:
+            raise TypeError("knn_normalize expects bad as an int64 CUDA tensor of one element")
+        _lib.check(self.lib.calm_knn_normalize(_ptr(x, bf16_ok=True), x.stride(0) if N > 1 else max(x.stride(0), D), _st(x),
+                                               _ptr(out), bad.data_ptr(), N, D, _stream()), "calm_knn_normalize")
+
+    def knn_merge(self, sims, base, best_sim, best_idx, Nq, n, k):
+        """The running top-k state (best_sim fp32 [Nq, k], best_idx int64 [Nq, k]; empty slot = (-inf, -1)) merged with the
+        similarities sims [Nq, n] (fp32, unit column stride, any row stride) of the bank items base .. base + n - 1, under
+        the order similarity descending, then bank index ascending."""
+        if sims.dim() != 2 or tuple(sims.shape) != (Nq, n) or sims.stride(1) != 1:
+            raise ValueError(f"knn_merge: sims [Nq, n] = [{Nq}, {n}] with unit column stride expected")
+        self._knn_state("knn_merge", best_sim, best_idx, Nq, k)
+        _lib.check(self.lib.calm_knn_merge(_ptr(sims), sims.stride(0) if Nq > 1 else max(sims.stride(0), n), int(base),
+                                           best_sim.data_ptr(), best_idx.data_ptr(), Nq, n, k, _stream()), "calm_knn_merge")
+
+    def knn_vote(self, best_sim, best_idx, bank_labels, inv_T, scores, Nq, k, C):
+        """scores [Nq, C] (fp32, unit column stride) = the votes of the state's neighbours for their labels (bank_labels
+        int64 CUDA [Nb]) with weight exp((sim - the row's largest sim) * inv_T); every element is overwritten."""
+        self._knn_state("knn_vote", best_sim, best_idx, Nq, k)
+        if not bank_labels.is_cuda or bank_labels.dtype != torch.int64 or bank_labels.dim() != 1 or not bank_labels.is_contiguous():
+            raise TypeError("knn_vote expects bank_labels as a contiguous int64 CUDA tensor [Nb]")
+        if scores.dim() != 2 or tuple(scores.shape) != (Nq, C) or scores.stride(1) != 1:
+            raise ValueError(f"knn_vote: scores [Nq, C] = [{Nq}, {C}] with unit column stride expected")
+        _lib.check(self.lib.calm_knn_vote(best_sim.data_ptr(), best_idx.data_ptr(), bank_labels.data_ptr(), bank_labels.numel(),
+                                          float(inv_T), _ptr(scores), scores.stride(0) if Nq > 1 else max(scores.stride(0), C),
+                                          Nq, k, C, _stream()), "calm_knn_vote")
 
     # ---- helpers ----------------------------------------------------------------------
     def add(self, a, b, out, n):

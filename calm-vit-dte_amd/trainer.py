@@ -46,6 +46,11 @@ as set by torchrun):
         patches (calm_mim_draw), the masked tokens as the model's input (calm_mim_apply), the Huber loss over the masked
         elements alone against the clean tokens (calm_mim_huber_fwd / _bwd), and the hand-over of the pre-trained
         `autoencoder.*` tensors to a classifier.
+  * `KnnProbe` / `knn_evaluate` / `Predictor(features=True)` / `train(knn=)`   (no counterpart)
+        weighted k-NN probe of the frozen backbone features (Wu et al. 2018, DINO's eval_knn): L2-normalised rows
+        (calm_knn_normalize), the exact k nearest bank features selected chunk by chunk under a total order (calm_gemm on
+        the fp32 pipe + calm_knn_merge), temperature-weighted votes (calm_knn_vote) ranked by `EvalMetrics`; run behind the
+        validation report of a pre-training run.
 
 The model also works under stock `torch.nn.parallel.DistributedDataParallel` (that is what the
 reference's train() does with it); the reducer here is the MI355X-tuned equivalent.  Under DDP the step
@@ -621,6 +626,248 @@ class ReconMetrics:
         elems, imgs = max(v[5], 1.0), max(n - bad, 1)
         return {"n": n, "nonfinite": bad, "huber": v[2] / elems, "mae": v[3] / elems, "mse": v[4] / elems,
                 "psnr": v[6] / imgs, "ssim": v[7] / imgs if self.ssim else None}
+
+
+KNN_MAX_K = 256                                     # calm_knn_merge / calm_knn_vote (include/calm_vit.h)
+_KNN_LAST = torch.iinfo(torch.int64).max            # where an empty slot sorts by index: behind every bank item
+
+
+def knn_normalize_torch(x):
+    """What calm_knn_normalize computes, in torch: (x / ||x|| as fp32 [N, D], the number of zeroed rows as an int64
+    0-dim tensor).  A row with a non-finite element, or whose fp32 norm is 0 or not finite, becomes all +0.0."""
+    xf = x.float()
+    nrm = (xf * xf).sum(dim=1).sqrt()
+    ok = torch.isfinite(xf).all(dim=1) & (nrm > 0) & torch.isfinite(nrm)
+    safe = torch.where(ok, nrm, torch.ones_like(nrm))
+    out = torch.where(ok[:, None], xf / safe[:, None], torch.zeros_like(xf))
+    return out, (~ok).sum()
+
+
+def knn_merge_torch(sims, base, best_sim, best_idx):
+    """What calm_knn_merge does to the running state (best_sim fp32 [Nq, k], best_idx int64 [Nq, k], rewritten in place)
+    with the chunk sims [Nq, n] of bank items base .. base + n - 1: the best k of state and chunk under similarity
+    descending, then bank index ascending — two stable sorts.  A NaN is -inf; -0.0 equals +0.0 and keeps its bits; an
+    empty slot (-inf, -1) sorts behind a real -inf."""
+    Nq, n = sims.shape
+    k = best_sim.shape[1]
+    s = sims.float()
+    s = torch.where(torch.isnan(s), torch.full_like(s, float("-inf")), s)
+    idx = (int(base) + torch.arange(n, dtype=torch.int64, device=s.device)).expand(Nq, n)
+    S, I = torch.cat([best_sim, s], dim=1), torch.cat([best_idx, idx], dim=1)
+    by_idx = torch.where(I < 0, torch.full_like(I, _KNN_LAST), I).sort(dim=1, stable=True).indices
+    S, I = S.gather(1, by_idx), I.gather(1, by_idx)
+    by_sim = S.sort(dim=1, descending=True, stable=True).indices[:, :k]
+    S, I = S.gather(1, by_sim), I.gather(1, by_sim)
+    best_sim.copy_(torch.where(I < 0, torch.full_like(S, float("-inf")), S))
+    best_idx.copy_(torch.where(I < 0, torch.full_like(I, -1), I))
+
+
+def knn_vote_torch(best_sim, best_idx, bank_labels, inv_T, num_classes):
+    """What calm_knn_vote writes, in torch: scores fp32 [Nq, C], the neighbours' weights exp((sim - the row's largest sim)
+    * inv_T) added to their labels' classes slot by slot in ascending order (one fp32 addition per slot, so classes with
+    equal votes get equal bits).  Empty slots, indices outside the bank and labels outside [0, C) vote for nothing."""
+    Nq, k = best_sim.shape
+    C, Nb = int(num_classes), bank_labels.numel()
+    scores = torch.zeros(Nq, C, dtype=torch.float32, device=best_sim.device)
+    rows = torch.arange(Nq, device=best_sim.device)
+    s0 = best_sim[:, 0]
+    for j in range(k):
+        id_j, s_j = best_idx[:, j], best_sim[:, j]
+        inside = (id_j >= 0) & (id_j < Nb)
+        lab = bank_labels[id_j.clamp(0, max(Nb - 1, 0))] if Nb else torch.full_like(id_j, -1)
+        votes = inside & (lab >= 0) & (lab < C)
+        d = torch.where(s_j == s0, torch.zeros_like(s_j), s_j - s0)
+        w = torch.exp(d * torch.tensor(float(inv_T), dtype=torch.float32, device=d.device))
+        scores[rows[votes], lab[votes]] += w[votes]
+    return scores
+
+
+class KnnProbe:
+    """Weighted k-NN probe on frozen features (Wu et al. 2018, DINO's eval_knn): the bank and the queries are L2-normalised,
+    every query takes its k nearest bank features by cosine similarity, each neighbour votes for its label with weight
+    exp(sim / T), and the votes are ranked by an internal `EvalMetrics`.  No training, deterministic.
+
+    The neighbours are EXACT under a total order — similarity descending, then bank index ascending — selected chunk by
+    chunk (`chunk` bank rows at a time: the [Nq, Nb] similarity matrix never exists), so ties are decided and the result
+    does not depend on the chunking.  On CUDA fp32 / bf16 features the work is calm_knn_normalize, calm_gemm on the fp32
+    pipe, calm_knn_merge and calm_knn_vote (include/calm_vit.h) with no host synchronisation until read(); otherwise the
+    torch twins above.
+
+    reset(); add_bank(features [N, D], labels int64 [N]) per bank batch; gather_bank() once when the bank is spread over
+    ranks; query(features, labels) per query batch (neighbours(features) -> (sims, idx) [Nq, k] is the retrieval alone);
+    all_reduce(); read().  A bank smaller than k is allowed: the empty slots (-inf, -1) do not vote."""
+
+    def __init__(self, num_classes, k=20, temperature=0.07, topk=(1, 5), chunk=16384, confusion=False, device="cpu"):
+        if isinstance(k, bool) or int(k) != k or not 1 <= k <= KNN_MAX_K:
+            raise ValueError(f"KnnProbe: k is an integer within 1 .. {KNN_MAX_K}, got {k!r}")
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not 0.0 < temperature < float("inf"):
+            raise ValueError(f"KnnProbe: temperature is a positive finite number, got {temperature!r}")
+        if isinstance(chunk, bool) or int(chunk) != chunk or chunk < 1:
+            raise ValueError(f"KnnProbe: chunk counts bank rows per merge (>= 1), got {chunk!r}")
+        self.metrics = EvalMetrics(num_classes, topk=topk, confusion=confusion, device=device)
+        self.num_classes, self.topk = self.metrics.num_classes, self.metrics.topk
+        self.k, self.temperature, self.chunk = int(k), float(temperature), int(chunk)
+        self.device = torch.device(device)
+        self.zeroed = torch.zeros(2, dtype=torch.int64, device=device)         # bank rows, query rows
+        self.reset()
+
+    def reset(self):
+        self.metrics.reset()
+        self.zeroed.zero_()
+        self.width = None
+        self._parts, self._bank, self._labels = [], None, None
+
+    # ---- the three steps, on the kernels or on the twins -----------------------------------------------------------------
+    @staticmethod
+    def _kernels(t):
+        from . import backend
+        return backend.knn_kernels_take(t)
+
+    def _check(self, who, features, labels):
+        if not isinstance(features, torch.Tensor) or features.dim() != 2 or not features.is_floating_point():
+            raise TypeError(f"KnnProbe.{who}: features is a floating-point tensor [N, D]")
+        if self.width is not None and features.shape[1] != self.width:
+            raise ValueError(f"KnnProbe.{who}: features are {features.shape[1]} wide, the probe has seen {self.width}")
+        if features.shape[1] < 1:
+            raise ValueError(f"KnnProbe.{who}: features need at least one column")
+        if labels is not None and (not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64
+                                   or tuple(labels.shape) != (features.shape[0],)):
+            raise TypeError(f"KnnProbe.{who}: labels is an int64 tensor [N] = [{features.shape[0]}]")
+        self.width = features.shape[1]
+
+    def _normalize(self, features, slot):
+        from . import backend
+        f = features.detach().to(self.device)
+        N, D = f.shape
+        if self._kernels(f):
+            f = f if f.stride(1) == 1 else f.contiguous()
+            out = torch.empty(N, D, dtype=torch.float32, device=f.device)
+            backend.get_backend().knn_normalize(f, out, self.zeroed[slot:slot + 1], N, D)
+            return out
+        out, bad = knn_normalize_torch(f)
+        self.zeroed[slot] += bad
+        return out
+
+    # ---- the bank -------------------------------------------------------------------------------------------------------
+    def add_bank(self, features, labels):
+        """Normalise and append: features [N, D], labels int64 [N]; zeroed rows (non-finite, or norm 0) are counted."""
+        self._check("add_bank", features, labels)
+        self._parts.append((self._normalize(features, 0), labels.detach().to(self.device)))
+        self._bank = None
+
+    def bank(self):
+        """(features fp32 [Nb, D] normalised, labels int64 [Nb]) as added, or as gather_bank left them."""
+        if self._bank is None:
+            if not self._parts:
+                return None, None
+            self._bank = torch.cat([f for f, _ in self._parts]).contiguous()
+            self._labels = torch.cat([l for _, l in self._parts]).contiguous()
+            self._parts = [(self._bank, self._labels)]
+        return self._bank, self._labels
+
+    def gather_bank(self, process_group=None, world_layout="strided"):
+        """All-gather every rank's shard and lay the bank out in DATASET order on every rank: rank r's j-th row is item
+        r + j * world (world_layout="strided", the layout of `validation_shard`), or the shards one behind the other
+        ("concat").  Shards are padded to the longest for the exchange, then trimmed.  Bank indices, and so ties, then do
+        not depend on the world size.  Without an initialised process group the bank stays as it is."""
+        if world_layout not in ("strided", "concat"):
+            raise ValueError(f'KnnProbe.gather_bank: world_layout is "strided" or "concat", got {world_layout!r}')
+        if process_group is None and not (dist.is_available() and dist.is_initialized()):
+            return
+        world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+        feats, labels = self.bank()
+        if feats is None:
+            raise ValueError("KnnProbe.gather_bank: every rank adds its shard with add_bank first")
+        sizes = torch.zeros(world, dtype=torch.int64, device=self.device)
+        sizes[rank] = feats.shape[0]
+        dist.all_reduce(sizes, group=process_group)
+        sizes = [int(v) for v in sizes.cpu()]
+        longest, total, D = max(sizes), sum(sizes), feats.shape[1]
+        if world_layout == "strided" and sizes != [len(range(r, total, world)) for r in range(world)]:
+            raise ValueError(f"KnnProbe.gather_bank: shards of {sizes} rows are not the strided shards of {total} items")
+        pad_f = torch.zeros(longest, D, dtype=torch.float32, device=self.device)
+        pad_l = torch.zeros(longest, dtype=torch.int64, device=self.device)
+        pad_f[:feats.shape[0]], pad_l[:feats.shape[0]] = feats, labels
+        all_f = [torch.empty_like(pad_f) for _ in range(world)]
+        all_l = [torch.empty_like(pad_l) for _ in range(world)]
+        dist.all_gather(all_f, pad_f, group=process_group)
+        dist.all_gather(all_l, pad_l, group=process_group)
+        bank = torch.empty(total, D, dtype=torch.float32, device=self.device)
+        bank_l = torch.empty(total, dtype=torch.int64, device=self.device)
+        at = 0
+        for r, n in enumerate(sizes):
+            if world_layout == "strided":
+                bank[r::world], bank_l[r::world] = all_f[r][:n], all_l[r][:n]
+            else:
+                bank[at:at + n], bank_l[at:at + n] = all_f[r][:n], all_l[r][:n]
+                at += n
+        self._bank, self._labels = bank, bank_l
+        self._parts = [(bank, bank_l)]
+        dist.all_reduce(self.zeroed[0:1], group=process_group)
+
+    # ---- the queries ----------------------------------------------------------------------------------------------------
+    def _neighbours(self, q):
+        from . import backend
+        bank, _ = self.bank()
+        if bank is None or bank.shape[0] == 0:
+            raise ValueError("KnnProbe: the bank is empty (add_bank first)")
+        Nq, D = q.shape
+        Nb, k = bank.shape[0], self.k
+        best_sim = torch.full((Nq, k), float("-inf"), dtype=torch.float32, device=q.device)
+        best_idx = torch.full((Nq, k), -1, dtype=torch.int64, device=q.device)
+        if Nq == 0:
+            return best_sim, best_idx
+        kernels = self._kernels(q)
+        scratch = torch.empty(Nq, min(self.chunk, Nb), dtype=torch.float32, device=q.device) if kernels else None
+        for base in range(0, Nb, self.chunk):
+            rows = bank[base:base + self.chunk]
+            n = rows.shape[0]
+            if kernels:
+                be = backend.get_backend()
+                with backend.fp32_matmul():                     # queries [Nq, D] x rows [n, D]^T, both k-contiguous
+                    be.gemm(q, rows, scratch, Nq, n, D, (D, 1, 0, 0), (D, 1, 0, 0), (scratch.stride(0), 0, 0))
+                be.knn_merge(scratch[:, :n], base, best_sim, best_idx, Nq, n, k)
+            else:
+                knn_merge_torch(q @ rows.t(), base, best_sim, best_idx)
+        return best_sim, best_idx
+
+    def neighbours(self, features):
+        """(sims fp32 [Nq, k], idx int64 [Nq, k]): the k nearest bank items of every row by cosine similarity, sorted by
+        similarity descending, then bank index ascending; (-inf, -1) where the bank has fewer than k items."""
+        self._check("neighbours", features, None)
+        return self._neighbours(self._normalize(features, 1))
+
+    def query(self, features, labels):
+        """neighbours, the vote, and one `EvalMetrics.update(scores, labels)`; returns the scores fp32 [Nq, C]."""
+        from . import backend
+        self._check("query", features, labels)
+        best_sim, best_idx = self._neighbours(self._normalize(features, 1))
+        _, bank_labels = self.bank()
+        Nq, C = best_sim.shape[0], self.num_classes
+        if self._kernels(best_sim) and Nq > 0:
+            scores = torch.empty(Nq, C, dtype=torch.float32, device=best_sim.device)
+            backend.get_backend().knn_vote(best_sim, best_idx, bank_labels, 1.0 / self.temperature, scores, Nq, self.k, C)
+        else:
+            scores = knn_vote_torch(best_sim, best_idx, bank_labels, 1.0 / self.temperature, C)
+        self.metrics.update(scores, labels.to(scores.device))
+        return scores
+
+    def all_reduce(self, group=None):
+        """Sum the tallies over the ranks (the bank's zeroed rows were summed by gather_bank)."""
+        self.metrics.all_reduce(group)
+        dist.all_reduce(self.zeroed[1:2], op=dist.ReduceOp.SUM, group=group)
+
+    def read(self):
+        """The report: n, skipped, bank, bank_zeroed, query_zeroed, k, temperature, top<k>, per_class_accuracy,
+        mean_per_class_accuracy and, if kept, confusion — `EvalMetrics.read()` of the votes without its loss (a
+        cross-entropy of vote sums means nothing)."""
+        rep = self.metrics.read()
+        bank, _ = self.bank()
+        zeroed = [int(v) for v in self.zeroed.cpu()]
+        out = {"n": rep["n"], "skipped": rep["skipped"], "bank": 0 if bank is None else int(bank.shape[0]),
+               "bank_zeroed": zeroed[0], "query_zeroed": zeroed[1], "k": self.k, "temperature": self.temperature}
+        out.update({key: v for key, v in rep.items() if key not in ("n", "skipped", "nonfinite", "loss")})
+        return out
 
 
 def mim_huber_torch(tokens, target, mask, patch, delta=1.0, masked=None):
@@ -1829,11 +2076,15 @@ class Predictor:
     of the host enqueueing every kernel.  The spectral-norm sigma products of eval mode and the bf16 weight copies are part
     of the captured region and read the parameters where they live, so an in-place update of the weights (an optimizer
     step, load_state_dict) is seen by the next replay.  A batch of any other shape or dtype (a ragged last batch) runs
-    eagerly, lean.  Outputs of a replay are copies: they stay valid across later calls.  close() releases the graph."""
+    eagerly, lean.  Outputs of a replay are copies: they stay valid across later calls.  close() releases the graph.
 
-    def __init__(self, model, example_x=None, autocast_dtype=None, graph=False, warmup=2):
+    features=True: `predictor(x)` returns `model.features(x)` (ViT.features: the pooled backbone output [B, D]) instead of
+    `model(x)`, lean / graph / autocast as above."""
+
+    def __init__(self, model, example_x=None, autocast_dtype=None, graph=False, warmup=2, features=False):
         self.model = model
         self.autocast_dtype = autocast_dtype
+        self.features = bool(features)
         self.graph = None
         self.x = self.out = None
         if graph:
@@ -1858,7 +2109,7 @@ class Predictor:
     def _forward(self, x):
         with torch.autocast(device_type="cuda", dtype=self.autocast_dtype or torch.bfloat16,
                             enabled=self.autocast_dtype is not None and x.is_cuda):
-            return self.model(x)
+            return self.model.features(x) if self.features else self.model(x)
 
     def _lean(self, fn, x):
         """fn(x) in eval mode, without grad, with the lean switch on; flag and switch restored."""
@@ -1990,6 +2241,85 @@ def evaluate(model, batches, lean=False, graph=False, autocast_dtype=None, trans
             tallies.all_reduce(process_group)
         return tallies.read()
     return correct / max(total, 1)
+
+
+def knn_evaluate(model, bank_batches, query_batches, num_classes, k=20, temperature=0.07, topk=(1, 5), lean=True, graph=False,
+                 autocast_dtype=None, transform=None, transform_out="tokens", ema=None, process_group=None, features=None,
+                 confusion=False):
+    """Weighted k-NN accuracy of the model's frozen features (`KnnProbe`): every rank embeds its bank shard (batches of
+    (x, int64 labels)), the shards are gathered into dataset order (`KnnProbe.gather_bank`: rank r holds items r, r + world,
+    ..., what `validation_shard` hands out), every rank embeds and queries its query shard, the tallies are summed over
+    `process_group` — or the default group when torch.distributed is initialised — and every rank returns
+    `KnnProbe.read()` of the whole set.  The feature is `model.features(x)` (ViT.features: the pooled backbone output)
+    through a `Predictor(features=True)` — lean kernels; graph=True captures the forward at the first batch's shape and
+    replays it, other shapes run eagerly — or, with lean=False and graph=False, the plain call in eval mode.
+    features: a callable x -> [B, D] that replaces the model forward (a head of the caller's own).  transform,
+    transform_out and ema are `evaluate`'s.  The training flag and the lean switch are as before when the call returns
+    or raises."""
+    if ema is not None:
+        if ema.model is not model:
+            raise ValueError("knn_evaluate: ema= must be the ModelEMA of the model being evaluated")
+        with ema.applied():
+            return knn_evaluate(model, bank_batches, query_batches, num_classes, k=k, temperature=temperature, topk=topk,
+                                lean=lean, graph=graph, autocast_dtype=autocast_dtype, transform=transform,
+                                transform_out=transform_out, process_group=process_group, features=features,
+                                confusion=confusion)
+    if features is not None and not callable(features):
+        raise TypeError(f"knn_evaluate: features is a callable x -> [B, D], got {type(features).__name__}")
+    KnnProbe(num_classes, k=k, temperature=temperature, topk=topk)     # (a bad setting is refused before any forward)
+    if transform is not None:
+        if not isinstance(transform, DeviceResizedCrop):
+            raise TypeError(f"knn_evaluate: transform must be a DeviceResizedCrop, got {type(transform).__name__}")
+        if transform.kind != "center":
+            raise ValueError("knn_evaluate: transform takes a DeviceResizedCrop.center(...), the deterministic validation transform")
+        if transform_out not in ("tokens", "image"):
+            raise ValueError(f'knn_evaluate: transform_out is "tokens" or "image", got {transform_out!r}')
+        device = next(model.parameters()).device
+        if device.type != "cuda":
+            raise ValueError("knn_evaluate: transform= runs a HIP kernel, the model must be on a GPU")
+
+        def _transformed(src):
+            for packed, meta, labels in src:
+                yield transform(packed.to(device, non_blocking=True), meta, out=transform_out), labels.to(device)
+        bank_batches, query_batches = _transformed(bank_batches), _transformed(query_batches)
+    was_training = model.training
+    model.eval()
+    predictor = probe = None
+    try:
+        with torch.no_grad():
+            def embed(x):
+                nonlocal predictor
+                if features is not None:
+                    return features(x)
+                if lean or graph:
+                    if predictor is None:
+                        predictor = Predictor(model, example_x=x if graph else None, autocast_dtype=autocast_dtype, graph=graph,
+                                              features=True)
+                    return predictor(x)
+                with torch.autocast(device_type="cuda", dtype=autocast_dtype or torch.bfloat16,
+                                    enabled=autocast_dtype is not None and x.is_cuda):
+                    return model.features(x)
+
+            for x, labels in bank_batches:
+                f = embed(x)
+                if probe is None:
+                    probe = KnnProbe(num_classes, k=k, temperature=temperature, topk=topk, confusion=confusion, device=f.device)
+                probe.add_bank(f, labels.to(f.device, torch.int64))
+            if probe is None:
+                raise ValueError("knn_evaluate: the bank needs at least one batch on every rank")
+            distributed = process_group is not None or (dist.is_available() and dist.is_initialized())
+            if distributed:
+                probe.gather_bank(process_group)
+            for x, labels in query_batches:
+                f = embed(x)
+                probe.query(f, labels.to(f.device, torch.int64))
+            if distributed:
+                probe.all_reduce(process_group)
+            return probe.read()
+    finally:
+        if predictor is not None:
+            predictor.close()
+        model.train(was_training)
 
 
 def validation_shard(dataset, rank, world):
@@ -3980,7 +4310,7 @@ def _make_step(task, model, optimizer, reducer, accumulate, teacher, distill_kw,
 
 
 def _validate_epoch(task, model, ema, val_dataset, rank, world, device, batch_size, transform, epoch, n_steps,
-                    checkpoint_path, val_log, best, verbose, transform_out="tokens"):
+                    checkpoint_path, val_log, best, verbose, transform_out="tokens", knn=None):
     """One validation pass of train(): every rank evaluates its shard (live weights, then the averaged ones), the reports
     are all-reduced inside evaluate; the caller's rank 0 passes checkpoint_path / val_log / verbose and does the writing.
     The RNG states and the training flag are as before when it returns.  The task decides what is measured (for "reg" the
@@ -4007,6 +4337,20 @@ def _validate_epoch(task, model, ema, val_dataset, rank, world, device, batch_si
                   transform_out=transform_out, **task.eval_kw)
         rep = evaluate(model, batches(), **kw)
         rep_ema = evaluate(model, batches(), ema=ema, **kw) if ema is not None else None
+        knn_rep = knn_ema = None
+        if knn is not None:
+            knn["seen"] += 1
+            if knn["seen"] % int(knn["every"]) == 0:
+                def labelled(data):                            # (the probe needs the labels a generative validation drops)
+                    for batch in DataLoader(data, batch_size=int(knn["batch_size"] or batch_size), shuffle=False,
+                                            collate_fn=collate, num_workers=0):
+                        yield batch if transform is not None else (batch[0].to(device, non_blocking=True), batch[1].to(device))
+                bank = validation_shard(knn["bank"], rank, world)
+                knn_kw = dict(k=knn["k"], temperature=knn["temperature"], lean=True, autocast_dtype=kw["autocast_dtype"],
+                              transform=transform, transform_out=transform_out)
+                knn_rep = knn_evaluate(model, labelled(bank), labelled(shard), knn["num_classes"], **knn_kw)
+                if ema is not None:
+                    knn_ema = knn_evaluate(model, labelled(bank), labelled(shard), knn["num_classes"], ema=ema, **knn_kw)
     finally:
         torch.set_rng_state(cpu_rng)
         if dev_rng is not None:
@@ -4016,10 +4360,19 @@ def _validate_epoch(task, model, ema, val_dataset, rank, world, device, batch_si
     line = {"epoch": epoch + 1, "step": n_steps, **scalars(rep)}
     if rep_ema is not None:
         line["ema"] = scalars(rep_ema)
+    if knn_rep is not None:
+        line["knn"] = scalars(knn_rep)
+    if knn_ema is not None:
+        line["ema"]["knn"] = scalars(knn_ema)
     if verbose:
         for tag, r in (("", rep), (" (EMA)", rep_ema)):
             if r is not None:
                 print(f"Epoch: {epoch + 1}, Validation{tag}: {task.val_text(r)}")
+        for tag, r in (("", knn_rep), (" (EMA)", knn_ema)):
+            if r is not None:
+                tops = ", ".join(f"top-{t}: {100.0 * r[f'top{t}']:.4f}%" for t in (1, 5))
+                print(f"Epoch: {epoch + 1}, k-NN{tag} (k={r['k']}, T={r['temperature']}): {tops}, Bank: {r['bank']}, "
+                      f"Samples: {r['n']}")
     if val_log is not None:
         os.makedirs(os.path.dirname(os.path.abspath(val_log)), exist_ok=True)
         with open(val_log, "a") as f:
@@ -4038,7 +4391,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
                       device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path, snapshot_every,
                       accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task, teacher, distill,
                       param_groups, scheduler_step, monitor=None, random_erasing=None, label_smoothing=0.0, rand_augment=None,
-                      sam=None, lamb=None, drop_path=None, loss=None, mim=None):
+                      sam=None, lamb=None, drop_path=None, loss=None, mim=None, knn=None):
     """Every refusal train() makes from its arguments alone: it touches no device and no process group, so a bad call
     fails before either exists.  Returns the normalised values the job is assembled from: accumulate (int), ema_kw
     (None without ema), distill_kw (DistillTrainStep's keywords, {} without a teacher), teacher_mod, resize (the
@@ -4054,6 +4407,7 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
     drop_kw = _drop_path_settings(drop_path)
     loss_kw = _loss_settings("train", loss)
     mim_kw = _mim_settings("train", mim)
+    knn_kw = _knn_settings(knn, val_dataset, num_classes)
     if scheduler_step not in ("epoch", "step"):
         raise ValueError(f'train: scheduler_step is "epoch" or "step", got {scheduler_step!r}')
     if param_groups is not None and not (isinstance(optimizer, str) and optimizer == "fused"):
@@ -4244,7 +4598,28 @@ def _check_train_args(initializer, optimizer, use_gpu, num_classes, device_colla
     return SimpleNamespace(accumulate=accumulate, ema_kw=ema_kw, distill_kw=distill_kw, teacher_mod=teacher_mod, resize=resize,
                            window=window, reg=reg, per_step=scheduler_step == "step", monitor_kw=monitor_kw, erase=erase,
                            label_smoothing=float(label_smoothing), rand_augment=randaug, sam_kw=sam_kw, lamb=lamb_kw,
-                           drop_path=drop_kw, loss=loss_kw, mim=mim_kw)
+                           drop_path=drop_kw, loss=loss_kw, mim=mim_kw, knn=knn_kw)
+
+
+def _knn_settings(knn, val_dataset, num_classes):
+    """knn= of train() -> None, or {"bank", "k", "temperature", "every", "batch_size", "num_classes", "seen"}."""
+    if knn is None or knn is False:
+        return None
+    kw = dict(knn) if isinstance(knn, dict) else {"bank": knn}
+    if not set(kw) <= {"bank", "k", "temperature", "every", "batch_size"} or kw.get("bank") is None:
+        raise ValueError(f'train: knn takes a bank dataset, or a dict with "bank" (needed), "k", "temperature", "every", '
+                         f'"batch_size", got {sorted(kw) if isinstance(knn, dict) else knn!r}')
+    if val_dataset is None:
+        raise ValueError("train: knn= needs val_dataset (its samples are the queries of the probe)")
+    kw = {"k": 20, "temperature": 0.07, "every": 1, "batch_size": None, **kw}
+    if not hasattr(kw["bank"], "__len__") or not hasattr(kw["bank"], "__getitem__") or len(kw["bank"]) < 1:
+        raise ValueError('train: knn["bank"] is a map-style dataset of (x, integer label) with at least one sample')
+    if isinstance(kw["every"], bool) or int(kw["every"]) != kw["every"] or kw["every"] < 1:
+        raise ValueError(f'train: knn["every"] counts validation passes between probes (>= 1), got {kw["every"]!r}')
+    if kw["batch_size"] is not None and (int(kw["batch_size"]) != kw["batch_size"] or kw["batch_size"] < 1):
+        raise ValueError(f'train: knn["batch_size"] counts samples (>= 1), got {kw["batch_size"]!r}')
+    KnnProbe(num_classes, k=kw["k"], temperature=kw["temperature"])     # (refuses a bad k / temperature / class count here)
+    return {**kw, "num_classes": int(num_classes), "seen": 0}
 
 
 def _drop_path_settings(drop_path):
@@ -4510,7 +4885,8 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
           ema=None, snapshot_path=None, snapshot_every=None, resume=None, accumulate=1, val_dataset=None, val_every=1,
           val_batch_size=None, val_transform=None, val_topk=(1, 5), task="cls", kl_weight=0.1, samples_dir=None,
           teacher=None, distill=None, param_groups=None, scheduler_step="epoch", monitor=None, random_erasing=None,
-          label_smoothing=0.0, rand_augment=None, sam=None, lamb=None, drop_path=None, loss=None, mim=None):
+          label_smoothing=0.0, rand_augment=None, sam=None, lamb=None, drop_path=None, loss=None, mim=None,
+          knn=None):
     """Per-rank training job: the reference's `train(initializer, optimizer, scheduler, use_gpu, dataset, epochs,
     batch_size)` (distributed_trainer_cls.py:25-114) on torch.distributed + RCCL instead of Spark's TorchDistributor —
     start one process per GPU with `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
@@ -4776,7 +5152,17 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
     one); rank 0 prints one line with the settings.  `load_backbone(classifier, checkpoint)` then hands the pre-trained
     `autoencoder.*` tensors to a classifier for fine-tuning.  Refused: task="cls", unknown keys, a ratio outside (0, 1), a
     patch that is not a positive int; an image side that is no multiple of the patch, or more than 32 patches per row, at
-    the first batch."""
+    the first batch.
+
+    knn=bank_dataset or {"bank": dataset, "k": 20, "temperature": 0.07, "every": 1, "batch_size": None} (needs val_dataset):
+    a weighted k-NN probe of the frozen backbone features (`knn_evaluate`, `KnnProbe`) behind the validation report, on every
+    `every`-th validation pass, for the live weights and for the averaged ones — what a pre-training run (task="reg",
+    mim=) otherwise only learns from a fine-tuning.  The bank yields what val_dataset yields ((x, integer label);
+    val_transform applies to both), each rank embeds its `validation_shard` of the bank and of the queries, the bank is
+    gathered into dataset order, so the result does not depend on the world size.  Rank 0 prints `Epoch: e, k-NN (k=20,
+    T=0.07): top-1: ...%, top-5: ...%, Bank: N, Samples: n`; the validation log line gains "knn": {...} and "ema": {...,
+    "knn": {...}}.  The best-checkpoint rule does not change and training is untouched: the parameters equal those of
+    the same run without knn= bit for bit."""
     from functools import partial
     from torch.utils.data import DataLoader, DistributedSampler
     from . import backend as _backend
@@ -4784,7 +5170,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
                           device_augment, device_resize, resize_window, random_resized_crop, ema, snapshot_path,
                           snapshot_every, accumulate, val_dataset, val_every, val_batch_size, val_transform, val_topk, task,
                           teacher, distill, param_groups, scheduler_step, monitor, random_erasing, label_smoothing, rand_augment,
-                          sam, lamb, drop_path, loss, mim)
+                          sam, lamb, drop_path, loss, mim, knn)
     accumulate, per_step, teacher_mod = args.accumulate, args.per_step, args.teacher_mod
     rank, local_rank, world = init_distributed(use_gpu)
     main = rank == 0 and local_rank == 0                    # the one process that prints and writes
@@ -4874,7 +5260,7 @@ def train(initializer, optimizer, scheduler=None, use_gpu=True, dataset=None, ep
         validate = partial(_validate_epoch, job, model, ema_obj, val_dataset, rank, world, device,
                            val_batch_size or batch_size, val_transform, checkpoint_path=checkpoint_path if main else None,
                            val_log=val_log if main else None, best=val_best, verbose=main,
-                           transform_out="tokens" if device_collate or not args.reg else "image")
+                           transform_out="tokens" if device_collate or not args.reg else "image", knn=args.knn)
     try:
         if resume is not None:
             progress = st.load(resume)

@@ -1432,6 +1432,53 @@ int calm_mim_huber_bwd(const float* tokens, const float* target, const uint8_t* 
                        const float* dloss /* device scalar */, float* dtokens, int32_t B, int32_t S, int32_t p,
                        int64_t masked, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Weighted k-NN probe on frozen features (additions to ABI v7 — no existing signature or struct changes, so the version
+ * number stays; csrc/knn.hip; the protocol of Wu et al. 2018 and DINO's eval_knn, no counterpart in the reference): rows
+ * are L2-normalised, the k nearest bank items of every query are selected EXACTLY, chunk by chunk, and their labels vote
+ * with weight exp(sim / T).  The similarities are calm_gemm's (queries [Nq,D] x a bank chunk [n,D]^T, fp32) in a scratch.
+ * All three enqueue on `stream`, never synchronise, use no float atomics and repeat bit for bit.
+ *
+ * calm_knn_normalize: out[i, :] = x[i, :] / ||x[i, :]||.  x [N,D] fp32 or bf16 (x_type CALM_ST_F32 / CALM_ST_BF16), unit
+ *   column stride, row stride ld elements; out fp32 [N,D] contiguous.  The squared norm is summed in fp32 in a fixed order
+ *   (one wave per row).  A row that holds a non-finite element, or whose fp32 norm is 0 or not finite, becomes all +0.0f
+ *   and the DEVICE counter bad[0] gains 1 (an integer add).  16-byte loads when x is 16-byte aligned and ld is a multiple
+ *   of the elements in 16 bytes, element loads otherwise.
+ *   CALM_E_INVAL: null x / out / bad, N < 0, D < 1, ld < D, an x_type other than the two;  CALM_E_UNSUPP: D > 4096;
+ *   CALM_E_LAYOUT: x not aligned to its element, out not 4-byte aligned.  N == 0 returns 0 without a launch.
+ *
+ * calm_knn_merge: sims fp32 [Nq,n], unit column stride, row stride ld; element (q, j) is the similarity of query q to
+ *   bank item base + j.  best_sim fp32 [Nq,k] and best_idx int64 [Nq,k] are the running state, read and rewritten: on
+ *   return they hold the best k of (old state U this chunk), sorted, under the TOTAL order
+ *       similarity descending, then bank index ascending.
+ *   Values compare as floats (-0.0 == +0.0: the index decides; the stored bits are the element's own); a NaN similarity
+ *   ranks, and is stored, as -inf.  An empty slot is (-inf, -1): it ranks below every real entry, a real -inf included.
+ *   The caller resets the state by filling it with empty slots, and gives every bank item to the state once.  Because
+ *   the order is total, the state after any chunking of the bank, in any order of the chunks, is the same bit for bit.
+ *   One workgroup per query: a compare pass against the state's k-th entry (a row without a candidate writes nothing),
+ *   an 8-bit radix select over the candidates' keys when they do not fit the LDS, a bitonic sort of at most 1024 entries.
+ *   CALM_E_INVAL: null sims / best_sim / best_idx, k < 1, n < 1, Nq < 0, ld < n, base < 0, base + n > 2^63 - 1;
+ *   CALM_E_UNSUPP: k > 256, Nq >= 2^31;  CALM_E_LAYOUT: a tensor not aligned to its element.  Nq == 0 returns 0
+ *   without a launch.
+ *
+ * calm_knn_vote: scores fp32 [Nq,C], row stride ld, every element overwritten:
+ *       scores[q, c] = sum over the slots j, ascending, with best_idx[q, j] in [0, Nb) and bank_labels[best_idx[q, j]] == c
+ *                      of exp((best_sim[q, j] - best_sim[q, 0]) * inv_T)
+ *   (the difference of two equal values is taken as 0, also of two -inf).  Subtracting the row's largest similarity
+ *   changes no ranking and keeps every weight in (0, 1].  A label outside [0, C) votes for nothing; a class without a
+ *   neighbour gets exactly +0.0f; two classes with bit-equal votes get bit-equal scores.  bank_labels int64 [Nb].
+ *   CALM_E_INVAL: null best_sim / best_idx / bank_labels / scores, k < 1, C < 1, Nq < 0, Nb < 0, ld < C, inv_T <= 0 or
+ *   not finite;  CALM_E_UNSUPP: k > 256, Nq >= 2^31;  CALM_E_LAYOUT: a tensor not aligned to its element.  Nq == 0
+ *   returns 0 without a launch.
+ * All refusals come before any launch.
+ * ------------------------------------------------------------------------------------- */
+int calm_knn_normalize(const void* x, int64_t ld, int32_t x_type, float* out /* [N,D] */, int64_t* bad /* device, [1] */,
+                       int64_t N, int32_t D, void* stream);
+int calm_knn_merge(const float* sims, int64_t ld, int64_t base, float* best_sim /* [Nq,k] */, int64_t* best_idx /* [Nq,k] */,
+                   int64_t Nq, int32_t n, int32_t k, void* stream);
+int calm_knn_vote(const float* best_sim, const int64_t* best_idx, const int64_t* bank_labels /* [Nb] */, int64_t Nb,
+                  float inv_T, float* scores /* [Nq,C] */, int64_t ld, int64_t Nq, int32_t k, int32_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
